@@ -8,7 +8,11 @@ GPU (BASELINE.json configs[2], "C3": random start/goal crowd, neighborDist 5, ma
 state and actions resident in HBM.  value = agents advanced per second over all GPUs.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C5] [--mode step|orca]
-                  [--variant walls|free] [--starts overlap|separated] [--no-cpu-baseline]
+                  [--variant walls|free] [--starts overlap|separated] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given and
+prints the result line.  --full adds everything else: the per-kernel / roofline figures (sampled launch events in the timed
+region), the per-call ORCA comparison, the replay through the CPU oracle (--verify) and the CPU baseline.
 
 N > 1: one rank per GPU (torch.distributed.run; when this script is started directly with --gpus N it
 starts the N ranks itself, as a child process, before anything touches the GPU, and relays rank 0's line);
@@ -41,6 +45,10 @@ BYTES_STEP_KERNEL_ORCA = 52
 BYTES_OBS_KERNEL = 256        # the 64-float observation row
 # clocks settle: the warm-up runs at least this long whatever --warmup says (CA_BENCH_MIN_WARM: diagnostic override)
 MIN_WARM_SECONDS = float(os.environ.get("CA_BENCH_MIN_WARM", "1.0"))
+# the crowd settles: the timed region starts after at least this many steps, whatever --warmup says -- the contracted
+# regime of tests/test_gpu_parity.py::test_parity_in_the_settled_regime_the_bench_times (CA_BENCH_SETTLE_STEPS: diagnostic override)
+SETTLE_STEPS = int(os.environ.get("CA_BENCH_SETTLE_STEPS", "10000"))
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs, all ranks together: a seeded sample of whole arenas when the outputs are larger
 
 
 def parse():
@@ -56,18 +64,27 @@ def parse():
                     help="SURVEY 8d: A = with the boundary polygon (default), B = obstacle-free")
     ap.add_argument("--starts", default="overlap", choices=["overlap", "separated"],
                     help="SURVEY 8d: uniform starts (overlaps allowed, default) or rejection-sampled non-overlapping starts")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel / roofline figures, the "
+                         "per-call ORCA comparison, --verify (default 8) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--rollout-chunk", type=int, default=50,
                     help="--mode orca: steps per ca_rollout call (the ORCA-only policy rollout of env.py:570-573 / ALAN:106-123); "
                          "1 = one ca_orca_step call per step")
     ap.add_argument("--arenas", type=int, default=None, help="diagnostic: override the workload's arena count (batch-size studies)")
-    ap.add_argument("--verify", type=int, default=8,
+    ap.add_argument("--verify", type=int, default=None,
                     help="after the timed region (outside it): replay this many arenas of the rank through the CPU oracle for EVERY step "
-                         "the GPU ran (warm-up + timed) with the same actions and compare the state bit for bit; 0 = off")
+                         "the GPU ran (warm-up + timed) with the same actions and compare the state bit for bit; 0 = off "
+                         "(default: 8 with --full, else 0)")
     ap.add_argument("--as-rank", type=int, default=None,
                     help="rehearsal (tests): a single process plays rank R of a larger job -- arena offset R * arenas, action seed of rank R")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.verify is None:
+        args.verify = 8 if args.full else 0
+    return args
 
 
 def launch_ranks(args):
@@ -278,6 +295,120 @@ def counters_for(workload, mode, variant, starts, kernels):
         os.path.basename(files[-1]), sha)
 
 
+def dump_outputs(env, mode, out_dir, suffix="", max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what the timed path handed its caller after its last step -- positions, velocities and done flags, plus
+    reward and observation (mode step) or the bandit's last actions and weights (mode alan) -- as out_dir/<name><suffix>.npy,
+    float32 fields as they are, integer fields as float64 (exact).  Every array has the arena as its first axis; when all
+    arenas together exceed max_bytes, the same seeded sample of whole arenas is kept in every array."""
+    import numpy as np
+    from collision_avoidance_amd import _lib
+    names = ["POS_X", "POS_Y", "VEL_X", "VEL_Y", "AGENT_DONE", "ARENA_DONE"]
+    if mode == "step":
+        names += ["REWARD", "OBS"]
+    if mode == "alan":
+        names += ["ALAN_ACTION", "ALAN_WEIGHTS"]
+    arrays = {}
+    for name in names:
+        a = env.get(getattr(_lib, "FLD_" + name))
+        arrays[name.lower()] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    per_arena = sum(a.nbytes for a in arrays.values()) // env.A
+    keep = env.A
+    if per_arena * env.A > max_bytes:
+        keep = max(1, max_bytes // per_arena)
+        idx = np.sort(np.random.RandomState(0).choice(env.A, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
+    sys.stderr.write("bench.py: wrote %d arrays of %d of %d arenas to %s\n" % (len(arrays), keep, env.A, out_dir))
+
+
+def kernel_figures(ktimes, agents, full_step, dt, args):
+    """--full: the per-kernel times of the sampled launches of the timed region, the HBM roofline of the dominant kernel and
+    the vector-ALU view from the committed counter profile of these sources (counters_for)."""
+    kbytes_of = {"nbr_kernel": 0, "step_kernel": BYTES_STEP_KERNEL_FULL if full_step else BYTES_STEP_KERNEL_ORCA,
+                 "obs_kernel": BYTES_OBS_KERNEL}
+    kms_of = {k: v[1] for k, v in ktimes.items() if v[0] > 0 and k in kbytes_of}   # (a T-step launch is reported per step)
+    # dominant kernel: strictly the longest average launch (no tie-break)
+    dom = max(kms_of, key=lambda k: kms_of[k])
+    kms, kbytes = kms_of[dom], kbytes_of[dom]
+    achieved = agents * kbytes / (kms * 1e-3) / 1e9
+    per_kernel = {k: {"ms": round(v, 5), "algorithmic_bytes_per_agent": kbytes_of[k],
+                      "algorithmic_GB_per_s": agents * kbytes_of[k] / (v * 1e-3) / 1e9,
+                      "frac": agents * kbytes_of[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                  for k, v in kms_of.items()}
+    cj, csrc = counters_for(args.workload, args.mode, args.variant, args.starts, kms_of)
+    traffic, traffic_low, traffic_high, traffic_detail, valu = None, None, None, {"source": csrc}, None
+    if cj is not None:
+        kk = cj.get("kernels", {})
+        if dom in kk and "hbm_bytes_high" in kk[dom]:
+            # FETCH_SIZE on gfx950 tallies the 128-B requests of wide reads at 64 B: the true figure lies between the
+            # reported one (low) and the one with FETCH doubled (high); `traffic` quotes the conservative high end
+            traffic_low, traffic_high = kk[dom].get("hbm_bytes_low"), kk[dom]["hbm_bytes_high"]
+            traffic = traffic_high
+        traffic_detail = {"source": csrc, "src_sha": cj.get("src_sha"),
+                          "per_kernel": {k: {x: kk[k].get(x) for x in ("FETCH_SIZE_KB", "WRITE_SIZE_KB", "hbm_bytes_low",
+                                                                       "hbm_bytes_high", "algorithmic_bytes")}
+                                         for k in kms_of if k in kk}}
+        try:  # vector-ALU view (SURVEY 8d): wave-level VALU instructions per launch x 64 lanes over the live kernel times
+            cnt = {k: float(kk[k]["SQ_INSTS_VALU"]) for k in kms_of}
+            lane_ops = 64.0 * sum(cnt.values())
+            tsum = sum(kms_of.values()) * 1e-3
+
+            def issue_cycles(c, cheap_other):
+                """Vector-issue cycles of one launch from the instruction-class counters and the measured issue
+                cost of each class on gfx950 (profiles/r02_valu_issue_rates_microbench.txt): v_add / v_mul_f32 2.7,
+                v_fma_f32 3.9, transcendental 8.3, conversions / 64-bit integer 4.2; 32-bit integer and the rest
+                (compares, selects, moves, min / max, DPP ...) between 2.7 (and, add, mov) and 4.2 (the others):
+                `cheap_other` picks the end of that range."""
+                known = ("SQ_INSTS_VALU_ADD_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_TRANS_F32",
+                         "SQ_INSTS_VALU_INT32", "SQ_INSTS_VALU_INT64", "SQ_INSTS_VALU_CVT")
+                if not all(x in c for x in known):
+                    return float(c["SQ_INSTS_VALU"]) * ISSUE_CYCLES_PER_VALU
+                other = float(c["SQ_INSTS_VALU"]) - sum(float(c[x]) for x in known)
+                flex = 2.7 if cheap_other else 4.2
+                return ((float(c["SQ_INSTS_VALU_ADD_F32"]) + float(c["SQ_INSTS_VALU_MUL_F32"])) * 2.7 +
+                        float(c["SQ_INSTS_VALU_FMA_F32"]) * 3.9 + float(c["SQ_INSTS_VALU_TRANS_F32"]) * 8.3 +
+                        (float(c["SQ_INSTS_VALU_INT64"]) + float(c["SQ_INSTS_VALU_CVT"])) * 4.2 +
+                        (float(c["SQ_INSTS_VALU_INT32"]) + max(0.0, other)) * flex)
+            bound_hi = {k: issue_cycles(kk[k], False) / N_SIMDS / CLOCK_HZ * 1e3 for k in kms_of}
+            bound_lo = {k: issue_cycles(kk[k], True) / N_SIMDS / CLOCK_HZ * 1e3 for k in kms_of}
+            valu = {"wave_insts_per_step": cnt, "lane_ops_per_s": lane_ops / tsum,
+                    "peak_lane_ops_per_s": VALU_PEAK_LANE_OPS, "frac": lane_ops / tsum / VALU_PEAK_LANE_OPS,
+                    "per_kernel_frac": {k: 64.0 * cnt[k] / (kms_of[k] * 1e-3) / VALU_PEAK_LANE_OPS for k in kms_of},
+                    # the bound that matters: every vector instruction of the launch issued back to back on its SIMD,
+                    # priced per instruction class; [low, high] for the classes whose members differ in cost
+                    "issue_bound_ms": bound_hi, "issue_bound_ms_low": bound_lo,
+                    "frac_of_issue_bound": {k: bound_hi[k] / kms_of[k] for k in kms_of},
+                    "frac_of_issue_bound_low": {k: bound_lo[k] / kms_of[k] for k in kms_of},
+                    "source": "%s (SQ_INSTS_VALU and instruction-class counters per launch, same kernel sources and flags) "
+                              "over the live kernel times" % csrc}
+        except Exception:
+            valu = None
+    limited_by = None
+    if valu is not None and traffic is not None:
+        hbm_frac = traffic / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS
+        limited_by = "valu-issue" if valu["frac_of_issue_bound_low"][dom] > hbm_frac else "hbm"
+    return {
+        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "traffic_low": traffic_low, "traffic_high": traffic_high,
+                     # what the COUNTERS of this build say limits the dominant kernel: its vector-issue time (see `valu`)
+                     # against the time its measured HBM traffic needs at the peak; null without a counter profile of
+                     # these sources -- the HBM fraction above is reported because the metric asks for it
+                     "limited_by": limited_by,
+                     "algorithmic_bytes_per_agent": kbytes, "kernel_ms": kms, "per_kernel": per_kernel,
+                     "traffic_detail": traffic_detail},
+        "valu": valu,
+        "kernels_ms": dict({k: round(v, 5) for k, v in kms_of.items()}, sum=round(sum(kms_of.values()), 5),
+                           wall_per_step=dt / args.steps * 1e3,
+                           sampled_launches={k: v[0] for k, v in ktimes.items() if v[0] > 0},
+                           note="mean duration of the SAMPLED launches (start / stop events on their own dispatch: such a launch is "
+                                "serialised against its neighbours); unsampled launches overlap their ramp-up and drain with the "
+                                "neighbouring kernels by a few tenths of a microsecond, so wall_per_step may lie slightly below the sum"),
+    }
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -336,20 +467,20 @@ def main():
                                    obstacles="scenario" if args.variant == "walls" else [])
     gen = torch.Generator(device="cuda").manual_seed(1234 + job_rank)
     pool = (torch.rand((16, A, N), device="cuda", generator=gen) - 0.5)  # actions in [-0.5, 0.5] rad
-    full = args.mode == "step"
+    full_step = args.mode == "step"
     alan_mode = args.mode == "alan"
     if alan_mode:
         from collision_avoidance_amd import alan as _alan
         env.alan_configure(_alan.DEFAULT_ACTIONS)
 
-    chunk = 1 if full else max(1, args.rollout_chunk)
+    chunk = 1 if full_step else max(1, args.rollout_chunk)
     if args.steps % chunk or args.warmup % chunk:
         raise SystemExit("bench.py: --steps and --warmup must be multiples of --rollout-chunk (%d)" % chunk)
     lanes_per_agent = env.launch_info()["lanes_per_agent"]
     steps_per_launch = chunk if (chunk > 1 and env.launch_info()["rollout_one_launch"]) else 1   # (else ca_rollout is a loop of launches)
 
     def one_step(i):  # the production call: one ca_step (neighbours -> ORCA solve -> observation) ...
-        if full:
+        if full_step:
             env._call("ca_step", env.h, pool[i % 16].data_ptr(), _lib.F_STATS | _lib.F_OBS)
         elif alan_mode:
             if i % chunk == 0:   # run_sim(mode=1) without the break: `chunk` online steps per call
@@ -359,26 +490,39 @@ def main():
         elif i % chunk == 0:   # ... or one ca_rollout per `chunk` steps of an ORCA-only policy rollout
             env._call("ca_rollout", env.h, chunk, _lib.F_STATS)
 
-    # warm-up: W steps, and on until MIN_WARM_SECONDS have passed (a 5-step warm-up leaves the clocks cold:
-    # round 1's driver run read 84 us per kernel where a settled chip reads 78)
+    # warm-up: max(W, SETTLE_STEPS) steps (the settled crowd), and the chip busy for at least MIN_WARM_SECONDS (a 5-step warm-up
+    # leaves the clocks cold: round 1's driver run read 84 us per kernel where a settled chip reads 78).  Steps that only keep the
+    # clocks busy run from a snapshot of the state that is restored afterwards, before the last 50 launches of the warm-up: the
+    # timed region starts from the state after exactly warm_run steps, so the same arguments give the same inputs in every run.
+    warm_run = max(args.warmup, -(-SETTLE_STEPS // chunk) * chunk)
+    tail = min(warm_run, 50 * chunk)
+    clock_steps = 0                   # steps run from the snapshot and discarded
     tw = time.perf_counter()
-    for i in range(args.warmup):
+    for i in range(warm_run - tail):
         one_step(i)
     torch.cuda.synchronize()
-    warm_run = args.warmup
-    while time.perf_counter() - tw < MIN_WARM_SECONDS:
-        for i in range(50 * chunk):
-            one_step(warm_run + i)
-        warm_run += 50 * chunk
-        torch.cuda.synchronize()
+    if time.perf_counter() - tw < MIN_WARM_SECONDS:
+        snapshot = env.get_state()
+        i = warm_run - tail
+        while time.perf_counter() - tw < MIN_WARM_SECONDS:
+            for _ in range(50 * chunk):
+                one_step(i)
+                i += 1
+            torch.cuda.synchronize()
+        clock_steps = i - (warm_run - tail)
+        env.set_state(snapshot)
+    for i in range(warm_run - tail, warm_run):
+        one_step(i)
+    torch.cuda.synchronize()
     env.reset_stats()
-    # The kernel launches of every 32nd step of the timed region (short runs: every (steps // 2)-th) carry a start and a stop event on
-    # their own dispatch (hipExtLaunchKernel inside the library, on the stream the kernels run on).  A sampled step costs ~10 us of
-    # dispatch serialisation (measured, round 5: sampling every step 119 us per step, every 8th 110.4, every 64th 109.3), so the
-    # default run brackets 62 of its 2000 steps (0.3 % of the region) and the driver's --steps 20 two (0.9 %).
-    # CA_BENCH_PROFILE_PERIOD overrides the period (diagnostic).
-    env.profile(int(os.environ["CA_BENCH_PROFILE_PERIOD"]) if "CA_BENCH_PROFILE_PERIOD" in os.environ else
-                (1 if steps_per_launch > 1 else max(1, min(32, args.steps // 2))))
+    if args.full:
+        # The kernel launches of every 32nd step of the timed region (short runs: every (steps // 2)-th) carry a start and a stop event on
+        # their own dispatch (hipExtLaunchKernel inside the library, on the stream the kernels run on).  A sampled step costs ~10 us of
+        # dispatch serialisation (measured, round 5: sampling every step 119 us per step, every 8th 110.4, every 64th 109.3), so the
+        # default run brackets 62 of its 2000 steps (0.3 % of the region) and the driver's --steps 20 two (0.9 %).
+        # CA_BENCH_PROFILE_PERIOD overrides the period (diagnostic).
+        env.profile(int(os.environ["CA_BENCH_PROFILE_PERIOD"]) if "CA_BENCH_PROFILE_PERIOD" in os.environ else
+                    (1 if steps_per_launch > 1 else max(1, min(32, args.steps // 2))))
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -392,12 +536,16 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    ktimes = env.profile_read()
-    env.profile(0)
+    ktimes = None
+    if args.full:
+        ktimes = env.profile_read()
+        env.profile(0)
     st = env.stats()
+    if args.dump_outputs:
+        dump_outputs(env, args.mode, args.dump_outputs, "" if world == 1 else "_rank%d" % rank, DUMP_MAX_BYTES // world)
     steps_run = warm_run + args.steps      # every step this environment has been advanced since its scenario was drawn
     per_step_calls = None
-    if not full and not alan_mode and chunk > 1:   # the same ORCA-only workload through one ca_orca_step call per step, for comparison
+    if args.full and not full_step and not alan_mode and chunk > 1:   # the same ORCA-only workload through one ca_orca_step call per step, for comparison
         torch.cuda.synchronize()
         n2 = max(chunk, min(args.steps, 500))
         t1 = time.perf_counter()
@@ -430,79 +578,16 @@ def main():
     if rank == 0:
         agents = A * N
         value = world * agents * args.steps / dt
-        kbytes_of = {"nbr_kernel": 0, "step_kernel": BYTES_STEP_KERNEL_FULL if full else BYTES_STEP_KERNEL_ORCA,
-                     "obs_kernel": BYTES_OBS_KERNEL}
-        kms_of = {k: v[1] for k, v in ktimes.items() if v[0] > 0 and k in kbytes_of}   # (a T-step launch is reported per step)
-        # dominant kernel: strictly the longest average launch (no tie-break)
-        dom = max(kms_of, key=lambda k: kms_of[k])
-        kms, kbytes = kms_of[dom], kbytes_of[dom]
-        achieved = agents * kbytes / (kms * 1e-3) / 1e9
-        per_kernel = {k: {"ms": round(v, 5), "algorithmic_bytes_per_agent": kbytes_of[k],
-                          "algorithmic_GB_per_s": agents * kbytes_of[k] / (v * 1e-3) / 1e9,
-                          "frac": agents * kbytes_of[k] / (v * 1e-3) / 1e9 / HBM_PEAK_GBS}
-                      for k, v in kms_of.items()}
-        cj, csrc = counters_for(args.workload, args.mode, args.variant, args.starts, kms_of)
-        traffic, traffic_low, traffic_high, traffic_detail, valu = None, None, None, {"source": csrc}, None
-        if cj is not None:
-            kk = cj.get("kernels", {})
-            if dom in kk and "hbm_bytes_high" in kk[dom]:
-                # FETCH_SIZE on gfx950 tallies the 128-B requests of wide reads at 64 B: the true figure lies between the
-                # reported one (low) and the one with FETCH doubled (high); `traffic` quotes the conservative high end
-                traffic_low, traffic_high = kk[dom].get("hbm_bytes_low"), kk[dom]["hbm_bytes_high"]
-                traffic = traffic_high
-            traffic_detail = {"source": csrc, "src_sha": cj.get("src_sha"),
-                              "per_kernel": {k: {x: kk[k].get(x) for x in ("FETCH_SIZE_KB", "WRITE_SIZE_KB", "hbm_bytes_low",
-                                                                           "hbm_bytes_high", "algorithmic_bytes")}
-                                             for k in kms_of if k in kk}}
-            try:  # vector-ALU view: wave-level VALU instructions per launch x 64 lanes over the live kernel times
-                cnt = {k: float(kk[k]["SQ_INSTS_VALU"]) for k in kms_of}
-                lane_ops = 64.0 * sum(cnt.values())
-                tsum = sum(kms_of.values()) * 1e-3
-
-                def issue_cycles(c, cheap_other):
-                    """Vector-issue cycles of one launch from the instruction-class counters and the measured issue
-                    cost of each class on gfx950 (profiles/r02_valu_issue_rates_microbench.txt): v_add / v_mul_f32 2.7,
-                    v_fma_f32 3.9, transcendental 8.3, conversions / 64-bit integer 4.2; 32-bit integer and the rest
-                    (compares, selects, moves, min / max, DPP ...) between 2.7 (and, add, mov) and 4.2 (the others):
-                    `cheap_other` picks the end of that range."""
-                    known = ("SQ_INSTS_VALU_ADD_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_TRANS_F32",
-                             "SQ_INSTS_VALU_INT32", "SQ_INSTS_VALU_INT64", "SQ_INSTS_VALU_CVT")
-                    if not all(x in c for x in known):
-                        return float(c["SQ_INSTS_VALU"]) * ISSUE_CYCLES_PER_VALU
-                    other = float(c["SQ_INSTS_VALU"]) - sum(float(c[x]) for x in known)
-                    flex = 2.7 if cheap_other else 4.2
-                    return ((float(c["SQ_INSTS_VALU_ADD_F32"]) + float(c["SQ_INSTS_VALU_MUL_F32"])) * 2.7 +
-                            float(c["SQ_INSTS_VALU_FMA_F32"]) * 3.9 + float(c["SQ_INSTS_VALU_TRANS_F32"]) * 8.3 +
-                            (float(c["SQ_INSTS_VALU_INT64"]) + float(c["SQ_INSTS_VALU_CVT"])) * 4.2 +
-                            (float(c["SQ_INSTS_VALU_INT32"]) + max(0.0, other)) * flex)
-                bound_hi = {k: issue_cycles(kk[k], False) / N_SIMDS / CLOCK_HZ * 1e3 for k in kms_of}
-                bound_lo = {k: issue_cycles(kk[k], True) / N_SIMDS / CLOCK_HZ * 1e3 for k in kms_of}
-                valu = {"wave_insts_per_step": cnt, "lane_ops_per_s": lane_ops / tsum,
-                        "peak_lane_ops_per_s": VALU_PEAK_LANE_OPS, "frac": lane_ops / tsum / VALU_PEAK_LANE_OPS,
-                        "per_kernel_frac": {k: 64.0 * cnt[k] / (kms_of[k] * 1e-3) / VALU_PEAK_LANE_OPS for k in kms_of},
-                        # the bound that matters: every vector instruction of the launch issued back to back on its SIMD,
-                        # priced per instruction class; [low, high] for the classes whose members differ in cost
-                        "issue_bound_ms": bound_hi, "issue_bound_ms_low": bound_lo,
-                        "frac_of_issue_bound": {k: bound_hi[k] / kms_of[k] for k in kms_of},
-                        "frac_of_issue_bound_low": {k: bound_lo[k] / kms_of[k] for k in kms_of},
-                        "source": "%s (SQ_INSTS_VALU and instruction-class counters per launch, same kernel sources and flags) "
-                                  "over the live kernel times" % csrc}
-            except Exception:
-                valu = None
-        limited_by = None
-        if valu is not None and traffic is not None:
-            hbm_frac = traffic / (kms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            limited_by = "valu-issue" if valu["frac_of_issue_bound_low"][dom] > hbm_frac else "hbm"
         out = {
             "metric": "agent-steps/sec (whole node), %d arenas x %d agents per GPU" % (A, N),
             "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "warmup_steps_run": warm_run, "ms_per_step": dt / args.steps * 1e3,
+            "warmup": args.warmup, "warmup_steps_run": warm_run, "warmup_clock_steps": clock_steps, "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("%s: %d arenas x %d agents per GPU, " + ("random start/goal crowd (ALAN recipe), " if scn.startswith("crowd") else "ALAN '" + scn + "' scenario, ") +
                                     "neighborDist %.1f, maxNeighbors %d, %s, %s, %s starts") %
                                    (args.workload, A, N, w["neighbor_dist"], w["max_neighbors"],
-                                    "full env step (action -> ORCA -> reward/done -> laser obs)" if full
+                                    "full env step (action -> ORCA -> reward/done -> laser obs)" if full_step
                                     else ("ALAN online step (softmax draw -> ORCA -> bandit update; no observation)" if alan_mode
                                           else "ORCA-only step (no observation)"),
                                     "boundary walls" if args.variant == "walls" else "obstacle-free", args.starts),
@@ -517,25 +602,9 @@ def main():
             # slowest rank's own rate over the fastest's (1.0 = no straggler); from the per-rank times of the ONE all_gather
             "efficiency": (min(d["agent_steps"] / max(1, d["own_ns"]) for d in per_rank_stats) /
                            max(d["agent_steps"] / max(1, d["own_ns"]) for d in per_rank_stats)),
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_low": traffic_low, "traffic_high": traffic_high,
-                         # what the COUNTERS of this build say limits the dominant kernel: its vector-issue time (see `valu`)
-                         # against the time its measured HBM traffic needs at the peak; null without a counter profile of
-                         # these sources -- the HBM fraction above is reported because the metric asks for it
-                         "limited_by": limited_by,
-                         "algorithmic_bytes_per_agent": kbytes, "kernel_ms": kms, "per_kernel": per_kernel,
-                         "traffic_detail": traffic_detail},
-            "valu": valu,
-            "kernels_ms": dict({k: round(v, 5) for k, v in kms_of.items()}, sum=round(sum(kms_of.values()), 5),
-                               wall_per_step=dt / args.steps * 1e3,
-                               sampled_launches={k: v[0] for k, v in ktimes.items() if v[0] > 0},
-                               note="mean duration of the SAMPLED launches (start / stop events on their own dispatch: such a launch is "
-                                    "serialised against its neighbours); unsampled launches overlap their ramp-up and drain with the "
-                                    "neighbouring kernels by a few tenths of a microsecond, so wall_per_step may lie slightly below the sum"),
-            "full_step_algorithmic": {"bytes_per_agent": 316 if full else 52,
-                                      "GB_per_s": agents * (316 if full else 52) / (dt / args.steps) / 1e9,
-                                      "frac": agents * (316 if full else 52) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
+            "full_step_algorithmic": {"bytes_per_agent": 316 if full_step else 52,
+                                      "GB_per_s": agents * (316 if full_step else 52) / (dt / args.steps) / 1e9,
+                                      "frac": agents * (316 if full_step else 52) / (dt / args.steps) / 1e9 / HBM_PEAK_GBS},
             "stats": {k: total_stats[k] for k in cad.STAT_KEYS},
             "launch": env.launch_info(),
             "src_sha": _b.loaded_sha(),      # compiled into the library that ran (ca_source_sha)
@@ -544,6 +613,8 @@ def main():
             "collectives": {"data_path": 0, "job": "one all_gather of the per-rank record (statistics, device, dt)",
                             "timing_barriers": 2 if dist is not None else 0},
         }
+        if args.full:
+            out.update(kernel_figures(ktimes, agents, full_step, dt, args))
         if verified is not None:      # rank 0's own record + the verdict of every rank (folded into the one all_gather)
             out["verified"] = dict(verified, bit_exact=all(d["verified"] == 1 for d in per_rank_stats),
                                    ranks_verified=sum(1 for d in per_rank_stats if d["verified"] == 1))
@@ -555,7 +626,7 @@ def main():
         if sum(d["agent_steps"] for d in per_rank_stats) != world * agents * args.steps:
             raise SystemExit("bench.py: the ranks report %d agent-steps, expected %d" %
                              (sum(d["agent_steps"] for d in per_rank_stats), world * agents * args.steps))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, args.mode, args.cpu_seconds, args.variant, args.starts)
             try:   # the reference's OWN Python loop cannot run on this box (it never travels): quote the committed measurement
                 j = json.load(open(os.path.join(ROOT, "profiles", "r05_reference_python_loop.json")))

@@ -23,9 +23,10 @@ def _bench(extra, env_extra, workload=("--workload", "C2")):
     env = dict(os.environ)
     env.update(env_extra)
     env["CA_BENCH_MIN_WARM"] = "0"      # exactly --warmup steps: the runs below must start the timed region in the same state
+    env["CA_BENCH_SETTLE_STEPS"] = "0"
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + list(workload) + ["--steps", str(STEPS), "--warmup", str(WARM),
-                                                                              "--no-cpu-baseline"] + extra
+                                                                              "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

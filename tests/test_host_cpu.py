@@ -213,3 +213,34 @@ def test_bench_verify_checker_logic():
     assert not bad["bit_exact"] and bad["mismatch"].startswith("POS_X: 1 of"), bad
     off = bench.verify_against_oracle(_FakeGpu(A, N, "crowd", p, pool, warm, timed), args, w, p, "crowd", 0, pool, warm + timed + 1, timed)
     assert not off["bit_exact"]                                    # one step more or less is a mismatch too
+
+
+def test_bench_dump_outputs_cap_and_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, within the byte cap, and when the cap forces a sample, the same
+    seeded arenas in every array (each array here holds its arena index, so a misaligned sample shows)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from collision_avoidance_amd.vec_env import VecCollisionAvoidanceEnv
+
+    class _Env(object):
+        A, N, K, S, n_actions = 300, 16, 5, 4, 8
+
+        def get(self, field):
+            shape, dt = VecCollisionAvoidanceEnv._shape_dtype(self, field)
+            if field in (_lib.FLD_ALAN_WEIGHTS, _lib.FLD_ALAN_TIMES):
+                shape = (self.A, self.N, self.n_actions)     # get() hands these out as [A, N, n_actions]
+            return np.broadcast_to(np.arange(self.A).reshape((-1,) + (1,) * (len(shape) - 1)), shape).astype(dt)
+
+    for mode, cap, keep in (("step", 1 << 30, 300), ("step", 1 << 20, None), ("alan", 200000, None), ("orca", 1 << 30, 300)):
+        out = tmp_path / ("%s_%d" % (mode, cap))
+        bench.dump_outputs(_Env(), mode, str(out), max_bytes=cap)
+        files = sorted(out.iterdir())
+        assert sum(f.stat().st_size for f in files) <= cap + 256 * len(files)       # (+ the .npy headers)
+        arrays = {f.name: np.load(str(f)) for f in files}
+        assert "obs.npy" in arrays if mode == "step" else "alan_weights.npy" in arrays if mode == "alan" else len(arrays) == 6
+        first = arrays["pos_x.npy"][:, 0]
+        assert keep is None or len(first) == keep
+        assert 0 < len(first) <= 300 and np.all(np.diff(first) > 0)
+        for name, a in arrays.items():
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            assert np.array_equal(a.reshape(len(a), -1)[:, 0], first), name

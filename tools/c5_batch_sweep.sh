@@ -9,7 +9,7 @@ echo "# C5 batch sweep: bench.py --workload C5 --arenas A (512 agents per arena)
 echo "# arenas mode    G agent-steps/s   ms/step   kernels_ms   verified" >> $OUT
 for A in 128 256 512 1024 2048; do
   for M in step orca; do
-    timeout -k 10 300 python3 $R/bench.py --workload C5 --arenas $A --mode $M --no-cpu-baseline --steps 1000 --warmup 100 > $O/c5_${A}_$M.json 2>> $O/err.txt || { tail $O/err.txt; exit 1; }
+    timeout -k 10 300 python3 $R/bench.py --full --workload C5 --arenas $A --mode $M --no-cpu-baseline --steps 1000 --warmup 100 > $O/c5_${A}_$M.json 2>> $O/err.txt || { tail $O/err.txt; exit 1; }
     python3 -c "
 import json;d=json.load(open('$O/c5_${A}_$M.json'))
 print('%6d %-5s %8.3f G  %8.4f ms  %s  verified=%s' % ($A,'$M',d['value']/1e9,d['ms_per_step'],{k:round(v,4) for k,v in d['kernels_ms'].items() if isinstance(v,float)},d['verified']['bit_exact']))" | tee -a $OUT

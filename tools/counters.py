@@ -51,7 +51,7 @@ def main():
     step_bytes = 60 if mode == "step" else 52
     alg = {"nbr_kernel": 0, "step_kernel": step_bytes * A * N, "obs_kernel": 256 * A * N, "lp3_kernel": 0}
     out = {"src_sha": b.loaded_sha(), "workload": workload, "mode": mode,
-           "note": "rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_*) of `python3 bench.py --workload %s --mode %s "
+           "note": "rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_*) of `python3 bench.py --full --workload %s --mode %s "
                    "--steps 20 --warmup 5 --no-cpu-baseline`; means over the launches of a pass; KB per launch; "
                    "hbm_bytes_low uses FETCH_SIZE as reported, hbm_bytes_high doubles it (gfx950 tallies the 128-B "
                    "requests of wide coalesced reads at 64 B). %s" % (workload, mode, " ".join(sys.argv[9:])),

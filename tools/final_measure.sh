@@ -9,7 +9,7 @@ TAG=$1; PART=$2
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 if [ "$PART" = 1 ]; then
   $B > $O/bench_C3_step.json 2> $O/err.txt || exit 1
   $B --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_C3_step_driver_like_20_steps.json 2>> $O/err.txt || exit 1
@@ -27,7 +27,7 @@ if [ "$PART" = 1 ]; then
 fi
 if [ "$PART" = 2 ]; then
   rm -rf $O/trace_C3
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_C3 -o trace -- python3 $R/bench.py --no-cpu-baseline --steps 2000 --warmup 200 > $O/trace_C3.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_C3 -o trace -- python3 $R/bench.py --full --no-cpu-baseline --steps 2000 --warmup 200 > $O/trace_C3.log 2>&1 || exit 1
   python3 $R/tools/settled_kernel_stats.py $O/trace_C3 500 > $O/kernel_stats_rocprofv3_settled.csv || exit 1
   cp $(find $O/trace_C3 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_rocprofv3_all_launches.csv
   rm -rf $O/trace_C3
@@ -37,7 +37,7 @@ if [ "$PART" = 3 ]; then PART=pmc; WL="C5 C2"; fi
 if [ "$PART" = pmc ]; then
   for W in $WL; do
     case $W in C3) A=4096; N=64;; C5) A=256; N=512;; C2) A=1024; N=16;; esac
-    CMD="python3 $R/bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline"
+    CMD="python3 $R/bench.py --full --workload $W --steps 20 --warmup 5 --no-cpu-baseline"
     rm -rf $O/pmc_$W; mkdir -p $O/pmc_$W
     rocprofv3 --output-format csv --pmc FETCH_SIZE -d $O/pmc_$W/fetch -- $CMD > $O/pmc_$W/fetch.log 2>&1 || exit 1
     rocprofv3 --output-format csv --pmc WRITE_SIZE -d $O/pmc_$W/write -- $CMD > $O/pmc_$W/write.log 2>&1 || exit 1

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; T=${1:-s}; O=$R/gpurun_out/$T; mkdir -p $O; cd
 timeout -k 10 1000 python3 -m pytest $R/tests -m gpu -q > $O/gpu_tests.log 2>&1; rc=$?
 grep -E "^(FAILED|ERROR)|passed|failed" $O/gpu_tests.log | tail -40
 if [ "$2" = bench ]; then
-  B="python3 $R/bench.py --no-cpu-baseline"
+  B="python3 $R/bench.py --full --no-cpu-baseline"
   timeout -k 10 300 $B > $O/bench_C3_step.json 2> $O/err.txt || { tail $O/err.txt; exit 1; }
   timeout -k 10 300 $B --mode orca > $O/bench_C3_orca.json 2>> $O/err.txt || { tail $O/err.txt; exit 1; }
   for W in C2 C5; do timeout -k 10 300 $B --workload $W > $O/bench_$W.json 2>> $O/err.txt || { tail $O/err.txt; exit 1; }; done
