@@ -24,7 +24,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_get_stats", "ca_reset_stats", "ca_sync", "ca_debug_math", "ca_profile", "ca_profile_read", "ca_launch_info",
            "ca_alan_configure", "ca_alan_step", "ca_alan_rollout", "ca_reset_masked", "ca_get_obstacles",
            "ca_set_obstacles_per_arena", "ca_get_obstacles_arena", "ca_solver_info", "ca_source_sha", "ca_host_alloc", "ca_host_free",
-           "ca_step_packed", "ca_allow_obstacle_overflow")
+           "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena")
 
 
 class Config(C.Structure):
@@ -95,6 +95,8 @@ def load():
     L.ca_observe.argtypes = [vp]
     L.ca_rollout.argtypes = [vp, i32, u32]
     L.ca_alan_configure.argtypes = [vp, vp, i32, C.c_double, C.c_double, C.c_double]
+    L.ca_alan_configure_per_arena.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double]
+    L.ca_alan_actions_arena.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.ca_alan_step.argtypes = [vp, vp, i32, u32]
     L.ca_alan_rollout.argtypes = [vp, i32, u32]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]

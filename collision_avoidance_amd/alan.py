@@ -37,12 +37,14 @@ class Collision_Avoidance_Sim(object):
     """Same constructor and run_sim()/reset() contract as ALAN_true.py:10-131 (no Tk window).
 
     n_arenas > 1 runs that many independent episodes of the scenario side by side (arena g of a handle
-    is keyed by (seed, g)); run_sim() then returns arrays with one entry per arena."""
+    is keyed by (seed, g)); run_sim() then returns arrays with one entry per arena.  arena_actions (a list of
+    n_arenas action sets) gives every arena a set of its own -- what alan_train.MCMC_trainer evaluates its
+    chains' proposals with."""
 
     POLL = 256   # steps enqueued between two looks at the arena_done flags
 
     def __init__(self, numAgents=50, scenario="crowd", online_actions=None, visualize=False, device=0, seed=0,
-                 n_arenas=1):
+                 n_arenas=1, arena_actions=None):
         self.numAgents, self.scenario = numAgents, scenario
         self.timeStep, self.maxSpeed, self.radius = 1 / 60., 1, 0.5
         self.gamma, self.timewindow, self.online_temp = 0.6, 2, 0.2                # ALAN_true.py:47-49
@@ -51,12 +53,17 @@ class Collision_Avoidance_Sim(object):
         self._device, self._seed, self.n_arenas = device, seed, int(n_arenas)
         self._resets = 0
         self.vec = None
-        self.reset(online_actions)
+        self.reset(online_actions, arena_actions)
 
-    def reset(self, online_actions=None):
+    def reset(self, online_actions=None, arena_actions=None):
+        """A new random world (ALAN_true.py:133-139).  online_actions: one set for every arena (None: the default
+        eight); arena_actions: a list of n_arenas sets, one per arena (it takes precedence over online_actions)."""
         from . import _lib
         from .vec_env import VecCollisionAvoidanceEnv
+        if arena_actions is not None and len(arena_actions) != self.n_arenas:
+            raise ValueError("reset: %d arena action sets for %d arenas" % (len(arena_actions), self.n_arenas))
         self.online_actions = self.default_online_actions if online_actions is None else list(online_actions)
+        self.arena_actions = None if arena_actions is None else [list(a) for a in arena_actions]
         if self.vec is not None:
             self.vec.close()
         p = scenarios.alan_params(self.numAgents, self.scenario)
@@ -67,7 +74,10 @@ class Collision_Avoidance_Sim(object):
                                             device=self._device, seed=self._seed, use_torch=False,
                                             arena_offset=self._resets * self.n_arenas)
         self._resets += 1
-        self.vec.alan_configure(self.online_actions, self.online_temp, self.timewindow, self.timeStep)
+        if self.arena_actions is not None:
+            self.vec.alan_configure_per_arena(self.arena_actions, self.online_temp, self.timewindow, self.timeStep)
+        else:
+            self.vec.alan_configure(self.online_actions, self.online_temp, self.timewindow, self.timeStep)
         self.step_count, self.TTime = 0, 0
         start = np.stack([self.vec.get(_lib.FLD_POS_X), self.vec.get(_lib.FLD_POS_Y)], -1)
         goal = np.stack([self.vec.get(_lib.FLD_GOAL_X), self.vec.get(_lib.FLD_GOAL_Y)], -1)

@@ -25,10 +25,12 @@ struct AlanArgs {
     const int *step_count, *arena_done, *episode;
     unsigned long long* arena_stats;
     double act_c[ALAN_MAX_ACTIONS], act_s[ALAN_MAX_ACTIONS];  // (cos, sin) of every action's angle
+    const double2* tab;   // per-arena sets: [A][ALAN_MAX_ACTIONS] (cos, sin) and [A] counts (ca_common.h alan_count / alan_cs)
+    const int* tab_n;
     double temp, window, dt, reward_scale;
     uint64_t seed;
     int64_t arena_offset;
-    int A, N, nA;
+    int A, N, nA;         // nA: the stride of w / t (per-arena sets: the largest)
     uint32_t flags;
 };
 
@@ -52,11 +54,13 @@ __device__ __forceinline__ double np_sum(int n, Get get) {
     return res;
 }
 
+// ALAN = 1: one action set for the handle; 2: a set per arena (the loops run over the arena's own count, stride nA)
+template <int ALAN>
 __global__ __launch_bounds__(ALAN_BS) void alan_select_kernel(const AlanArgs p) {
     extern __shared__ double s_ps[];  // [n_actions][lane]: sized by the launch (8 B x n_actions x ALAN_BS)
     const int q = blockIdx.x * ALAN_BS + threadIdx.x;
     if (q >= p.A * p.N) return;
-    const int a = q / p.N, i = q - a * p.N, nA = p.nA;
+    const int a = q / p.N, i = q - a * p.N, nA = p.nA, nk = alan_count<ALAN>(p, a);
     if ((p.flags & 16u) && p.arena_done[a] != 0) {  // CA_F_FREEZE: tell the update kernel, keep the last action
         p.action[q] = ~p.action[q];
         return;
@@ -64,10 +68,10 @@ __global__ __launch_bounds__(ALAN_BS) void alan_select_kernel(const AlanArgs p) 
     double* ps = s_ps + threadIdx.x;
     // weights and times are stored [A][n_actions][N]: the lanes of a wave read consecutive doubles
     const double* w = p.w + (size_t)a * nA * p.N + i;
-    for (int k = 0; k < nA; ++k) ps[k * ALAN_BS] = exp64(w[(size_t)k * p.N] / p.temp);  // ALAN:580-581
-    const double sum = np_sum(nA, [&](int k) { return ps[k * ALAN_BS]; });
+    for (int k = 0; k < nk; ++k) ps[k * ALAN_BS] = exp64(w[(size_t)k * p.N] / p.temp);  // ALAN:580-581
+    const double sum = np_sum(nk, [&](int k) { return ps[k * ALAN_BS]; });
     double acc = 0.0;
-    for (int k = 0; k < nA; ++k) {                                                 // ALAN:582
+    for (int k = 0; k < nk; ++k) {                                                 // ALAN:582
         const double v = ps[k * ALAN_BS] / sum;
         ps[k * ALAN_BS] = v;
         acc += v;
@@ -79,23 +83,25 @@ __global__ __launch_bounds__(ALAN_BS) void alan_select_kernel(const AlanArgs p) 
         double u1;
         rng2(p.seed, p.arena_offset + a, i, RNG_ALAN + (p.episode[a] << 8), (uint32_t)p.step_count[a], &ui, &u1);
     }
-    int id = nA - 1;
+    int id = nk - 1;
     double run = 0.0;
     bool found = false;
-    for (int k = 0; k < nA - 1; ++k) {
+    for (int k = 0; k < nk - 1; ++k) {
         run += ps[k * ALAN_BS];
         if (!found && run / acc > ui) { id = k; found = true; }
     }
     p.action[q] = id;
     double gx, gy;
     pref_dir64(p.pos_x[q], p.pos_y[q], p.goal_x[q], p.goal_y[q], &gx, &gy);        // ALAN:588
-    const double cs = p.act_c[id], sn = p.act_s[id];                                // ALAN:592-595
+    double cs, sn;
+    alan_cs<ALAN>(p, a, id, &cs, &sn);                                               // ALAN:592-595
     const double lx = gx * cs - gy * sn, ly = gx * sn + gy * cs;
     const size_t an = (size_t)p.A * p.N;  // dirs: [4][A*N]
     p.dirs[q] = gx; p.dirs[an + q] = gy; p.dirs[2 * an + q] = lx; p.dirs[3 * an + q] = ly;
     p.pref_x[q] = (float)lx; p.pref_y[q] = (float)ly;                               // ALAN:598
 }
 
+template <int ALAN>
 __global__ __launch_bounds__(ALAN_BS) void alan_update_kernel(const AlanArgs p) {
     const int q = blockIdx.x * ALAN_BS + threadIdx.x;
     if (q >= p.A * p.N) return;
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(ALAN_BS) void alan_update_kernel(const AlanArgs p) 
         p.action[q] = ~id;
         return;
     }
-    const int a = q / p.N, nA = p.nA;
+    const int a = q / p.N, nA = p.nA, nk = alan_count<ALAN>(p, a);
     const size_t an = (size_t)p.A * p.N;
     const double d[4] = {p.dirs[q], p.dirs[an + q], p.dirs[2 * an + q], p.dirs[3 * an + q]};
     const float vxf = p.vel_x[q], vyf = p.vel_y[q];
@@ -131,7 +137,7 @@ __global__ __launch_bounds__(ALAN_BS) void alan_update_kernel(const AlanArgs p) 
     const int i = q - a * p.N;
     double* w = p.w + (size_t)a * nA * p.N + i;
     double* t = p.t + (size_t)a * nA * p.N + i;
-    for (int k = 0; k < nA; ++k) {                                                  // ALAN:616-628
+    for (int k = 0; k < nk; ++k) {                                                  // ALAN:616-628
         double tk = t[(size_t)k * p.N] + p.dt;
         double wk = w[(size_t)k * p.N];
         if (tk >= p.window) { tk = 0.0; wk = 0.0; }

@@ -4,6 +4,10 @@
 #include "ca_math.h"
 #include <utility>
 
+// Tag of the kernels' per-arena-action-set instantiations (step_kernel / quad_kernel <..., true, AlanArenaSets>).  Declared
+// outside the namespace so that the instantiations' names read like the others' (tools/kernel_resources.py).
+struct AlanArenaSets;
+
 namespace ca {
 
 constexpr int SMAX = 16;      // CA_MAX_OBST_NEIGHBORS (LDS line table; the register-line and quad kernels hold 4)
@@ -59,8 +63,28 @@ struct AlanCold {
     float* reward;          // [A*N]
     double act_c[32], act_s[32];  // (cos, sin) of every action's angle
     double temp, window, dt, reward_scale;
-    int nA;
+    const double2* tab;     // per-arena sets (ca_alan_configure_per_arena): [A][32] (cos, sin) of arena a's actions; else null
+    const int* tab_n;       // [A] actions of arena a (at most nA, which stays the stride of w / t); else null
+    int nA;                 // one set: its size; per-arena sets: the largest
 };
+
+// The action set of arena a.  ALAN = 1: one set for the whole handle -- act_c / act_s and nA, scalar loads, loops of one
+// trip count per wave.  ALAN = 2: a set per arena -- the arena index is not wave-uniform (small arenas share a wave, the
+// four-lanes kernel packs several per workgroup), so count and (cos, sin) are per-lane global loads of the L2-resident table.
+template <int ALAN, class AL>
+__device__ __forceinline__ int alan_count(const AL& al, int a) {
+    if constexpr (ALAN == 2) return al.tab_n[a];
+    else return al.nA;
+}
+template <int ALAN, class AL>
+__device__ __forceinline__ void alan_cs(const AL& al, int a, int id, double* cs, double* sn) {
+    if constexpr (ALAN == 2) {
+        const double2 v = al.tab[(size_t)a * 32 + id];
+        *cs = v.x; *sn = v.y;
+    } else {
+        *cs = al.act_c[id]; *sn = al.act_s[id];
+    }
+}
 
 struct StepArgs {
     const float *pos_x, *pos_y, *vel_x, *vel_y, *pref_x, *pref_y;

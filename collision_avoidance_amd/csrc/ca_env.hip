@@ -57,8 +57,15 @@ struct ca_env {
     bool alan_lane = false;       // ca_alan_step runs as ONE launch of the register-line lane kernel (its ALAN instantiation)   // the bandit's arguments for the four-lanes kernel (ca_common.h)
     int* mask_buf = nullptr;  // staging for ca_reset_masked's host mask
     std::vector<std::pair<void*, size_t>> host_allocs;   // page-locked host buffers handed out by ca_host_alloc (freed by ca_host_free / ca_destroy)
-    int n_actions = 0;
+    int n_actions = 0;   // one set: its size; per-arena sets: the largest (the stride of alan_w / alan_t)
     double act_c[CA_ALAN_MAX_ACTIONS], act_s[CA_ALAN_MAX_ACTIONS];
+    // per-arena sets (ca_alan_configure_per_arena): [A][CA_ALAN_MAX_ACTIONS] (cos, sin) and [A] counts, on the device and a
+    // host copy for ca_alan_actions_arena; alan_per selects the kernels' ALAN = 2 instantiations
+    bool alan_per = false;
+    double2* d_act_tab = nullptr;
+    int* d_act_n = nullptr;
+    std::vector<double> h_act_tab;
+    std::vector<int> h_act_n;
     double alan_temp = 0.2, alan_window = 2.0, alan_dt = 1.0 / 60.0;
     ObstDev* d_obst = nullptr;
     std::vector<ObstDev> h_obst;     // every table, concatenated
@@ -279,6 +286,23 @@ static void launch_nbr_k(ca_env* e, const StepArgs& a_in) {
         default: launch_k(ps, nbr_kernel<KMAX, 1024, SM>, grid, block, 0, e->stream, a); break;
     }
 }
+template <int KMAX, int ST, class... PER>
+static hipError_t launch_alan_lane(ca_env* e, ProfScope& ps, const StepArgs& a) {
+    const dim3 grid(e->grid), block(e->BS);
+    if constexpr (ST > 0) {
+        if (e->SMX > ST) {   // (obstacle-neighbour lists of up to 16: "congested", the doorway world)
+            if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, 16, true, PER...>, grid, block, e->lds, e->stream, a);
+            else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, 16, true, PER...>, grid, block, e->lds, e->stream, a);
+        } else {
+            if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, ST, true, PER...>, grid, block, e->lds, e->stream, a);
+            else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, ST, true, PER...>, grid, block, e->lds, e->stream, a);
+        }
+    } else {                 // (the LDS line table: "deadlock", "blocks")
+        if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, 0, true, 1, SMAX, true, PER...>, grid, block, e->lds, e->stream, a);
+        else launch_k(ps, step_kernel<KMAX, 128, 0, true, 1, SMAX, true, PER...>, grid, block, e->lds, e->stream, a);
+    }
+    return hipGetLastError();
+}
 template <int KMAX, int ST, bool FUSE>
 static hipError_t launch_step_kf(ca_env* e, const StepArgs& a) {
     if (!FUSE) launch_nbr_k<KMAX, (ST > 0 ? ST : SMAX)>(e, a);  // neighbour search as a launch of its own (diagnostic: CA_FUSE_NBR=0)
@@ -298,19 +322,8 @@ static hipError_t launch_step_kf(ca_env* e, const StepArgs& a) {
     }
     if constexpr (FUSE && KMAX <= 10) {
         if (a.alan != nullptr) {   // the ALAN bandit inside the launch (alan_pick allowed it: alan_lane)
-            if constexpr (ST > 0) {
-                if (e->SMX > ST) {   // (obstacle-neighbour lists of up to 16: "congested", the doorway world)
-                    if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, 16, true>, grid, block, e->lds, e->stream, a);
-                    else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, 16, true>, grid, block, e->lds, e->stream, a);
-                } else {
-                    if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, ST, true>, grid, block, e->lds, e->stream, a);
-                    else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, ST, true>, grid, block, e->lds, e->stream, a);
-                }
-            } else {                 // (the LDS line table: "deadlock", "blocks")
-                if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, 0, true, 1, SMAX, true>, grid, block, e->lds, e->stream, a);
-                else launch_k(ps, step_kernel<KMAX, 128, 0, true, 1, SMAX, true>, grid, block, e->lds, e->stream, a);
-            }
-            return hipGetLastError();
+            if (e->alan_per) return launch_alan_lane<KMAX, ST, AlanArenaSets>(e, ps, a);   // (a set per arena)
+            return launch_alan_lane<KMAX, ST>(e, ps, a);
         }
     }
     if constexpr (FUSE && ST > 0) {
@@ -341,16 +354,20 @@ static hipError_t launch_step_k(ca_env* e, const StepArgs& a) {
 #endif
     return launch_step_kf<KMAX, ST, true>(e, a);
 }
-template <int KMAX, int SQ, bool ALAN>
+template <int KMAX, int SQ, bool ALAN, class... PER>
 static const void* quad_fn_k(int BS) {
     switch (BS) {
-        case 64: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 64, SQ, ALAN>);
-        case 128: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 128, SQ, ALAN>);
-        case 256: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 256, SQ, ALAN>);
-        default: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 512, SQ, ALAN>);
+        case 64: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 64, SQ, ALAN, PER...>);
+        case 128: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 128, SQ, ALAN, PER...>);
+        case 256: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 256, SQ, ALAN, PER...>);
+        default: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 512, SQ, ALAN, PER...>);
     }
 }
 static const void* quad_fn(const ca_env* e, bool alan = false) {
+    if (alan && e->alan_per) {   // (a set per arena)
+        if (e->KT == 5) return e->SQ == 4 ? quad_fn_k<5, 4, true, AlanArenaSets>(e->BSq) : quad_fn_k<5, 16, true, AlanArenaSets>(e->BSq);
+        return e->SQ == 4 ? quad_fn_k<10, 4, true, AlanArenaSets>(e->BSq) : quad_fn_k<10, 16, true, AlanArenaSets>(e->BSq);
+    }
     if (alan) {
         if (e->KT == 5) return e->SQ == 4 ? quad_fn_k<5, 4, true>(e->BSq) : quad_fn_k<5, 16, true>(e->BSq);
         return e->SQ == 4 ? quad_fn_k<10, 4, true>(e->BSq) : quad_fn_k<10, 16, true>(e->BSq);
@@ -392,8 +409,11 @@ static hipError_t set_lds_attr(size_t lds) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (r != hipSuccess) return r;
     }
-    if constexpr (ST == 0 && KMAX <= 10 && BS <= 128) {   // the ALAN instantiation of the LDS line table (two waves: 57 KB)
+    if constexpr (ST == 0 && KMAX <= 10 && BS <= 128) {   // the ALAN instantiations of the LDS line table (two waves: 57 KB)
         r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, 0, true, 1, SMAX, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (r != hipSuccess) return r;
+        r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, 0, true, 1, SMAX, true, AlanArenaSets>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (r != hipSuccess) return r;
     }
@@ -882,7 +902,8 @@ int ca_destroy(ca_env* e) {
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
-                    e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf};
+                    e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
+                    e->d_act_tab, e->d_act_n};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1487,6 +1508,49 @@ int ca_orca_step(ca_env* e, uint32_t flags) {
     return do_step(e, nullptr, flags);
 }
 
+// (cos, sin) of atan2(y, x) = the normalised vector (ALAN:592-595); a zero-length action keeps the goal direction
+static void alan_unit(double x, double y, double* c, double* s) {
+    const double len = std::sqrt(x * x + y * y);
+    *c = len == 0.0 ? 1.0 : x / len;
+    *s = len == 0.0 ? 0.0 : y / len;
+}
+
+// Fresh bandit state for nA actions per agent (weights and times zeroed), then the kernels' arguments; the caller has filled
+// act_c / act_s (one set) or h_act_tab / h_act_n (per arena) and set alan_per.
+static int alan_install(ca_env* e, int nA, double temp, double timewindow, double time_step) {
+    for (double** b : {&e->alan_w, &e->alan_t, &e->alan_dirs, &e->alan_u}) { if (*b) hipFree(*b); *b = nullptr; }
+    if (e->alan_action) { hipFree(e->alan_action); e->alan_action = nullptr; }
+    const size_t an = AN(e);
+    HIPCHK(e, dalloc(e, &e->alan_w, an * (size_t)nA));
+    HIPCHK(e, dalloc(e, &e->alan_t, an * (size_t)nA));
+    HIPCHK(e, dalloc(e, &e->alan_dirs, an * 4));
+    HIPCHK(e, dalloc(e, &e->alan_u, an));
+    HIPCHK(e, dalloc(e, &e->alan_action, an));
+    if (e->alan_per) {
+        const size_t A = (size_t)e->cfg.n_arenas;
+        if (!e->d_act_tab) HIPCHK(e, hipMalloc((void**)&e->d_act_tab, A * CA_ALAN_MAX_ACTIONS * sizeof(double2)));
+        if (!e->d_act_n) HIPCHK(e, hipMalloc((void**)&e->d_act_n, A * sizeof(int)));
+        HIPCHK(e, hipMemcpyAsync(e->d_act_tab, e->h_act_tab.data(), A * CA_ALAN_MAX_ACTIONS * sizeof(double2),
+                                 hipMemcpyHostToDevice, e->stream));
+        HIPCHK(e, hipMemcpyAsync(e->d_act_n, e->h_act_n.data(), A * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->n_actions = nA;
+    e->alan_temp = temp; e->alan_window = timewindow; e->alan_dt = time_step;
+    {   // the same arguments for the kernels that run the bandit inside their launch (ca_quad.h, ca_step.h)
+        if (!e->d_alan) HIPCHK(e, hipMalloc((void**)&e->d_alan, sizeof(AlanCold)));
+        AlanCold h;
+        memset(&h, 0, sizeof h);
+        h.w = e->alan_w; h.t = e->alan_t; h.action = e->alan_action; h.reward = e->reward;
+        memcpy(h.act_c, e->act_c, sizeof h.act_c); memcpy(h.act_s, e->act_s, sizeof h.act_s);
+        h.temp = temp; h.window = timewindow; h.dt = time_step; h.reward_scale = e->cfg.reward_scale; h.nA = nA;
+        h.tab = e->alan_per ? e->d_act_tab : nullptr;
+        h.tab_n = e->alan_per ? e->d_act_n : nullptr;
+        HIPCHK(e, upload(e, e->d_alan, &h, sizeof h));
+    }
+    return alan_pick(e);
+}
+
 int ca_alan_configure(ca_env* e, const double* actions_xy, int32_t n_actions, double temp, double timewindow,
                       double time_step) {
     if (!e || !actions_xy) return fail(e, CA_EINVAL, "ca_alan_configure: null argument");
@@ -1496,33 +1560,57 @@ int ca_alan_configure(ca_env* e, const double* actions_xy, int32_t n_actions, do
         return fail(e, CA_EINVAL, "ca_alan_configure: temp, timewindow and time_step must be positive");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    for (double** b : {&e->alan_w, &e->alan_t, &e->alan_dirs, &e->alan_u}) { if (*b) hipFree(*b); *b = nullptr; }
-    if (e->alan_action) { hipFree(e->alan_action); e->alan_action = nullptr; }
     e->n_actions = 0;
-    const size_t an = AN(e);
-    HIPCHK(e, dalloc(e, &e->alan_w, an * (size_t)n_actions));
-    HIPCHK(e, dalloc(e, &e->alan_t, an * (size_t)n_actions));
-    HIPCHK(e, dalloc(e, &e->alan_dirs, an * 4));
-    HIPCHK(e, dalloc(e, &e->alan_u, an));
-    HIPCHK(e, dalloc(e, &e->alan_action, an));
+    for (int k = 0; k < n_actions; ++k) alan_unit(actions_xy[2 * k], actions_xy[2 * k + 1], &e->act_c[k], &e->act_s[k]);
+    e->alan_per = false;   // (back to one set for every arena)
+    return alan_install(e, n_actions, temp, timewindow, time_step);
+}
+
+int ca_alan_configure_per_arena(ca_env* e, const double* actions_xy, const int32_t* n_actions, double temp, double timewindow,
+                                double time_step) {
+    if (!e || !actions_xy || !n_actions) return fail(e, CA_EINVAL, "ca_alan_configure_per_arena: null argument");
+    const int A = e->cfg.n_arenas;
+    int nmax = 0;
+    for (int a = 0; a < A; ++a) {
+        if (n_actions[a] < 1 || n_actions[a] > CA_ALAN_MAX_ACTIONS)
+            return fail(e, CA_ERANGE, "ca_alan_configure_per_arena: n_actions[%d]=%d out of range 1..%d", a, n_actions[a],
+                        CA_ALAN_MAX_ACTIONS);
+        nmax = n_actions[a] > nmax ? n_actions[a] : nmax;
+    }
+    if (!(temp > 0.0) || !(timewindow > 0.0) || !(time_step > 0.0))
+        return fail(e, CA_EINVAL, "ca_alan_configure_per_arena: temp, timewindow and time_step must be positive");
+    HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    for (int k = 0; k < n_actions; ++k) {  // (cos, sin) of atan2(y, x) = the normalised vector (ALAN:592-595)
-        const double x = actions_xy[2 * k], y = actions_xy[2 * k + 1], len = std::sqrt(x * x + y * y);
-        e->act_c[k] = len == 0.0 ? 1.0 : x / len;
-        e->act_s[k] = len == 0.0 ? 0.0 : y / len;
+    e->n_actions = 0;
+    e->h_act_tab.assign((size_t)A * CA_ALAN_MAX_ACTIONS * 2, 0.0);
+    e->h_act_n.assign(n_actions, n_actions + A);
+    size_t off = 0;
+    for (int a = 0; a < A; ++a)
+        for (int k = 0; k < n_actions[a]; ++k, ++off) {
+            double* cs = &e->h_act_tab[((size_t)a * CA_ALAN_MAX_ACTIONS + k) * 2];
+            alan_unit(actions_xy[2 * off], actions_xy[2 * off + 1], cs, cs + 1);
+        }
+    e->alan_per = true;
+    return alan_install(e, nmax, temp, timewindow, time_step);
+}
+
+int ca_alan_actions_arena(ca_env* e, int32_t arena, double* cs_xy, int32_t cap, int32_t* n_out) {
+    if (!e || !n_out) return fail(e, CA_EINVAL, "ca_alan_actions_arena: null argument");
+    if (arena < 0 || arena >= e->cfg.n_arenas)
+        return fail(e, CA_ERANGE, "ca_alan_actions_arena: arena %d of %d", arena, e->cfg.n_arenas);
+    if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_actions_arena: call ca_alan_configure first");
+    const int n = e->alan_per ? e->h_act_n[arena] : e->n_actions;
+    *n_out = n;
+    if (!cs_xy) return CA_OK;
+    for (int k = 0; k < n && k < cap; ++k) {
+        if (e->alan_per) {
+            cs_xy[2 * k] = e->h_act_tab[((size_t)arena * CA_ALAN_MAX_ACTIONS + k) * 2];
+            cs_xy[2 * k + 1] = e->h_act_tab[((size_t)arena * CA_ALAN_MAX_ACTIONS + k) * 2 + 1];
+        } else {
+            cs_xy[2 * k] = e->act_c[k]; cs_xy[2 * k + 1] = e->act_s[k];
+        }
     }
-    e->n_actions = n_actions;
-    e->alan_temp = temp; e->alan_window = timewindow; e->alan_dt = time_step;
-    {   // the same arguments for the four-lanes kernel, which runs the bandit inside its launch (ca_quad.h)
-        if (!e->d_alan) HIPCHK(e, hipMalloc((void**)&e->d_alan, sizeof(AlanCold)));
-        AlanCold h;
-        memset(&h, 0, sizeof h);
-        h.w = e->alan_w; h.t = e->alan_t; h.action = e->alan_action; h.reward = e->reward;
-        memcpy(h.act_c, e->act_c, sizeof h.act_c); memcpy(h.act_s, e->act_s, sizeof h.act_s);
-        h.temp = temp; h.window = timewindow; h.dt = time_step; h.reward_scale = e->cfg.reward_scale; h.nA = n_actions;
-        HIPCHK(e, upload(e, e->d_alan, &h, sizeof h));
-    }
-    return alan_pick(e);
+    return CA_OK;
 }
 
 int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags) {
@@ -1556,13 +1644,15 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
     p.step_count = e->step_count; p.arena_done = e->arena_done; p.episode = e->episode; p.arena_stats = e->arena_stats;
     memcpy(p.act_c, e->act_c, sizeof p.act_c);
     memcpy(p.act_s, e->act_s, sizeof p.act_s);
+    p.tab = e->alan_per ? e->d_act_tab : nullptr; p.tab_n = e->alan_per ? e->d_act_n : nullptr;
     p.temp = e->alan_temp; p.window = e->alan_window; p.dt = e->alan_dt; p.reward_scale = c.reward_scale;
     p.seed = c.seed; p.arena_offset = c.arena_offset; p.A = c.n_arenas; p.N = c.n_agents; p.nA = e->n_actions;
     p.flags = flags;
     const dim3 grid((unsigned)((AN(e) + ALAN_BS - 1) / ALAN_BS)), block(ALAN_BS);
     {
         ProfScope ps(e, KIND_RESET);
-        launch_k(ps, alan_select_kernel, grid, block, (size_t)e->n_actions * ALAN_BS * 8, e->stream, p);
+        if (e->alan_per) launch_k(ps, alan_select_kernel<2>, grid, block, (size_t)e->n_actions * ALAN_BS * 8, e->stream, p);
+        else launch_k(ps, alan_select_kernel<1>, grid, block, (size_t)e->n_actions * ALAN_BS * 8, e->stream, p);
     }
     HIPCHK(e, hipGetLastError());
     StepArgs a;
@@ -1570,7 +1660,8 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
     HIPCHK(e, launch_step(e, a));
     {
         ProfScope ps(e, KIND_RESET);
-        launch_k(ps, alan_update_kernel, grid, block, 0, e->stream, p);
+        if (e->alan_per) launch_k(ps, alan_update_kernel<2>, grid, block, 0, e->stream, p);
+        else launch_k(ps, alan_update_kernel<1>, grid, block, 0, e->stream, p);
     }
     HIPCHK(e, hipGetLastError());
     e->orient_valid = true;

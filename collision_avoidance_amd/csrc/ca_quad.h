@@ -169,8 +169,12 @@ __host__ __device__ inline size_t quad_lds_bytes(int BS, int KMAX, int SQ, int n
 // direction rotated by the action -> [the ORCA step] -> reward of the action -> sliding-window update of weights and times.
 // Weights and times live in LDS for the whole launch ([action][agent slot] fp64), the four lanes of a quad share the
 // actions (exp64 of the softmax, the window update), the draw is keyed by (seed, global arena, agent, episode, step) as ever.
-template <int KMAX, int BS, int SQ, bool ALAN = false>
+// PER (ALAN instantiation only): AlanArenaSets = an action set per arena -- the loops run over the arena's own count (nk), the
+// LDS rows keep the stride of the largest set (nA); a trailing pack, empty in every other instantiation (names and code as
+// they were).
+template <int KMAX, int BS, int SQ, bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
+    constexpr int AM = !ALAN ? 0 : (sizeof...(PER) > 0 ? 2 : 1);   // the set mode of alan_count / alan_cs
     static_assert(POOL_SLOTS == 16, "a wave holds 16 quads: one line-table slot each");
     static_assert(SQ == 4 || SQ == 16, "obstacle lists of 4 or 16");
     static_assert(!CA_NBW16(BS / 4), "the quad kernel stores 8-bit agent-neighbour ids: at most 256 agent slots per workgroup "
@@ -235,13 +239,14 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
 
     typedef const __attribute__((address_space(4))) AlanCold AlanK;
-    int nA = 0, last_id = 0;
+    int nA = 0, nk = 0, last_id = 0;
     float last_rew = 0.0f;
     double acc_rew = 0.0;
     if constexpr (ALAN) {
         const AlanK& al = *(AlanK*)p.alan;
         nA = al.nA;
-        for (int k = q; k < nA; k += 4) {
+        nk = (AM == 2 && !in_arena) ? 0 : alan_count<AM>(al, a);   // (one set: nA)
+        for (int k = q; k < nk; k += 4) {
             s_w[k * NS + slot] = in_arena ? al.w[((size_t)a * nA + k) * N + i] : 0.0;
             s_w[(nA + k) * NS + slot] = in_arena ? al.t[((size_t)a * nA + k) * N + i] : 0.0;
         }
@@ -279,12 +284,12 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         if constexpr (ALAN) {
             const AlanK& al = *(AlanK*)p.alan;
             if (active)
-                for (int k = q; k < nA; k += 4) s_ps[k * NS + slot] = exp64(s_w[k * NS + slot] / al.temp);   // ALAN:580-581
+                for (int k = q; k < nk; k += 4) s_ps[k * NS + slot] = exp64(s_w[k * NS + slot] / al.temp);   // ALAN:580-581
             wave_lds_sync();
             if (active) {   // (the four lanes alike from here: every lane of the quad holds the draw and the directions)
-                const double sum = np_sum(nA, [&](int k) { return s_ps[k * NS + slot]; });
+                const double sum = np_sum(nk, [&](int k) { return s_ps[k * NS + slot]; });
                 double acc = 0.0;
-                for (int k = 0; k < nA; ++k) {   // ALAN:582: the normalised terms, in order (the four lanes of the quad store the
+                for (int k = 0; k < nk; ++k) {   // ALAN:582: the normalised terms, in order (the four lanes of the quad store the
                     const double v = s_ps[k * NS + slot] / sum;   // same value to the same word: one instruction, in lockstep)
                     s_ps[k * NS + slot] = v;
                     acc += v;
@@ -292,15 +297,16 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                 double ui, u1;
                 if (p.alan_u) ui = p.alan_u[gq];
                 else rng2(c.seed, c.arena_offset + a, i, RNG_ALAN + (epi << 8), (uint32_t)steps, &ui, &u1);
-                act_id = nA - 1;   // np.random.choice (ALAN:585): first action whose normalised cdf exceeds u
+                act_id = nk - 1;   // np.random.choice (ALAN:585): first action whose normalised cdf exceeds u
                 double run = 0.0;
                 bool found = false;
-                for (int k = 0; k < nA - 1; ++k) {
+                for (int k = 0; k < nk - 1; ++k) {
                     run += s_ps[k * NS + slot];
                     if (!found && run / acc > ui) { act_id = k; found = true; }
                 }
                 pref_dir64(pos.x, pos.y, gx, gy, &dgx, &dgy);                       // ALAN:588
-                const double cs = al.act_c[act_id], sn = al.act_s[act_id];         // ALAN:592-595
+                double cs, sn;
+                alan_cs<AM>(al, a, act_id, &cs, &sn);                             // ALAN:592-595
                 dlx = dgx * cs - dgy * sn; dly = dgx * sn + dgy * cs;
                 pref = mk((float)dlx, (float)dly);                                  // ALAN:598
             }
@@ -606,7 +612,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                 }
                 const double vx = (double)vel.x, vy = (double)vel.y;
                 const double Rw = al.reward_scale * (vx * dgx + vy * dgy) + (1.0 - al.reward_scale) * (vx * dlx + vy * dly);
-                for (int k = q; k < nA; k += 4) {
+                for (int k = q; k < nk; k += 4) {
                     double tk = s_t[k * NS + slot] + al.dt;
                     double wk = s_w[k * NS + slot];
                     if (tk >= al.window) { tk = 0.0; wk = 0.0; }
@@ -640,7 +646,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     if constexpr (ALAN) {
         const AlanK& al = *(AlanK*)p.alan;
         if (in_arena && touched) {
-            for (int k = q; k < nA; k += 4) {
+            for (int k = q; k < nk; k += 4) {
                 al.w[((size_t)a * nA + k) * N + i] = s_w[k * NS + slot];
                 al.t[((size_t)a * nA + k) * N + i] = s_t[k * NS + slot];
             }

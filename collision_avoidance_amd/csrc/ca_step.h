@@ -88,8 +88,11 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 // LP3 pool, which is free then: at most ML actions), reward and the sliding-window update of weights / times (global memory,
 // [A][nA][N]) where the epilogue begins; the goal direction is derived again there from the staged pre-step position instead of
 // living in registers across the solve.  Same arithmetic as ca_alan.h's kernels, which remain the three-launch form of the rest.
-template <int KMAX, int BS, int ST, bool FUSE, int HELP = 1, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false>
+// PER (ALAN instantiation only): AlanArenaSets = an action set per arena (ca_alan_configure_per_arena; ca_common.h
+// alan_count / alan_cs); a trailing pack, empty in every other instantiation, so that those keep their names and their code.
+template <int KMAX, int BS, int ST, bool FUSE, int HELP = 1, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
+    constexpr int AM = !ALAN ? 0 : (sizeof...(PER) > 0 ? 2 : 1);   // the set mode of alan_count / alan_cs
     extern __shared__ float4 smem4[];
     constexpr bool LISTP = BS > 64;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
     //                                   scan of the staged arena is as fast -- round 5 measured the lists there: 57.7 against 57.3 us)
@@ -148,33 +151,34 @@ __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1)
         } else if constexpr (ALAN) {   // ALAN:578-598: softmax over the action weights, one draw, goal direction rotated by the action
             typedef const __attribute__((address_space(4))) AlanCold AlanK;
             const AlanK& al = *(AlanK*)p.alan;
-            const int nA = al.nA;
+            const int nA = al.nA, nk = alan_count<AM>(al, a);   // stride | this arena's actions (ALAN = 2: a set per arena)
             // [k][lane] in the wave's LP3 pool (ML doubles per lane), or -- LDS line table -- over the table itself, which is
             // empty until the barrier below (2 (K + S) doubles per lane); ca_alan_configure checks that the actions fit
             constexpr int PSTR = ST > 0 ? 64 : BS;
             double* ps = ST > 0 ? reinterpret_cast<double*>(s_lines + (size_t)(tid >> 6) * (2 * ML) * POOL_SLOTS) + (tid & 63)
                                 : reinterpret_cast<double*>(s_lines) + tid;
             const double* w = al.w + (size_t)a * nA * N + i;
-            for (int k = 0; k < nA; ++k) ps[k * PSTR] = exp64(w[(size_t)k * N] / al.temp);
-            const double sum = np_sum(nA, [&](int k) { return ps[k * PSTR]; });
+            for (int k = 0; k < nk; ++k) ps[k * PSTR] = exp64(w[(size_t)k * N] / al.temp);
+            const double sum = np_sum(nk, [&](int k) { return ps[k * PSTR]; });
             double acc = 0.0;
-            for (int k = 0; k < nA; ++k) { const double v = ps[k * PSTR] / sum; ps[k * PSTR] = v; acc += v; }
+            for (int k = 0; k < nk; ++k) { const double v = ps[k * PSTR] / sum; ps[k * PSTR] = v; acc += v; }
             double ui, u1;
             if (p.alan_u) ui = p.alan_u[q];
             else {
                 const StepCold* cp = p.cold;
                 rng2(cp->seed, cp->arena_offset + a, i, RNG_ALAN + (cp->episode[a] << 8), (uint32_t)cp->step_count[a], &ui, &u1);
             }
-            int act_id = nA - 1;
+            int act_id = nk - 1;
             double run = 0.0;
             bool found = false;
-            for (int k = 0; k < nA - 1; ++k) {
+            for (int k = 0; k < nk - 1; ++k) {
                 run += ps[k * PSTR];
                 if (!found && run / acc > ui) { act_id = k; found = true; }
             }
             double dgx, dgy;
             pref_dir64(pos.x, pos.y, p.goal_x[q], p.goal_y[q], &dgx, &dgy);
-            const double cs = al.act_c[act_id], sn = al.act_s[act_id];
+            double cs, sn;
+            alan_cs<AM>(al, a, act_id, &cs, &sn);
             pref = mk((float)(dgx * cs - dgy * sn), (float)(dgx * sn + dgy * cs));
             pf32 = mk(__int_as_float(act_id), 0.0f);   // (the lane's slot of the goal direction carries the action: no action tensor here)
         } else {
@@ -450,10 +454,11 @@ __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1)
         typedef const __attribute__((address_space(4))) AlanCold AlanK;
         const AlanK& al = *(AlanK*)p.alan;
         if (active) {
-            const int act_id = __float_as_int(pf32.x), nA = al.nA;
+            const int act_id = __float_as_int(pf32.x), nA = al.nA, nk = alan_count<AM>(al, a);
             double dgx, dgy;
             pref_dir64(s_px[tid], s_py[tid], c.goal_x[q], c.goal_y[q], &dgx, &dgy);   // the prologue's values again, bit for bit
-            const double cs = al.act_c[act_id], sn = al.act_s[act_id];
+            double cs, sn;
+            alan_cs<AM>(al, a, act_id, &cs, &sn);
             const double dlx = dgx * cs - dgy * sn, dly = dgx * sn + dgy * cs;
             {
                 const float scale = (float)al.reward_scale;
@@ -466,7 +471,7 @@ __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1)
             const double Rw = al.reward_scale * (vx * dgx + vy * dgy) + (1.0 - al.reward_scale) * (vx * dlx + vy * dly);
             double* w = al.w + (size_t)a * nA * N + i;
             double* t = al.t + (size_t)a * nA * N + i;
-            for (int k = 0; k < nA; ++k) {
+            for (int k = 0; k < nk; ++k) {
                 double tk = t[(size_t)k * N] + al.dt;
                 double wk = w[(size_t)k * N];
                 if (tk >= al.window) { tk = 0.0; wk = 0.0; }

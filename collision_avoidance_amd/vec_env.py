@@ -446,6 +446,26 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_alan_configure", self.h, _ptr(a), a.shape[0], float(temp), float(timewindow), float(time_step))
         self.n_actions = a.shape[0]
 
+    def alan_configure_per_arena(self, action_sets, temp=0.2, timewindow=2.0, time_step=1 / 60.):
+        """An action set per arena (ca_alan_configure_per_arena): `action_sets` is a list of A lists of (x, y), each of
+        1..32 actions; weights and times zeroed.  n_actions becomes the largest set (the stride of the weights / times,
+        whose rows beyond an arena's own set stay zero), so get_state / set_state work unchanged."""
+        if len(action_sets) != self.A:
+            raise ValueError("alan_configure_per_arena: %d action sets for %d arenas" % (len(action_sets), self.A))
+        sets = [np.asarray(acts, np.float64).reshape(-1, 2) for acts in action_sets]
+        n = np.ascontiguousarray([s.shape[0] for s in sets], np.int32)
+        xy = np.ascontiguousarray(np.concatenate(sets, 0) if n.sum() else np.zeros((0, 2)), np.float64)
+        self._call("ca_alan_configure_per_arena", self.h, _ptr(xy), _ptr(n), float(temp), float(timewindow), float(time_step))
+        self.n_actions = int(n.max())
+
+    def alan_actions(self, arena):
+        """The action set of `arena` as the kernels use it (ca_alan_actions_arena): [n, 2] unit (cos, sin) pairs."""
+        cnt = C.c_int32(0)
+        self._call("ca_alan_actions_arena", self.h, int(arena), None, 0, C.byref(cnt))
+        out = np.zeros((max(cnt.value, 1), 2), np.float64)
+        self._call("ca_alan_actions_arena", self.h, int(arena), _ptr(out), cnt.value, C.byref(cnt))
+        return out[:cnt.value]
+
     def alan_step(self, u=None, with_obs=False, stats=False, freeze=False):
         """reference online_step (ALAN_true.py:569-628) + step counter + goal test (ALAN:118-121).
         u [A,N] float64: the uniforms behind np.random.choice, one per agent (numpy or device tensor);

@@ -249,6 +249,19 @@ int ca_rollout(ca_env* env, int32_t steps, uint32_t flags);
  * CA_F_STATS, CA_F_FREEZE. */
 int ca_alan_configure(ca_env* env, const double* actions_xy, int32_t n_actions, double temp, double timewindow,
                       double time_step);
+/* One action set per arena (the trainer's proposals side by side: Train_ALAN_action_space.py:53-67 evaluates one set over
+ * `num` worlds; here many sets, each over arenas of its own, advance in the same launches).
+ *   n_actions  : HOST array [A], each 1..CA_ALAN_MAX_ACTIONS
+ *   actions_xy : HOST array [sum(n_actions), 2], all arenas' sets back to back (like ca_set_obstacles_per_arena)
+ * Each action is normalised as ca_alan_configure does it; temp / timewindow / time_step as there.  Weights and times start at
+ * zero and keep the shape [A, max(n_actions), N]: rows k >= n_actions[a] of arena a are zero and never touched.  Every form of
+ * the step (ca_solver_info) runs with per-arena sets; the fused forms are sized by the largest set.  ca_alan_configure
+ * afterwards returns the handle to one set for all arenas, and this call may follow that one. */
+int ca_alan_configure_per_arena(ca_env* env, const double* actions_xy, const int32_t* n_actions, double temp,
+                                double timewindow, double time_step);
+/* The action set of one arena as the kernels use it (after either configure call): unit (cos, sin) pairs, host array
+ * [cap, 2] (may be NULL); *n_out = the number of actions of that arena (at most cap pairs are written). */
+int ca_alan_actions_arena(ca_env* env, int32_t arena, double* cs_xy, int32_t cap, int32_t* n_out);
 int ca_alan_step(ca_env* env, const double* u, int32_t u_is_device, uint32_t flags);
 /* `steps` consecutive ca_alan_step(env, NULL, 0, flags) calls without returning to the host: with
  * CA_F_FREEZE this is run_sim(mode=1) (ALAN:106-123) for every arena at once.  Where the handle uses the four-lanes kernel
