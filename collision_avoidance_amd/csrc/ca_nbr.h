@@ -167,11 +167,10 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
             __syncthreads();
             // Cells half a neighbour range wide (the 5 x 5 block around an agent's cell covers its range with 156 / 225 of
             // the area of 3 x 3 cells a full range wide: a third fewer candidates), or wider when the arena is so large that
-            // 32 x 32 of them would not cover it; RC = cells to either side that can hold a neighbour (1 or 2).
+            // 32 x 32 of them would not cover it.
             const float x0 = unord(s_box[0]), y0 = unord(s_box[1]);
             const float ex = unord(s_box[2]) - x0, ey = unord(s_box[3]) - y0;
             const float cs = fmaxf((GMAX >= 32 ? 0.5f : 1.0f) * p.neighbor_dist, fmaxf(ex, ey) * (1.0f / (GMAX - 0.5f)));
-            const int RC = (cs >= p.neighbor_dist) ? 1 : 2;
             const float ics = 1.0f / cs;
             const int Gx = min(GMAX, (int)(ex * ics) + 1), Gy = min(GMAX, (int)(ey * ics) + 1);
             const int cx = min(Gx - 1, max(0, (int)((pos.x - x0) * ics))), cy = min(Gy - 1, max(0, (int)((pos.y - y0) * ics)));
@@ -208,13 +207,21 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
             __syncthreads();
             const float rangeSq0 = sqr(p.neighbor_dist);
             float rangeK = rangeSq0;  // distance of the current K-th entry once the list is full
-            auto row_range = [&](int ry, int& lo, int& hi) {
-                const int row = cy + ry;
-                lo = 0; hi = 0;
-                if (active && row >= 0 && row < Gy) {
-                    lo = s_cstart[row * Gx + max(cx - RC, 0)];
-                    hi = s_cstart[row * Gx + min(cx + RC, Gx - 1) + 1];
-                }
+            // WHICH CELLS.  Not a fixed block cx +- RC: pos - x0 and its product with ics are rounded, so a candidate a few
+            // ulps inside the range can land one cell beyond such a block (a pair at |dx| = nd - 1 ulp, 3 cells apart at
+            // cs = nd / 2).  A candidate that passes fl(fl(dx^2) + fl(dy^2)) < fl(nd^2) has fl(dx^2) < fl(nd^2), hence
+            // |xi - xj| < nd (1 + 2^-21) < B = nd * 1.0001 + 1e-4 (and so in y): xj >= xi - B exactly, and as xj is a float,
+            // fl(xi - B) <= xj.  The cell index (the same expression as below) is monotone in the coordinate, so the cell of
+            // xj lies between the cells of fl(xi - B) and fl(xi + B) -- the bounds the pair kernel takes (ca_pair.h).
+            const float B = p.neighbor_dist * 1.0001f + 1e-4f;
+            // (both ends clamped to the grid, as cx / cy are: every LDS index below stays in bounds whatever the positions hold)
+            auto cell_of = [&](float v, float v0, int G) { return min(G - 1, max(0, (int)((v - v0) * ics))); };
+            const int cxlo = cell_of(pos.x - B, x0, Gx), cxhi = cell_of(pos.x + B, x0, Gx);
+            const int cylo = cell_of(pos.y - B, y0, Gy), cyhi = cell_of(pos.y + B, y0, Gy);
+            const int rowend = active ? cyhi : cylo - 1;
+            auto row_range = [&](int row, int& lo, int& hi) {
+                lo = s_cstart[row * Gx + cxlo];
+                hi = s_cstart[row * Gx + cxhi + 1];
             };
             auto visit = [&](int j, const V2& o) {
                 const float dsq = absSq(pos - o);
@@ -224,11 +231,11 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
                     if (ncnt == K) rangeK = key_dist(nkey[KMAX - 1]);
                 }
             };
-            int lo_n, hi_n;
-            row_range(-RC, lo_n, hi_n);
-            for (int ry = -RC; ry <= RC; ++ry) {
+            int lo_n = 0, hi_n = 0;
+            if (cylo <= rowend) row_range(cylo, lo_n, hi_n);
+            for (int row = cylo; row <= rowend; ++row) {
                 const int lo = lo_n, hi = hi_n;
-                if (ry < RC) row_range(ry + 1, lo_n, hi_n);  // the next row's bounds are in flight during this row
+                if (row < rowend) row_range(row + 1, lo_n, hi_n);  // the next row's bounds are in flight during this row
                 int t = lo + (helper ? 1 : 0);
                 if constexpr (SXY) {
                     int jn = 0;
