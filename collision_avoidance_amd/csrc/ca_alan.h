@@ -9,7 +9,7 @@ namespace ca {
 // ALAN online action selection (ALAN_true.py:569-628), one lane per agent, around the ORCA step:
 //   alan_select_kernel : softmax over the agent's action weights, one draw, preferred velocity =
 //                        goal direction rotated by the chosen action (ALAN:578-598);
-//   [nbr_kernel + step_kernel in ORCA mode: sim.doStep(), step counter, goal test (ALAN:601, 118-121)]
+//   [step_kernel in ORCA mode: sim.doStep(), step counter, goal test (ALAN:601, 118-121)]
 //   alan_update_kernel : reward of the executed action, sliding-window bandit update (ALAN:603-628).
 // Weights, times and the reward that feeds them are fp64 like the reference's Python floats.
 // ============================================================================================

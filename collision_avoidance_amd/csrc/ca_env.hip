@@ -83,15 +83,12 @@ struct ca_env {
     int LS = 1, apb = 1, linv = 65536, dense = 0;   // lanes per arena, arenas per workgroup, ceil(2^16 / LS), packed back to back (ca_common.h StepArgs)
     // diagnostic environment switches, read ONCE by ca_create (a handle never changes behaviour because the environment did):
     // -1 = unset, else the first character's digit
-    struct { int reg_lines = -1, nbr_help = -1, pair = -1, pair_min = 129, alan_fused = -1; } sw;
-    int BSn = 64, grid_n = 1;  // the neighbour kernel's own workgroup size
-    bool fuse_nbr = true;       // neighbour search at the head of the solve kernel (default) or as its own launch
+    struct { int reg_lines = -1, pair = -1, alan_fused = -1; } sw;
     int ST = 0, KT = 16;  // solve-kernel variant: ST > 0 = register lines with ST obstacle slots; KT = KMAX
     int SMX = 4;          // ... and the capacity of its obstacle-neighbour list (4, or 16: agents with more than ST are solved apart)
     int max_edges = 0;    // edges of the largest installed obstacle table (the variant depends on it: pick_variant)
     int n_cus = 256;      // compute units of the device (pick_variant: is the batch resident with the LDS line table?)
-    bool help = false;     // large arenas: helper lanes in the uniform-grid neighbour scan (ca_nbr.h, HELP = 2)
-    bool pair = false;     // large arenas: two lanes per agent for the whole step (ca_pair.h); replaces `help` where chosen
+    bool pair = false;     // large arenas: two lanes per agent for the whole step (ca_pair.h)
     size_t lds_p = 0;
     bool quad = false;     // four lanes per agent (ca_quad.h): small batches / small arenas
     bool quad_roll = false;  // ... for ca_rollout's one-launch-for-T-steps form (pays a little longer than for single steps)
@@ -145,7 +142,7 @@ static int overflow_status(ca_env* e, const char* where) {
                 e->S, CA_MAX_OBST_NEIGHBORS);
 }
 
-enum { KIND_NBR = 0, KIND_STEP = 1, KIND_OBS = 2, KIND_RESET = 3 };
+enum { KIND_NBR = 0, KIND_STEP = 1, KIND_OBS = 2, KIND_RESET = 3 };   // (KIND_NBR: the neighbour search has no launch of its own)
 enum { CA_ROLLOUT_MAX_T = 256 };  // steps per launch of the one-launch rollout (ca_rollout)  // KIND_RESET also times the small ALAN kernels
 static hipEvent_t prof_event(ca_env* e) {
     if (!e->free_events.empty()) { hipEvent_t ev = e->free_events.back(); e->free_events.pop_back(); return ev; }
@@ -262,7 +259,7 @@ static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t fla
     a.arena_done = e->arena_done; a.arena_stats = e->arena_stats; a.cold = e->d_cold;
     a.obst = e->d_obst; a.tab_off = e->d_tab_off; a.actions = actions; a.alan = nullptr; a.alan_u = nullptr;
 #ifdef CA_STAMPS
-    a.order = e->fuse_nbr ? e->d_order : nullptr;  // (the order is sized for the solve kernel's grid)
+    a.order = e->d_order;
 #endif
     a.reset_px = nullptr; a.reset_py = nullptr; a.reset_mask = nullptr; a.dbg = e->dbg;
     a.n_obst = e->h_tab_off.empty() ? (int)e->h_obst.size() : 0; a.A = c.n_arenas; a.N = c.n_agents; a.P = e->P; a.logP = e->logP;
@@ -272,166 +269,80 @@ static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t fla
     a.time_horizon_obst = c.time_horizon_obst; a.radius = c.radius; a.max_speed = c.max_speed;
 }
 
-template <int KMAX, int SM>
-static void launch_nbr_k(ca_env* e, const StepArgs& a_in) {
-    const dim3 grid(e->grid_n), block(e->BSn);
-    ProfScope ps(e, KIND_NBR);
-    StepArgs a = a_in;
-    a.apb = e->BSn / e->P; a.LS = e->P; a.linv = 65536 / e->P; a.dense = 0;   // (the stand-alone neighbour kernel may run with a workgroup size of its own: CA_NBR_BS)
-    switch (e->BSn) {
-        case 64: launch_k(ps, nbr_kernel<KMAX, 64, SM>, grid, block, 0, e->stream, a); break;
-        case 128: launch_k(ps, nbr_kernel<KMAX, 128, SM>, grid, block, 0, e->stream, a); break;
-        case 256: launch_k(ps, nbr_kernel<KMAX, 256, SM>, grid, block, 0, e->stream, a); break;
-        case 512: launch_k(ps, nbr_kernel<KMAX, 512, SM>, grid, block, 0, e->stream, a); break;
-        default: launch_k(ps, nbr_kernel<KMAX, 1024, SM>, grid, block, 0, e->stream, a); break;
+// ---- the solve launch of a step ----------------------------------------------------------------------------------------
+// The one place where the variant the handle chose (pick_variant, alan_pick, the quad switches of ca_create) becomes a kernel
+// instantiation, a grid, a block and a dynamic LDS size: launch_step launches what solve_launch returns, apply_variant_attributes
+// and alan_pick raise the dynamic-LDS limit of exactly these kernels, and ca_launch_info reports the plain single-step form.
+struct SolveLaunch { const void* fn; dim3 grid, block; size_t lds; };
+template <class F> static const void* fn_ptr(F* f) { return reinterpret_cast<const void*>(f); }
+// one lane per agent: register lines (ST = 4) or the LDS line table (ST = 0); the ALAN instantiations exist for one and two waves
+template <int KMAX, int ST, int SMX, bool ALAN, class... PER>
+static const void* step_fn_for(int BS) {
+    if constexpr (ALAN) {
+        return BS == 64 ? fn_ptr(&step_kernel<KMAX, 64, ST, SMX, true, PER...>) : fn_ptr(&step_kernel<KMAX, 128, ST, SMX, true, PER...>);
+    } else {
+        switch (BS) {
+            case 64: return fn_ptr(&step_kernel<KMAX, 64, ST, SMX>);
+            case 128: return fn_ptr(&step_kernel<KMAX, 128, ST, SMX>);
+            case 256: return fn_ptr(&step_kernel<KMAX, 256, ST, SMX>);
+            case 512: return fn_ptr(&step_kernel<KMAX, 512, ST, SMX>);
+            default: return fn_ptr(&step_kernel<KMAX, 1024, ST, SMX>);
+        }
     }
 }
-template <int KMAX, int ST, class... PER>
-static hipError_t launch_alan_lane(ca_env* e, ProfScope& ps, const StepArgs& a) {
-    const dim3 grid(e->grid), block(e->BS);
-    if constexpr (ST > 0) {
-        if (e->SMX > ST) {   // (obstacle-neighbour lists of up to 16: "congested", the doorway world)
-            if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, 16, true, PER...>, grid, block, e->lds, e->stream, a);
-            else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, 16, true, PER...>, grid, block, e->lds, e->stream, a);
-        } else {
-            if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, ST, true, PER...>, grid, block, e->lds, e->stream, a);
-            else launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, ST, true, PER...>, grid, block, e->lds, e->stream, a);
-        }
-    } else {                 // (the LDS line table: "deadlock", "blocks")
-        if (e->BS == 64) launch_k(ps, step_kernel<KMAX, 64, 0, true, 1, SMAX, true, PER...>, grid, block, e->lds, e->stream, a);
-        else launch_k(ps, step_kernel<KMAX, 128, 0, true, 1, SMAX, true, PER...>, grid, block, e->lds, e->stream, a);
-    }
-    return hipGetLastError();
-}
-template <int KMAX, int ST, bool FUSE>
-static hipError_t launch_step_kf(ca_env* e, const StepArgs& a) {
-    if (!FUSE) launch_nbr_k<KMAX, (ST > 0 ? ST : SMAX)>(e, a);  // neighbour search as a launch of its own (diagnostic: CA_FUSE_NBR=0)
-    const dim3 grid(e->grid), block(e->BS);
-    ProfScope ps(e, KIND_STEP);
-    if constexpr (FUSE && ST > 0) {
-        if (e->pair) {  // two lanes per agent (ca_pair.h): one arena per workgroup of 2 P lanes
-            if (e->BS == 256) launch_k(ps, pair_kernel<KMAX, 256>, grid, dim3(512), e->lds_p, e->stream, a);
-            else launch_k(ps, pair_kernel<KMAX, 512>, grid, dim3(1024), e->lds_p, e->stream, a);
-            return hipGetLastError();
-        }
-        if (e->help) {  // twice the lanes: the upper half helps in the neighbour scan of its arena and ends (ca_nbr.h)
-            if (e->BS == 256) launch_k(ps, step_kernel<KMAX, 256, ST, true, 2>, grid, dim3(512), e->lds, e->stream, a);
-            else launch_k(ps, step_kernel<KMAX, 512, ST, true, 2>, grid, dim3(1024), e->lds, e->stream, a);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (FUSE && KMAX <= 10) {
-        if (a.alan != nullptr) {   // the ALAN bandit inside the launch (alan_pick allowed it: alan_lane)
-            if (e->alan_per) return launch_alan_lane<KMAX, ST, AlanArenaSets>(e, ps, a);   // (a set per arena)
-            return launch_alan_lane<KMAX, ST>(e, ps, a);
-        }
-    }
-    if constexpr (FUSE && ST > 0) {
-        if (e->SMX > ST) {  // register lines, obstacle-neighbour lists of up to 16 (agents with more than ST are solved apart)
-            switch (e->BS) {
-                case 64: launch_k(ps, step_kernel<KMAX, 64, ST, true, 1, 16>, grid, block, e->lds, e->stream, a); break;
-                case 128: launch_k(ps, step_kernel<KMAX, 128, ST, true, 1, 16>, grid, block, e->lds, e->stream, a); break;
-                case 256: launch_k(ps, step_kernel<KMAX, 256, ST, true, 1, 16>, grid, block, e->lds, e->stream, a); break;
-                case 512: launch_k(ps, step_kernel<KMAX, 512, ST, true, 1, 16>, grid, block, e->lds, e->stream, a); break;
-                default: launch_k(ps, step_kernel<KMAX, 1024, ST, true, 1, 16>, grid, block, e->lds, e->stream, a); break;
-            }
-            return hipGetLastError();
-        }
-    }
-    switch (e->BS) {  // (neighbour search +) lines + LP + integration + reward/done
-        case 64: launch_k(ps, step_kernel<KMAX, 64, ST, FUSE>, grid, block, e->lds, e->stream, a); break;
-        case 128: launch_k(ps, step_kernel<KMAX, 128, ST, FUSE>, grid, block, e->lds, e->stream, a); break;
-        case 256: launch_k(ps, step_kernel<KMAX, 256, ST, FUSE>, grid, block, e->lds, e->stream, a); break;
-        case 512: launch_k(ps, step_kernel<KMAX, 512, ST, FUSE>, grid, block, e->lds, e->stream, a); break;
-        default: launch_k(ps, step_kernel<KMAX, 1024, ST, FUSE>, grid, block, e->lds, e->stream, a); break;
-    }
-    return hipGetLastError();
-}
-template <int KMAX, int ST>
-static hipError_t launch_step_k(ca_env* e, const StepArgs& a) {
-#ifdef CA_WITH_UNFUSED_NBR   // diagnostic build: the neighbour search as a launch of its own (CA_FUSE_NBR=0 / CA_NBR_BS)
-    if (!e->fuse_nbr) return launch_step_kf<KMAX, ST, false>(e, a);
-#endif
-    return launch_step_kf<KMAX, ST, true>(e, a);
+template <int KMAX>
+static const void* pair_fn_for(int BS) {
+    return BS == 256 ? fn_ptr(&pair_kernel<KMAX, 256>) : fn_ptr(&pair_kernel<KMAX, 512>);
 }
 template <int KMAX, int SQ, bool ALAN, class... PER>
-static const void* quad_fn_k(int BS) {
+static const void* quad_fn_for(int BS) {
     switch (BS) {
-        case 64: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 64, SQ, ALAN, PER...>);
-        case 128: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 128, SQ, ALAN, PER...>);
-        case 256: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 256, SQ, ALAN, PER...>);
-        default: return reinterpret_cast<const void*>(&quad_kernel<KMAX, 512, SQ, ALAN, PER...>);
+        case 64: return fn_ptr(&quad_kernel<KMAX, 64, SQ, ALAN, PER...>);
+        case 128: return fn_ptr(&quad_kernel<KMAX, 128, SQ, ALAN, PER...>);
+        case 256: return fn_ptr(&quad_kernel<KMAX, 256, SQ, ALAN, PER...>);
+        default: return fn_ptr(&quad_kernel<KMAX, 512, SQ, ALAN, PER...>);
     }
 }
-static const void* quad_fn(const ca_env* e, bool alan = false) {
-    if (alan && e->alan_per) {   // (a set per arena)
-        if (e->KT == 5) return e->SQ == 4 ? quad_fn_k<5, 4, true, AlanArenaSets>(e->BSq) : quad_fn_k<5, 16, true, AlanArenaSets>(e->BSq);
-        return e->SQ == 4 ? quad_fn_k<10, 4, true, AlanArenaSets>(e->BSq) : quad_fn_k<10, 16, true, AlanArenaSets>(e->BSq);
-    }
-    if (alan) {
-        if (e->KT == 5) return e->SQ == 4 ? quad_fn_k<5, 4, true>(e->BSq) : quad_fn_k<5, 16, true>(e->BSq);
-        return e->SQ == 4 ? quad_fn_k<10, 4, true>(e->BSq) : quad_fn_k<10, 16, true>(e->BSq);
-    }
-    if (e->KT == 5) return e->SQ == 4 ? quad_fn_k<5, 4, false>(e->BSq) : quad_fn_k<5, 16, false>(e->BSq);
-    return e->SQ == 4 ? quad_fn_k<10, 4, false>(e->BSq) : quad_fn_k<10, 16, false>(e->BSq);
+// the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
+// more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
+template <bool ALAN, class... PER>
+static const void* lane_fn_for(const ca_env* e) {
+    if (e->ST > 0 && e->SMX > 4) return e->KT == 5 ? step_fn_for<5, 4, 16, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 16, ALAN, PER...>(e->BS);
+    if (e->ST > 0) return e->KT == 5 ? step_fn_for<5, 4, 4, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 4, ALAN, PER...>(e->BS);
+    if (e->KT == 5) return step_fn_for<5, 0, SMAX, ALAN, PER...>(e->BS);
+    if constexpr (!ALAN) { if (e->KT == 16) return step_fn_for<16, 0, SMAX, false>(e->BS); }
+    return step_fn_for<10, 0, SMAX, ALAN, PER...>(e->BS);
 }
-// neighbour search + lines + LP + integration + reward/done, four lanes per agent, a.T steps
-static hipError_t launch_quad(ca_env* e, const StepArgs& a) {
+template <bool ALAN, class... PER>
+static const void* quad_fn_for(const ca_env* e) {   // (K <= 10)
+    if (e->SQ > 4) return e->KT == 5 ? quad_fn_for<5, 16, ALAN, PER...>(e->BSq) : quad_fn_for<10, 16, ALAN, PER...>(e->BSq);
+    return e->KT == 5 ? quad_fn_for<5, 4, ALAN, PER...>(e->BSq) : quad_fn_for<10, 4, ALAN, PER...>(e->BSq);
+}
+// alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
+static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout) {
+    const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
+    if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
+        const void* f = per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e));
+        return {f, dim3(e->grid_q), dim3(e->BSq), alan ? quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions) : e->lds_q};
+    }
+    if (e->pair)   // two lanes per agent (ca_pair.h): one arena per workgroup of 2 P lanes
+        return {e->KT == 5 ? pair_fn_for<5>(e->BS) : pair_fn_for<10>(e->BS), dim3(e->grid), dim3(2 * e->BS), e->lds_p};
+    const void* f = per ? lane_fn_for<true, AlanArenaSets>(e) : (alan ? lane_fn_for<true>(e) : lane_fn_for<false>(e));
+    return {f, dim3(e->grid), dim3(e->BS), e->lds};
+}
+// (above the 48 KiB that every kernel may take, a kernel's dynamic LDS needs its limit raised before the launch)
+static hipError_t allow_lds(const SolveLaunch& s) {
+    return s.lds > 48 * 1024 ? hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds) : hipSuccess;
+}
+// neighbour search + lines + LP + integration + reward/done (+ the ALAN bandit), a.T steps
+static hipError_t launch_step(ca_env* e, const StepArgs& a) {
+    const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1);
+    if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
     ProfScope ps(e, KIND_STEP, a.T > 1 ? a.T : 1);
     StepArgs arg = a;
     void* params[] = {&arg};
-    const bool alan = a.alan != nullptr;   // the bandit inside the launch (ca_alan_step / ca_alan_rollout)
-    const size_t lds = alan ? quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions) : e->lds_q;
-    if (ps.t0) return hipExtLaunchKernel(quad_fn(e, alan), dim3(e->grid_q), dim3(e->BSq), params, lds, e->stream, ps.t0, ps.t1, 0);
-    return hipLaunchKernel(quad_fn(e, alan), dim3(e->grid_q), dim3(e->BSq), params, lds, e->stream);
-}
-static hipError_t launch_step_any(ca_env* e, const StepArgs& a);
-static hipError_t launch_step(ca_env* e, const StepArgs& a) {
-    const hipError_t r = launch_step_any(e, a);
-    if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
-    return r;
-}
-static hipError_t launch_step_any(ca_env* e, const StepArgs& a) {
-    if (e->quad || (a.T > 1 && e->quad_roll) || (a.alan != nullptr && !e->alan_lane)) return launch_quad(e, a);
-    if (e->ST > 0) return e->KT == 5 ? launch_step_k<5, 4>(e, a) : launch_step_k<10, 4>(e, a);
-    if (e->K <= 5) return launch_step_k<5, 0>(e, a);
-    if (e->K <= 10) return launch_step_k<10, 0>(e, a);
-    return launch_step_k<16, 0>(e, a);
-}
-
-template <int KMAX, int BS, int ST>
-static hipError_t set_lds_attr(size_t lds) {
-    hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, ST, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (r != hipSuccess) return r;
-    if constexpr (ST > 0) {
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, ST, true, 1, 16>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (r != hipSuccess) return r;
-    }
-    if constexpr (ST == 0 && KMAX <= 10 && BS <= 128) {   // the ALAN instantiations of the LDS line table (two waves: 57 KB)
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, 0, true, 1, SMAX, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (r != hipSuccess) return r;
-        r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, 0, true, 1, SMAX, true, AlanArenaSets>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (r != hipSuccess) return r;
-    }
-#ifdef CA_WITH_UNFUSED_NBR
-    r = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<KMAX, BS, ST, false>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-#endif
-    return r;
-}
-template <int KMAX, int ST>
-static hipError_t set_lds_attr_k(int BS, size_t lds) {
-    switch (BS) {
-        case 64: return set_lds_attr<KMAX, 64, ST>(lds);
-        case 128: return set_lds_attr<KMAX, 128, ST>(lds);
-        case 256: return set_lds_attr<KMAX, 256, ST>(lds);
-        case 512: return set_lds_attr<KMAX, 512, ST>(lds);
-        default: return set_lds_attr<KMAX, 1024, ST>(lds);
-    }
+    if (ps.t0) return hipExtLaunchKernel(s.fn, s.grid, s.block, params, s.lds, e->stream, ps.t0, ps.t1, 0);
+    return hipLaunchKernel(s.fn, s.grid, s.block, params, s.lds, e->stream);
 }
 
 typedef void (*obs_fn_t)(const ObsArgs);
@@ -593,7 +504,7 @@ static hipError_t download(ca_env* e, void* dst, const void* src, size_t bytes) 
 
 // + the statically allocated LDS of the fused neighbour search: positions, and for >= 256 lanes the grid tables
 static size_t lds_static_bytes(const ca_env* e) {
-    return (e->help ? (size_t)e->KT * e->BS * 8 : 0) + (size_t)e->BS * 8 +
+    return (size_t)e->BS * 8 +
            (e->BS >= 1024 ? (size_t)e->BS * 2 + 16 + 1024 + 1028 : (e->BS >= 256 ? (size_t)e->BS * 2 + (size_t)e->BS * 8 + 16 + 4096 + 4100 : 0)) + 64;
 }
 
@@ -613,79 +524,44 @@ static void pick_variant(ca_env* e) {
     // (CA_REG_LINES, latched by ca_create: 0 forces the LDS line table, 1 the register lines wherever they exist)
     const bool allow = e->sw.reg_lines != 0, force = e->sw.reg_lines == 1;
     e->KT = e->K <= 5 ? 5 : (e->K <= 10 ? 10 : 16);
-    bool table_fits;
-    {
-        const bool h0 = e->help;
-        e->help = false;   // (the LDS line table never runs with helper lanes)
-        table_fits = step_lds_bytes(e->BS, e->K, e->S, 0, e->KT) + lds_static_bytes(e) <= 160 * 1024;
-        e->help = h0;
-    }
+    const size_t table_per_wg = step_lds_bytes(e->BS, e->K, e->S, 0, e->KT) + lds_static_bytes(e);
+    const bool table_fits = table_per_wg <= 160 * 1024;
     const bool small_world = e->max_edges <= 16;
     // ... or the batch is larger than the chip holds at once WITH the table: a 64-lane workgroup of the table kernel needs 28 KB of
     // LDS (K = 10, S = 16), five fit a CU, and from the 1281st workgroup on the launch runs in rounds of a kernel that is a third
     // occupied -- there the register lines win even in the two-way tube, where every sixth agent is solved apart (measured:
     // deadlock x 50 agents, 1280 arenas 49.6 us (table) / 64.8 us (registers) per ORCA step, 1536 arenas 81.6 / 67.7, 4096 arenas
     // 157.8 / 76.3; blocks x 20 agents, 8192 arenas 126.9 / 75.4; profiles/r04_g_many_edge_worlds.txt)
-    bool table_resident = table_fits;
-    if (table_fits) {
-        const bool h0 = e->help;
-        e->help = false;
-        const size_t per_wg = step_lds_bytes(e->BS, e->K, e->S, 0, e->KT) + lds_static_bytes(e);
-        e->help = h0;
-        table_resident = (long)e->grid <= (long)e->n_cus * (long)((160 * 1024) / per_wg);
-    }
+    const bool table_resident = table_fits && (long)e->grid <= (long)e->n_cus * (long)((160 * 1024) / table_per_wg);
     if (allow && e->K <= 10 && e->S <= 4) { e->ST = 4; e->SMX = 4; }
-    else if (allow && e->K <= 10 && e->fuse_nbr && (small_world || force || !table_resident)) { e->ST = 4; e->SMX = 16; }
+    else if (allow && e->K <= 10 && (small_world || force || !table_resident)) { e->ST = 4; e->SMX = 16; }
     else { e->ST = 0; e->SMX = 16; }
     e->lds = step_lds_bytes(e->BS, e->K, e->S, e->ST, e->KT);
-    {   // helper lanes for the uniform-grid neighbour scan: arenas of 192 .. 512 agents on the register-line kernel
-        e->help = e->sw.nbr_help != 0 && e->fuse_nbr   /* (CA_NBR_HELP=0: none) */ && e->ST > 0 && e->SMX == 4 && (e->BS == 256 || e->BS == 512) &&
-                  e->cfg.n_agents >= 192 && e->K > 0;
-    }
-    {   // two lanes per agent for the whole step (ca_pair.h) where the helper lanes were: a 512-agent arena is 8 waves of one
-        // lane per agent on its CU -- two per SIMD, each a long dependent chain; 16 waves with half the chain each fill it
-        // (CA_PAIR=0: the lane kernel, with helper lanes in the scan from 192 agents; CA_PAIR_MIN: smallest arena that takes it --
-        // arenas of 65 .. 128 agents, two waves, measured faster on the lane kernel: ca_pair.h)
-        const int pair_min = e->sw.pair_min;
-        e->pair = e->sw.pair != 0 && e->fuse_nbr && e->ST > 0 && e->SMX == 4 && (e->BS == 256 || e->BS == 512) &&
-                  e->cfg.n_agents >= pair_min && e->K > 0;
-        e->lds_p = pair_lds_bytes(e->BS, e->KT);
-    }
+    // two lanes per agent for the whole step (ca_pair.h), arenas of 129 .. 512 agents on register lines: a 512-agent arena is 8
+    // waves of one lane per agent on its CU -- two per SIMD, each a long dependent chain; 16 waves with half the chain each fill it
+    // (CA_PAIR=0: the one-lane register-line kernel; arenas of 65 .. 128 agents, two waves, measured faster on it: ca_pair.h)
+    e->pair = e->sw.pair != 0 && e->ST > 0 && e->SMX == 4 && (e->BS == 256 || e->BS == 512) && e->K > 0;
+    e->lds_p = pair_lds_bytes(e->BS, e->KT);
 }
 
 // the dynamic-LDS limits of the kernels pick_variant chose -- and, for BOTH callers (ca_create, and install_tables whenever a
 // world is installed and the variant may change), the check that the chosen kernel fits the CU's 160 KiB: the lane kernels by
-// their dynamic part + the statically declared arrays of the fused neighbour search, the two-lanes kernel by what the
+// their dynamic part + the statically declared arrays of the neighbour search, the two-lanes kernel by what the
 // compiled kernel itself reports (hipFuncGetAttributes).  *misfit = the kernel does not fit (the callers turn it into CA_ERANGE);
 // the return value carries genuine HIP failures only.
 static const size_t LDS_PER_CU = 160 * 1024;
 static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
+    const SolveLaunch plain = solve_launch(e, false, false);
+    *misfit = !e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU;
     hipError_t r = hipSuccess;
-    *misfit = false;
-    if (!e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU) { *misfit = true; return hipSuccess; }
-    if (r == hipSuccess && e->pair) {
-        const void* f = e->KT == 5 ? (e->BS == 256 ? reinterpret_cast<const void*>(&pair_kernel<5, 256>)
-                                                   : reinterpret_cast<const void*>(&pair_kernel<5, 512>))
-                                   : (e->BS == 256 ? reinterpret_cast<const void*>(&pair_kernel<10, 256>)
-                                                   : reinterpret_cast<const void*>(&pair_kernel<10, 512>));
+    if (e->pair) {
         hipFuncAttributes fa;
-        r = hipFuncGetAttributes(&fa, f);
-        if (r == hipSuccess && fa.sharedSizeBytes + e->lds_p > LDS_PER_CU) { *misfit = true; return hipSuccess; }
-        if (r == hipSuccess) r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_p);
+        r = hipFuncGetAttributes(&fa, plain.fn);
+        *misfit = r == hipSuccess && fa.sharedSizeBytes + plain.lds > LDS_PER_CU;
     }
-    if (r == hipSuccess && e->help && e->lds > 48 * 1024) {
-        const void* f = e->KT == 5 ? (e->BS == 256 ? reinterpret_cast<const void*>(&step_kernel<5, 256, 4, true, 2>)
-                                                   : reinterpret_cast<const void*>(&step_kernel<5, 512, 4, true, 2>))
-                                   : (e->BS == 256 ? reinterpret_cast<const void*>(&step_kernel<10, 256, 4, true, 2>)
-                                                   : reinterpret_cast<const void*>(&step_kernel<10, 512, 4, true, 2>));
-        r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds);
-    }
-    if (r == hipSuccess && e->lds > 48 * 1024) {
-        if (e->ST > 0) r = e->KT == 5 ? set_lds_attr_k<5, 4>(e->BS, e->lds) : set_lds_attr_k<10, 4>(e->BS, e->lds);
-        else if (e->K <= 5) r = set_lds_attr_k<5, 0>(e->BS, e->lds);
-        else if (e->K <= 10) r = set_lds_attr_k<10, 0>(e->BS, e->lds);
-        else r = set_lds_attr_k<16, 0>(e->BS, e->lds);
-    }
+    if (r != hipSuccess || *misfit) return r;
+    r = allow_lds(plain);
+    if (r == hipSuccess) r = allow_lds(solve_launch(e, false, true));   // (ca_rollout's one-launch form, where the handle has one)
     return r;
 }
 
@@ -699,10 +575,10 @@ static int alan_pick(ca_env* e) {
     const size_t lq = quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions);
     const bool on = e->sw.alan_fused != 0;   // (CA_ALAN_FUSED=0: the three-launch form everywhere)
     e->alan_fused = on && (e->quad || e->quad_roll) && lq <= 64 * 1024;
-    e->alan_lane = on && !e->quad && e->fuse_nbr && !e->help && !e->pair && e->BS <= 128 && e->K <= 10 &&
+    e->alan_lane = on && !e->quad && !e->pair && e->BS <= 128 && e->K <= 10 &&
                    e->n_actions <= (e->ST > 0 ? 4 + e->KT : 2 * (e->K + e->S));
-    if (e->alan_fused && lq > 48 * 1024)
-        HIPCHK(e, hipFuncSetAttribute(quad_fn(e, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lq));
+    if (e->alan_fused) HIPCHK(e, allow_lds(solve_launch(e, true, true)));   // (the ALAN rollout; on a quad handle the ALAN step too)
+    if (e->alan_lane) HIPCHK(e, allow_lds(solve_launch(e, true, false)));
     return CA_OK;
 }
 
@@ -753,10 +629,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     }
     {   // the diagnostic switches, once
         auto digit = [](const char* name) { const char* v = getenv(name); return (v && v[0] >= '0' && v[0] <= '9') ? v[0] - '0' : -1; };
-        e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.nbr_help = digit("CA_NBR_HELP"); e->sw.pair = digit("CA_PAIR");
-        e->sw.alan_fused = digit("CA_ALAN_FUSED");
-        const char* pm = getenv("CA_PAIR_MIN");
-        if (pm && atoi(pm) > 0) e->sw.pair_min = atoi(pm);
+        e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.pair = digit("CA_PAIR"); e->sw.alan_fused = digit("CA_ALAN_FUSED");
     }
     // launch geometry: P lanes per arena (power of two >= N), one or more whole arenas per block
     int P = 1, logP = 0;
@@ -766,19 +639,6 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     e->LS = P; e->apb = e->BS / P; e->linv = 65536 / P; e->dense = 0;   // (P a power of two: exact)
     e->grid = (cfg->n_arenas + e->apb - 1) / e->apb;
     {
-        const char* v = getenv("CA_NBR_BS");  // diagnostic switch: power of two in [max(P, 64), 1024]
-        const int want = v ? atoi(v) : 0;
-        const bool ok = want >= 64 && want <= 1024 && (want & (want - 1)) == 0 && want >= P &&
-                        CA_NBW16(want) == CA_NBW16(e->BS);  // the list entry width is a compile-time function of the block size
-        e->BSn = ok ? want : e->BS;
-        e->grid_n = (cfg->n_arenas + e->BSn / P - 1) / (e->BSn / P);
-        const char* f = getenv("CA_FUSE_NBR");  // diagnostic switch: 0 = separate neighbour kernel
-        e->fuse_nbr = !(f && f[0] == '0') && e->BSn == e->BS;
-#ifndef CA_WITH_UNFUSED_NBR   // the product library has the fused form only (the stand-alone kernel: build with -DCA_WITH_UNFUSED_NBR)
-        e->fuse_nbr = true; e->BSn = e->BS; e->grid_n = e->grid;
-#endif
-    }
-    {
         const char* v = getenv("CA_OBS_DENSE");  // diagnostic switch: 0 = one arena per observation workgroup
         e->obs_dense_on = cfg->n_agents < 16 && !(v && v[0] == '0');
     }
@@ -786,7 +646,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         // wave than P lanes each (the reference env's own 10-agent arenas: six per wave instead of four)
         const char* v = getenv("CA_DENSE");  // diagnostic switch: 0 = P lanes per arena
         const int N = cfg->n_agents;
-        if (!(v && v[0] == '0') && e->fuse_nbr && e->BS == 64 && P < 64 && 64 / N > 64 / P) {
+        if (!(v && v[0] == '0') && e->BS == 64 && P < 64 && 64 / N > 64 / P) {
             const int linv = (65536 + N - 1) / N;
             bool exact = true;
             for (int t = 0; t < 64; ++t) exact = exact && ((t * linv) >> 16) == t / N;
@@ -852,13 +712,11 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     if (r == hipSuccess) r = dalloc(e, &e->arena_steps, A);
     if (r == hipSuccess) r = dalloc(e, &e->d_obst, (size_t)1);
 #ifdef CA_STAMPS
-    if (r == hipSuccess) r = dalloc(e, &e->dbg, (size_t)std::max(std::max(e->grid * (2 * e->BS / 64), e->grid_n * (e->BSn / 64)), e->grid_q * (e->BSq / 64)) * 16);
+    if (r == hipSuccess) r = dalloc(e, &e->dbg, (size_t)std::max(e->grid * (2 * e->BS / 64), e->grid_q * (e->BSq / 64)) * 16);
     if (r == hipSuccess) r = dalloc(e, &e->dbg_obs, (size_t)cfg->n_arenas * ((cfg->n_agents + 15) / 16 + 16) * 4 * 16);
 #endif
     bool lds_misfit = false;
     if (r == hipSuccess) r = apply_variant_attributes(e, &lds_misfit);
-    if (r == hipSuccess && e->quad_roll && e->lds_q > 48 * 1024)
-        r = hipFuncSetAttribute(quad_fn(e), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_q);
     if (r == hipSuccess) {
         const int obs_bs = obs_block_threads(cfg->n_agents);
         const size_t ol = obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S));
@@ -1001,13 +859,13 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
     int me = 0;
     if (offs.empty()) me = (int)all.size();
     else for (size_t a = 0; a + 1 < offs.size(); ++a) me = std::max(me, offs[a + 1] - offs[a]);
-    struct { int ST, SMX, KT, max_edges; bool help, pair; size_t lds, lds_p; } old_v = {e->ST, e->SMX, e->KT, e->max_edges, e->help, e->pair, e->lds, e->lds_p};
+    struct { int ST, SMX, KT, max_edges; bool pair; size_t lds, lds_p; } old_v = {e->ST, e->SMX, e->KT, e->max_edges, e->pair, e->lds, e->lds_p};
     e->max_edges = me;
     pick_variant(e);
     bool misfit = false;
     const hipError_t ra = apply_variant_attributes(e, &misfit);
     if (misfit || ra != hipSuccess) {
-        e->ST = old_v.ST; e->SMX = old_v.SMX; e->KT = old_v.KT; e->max_edges = old_v.max_edges; e->help = old_v.help; e->pair = old_v.pair;
+        e->ST = old_v.ST; e->SMX = old_v.SMX; e->KT = old_v.KT; e->max_edges = old_v.max_edges; e->pair = old_v.pair;
         e->lds = old_v.lds; e->lds_p = old_v.lds_p;
         bool dummy = false;
         (void)apply_variant_attributes(e, &dummy);   // (the previous variant's limits again: the attribute calls are idempotent)
@@ -1688,8 +1546,7 @@ int ca_alan_rollout(ca_env* e, int32_t steps, uint32_t flags) {
                 if (rc) return rc;
                 continue;
             }
-            HIPCHK(e, launch_quad(e, a));
-            e->lists_trusted = e->lists_trusted || !(flags & CA_F_FREEZE);
+            HIPCHK(e, launch_step(e, a));   // (the four-lanes kernel: alan_fused)
             e->steps_done += (uint64_t)a.T;
         }
         e->orient_valid = true;
@@ -1814,7 +1671,6 @@ int ca_debug_set_order(ca_env* e, const int32_t* order) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (e->d_order) { HIPCHK(e, hipFree(e->d_order)); e->d_order = nullptr; }
     if (!order) return CA_OK;
-    if (!e->fuse_nbr) return fail(e, CA_EINVAL, "ca_debug_set_order: needs the fused neighbour search (CA_FUSE_NBR / CA_NBR_BS unset)");
     std::vector<char> seen((size_t)e->grid, 0);
     for (int b = 0; b < e->grid; ++b) {
         if (order[b] < 0 || order[b] >= e->grid || seen[order[b]]) return fail(e, CA_EINVAL, "ca_debug_set_order: not a permutation");
@@ -1946,9 +1802,10 @@ int ca_profile_read(ca_env* e, int32_t counts[4], float mean_ms[4]) {
 
 int ca_launch_info(ca_env* e, int32_t* block, int32_t* grid, int32_t* lds_bytes, int32_t* obs_grid) {
     if (!e) return CA_EINVAL;
-    if (block) *block = e->quad ? e->BSq : (e->pair ? 2 * e->BS : e->BS);
-    if (grid) *grid = e->quad ? e->grid_q : e->grid;
-    if (lds_bytes) *lds_bytes = (int32_t)(e->quad ? e->lds_q : (e->pair ? e->lds_p : e->lds));
+    const SolveLaunch s = solve_launch(e, false, false);   // (what a plain ca_step launches)
+    if (block) *block = (int32_t)s.block.x;
+    if (grid) *grid = (int32_t)s.grid.x;
+    if (lds_bytes) *lds_bytes = (int32_t)s.lds;
     if (obs_grid) {
         const int apb = obs_block_threads(e->cfg.n_agents) / 16;
         *obs_grid = obs_dense(e) ? (int32_t)(((size_t)e->cfg.n_arenas * e->cfg.n_agents + apb - 1) / apb)

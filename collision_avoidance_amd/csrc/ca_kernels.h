@@ -18,7 +18,7 @@
 // an arena are indexed so that they run on the XCD whose solve workgroup wrote the arena's state (ca_obs.h).
 // Diagnostics: the CA_STAMPS build (tools/stamps.py, tools/diag/placement.py; never the product library) adds phase
 // time stamps, a block order for the solve kernel and the two ca_debug_* entry points that read / install them.
-// ca_nbr.h claims 128 VGPRs for the stand-alone neighbour kernel on purpose (four waves per SIMD, see there).
+// ca_nbr.h's neighbour search claims 128 VGPRs on purpose (see there).
 //
 // Numerics contract: fp32, no FMA contraction (-ffp-contract=off), IEEE sqrt and division, the
 // operation order of SURVEY.md Appendix A.  The CPU oracle (oracle/) obeys the same contract, so

@@ -45,18 +45,11 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
 // ============================================================================================
 // Neighbour search for every agent (App. A.2): the obstacle edges within range and
 // the K nearest agents, written as the lists [A,S,N] / [A,K,N] that the solve kernel and the
-// observation read.  A kernel of its own because it needs almost no LDS (the arena's positions,
-// 8 B per lane): it runs at full occupancy and is issue-bound, whereas the solve kernel is tied to
-// its 16 B x (K+S) line table per lane.
+// observation read.  It runs at the head of the solve kernel (ca_step.h step_kernel).
 // ============================================================================================
 // SM: capacity of the register list of obstacle neighbours (S <= SM): 4 for the register-line solve, SMAX for the LDS table
-// HELP = 2: the workgroup is launched with 2 BS lanes; lanes BS .. 2 BS - 1 are HELPERS of agents 0 .. BS - 1 for the
-// uniform-grid scan only (large arenas: the scan is the longest dependent chain of the step and a 512-agent arena is
-// just 8 waves on its CU): main lane and helper take alternate candidates of every cell row, each keeping its K nearest,
-// the helper hands its list over through LDS and ends; the main lane inserts it into its own (keys are totally ordered:
-// the K smallest of the union are the serial scan's list).  Returns true for a helper lane (the caller returns too).
-template <int KMAX, int BS, int SM, int HELP = 1>
-__device__ __forceinline__ bool nbr_body(const StepArgs& p) {
+template <int KMAX, int BS, int SM>
+__device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #ifndef CA_NBR_NO_VGPR_PAD
     // Claim 128 VGPRs (the kernel needs 56): at most 4 waves then fit on a SIMD, so a launch that brings one
     // wave per SIMD slot (4096 x 64 lanes on 256 CUs) is spread evenly.  Without it the dispatcher puts
@@ -65,9 +58,7 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
 #endif
     __shared__ float s_px[BS];
     __shared__ float s_py[BS];
-    const int tid0 = threadIdx.x;
-    const bool helper = HELP > 1 && tid0 >= BS;   // (whole waves: BS is a multiple of 64)
-    const int tid = helper ? tid0 - BS : tid0;    // the agent slot this lane works for
+    const int tid = threadIdx.x;
     const int P = p.P;
     int la, i;
     lane_slot(p, tid, la, i);
@@ -79,10 +70,9 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
     const int lbase = tid - i;
     CA_STAMP(12);
     V2 pos = mk(0.0f, 0.0f);
-    if (active && !helper) pos = mk(p.pos_x[q], p.pos_y[q]);
-    if (!helper) { s_px[tid] = pos.x; s_py[tid] = pos.y; }
+    if (active) pos = mk(p.pos_x[q], p.pos_y[q]);
+    s_px[tid] = pos.x; s_py[tid] = pos.y;
     __syncthreads();
-    if (helper) pos = mk(s_px[tid], s_py[tid]);
 
     const float INF = __int_as_float(0x7f800000);
     // ---- obstacle neighbours (App. A.2): brute force over the edge table ----
@@ -107,8 +97,7 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
                 }
             }
         };
-        if (helper) {                // (helpers work in the agent scan only)
-        } else if (p.tab_off == nullptr) {  // one table for every arena: uniform loop, scalar loads of the edge records
+        if (p.tab_off == nullptr) {  // one table for every arena: uniform loop, scalar loads of the edge records
             for (int e = 0; e < p.n_obst; ++e) visit(p.obst[e], e, active);
         } else {                     // a table per arena (several arenas may share this wave): ids are local to it
             const int t0 = active ? p.tab_off[a] : 0, ne = active ? p.tab_off[a + 1] - t0 : 0;
@@ -120,7 +109,7 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
     }
     const int ocnt = oin < S ? oin : S;
     if constexpr (SM > 4) {   // a list of 16 keys is 32 registers: it goes to memory now, not after the agent scan
-        if (active && !helper) {
+        if (active) {
 #pragma unroll
             for (int k = 0; k < SM; ++k)
                 if (k >= sofs) p.obst_idx[((size_t)a * S + (k - sofs)) * N + i] = (unsigned short)key_index(okey[k]);
@@ -150,16 +139,16 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
             __shared__ unsigned short s_sorted[BS];
             auto ord = [](float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
             auto unord = [](unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); };
-            if (tid0 < 2) s_box[tid0] = 0xFFFFFFFFu;
-            if (tid0 >= 2 && tid0 < 4) s_box[tid0] = 0u;
-            for (int cidx = tid0; cidx < GMAX * GMAX; cidx += BS * HELP) s_ccnt[cidx] = 0;
+            if (tid < 2) s_box[tid] = 0xFFFFFFFFu;
+            if (tid >= 2 && tid < 4) s_box[tid] = 0u;
+            for (int cidx = tid; cidx < GMAX * GMAX; cidx += BS) s_ccnt[cidx] = 0;
             __syncthreads();
-            const bool in_arena = (a < p.a1) && (i < N) && !helper;  // frozen arenas skip the scan but keep the barriers
+            const bool in_arena = (a < p.a1) && (i < N);  // frozen arenas skip the scan but keep the barriers
             {  // the arena's bounding box: a reduction per wave, then one atomic per wave and corner
                 const unsigned ox = ord(pos.x), oy = ord(pos.y);
                 const unsigned bx0 = wave_min_u32(in_arena ? ox : 0xFFFFFFFFu), by0 = wave_min_u32(in_arena ? oy : 0xFFFFFFFFu);
                 const unsigned bx1 = wave_max_u32(in_arena ? ox : 0u), by1 = wave_max_u32(in_arena ? oy : 0u);
-                if ((tid0 & 63) == 63) {
+                if ((tid & 63) == 63) {
                     atomicMin(&s_box[0], bx0); atomicMin(&s_box[1], by0);
                     atomicMax(&s_box[2], bx1); atomicMax(&s_box[3], by1);
                 }
@@ -177,22 +166,22 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
             int rank = 0;
             if (in_arena) rank = atomicAdd(&s_ccnt[cy * Gx + cx], 1);
             __syncthreads();
-            if (tid0 < 64) {  // exclusive prefix sum over the cells: GMAX^2 / 64 cells per lane of the first wave
+            if (tid < 64) {  // exclusive prefix sum over the cells: GMAX^2 / 64 cells per lane of the first wave
                 constexpr int CPL = GMAX * GMAX / 64;
                 int cnt[CPL];
                 int sum = 0;
 #pragma unroll
-                for (int k = 0; k < CPL; ++k) { cnt[k] = s_ccnt[CPL * tid0 + k]; sum += cnt[k]; }
+                for (int k = 0; k < CPL; ++k) { cnt[k] = s_ccnt[CPL * tid + k]; sum += cnt[k]; }
                 int incl = sum;
 #pragma unroll
                 for (int off = 1; off < 64; off <<= 1) {
                     const int t = __shfl_up(incl, off);
-                    if (tid0 >= off) incl += t;
+                    if (tid >= off) incl += t;
                 }
                 int b = incl - sum;
 #pragma unroll
-                for (int k = 0; k < CPL; ++k) { s_cstart[CPL * tid0 + k] = b; b += cnt[k]; }
-                if (tid0 == 63) s_cstart[GMAX * GMAX] = incl;
+                for (int k = 0; k < CPL; ++k) { s_cstart[CPL * tid + k] = b; b += cnt[k]; }
+                if (tid == 63) s_cstart[GMAX * GMAX] = incl;
             }
             __syncthreads();
             // (up to 512 lanes the positions are sorted along with the indices: a candidate then is one LDS address, known
@@ -236,7 +225,7 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
             for (int row = cylo; row <= rowend; ++row) {
                 const int lo = lo_n, hi = hi_n;
                 if (row < rowend) row_range(row + 1, lo_n, hi_n);  // the next row's bounds are in flight during this row
-                int t = lo + (helper ? 1 : 0);
+                int t = lo;
                 if constexpr (SXY) {
                     int jn = 0;
                     float2 on = make_float2(0.0f, 0.0f);
@@ -244,31 +233,16 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
                     while (t < hi) {
                         const int j = jn;
                         const V2 o = mk(on.x, on.y);
-                        t += HELP;
+                        ++t;
                         if (t < hi) { jn = s_sorted[t]; on = s_sxy[t]; }  // the next candidate is in flight during this one
                         visit(j, o);
                     }
                 } else {
-                    for (; t < hi; t += HELP) {
+                    for (; t < hi; ++t) {
                         const int j = s_sorted[t];
                         visit(j, mk(s_px[j], s_py[j]));
                     }
                 }
-            }
-            if constexpr (HELP > 1) {  // the helper's list -> LDS -> the main lane's list
-                __shared__ double s_hkey[KMAX][BS];
-                if (helper) {
-#pragma unroll
-                    for (int k = 0; k < KMAX; ++k) s_hkey[k][tid] = nkey[k];
-                }
-                __syncthreads();
-                if (helper) return true;
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k)
-                    if (k >= kofs) sorted_insert<KMAX>(nkey, s_hkey[k][tid]);  // (an empty slot is the largest key: no effect)
-                ncnt = 0;
-#pragma unroll
-                for (int k = 0; k < KMAX; ++k) ncnt += (k >= kofs && key_index(nkey[k]) >= 0) ? 1 : 0;
             }
             scanned = true;
         }
@@ -367,12 +341,6 @@ __device__ __forceinline__ bool nbr_body(const StepArgs& p) {
         }
     }
     CA_STAMP(15);
-    return false;
-}
-
-template <int KMAX, int BS, int SM>
-__global__ __launch_bounds__(BS) void nbr_kernel(const StepArgs p) {
-    nbr_body<KMAX, BS, SM>(p);
 }
 
 }  // namespace ca

@@ -28,7 +28,7 @@
 //   * the per-agent scalar work (fp64 goal direction, done test, RNG) is done redundantly by the two lanes; lane 0 of a pair
 //     writes.
 // One workgroup = one arena = 2 P lanes (P = 256 or 512).  Selected by ca_create for arenas of 129 .. 512 agents with K <= 10 and
-// <= 4 obstacle neighbours (CA_PAIR=0 falls back to the lane kernel, with helper lanes in its scan from 192 agents).  Measured
+// <= 4 obstacle neighbours (CA_PAIR=0 falls back to the one-lane register-line kernel).  Measured
 // crossover, settled crowds, ORCA-only us per step, lane / pair: 1024 x 100 (circle) 59.2 / 67.0, 1024 x 128 65.1 / 69.4 -- arenas
 // of two waves stay on the lane kernel --, 512 x 180 71.7 / 49.2, 256 x 512 66.9 / 50.1.
 #pragma once

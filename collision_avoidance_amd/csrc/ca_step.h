@@ -79,7 +79,6 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 #ifndef CA_LB512
 #define CA_LB512 4   // waves per SIMD the 512-lane register-line kernel is built for (diagnostic: 2 = 256 VGPRs)
 #endif
-// HELP = 2: launched with 2 BS lanes, the upper half helps in the neighbour scan and ends (ca_nbr.h)
 // SMX: capacity of the obstacle-neighbour list (S <= SMX).  SMX > ST (register lines): the rare agent with more than ST
 // obstacle neighbours is solved apart (solve_many_obstacles)
 // ALAN (kernels of one and two waves, K <= 10 -- register lines with obstacle lists of 4 or 16, and the LDS line table: every world
@@ -90,8 +89,8 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 // living in registers across the solve.  Same arithmetic as ca_alan.h's kernels, which remain the three-launch form of the rest.
 // PER (ALAN instantiation only): AlanArenaSets = an action set per arena (ca_alan_configure_per_arena; ca_common.h
 // alan_count / alan_cs); a trailing pack, empty in every other instantiation, so that those keep their names and their code.
-template <int KMAX, int BS, int ST, bool FUSE, int HELP = 1, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
-__global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
+template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
+__global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (sizeof...(PER) > 0 ? 2 : 1);   // the set mode of alan_count / alan_cs
     extern __shared__ float4 smem4[];
     constexpr bool LISTP = BS > 64;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
@@ -99,10 +98,10 @@ __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1)
     __shared__ unsigned s_vmax2;   // (LISTP) the largest squared speed of the workgroup's arenas in this step, as float bits: see the pair count
     if constexpr (LISTP) { if (threadIdx.x == 0) s_vmax2 = 0u; }   // (barriers follow before its first use)
     CA_PRIO_START();
-    // FUSE: the neighbour search runs at the head of this kernel instead of in a launch of its own (one
-    // drain/fill less per step, and its dispatch skew overlaps useful work).  A lane later reads back only the
-    // lists of its own agent, which it wrote itself; the search's LDS arrays are not used again.
-    if constexpr (FUSE) { if (nbr_body<KMAX, BS, SMX, HELP>(p)) return; }
+    // The neighbour search runs at the head of this kernel (one drain/fill less per step than a launch of its own, and its
+    // dispatch skew overlaps useful work).  A lane later reads back only the lists of its own agent, which it wrote itself;
+    // the search's LDS arrays are not used again.
+    nbr_body<KMAX, BS, SMX>(p);
     constexpr int ML = ST + KMAX;  // register slots (ST > 0)
     const int tid = threadIdx.x;
     const int P = p.P;
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(BS * HELP, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1)
 
     CA_STAMP(1);
     CA_PRIO_POINT(1);
-    // ---- neighbour lists of this step (App. A.2), produced by nbr_kernel ----
+    // ---- neighbour lists of this step (App. A.2), written by nbr_body at the head of this kernel ----
     // (the list pointers as scalars of their own: left inside the 16-register tuple their kernel-argument load
     // arrives in, every use after a spill reloads the whole tuple -- 16 v_readlane for one pointer)
     const void* nb_idx_s = p.nb_idx;

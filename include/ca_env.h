@@ -301,8 +301,8 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * handle carries a start and a stop HIP event on its own dispatch (hipExtLaunchKernel on the handle's stream: the execution
  * time of the kernel, what rocprofv3 --kernel-trace reports; k = 1: every launch).  ca_profile_read synchronises and
  * returns, per kernel kind, the number of sampled launches and their mean duration in milliseconds since the last read
- * (kinds: 0 nbr_kernel -- only when the neighbour search runs as a launch of its own, CA_FUSE_NBR=0; normally it is the
- * head of step_kernel --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
+ * (kinds: 0 nbr_kernel -- always 0: the neighbour search is the head of step_kernel, with no launch of its own; the
+ * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
  * launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */

@@ -373,7 +373,7 @@ CASES = {
     "ck16": (16, 5.0, 5, "half"), "ck64": (64, 5.0, 10, "half"),
     "scan65": (65, 5.0, 10, "half"), "scan100": (100, 5.0, 10, "half"),
     "grid32_250_k16": (250, 5.0, 16, "half"), "grid32_300_world": (300, 5.0, 10, "half"),
-    "grid32_300_help": (300, 5.0, 10, "wide"),
+    "grid32_300_help": (300, 5.0, 10, "wide"),   # (the one-lane CA_PAIR=0 path; the scenes are seeded from the name, so it stays)
     "grid16_600": (600, 3.0, 10, "g16"), "grid16_1024": (1024, 3.0, 10, "g16"),
     "pair192": (192, 5.0, 10, "half"), "pair300": (300, 5.0, 10, "half"), "pair512": (512, 5.0, 10, "wide"),
 }

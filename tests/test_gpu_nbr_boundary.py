@@ -21,7 +21,7 @@ PATHS = {
     "scan65": (dict(CA_QUAD="0"), 1, 128), "scan100": (dict(CA_QUAD="0"), 1, 128),          # the 64-bit scan
     "grid32_250_k16": (dict(CA_QUAD="0"), 1, 256),               # one lane, GMAX 32: the LDS line table (K 16)
     "grid32_300_world": (dict(CA_QUAD="0"), 1, 512),             # ... more than four obstacle neighbours (SMX 16)
-    "grid32_300_help": (dict(CA_QUAD="0", CA_PAIR="0"), 1, 512),  # ... helper lanes
+    "grid32_300_help": (dict(CA_QUAD="0", CA_PAIR="0"), 1, 512),  # one lane, CA_PAIR=0: register lines, SMX 4, GMAX 32
     "grid16_600": (dict(CA_QUAD="0"), 1, 1024), "grid16_1024": (dict(CA_QUAD="0"), 1, 1024),   # one lane, GMAX 16
     "pair192": ({}, 2, 512), "pair300": ({}, 2, 1024), "pair512": ({}, 2, 1024),
 }

@@ -1,5 +1,5 @@
 """Large arenas (129 .. 512 agents): the two-lanes-per-agent solve kernel (csrc/ca_pair.h) is the default there and the
-lane kernel with helper lanes in the scan (CA_PAIR=0) its fallback -- both against the oracle, bit for bit, and against
+one-lane register-line kernel (CA_PAIR=0) its fallback -- both against the oracle, bit for bit, and against
 each other.  The pair kernel works through the arena in the order of its uniform grid, so per-agent results must not
 depend on where in that order an agent sits: actions, rewards, observation, auto-reset and per-arena freezing included."""
 import os
@@ -44,28 +44,29 @@ def test_pair_kernel_is_the_default_for_large_arenas_only():
                                              (256, 10, 5.0, "circle"), (226, 10, 5.0, "incoming")])
 def test_pair_and_helper_variants_step_with_actions_obs_autoreset(N, K, nd, scenario):
     """Full steps (actions in, reward and observation out) with statistics and auto-reset, a short episode cap so that the
-    reset happens inside the run: the default (pair) kernel, the CA_PAIR=0 fallback and the oracle agree bit for bit."""
+    reset happens inside the run: the default (pair) kernel, the CA_PAIR=0 one-lane fallback and the oracle agree bit for
+    bit.  (The name is from the helper-lane kernel that was the fallback once; it is kept so that the test ids stay.)"""
     A = 3
     p = H.scenario_params(scenario, N, max_neighbors=K, neighbor_dist=nd, max_step=7)
     pair = H.make_gpu(A, N, scenario, p, seed=9)
-    help_ = _with_pair("0", lambda: H.make_gpu(A, N, scenario, p, seed=9))
+    one = _with_pair("0", lambda: H.make_gpu(A, N, scenario, p, seed=9))
     orc = H.make_oracle(A, N, scenario, p, seed=9)
-    assert pair.launch_info()["lanes_per_agent"] == 2 and help_.launch_info()["lanes_per_agent"] == 1
+    assert pair.launch_info()["lanes_per_agent"] == 2 and one.launch_info()["lanes_per_agent"] == 1
     rng = np.random.RandomState(3)
     for s in range(16):
         act = rng.uniform(-1.0, 1.0, (A, N)).astype(np.float32)
         pair.step(act, stats=True, autoreset=True)
-        help_.step(act, stats=True, autoreset=True)
+        one.step(act, stats=True, autoreset=True)
         orc.step(act, flags=o.F_OBS | o.F_STATS | o.F_AUTORESET)
         if s % 5 == 4 or s == 15:
             H.assert_state_equal(pair, orc, "pair step %d" % s, obs=True, reward=True)
-            H.assert_state_equal(help_, orc, "helper step %d" % s, obs=True, reward=True)
+            H.assert_state_equal(one, orc, "one-lane fallback step %d" % s, obs=True, reward=True)
     H.assert_stats_equal(pair, orc, "pair")
-    H.assert_stats_equal(help_, orc, "helper")
+    H.assert_stats_equal(one, orc, "one-lane fallback")
     assert pair.stats()["episodes"] >= 2 * A      # the cap of 7 steps ended (and restarted) every arena at least twice
     np.testing.assert_array_equal(pair.get(_lib.FLD_ARENA_STATS)[:, [0, 1, 2, 3, 4, 6, 7]],
                                   orc.get(o.FLD_ARENA_STATS)[:, [0, 1, 2, 3, 4, 6, 7]])
-    pair.close(); help_.close()
+    pair.close(); one.close()
 
 
 def test_pair_done_modes_and_freeze():

@@ -142,7 +142,7 @@ CASES = [
     ("grid_circle", 2, 256, "circle", dict(), 40, 10),
     ("grid_incoming", 2, 226, "incoming", dict(), 60, 20),
     ("grid_smallrange", 2, 400, "crowd", dict(neighbor_dist=1.5, max_neighbors=5), 40, 10),
-    # ... with helper lanes in the scan (192-512 agents): list shorter than the register array (K = 7 of 10, 3 of 5),
+    # ... in arenas of 192-512 agents (the pair kernel): list shorter than the register array (K = 7 of 10, 3 of 5),
     # an arena that fills the 512-lane shape exactly, one just above the threshold
     ("grid_k7", 2, 300, "crowd", dict(neighbor_dist=4.0, max_neighbors=7), 30, 10),
     ("grid_k3", 3, 200, "crowd", dict(neighbor_dist=2.0, max_neighbors=3), 30, 10),
@@ -671,7 +671,7 @@ def test_world_without_obstacles_and_ragged_edges():
 
 
 def test_frozen_large_arenas_stay_untouched():
-    """CA_F_FREEZE with the helper-lane neighbour scan (200 agents per arena): an arena whose arena_done flag is set
+    """CA_F_FREEZE with the uniform-grid neighbour scan (200 agents per arena): an arena whose arena_done flag is set
     is left exactly as it is -- state, lists, counters -- while its neighbours in the batch advance (ALAN:121-123)."""
     from collision_avoidance_amd import _lib
     A, N = 3, 200

@@ -125,11 +125,12 @@ def test_action_set_files(tmp_path):
         alan_actions.load_actions(str(tmp_path / "bad.act"))
 
 
-def test_no_hot_kernel_uses_scratch_memory():
+def test_no_hot_kernel_instantiation_uses_scratch_memory():
     """A register spill in a solve / observation kernel is HBM traffic (round 1: 19 MB per launch) and a dependent
     memory round trip inside the LP: the compiler's own metadata must show 0 bytes of scratch for every hot kernel
-    (the LDS-line-table variant keeps LP3's projected lines in a private array by design).  Compiles the device
-    assembly once per source change (tools/kernel_resources.py, about a minute)."""
+    (the LDS-line-table variant keeps LP3's projected lines in a private array by design).  The instantiations are
+    named by step_kernel's parameter list <K, BS, ST, SMX, ALAN, ...>.  Compiles the device assembly once per source
+    change (tools/kernel_resources.py, about a minute)."""
     import shutil
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -139,8 +140,8 @@ def test_no_hot_kernel_uses_scratch_memory():
     kr.ensure_asm()
     rows = kr.parse()
     names = [r["name"] for r in rows]
-    for want in ("step_kernel<10, 64, 4, true, 1, 4, false>", "step_kernel<10, 64, 4, true, 1, 4, true>", "quad_kernel<5, 64, 4, false>",
-                 "quad_kernel<10, 256, 16, false>", "quad_kernel<5, 64, 4, true>", "pair_kernel<10, 512>", "step_kernel<5, 64, 4, true, 1, 16, false>"):
+    for want in ("step_kernel<10, 64, 4, 4, false>", "step_kernel<10, 64, 4, 4, true>", "quad_kernel<5, 64, 4, false>",
+                 "quad_kernel<10, 256, 16, false>", "quad_kernel<5, 64, 4, true>", "pair_kernel<10, 512>", "step_kernel<5, 64, 4, 16, false>"):
         assert any(n.startswith(want) for n in names), want
     bad = kr.spilling(rows)
     assert not bad, [(r["name"], r["scratch"], r["vgpr_spill"]) for r in bad]
@@ -148,9 +149,8 @@ def test_no_hot_kernel_uses_scratch_memory():
     # lists of 4 or 16 at every workgroup size, with and without the ALAN bandit; the four-lanes kernel in all its shapes; the
     # two-lanes kernel -- is present and has no scratch at all (round 4 exempted the multi-wave K = 10 / S = 16 shapes:
     # 32 B, 40 spilled registers; the reference's "deadlock" world with more than 64 agents selects them, ALAN:418-455)
-    want = ["step_kernel<%d, %d, 4, true, 1, %d, false>" % (k, bs, sm) for k in (5, 10) for bs in (64, 128, 256, 512, 1024) for sm in (4, 16)]
-    want += ["step_kernel<%d, %d, 4, true, 1, %d, true>" % (k, bs, sm) for k in (5, 10) for bs in (64, 128) for sm in (4, 16)]
-    want += ["step_kernel<%d, %d, 4, true, 2, 4, false>" % (k, bs) for k in (5, 10) for bs in (256, 512)]
+    want = ["step_kernel<%d, %d, 4, %d, false>" % (k, bs, sm) for k in (5, 10) for bs in (64, 128, 256, 512, 1024) for sm in (4, 16)]
+    want += ["step_kernel<%d, %d, 4, %d, true>" % (k, bs, sm) for k in (5, 10) for bs in (64, 128) for sm in (4, 16)]
     want += ["quad_kernel<%d, %d, %d, %s>" % (k, bs, sq, al) for k in (5, 10) for bs in (64, 128, 256, 512) for sq in (4, 16) for al in ("false", "true")]
     want += ["pair_kernel<10, 256>", "pair_kernel<10, 512>", "obs_kernel<256"]
     for w_ in want:
