@@ -1,7 +1,7 @@
 // ca_alan.h -- ALAN online action selection kernels
 // Part of the HIP kernels of libcaenv.so (see ca_kernels.h for the overview and the numerics contract).
 #pragma once
-#include "ca_common.h"
+#include "ca_rules.h"
 
 namespace ca {
 
@@ -34,26 +34,6 @@ struct AlanArgs {
     uint32_t flags;
 };
 
-// numpy's float64 add.reduce for n < 128: < 8 sequential, otherwise eight accumulators combined as a
-// fixed tree plus a sequential tail -- the value np.sum(ps) has at ALAN_true.py:582
-template <class Get>
-__device__ __forceinline__ double np_sum(int n, Get get) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int k = 0; k < n; ++k) res += get(k);
-        return res;
-    }
-    double r0 = get(0), r1 = get(1), r2 = get(2), r3 = get(3), r4 = get(4), r5 = get(5), r6 = get(6), r7 = get(7);
-    int k = 8;
-    for (; k < n - (n % 8); k += 8) {
-        r0 += get(k); r1 += get(k + 1); r2 += get(k + 2); r3 += get(k + 3);
-        r4 += get(k + 4); r5 += get(k + 5); r6 += get(k + 6); r7 += get(k + 7);
-    }
-    double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-    for (; k < n; ++k) res += get(k);
-    return res;
-}
-
 // ALAN = 1: one action set for the handle; 2: a set per arena (the loops run over the arena's own count, stride nA)
 template <int ALAN>
 __global__ __launch_bounds__(ALAN_BS) void alan_select_kernel(const AlanArgs p) {
@@ -68,34 +48,12 @@ __global__ __launch_bounds__(ALAN_BS) void alan_select_kernel(const AlanArgs p) 
     double* ps = s_ps + threadIdx.x;
     // weights and times are stored [A][n_actions][N]: the lanes of a wave read consecutive doubles
     const double* w = p.w + (size_t)a * nA * p.N + i;
-    for (int k = 0; k < nk; ++k) ps[k * ALAN_BS] = exp64(w[(size_t)k * p.N] / p.temp);  // ALAN:580-581
-    const double sum = np_sum(nk, [&](int k) { return ps[k * ALAN_BS]; });
-    double acc = 0.0;
-    for (int k = 0; k < nk; ++k) {                                                 // ALAN:582
-        const double v = ps[k * ALAN_BS] / sum;
-        ps[k * ALAN_BS] = v;
-        acc += v;
-    }
-    // np.random.choice(n, 1, p=ps) (ALAN:585): cdf = cumsum(p) / cdf[-1]; searchsorted(cdf, u, 'right')
-    double ui;
-    if (p.u) ui = p.u[q];
-    else {  // stream (seed, global arena, agent, RNG_ALAN + 256 x episode, step): a new stream every episode of the arena
-        double u1;
-        rng2(p.seed, p.arena_offset + a, i, RNG_ALAN + (p.episode[a] << 8), (uint32_t)p.step_count[a], &ui, &u1);
-    }
-    int id = nk - 1;
-    double run = 0.0;
-    bool found = false;
-    for (int k = 0; k < nk - 1; ++k) {
-        run += ps[k * ALAN_BS];
-        if (!found && run / acc > ui) { id = k; found = true; }
-    }
+    auto psk = [&](int k) -> double& { return ps[k * ALAN_BS]; };
+    alan_terms(nk, 0, 1, psk, [&](int k) { return w[(size_t)k * p.N]; }, p.temp);
+    const int id = alan_draw(nk, psk, [&] { return alan_uniform(p.u, q, p.seed, p.arena_offset, a, i, p.episode[a], p.step_count[a]); });
     p.action[q] = id;
-    double gx, gy;
-    pref_dir64(p.pos_x[q], p.pos_y[q], p.goal_x[q], p.goal_y[q], &gx, &gy);        // ALAN:588
-    double cs, sn;
-    alan_cs<ALAN>(p, a, id, &cs, &sn);                                               // ALAN:592-595
-    const double lx = gx * cs - gy * sn, ly = gx * sn + gy * cs;
+    double gx, gy, lx, ly;
+    alan_dirs<ALAN>(p, a, id, mk(p.pos_x[q], p.pos_y[q]), p.goal_x[q], p.goal_y[q], &gx, &gy, &lx, &ly);
     const size_t an = (size_t)p.A * p.N;  // dirs: [4][A*N]
     p.dirs[q] = gx; p.dirs[an + q] = gy; p.dirs[2 * an + q] = lx; p.dirs[3 * an + q] = ly;
     p.pref_x[q] = (float)lx; p.pref_y[q] = (float)ly;                               // ALAN:598
@@ -114,11 +72,8 @@ __global__ __launch_bounds__(ALAN_BS) void alan_update_kernel(const AlanArgs p) 
     const size_t an = (size_t)p.A * p.N;
     const double d[4] = {p.dirs[q], p.dirs[an + q], p.dirs[2 * an + q], p.dirs[3 * an + q]};
     const float vxf = p.vel_x[q], vyf = p.vel_y[q];
-    {   // env.py:389-400 in fp32, as ca_step reports it
-        const float scale = (float)p.reward_scale;
-        const float r_goal = vxf * (float)d[0] + vyf * (float)d[1];
-        const float r_polite = vxf * (float)d[2] + vyf * (float)d[3];
-        const float rew = scale * r_goal + (1.0f - scale) * r_polite;
+    {
+        const float rew = step_reward(p.reward_scale, mk(vxf, vyf), mk((float)d[0], (float)d[1]), mk((float)d[2], (float)d[3]));
         p.reward[q] = rew;
         if (p.flags & 2u) {
             double* sum = reinterpret_cast<double*>(&p.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]);
@@ -132,18 +87,11 @@ __global__ __launch_bounds__(ALAN_BS) void alan_update_kernel(const AlanArgs p) 
             }
         }
     }
-    const double vx = (double)vxf, vy = (double)vyf;                                // ALAN:606-613
-    const double R = p.reward_scale * (vx * d[0] + vy * d[1]) + (1.0 - p.reward_scale) * (vx * d[2] + vy * d[3]);
     const int i = q - a * p.N;
     double* w = p.w + (size_t)a * nA * p.N + i;
     double* t = p.t + (size_t)a * nA * p.N + i;
-    for (int k = 0; k < nk; ++k) {                                                  // ALAN:616-628
-        double tk = t[(size_t)k * p.N] + p.dt;
-        double wk = w[(size_t)k * p.N];
-        if (tk >= p.window) { tk = 0.0; wk = 0.0; }
-        if (k == id) wk = R;
-        t[(size_t)k * p.N] = tk; w[(size_t)k * p.N] = wk;
-    }
+    alan_update(p, mk(vxf, vyf), d[0], d[1], d[2], d[3], id, nk, 0, 1, [&](int k) -> double& { return w[(size_t)k * p.N]; },
+                [&](int k) -> double& { return t[(size_t)k * p.N]; });
     // the solve kernel left the goal direction in pref (its ORCA-mode epilogue); the reference's agent
     // still holds the velocity it was given at ALAN:598
     p.pref_x[q] = (float)d[2]; p.pref_y[q] = (float)d[3];

@@ -25,9 +25,11 @@
 // trajectories agree bit for bit.
 //
 // Files: ca_common.h (types, launch arguments), ca_lp.h (LP1/LP2/LP3), ca_lines.h (ORCA half-planes),
-// ca_nbr.h (neighbour search), ca_step.h (solve + reset kernels), ca_alan.h (ALAN bandit kernels), ca_obs.h (laser
+// ca_nbr.h (neighbour search), ca_rules.h (the environment's per-agent rules: actions, reward, done test, goals, resets,
+// ALAN's draw and update), ca_step.h (solve + reset kernels), ca_alan.h (ALAN bandit kernels), ca_obs.h (laser
 // observation).
 #pragma once
+#include "ca_rules.h"
 #include "ca_step.h"
 #include "ca_quad.h"
 #include "ca_pair.h"

@@ -208,13 +208,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
             pos0 = mk(p.pos_x[q0], p.pos_y[q0]);
             vel0 = mk(p.vel_x[q0], p.vel_y[q0]);
             if (p.actions) {
-                double pf_x, pf_y, sn, cs64;
-                pref_dir64(pos0.x, pos0.y, p.goal_x[q0], p.goal_y[q0], &pf_x, &pf_y);
-                sincos64((double)p.actions[q0], &sn, &cs64);
-                const double rl_x = pf_x * cs64 - pf_y * sn;
-                const double rl_y = pf_x * sn + pf_y * cs64;
-                pf0 = mk((float)pf_x, (float)pf_y);
-                pref0 = mk((float)rl_x, (float)rl_y);
+                action_pref(pos0, p.goal_x[q0], p.goal_y[q0], p.actions[q0], pf0, pref0);
             } else {
                 pref0 = mk(p.pref_x[q0], p.pref_y[q0]);
             }
@@ -511,9 +505,8 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
         pos = mk(s_px[i], s_py[i]) + vel * p.time_step;  // own pre-step position: still in the staged arena
     }
     CA_PSTAMP(8);
-    // ---- epilogue (ca_step.h, same order of operations; lane 0 of a pair writes) ----
-    typedef const __attribute__((address_space(4))) StepCold ColdP;
-    const ColdP& c = *(ColdP*)p.cold;
+    // ---- epilogue (lane 0 of a pair writes) ----
+    const ColdK& c = *(ColdK*)p.cold;
     pf32 = mk(reinterpret_cast<float*>(s_misc)[i * 4 + 0], reinterpret_cast<float*>(s_misc)[i * 4 + 1]);
     pref = mk(reinterpret_cast<float*>(s_misc)[i * 4 + 2], reinterpret_cast<float*>(s_misc)[i * 4 + 3]);
     {   // how far does any agent of the arena move in this step?
@@ -559,19 +552,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
         }
         pairs = pair_sum(pairs);
         if (active) {
-            bool wall = false;
-            if (p.tab_off == nullptr) {
-                for (int e = 0; e < p.n_obst; ++e) {
-                    const ObstDev o1 = p.obst[e];
-                    if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
-                }
-            } else {
-                const int ne = p.tab_off[a + 1] - p.tab_off[a];
-                for (int e = 0; e < ne; ++e) {
-                    const ObstDev o1 = load_obst(tab, e);
-                    if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
-                }
-            }
+            const bool wall = p.tab_off == nullptr ? touches_wall(p.obst, p.n_obst, pos, R) : touches_wall(tab, p.tab_off[a + 1] - p.tab_off[a], pos, R);
             if (h == 0) {
                 if (pairs) atomicAdd(&red[1], pairs);
                 if (wall) atomicAdd(&red[2], 1);
@@ -586,15 +567,10 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
     if (active) {
         gx = c.goal_x[q]; gy = c.goal_y[q];
         if (p.actions) {
-            const float scale = (float)c.reward_scale;
-            const float r_goal = vel.x * pf32.x + vel.y * pf32.y;
-            const float r_polite = vel.x * pref.x + vel.y * pref.y;  // pref still is the action-rotated direction (env.py:381)
-            rew = scale * r_goal + (1.0f - scale) * r_polite;
+            rew = step_reward(c.reward_scale, vel, pf32, pref);   // pref still is the action-rotated direction (env.py:381)
             if (h == 0) c.reward[q] = rew;
         } else {
-            double dx, dy;
-            pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-            pref = mk((float)dx, (float)dy);
+            pref = goal_dir(pos, gx, gy);
         }
     }
     // ---- step counter and done test (env.py:352-365, 404-410; ALAN:118-121, 547-566) ----
@@ -603,30 +579,15 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
     int done = active ? c.agent_done[q] : 1;
     int steps = active ? c.step_count[a] : 0;
     if (!p.actions && !nodone) ++steps;
-    if (active && !nodone) {
-        bool hit = false;
-        if (c.done_mode == 0) {
-            hit = (done == 0) && (pos.x < c.done_x_thresh);
+    if (active && !nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
+        if (c.done_mode == 2) {
+            regoal_draw(c, a, i, c.regoal_count[q], &gx, &gy);
         } else {
-            const double dx = (double)pos.x - gx, dy = (double)pos.y - gy;
-            const double lim = 2.0 * (double)p.radius;
-            hit = (dx * dx + dy * dy) < lim * lim;
-            if (c.done_mode == 1) hit = hit && (done == 0);
+            done = 1;
+            arrival_goal(c, q, &gx, &gy);
         }
-        if (hit) {
-            if (c.done_mode == 2) {
-                const int rc = c.regoal_count[q];
-                double u0, u1;
-                rng2(c.seed, c.arena_offset + a, i, RNG_REGOAL, (uint32_t)rc, &u0, &u1);
-                gx = uniform64((double)c.goal_x0, (double)c.goal_x1, u0);
-                gy = uniform64((double)c.goal_y0, (double)c.goal_y1, u1);
-            } else {
-                done = 1;
-                gx = c.goal2_x[q]; gy = c.goal2_y[q];
-            }
-            goal_changed = true;
-            if (h == 0) atomicAdd(&red[3], 1);
-        }
+        goal_changed = true;
+        if (h == 0) atomicAdd(&red[3], 1);
     }
     if (p.actions) ++steps;
     if (active && done == 0 && h == 0) atomicAdd(&red[0], 1);
@@ -641,23 +602,14 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
         c.goal_x[q] = gx; c.goal_y[q] = gy;
     }
 
-    bool all_done = false;
-    if (active) {
-        all_done = !nodone && (red[0] == 0);
-        if (c.max_step > 0 && steps >= c.max_step) all_done = true;
-    }
+    const bool all_done = active && episode_over(c, nodone, red[0], steps);
     const bool do_reset = all_done && (p.flags & 4u);  // CA_F_AUTORESET
     int epi = 0;
     if (do_reset) {  // env.py:461-488 for this arena
         epi = c.episode[a];
-        double u0, u1;
-        rng2(c.seed, c.arena_offset + a, i, RNG_RESET, (uint32_t)epi, &u0, &u1);
-        pos = mk((float)uniform64((double)c.spawn_x0, (double)c.spawn_x1, u0),
-                 (float)uniform64((double)c.spawn_y0, (double)c.spawn_y1, u1));
+        pos = spawn_draw(c, a, i, epi);
         done = 0;
-        double dx, dy;
-        pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-        pref = mk((float)dx, (float)dy);
+        pref = goal_dir(pos, gx, gy);
     }
     // sum of rewards: a fixed-shape tree over the wave's agents (lane 0 of every pair carries the value)
     if (p.actions && (p.flags & 2u)) {
@@ -667,28 +619,16 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
             atomicAdd(reinterpret_cast<double*>(&c.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), r);
     }
     // orientation of the observation frame (env.py:236): direction to the goal from the final state
-    float ox = pref.x, oy = pref.y;
-    if (active && !do_reset && (p.actions != nullptr || goal_changed)) {
-        double dx, dy;
-        pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-        ox = (float)dx; oy = (float)dy;
-    }
+    const V2 o = obs_frame(pref, active && !do_reset && (p.actions != nullptr || goal_changed), pos, gx, gy);
     __syncthreads();  // all lanes have read red[] and episode[]
     if (active && h == 0) {
         if (do_reset) c.agent_done[q] = 0;
-        c.orient_x[q] = ox; c.orient_y[q] = oy;
+        c.orient_x[q] = o.x; c.orient_y[q] = o.y;
         c.pos_x[q] = pos.x; c.pos_y[q] = pos.y;
         c.vel_x[q] = vel.x; c.vel_y[q] = vel.y;
         c.pref_x[q] = pref.x; c.pref_y[q] = pref.y;
         if (i == 0) {
-            unsigned long long* st = c.arena_stats + (size_t)a * ST_STRIDE;
-            if (red[1]) st[ST_COLL] += (unsigned)red[1];
-            if (red[2]) st[ST_OBST_COLL] += (unsigned)red[2];
-            if (red[3]) st[ST_GOALS] += (unsigned)red[3];
-            if (all_done) {
-                st[ST_EPISODES] += 1;
-                st[ST_LASTEP] = ((unsigned long long)(unsigned)steps << 32) | (unsigned)(N - red[0]);
-            }
+            flush_stats(c.arena_stats + (size_t)a * ST_STRIDE, red[1], red[2], red[3], all_done ? 1u : 0u, all_done, lastep_word(steps, N, red[0]));
             c.arena_done[a] = all_done ? 1 : 0;
             c.step_count[a] = do_reset ? 0 : steps;
             if (do_reset) c.episode[a] = epi + 1;

@@ -164,8 +164,7 @@ __host__ __device__ inline size_t quad_lds_bytes(int BS, int KMAX, int SQ, int n
 
 // SQ: obstacle-neighbour capacity of the variant (S <= SQ): 4 (the synthetic crowds: one boundary polygon) or 16 (the
 // reference's own worlds: doorway, blocks, tube -- env.py:77-123, ALAN:175-457)
-// ALAN: the online bandit of ALAN_true.py:569-628 around every step of the launch (ca_alan.h has the same arithmetic as kernels
-// of their own for the lane-per-agent path): softmax over the agent's action weights -> one draw -> preferred velocity = goal
+// ALAN: the online bandit of ALAN_true.py:569-628 around every step of the launch (its rules: ca_rules.h): softmax over the agent's action weights -> one draw -> preferred velocity = goal
 // direction rotated by the action -> [the ORCA step] -> reward of the action -> sliding-window update of weights and times.
 // Weights and times live in LDS for the whole launch ([action][agent slot] fp64), the four lanes of a quad share the
 // actions (exp64 of the softmax, the window update), the draw is keyed by (seed, global arena, agent, episode, step) as ever.
@@ -238,7 +237,6 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     float ox = pref.x, oy = pref.y;
     const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
 
-    typedef const __attribute__((address_space(4))) AlanCold AlanK;
     int nA = 0, nk = 0, last_id = 0;
     float last_rew = 0.0f;
     double acc_rew = 0.0;
@@ -270,44 +268,18 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
 #endif
         // ---- preferred velocity of this step (env.py:371-383) and the arena image ----
         V2 pf32 = mk(1.0f, 0.0f);
-        if (active && p.actions) {
-            double pf_x, pf_y, sn, cs;
-            pref_dir64(pos.x, pos.y, gx, gy, &pf_x, &pf_y);
-            sincos64((double)p.actions[gq], &sn, &cs);
-            const double rl_x = pf_x * cs - pf_y * sn;
-            const double rl_y = pf_x * sn + pf_y * cs;
-            pf32 = mk((float)pf_x, (float)pf_y);
-            pref = mk((float)rl_x, (float)rl_y);
-        }
+        if (active && p.actions) action_pref(pos, gx, gy, p.actions[gq], pf32, pref);
         int act_id = 0;
         double dgx = 1.0, dgy = 0.0, dlx = 1.0, dly = 0.0;   // goal direction and rotated direction of this step (ALAN:588-595)
         if constexpr (ALAN) {
             const AlanK& al = *(AlanK*)p.alan;
-            if (active)
-                for (int k = q; k < nk; k += 4) s_ps[k * NS + slot] = exp64(s_w[k * NS + slot] / al.temp);   // ALAN:580-581
+            auto psk = [&](int k) -> double& { return s_ps[k * NS + slot]; };
+            if (active) alan_terms(nk, q, 4, psk, [&](int k) { return s_w[k * NS + slot]; }, al.temp);
             wave_lds_sync();
-            if (active) {   // (the four lanes alike from here: every lane of the quad holds the draw and the directions)
-                const double sum = np_sum(nk, [&](int k) { return s_ps[k * NS + slot]; });
-                double acc = 0.0;
-                for (int k = 0; k < nk; ++k) {   // ALAN:582: the normalised terms, in order (the four lanes of the quad store the
-                    const double v = s_ps[k * NS + slot] / sum;   // same value to the same word: one instruction, in lockstep)
-                    s_ps[k * NS + slot] = v;
-                    acc += v;
-                }
-                double ui, u1;
-                if (p.alan_u) ui = p.alan_u[gq];
-                else rng2(c.seed, c.arena_offset + a, i, RNG_ALAN + (epi << 8), (uint32_t)steps, &ui, &u1);
-                act_id = nk - 1;   // np.random.choice (ALAN:585): first action whose normalised cdf exceeds u
-                double run = 0.0;
-                bool found = false;
-                for (int k = 0; k < nk - 1; ++k) {
-                    run += s_ps[k * NS + slot];
-                    if (!found && run / acc > ui) { act_id = k; found = true; }
-                }
-                pref_dir64(pos.x, pos.y, gx, gy, &dgx, &dgy);                       // ALAN:588
-                double cs, sn;
-                alan_cs<AM>(al, a, act_id, &cs, &sn);                             // ALAN:592-595
-                dlx = dgx * cs - dgy * sn; dly = dgx * sn + dgy * cs;
+            if (active) {   // (the four lanes alike from here: every lane of the quad holds the draw and the directions; the four
+                // lanes store the same normalised term to the same word: one instruction, in lockstep)
+                act_id = alan_draw(nk, psk, [&] { return alan_uniform(p.alan_u, gq, c.seed, c.arena_offset, a, i, epi, steps); });
+                alan_dirs<AM>(al, a, act_id, pos, gx, gy, &dgx, &dgy, &dlx, &dly);
                 pref = mk((float)dlx, (float)dly);                                  // ALAN:598
             }
         }
@@ -475,7 +447,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
             pos = pos + vel * p.time_step;
         }
         CA_STAMP(7);
-        // ---- epilogue (ca_step.h, same order of operations) ----
+        // ---- epilogue ----
         __syncthreads();  // every lane is done with the pre-step arena image
         if (q == 0) { s_px[slot] = pos.x; s_py[slot] = pos.y; }
         if (q == 0) { s_red[slot * 4 + 0] = 0; s_red[slot * 4 + 1] = 0; s_red[slot * 4 + 2] = 0; s_red[slot * 4 + 3] = 0; }
@@ -487,12 +459,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
             if (active)
                 for (int j = i + 1 + q; j < N; j += 4)
                     if (absSq(pos - mk(s_px[lbase + j], s_py[lbase + j])) < crSq) ++pairs;
-            bool wall = false;
-            if (active)
-                for (int e = q; e < nedge; e += 4) {
-                    const ObstDev o1 = load_obst(tab, e);
-                    if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
-                }
+            const bool wall = active && touches_wall(tab, nedge, pos, R, q, 4);
             pairs = quad_sum(pairs);
             const int walls = quad_sum(wall ? 1 : 0);
             if (active && q == 0) {
@@ -505,75 +472,47 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         float rew = 0.0f;
         if (active) {
             if (p.actions) {
-                const float scale = (float)c.reward_scale;
-                const float r_goal = vel.x * pf32.x + vel.y * pf32.y;
-                const float r_polite = vel.x * pref.x + vel.y * pref.y;
-                rew = scale * r_goal + (1.0f - scale) * r_polite;
+                rew = step_reward(c.reward_scale, vel, pf32, pref);
                 if (q == 0) c.reward[gq] = rew;
             } else {
-                double dx, dy;
-                pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-                pref = mk((float)dx, (float)dy);
+                pref = goal_dir(pos, gx, gy);
             }
         }
         CA_STAMP(9);
         // ---- step counter and done test (env.py:352-365, 404-410; ALAN:118-121, 547-566) ----
         bool goal_changed = false;
         if (active && !p.actions && !nodone) ++steps;
-        if (active && !nodone) {
-            bool hit = false;
-            if (c.done_mode == 0) {
-                hit = (done == 0) && (pos.x < c.done_x_thresh);
+        if (active && !nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
+            // (the element index behind an opaque move: the addresses of these rare stores are formed here, per event --
+            // hoisted out of the T-step loop they are nine 64-bit values carried, and at 512 lanes spilled, through every step)
+            int gq_e = gq;
+            if constexpr (BS >= 512) asm volatile("" : "+v"(gq_e));
+            if (c.done_mode == 2) {
+                regoal_draw(c, a, i, rc, &gx, &gy);
+                rc += 1;
+                if (q == 0) c.regoal_count[gq_e] = rc;
             } else {
-                const double dx = (double)pos.x - gx, dy = (double)pos.y - gy;
-                const double lim = 2.0 * (double)p.radius;
-                hit = (dx * dx + dy * dy) < lim * lim;
-                if (c.done_mode == 1) hit = hit && (done == 0);
+                done = 1;
+                arrival_goal(c, gq_e, &gx, &gy);
+                if (q == 0) { c.arrive_step[gq_e] = steps; c.agent_done[gq_e] = 1; }
             }
-            if (hit) {
-                // (the element index behind an opaque move: the addresses of these rare stores are formed here, per event --
-                // hoisted out of the T-step loop they are nine 64-bit values carried, and at 512 lanes spilled, through every step)
-                int gq_e = gq;
-                if constexpr (BS >= 512) asm volatile("" : "+v"(gq_e));
-                if (c.done_mode == 2) {
-                    double u0, u1;
-                    rng2(c.seed, c.arena_offset + a, i, RNG_REGOAL, (uint32_t)rc, &u0, &u1);
-                    gx = uniform64((double)c.goal_x0, (double)c.goal_x1, u0);
-                    gy = uniform64((double)c.goal_y0, (double)c.goal_y1, u1);
-                    rc += 1;
-                    if (q == 0) c.regoal_count[gq_e] = rc;
-                } else {
-                    done = 1;
-                    gx = c.goal2_x[gq_e]; gy = c.goal2_y[gq_e];
-                    if (q == 0) { c.arrive_step[gq_e] = steps; c.agent_done[gq_e] = 1; }
-                }
-                if (q == 0) { c.goal_x[gq_e] = gx; c.goal_y[gq_e] = gy; }
-                goal_changed = true;
-                if (q == 0) atomicAdd(&red[3], 1);
-            }
+            if (q == 0) { c.goal_x[gq_e] = gx; c.goal_y[gq_e] = gy; }
+            goal_changed = true;
+            if (q == 0) atomicAdd(&red[3], 1);
         }
         if (active && p.actions) ++steps;
         if (active && done == 0 && q == 0) atomicAdd(&red[0], 1);
         __syncthreads();
 
-        bool all_done = false;
-        if (active) {
-            all_done = !nodone && (red[0] == 0);
-            if (c.max_step > 0 && steps >= c.max_step) all_done = true;
-        }
+        const bool all_done = active && episode_over(c, nodone, red[0], steps);
         const bool do_reset = all_done && (p.flags & 4u);  // CA_F_AUTORESET
         if (do_reset) {  // env.py:461-488 for this arena
-            double u0, u1;
-            rng2(c.seed, c.arena_offset + a, i, RNG_RESET, (uint32_t)epi, &u0, &u1);
-            pos = mk((float)uniform64((double)c.spawn_x0, (double)c.spawn_x1, u0),
-                     (float)uniform64((double)c.spawn_y0, (double)c.spawn_y1, u1));
+            pos = spawn_draw(c, a, i, epi);
             done = 0;
             int gq_r = gq;
             if constexpr (BS >= 512) asm volatile("" : "+v"(gq_r));
             if (q == 0) c.agent_done[gq_r] = 0;
-            double dx, dy;
-            pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-            pref = mk((float)dx, (float)dy);
+            pref = goal_dir(pos, gx, gy);
         }
         CA_STAMP(10);
         // sum of rewards: the fixed-shape tree of ca_step.h over agent slots (one lane per slot here)
@@ -592,33 +531,14 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
             }
         }
         // orientation of the observation frame (env.py:236): direction to the goal from the final state
-        if (active) {
-            ox = pref.x; oy = pref.y;
-            if (!do_reset && (p.actions != nullptr || goal_changed)) {
-                double dx, dy;
-                pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-                ox = (float)dx; oy = (float)dy;
-            }
-        }
+        if (active) { const V2 o = obs_frame(pref, !do_reset && (p.actions != nullptr || goal_changed), pos, gx, gy); ox = o.x; oy = o.y; }
         if constexpr (ALAN) {   // reward of the executed action and the sliding-window update (ALAN:603-628)
             const AlanK& al = *(AlanK*)p.alan;
             if (active) {
-                {   // env.py:389-400 in fp32, as ca_step reports it
-                    const float scale = (float)al.reward_scale;
-                    const float r_goal = vel.x * (float)dgx + vel.y * (float)dgy;
-                    const float r_polite = vel.x * (float)dlx + vel.y * (float)dly;
-                    last_rew = scale * r_goal + (1.0f - scale) * r_polite;
-                    acc_rew += (double)last_rew;
-                }
-                const double vx = (double)vel.x, vy = (double)vel.y;
-                const double Rw = al.reward_scale * (vx * dgx + vy * dgy) + (1.0 - al.reward_scale) * (vx * dlx + vy * dly);
-                for (int k = q; k < nk; k += 4) {
-                    double tk = s_t[k * NS + slot] + al.dt;
-                    double wk = s_w[k * NS + slot];
-                    if (tk >= al.window) { tk = 0.0; wk = 0.0; }
-                    if (k == act_id) wk = Rw;
-                    s_t[k * NS + slot] = tk; s_w[k * NS + slot] = wk;
-                }
+                last_rew = step_reward(al.reward_scale, vel, mk((float)dgx, (float)dgy), mk((float)dlx, (float)dly));
+                acc_rew += (double)last_rew;
+                alan_update(al, vel, dgx, dgy, dlx, dly, act_id, nk, q, 4, [&](int k) -> double& { return s_w[k * NS + slot]; },
+                            [&](int k) -> double& { return s_t[k * NS + slot]; });
                 pref = mk((float)dlx, (float)dly);   // the agent still holds the velocity it was given at ALAN:598
                 last_id = act_id;
             }
@@ -629,7 +549,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
             acc_coll += (unsigned)red[1]; acc_wall += (unsigned)red[2]; acc_goals += (unsigned)red[3];
             if (all_done) {
                 acc_epis += 1;
-                lastep = ((unsigned long long)(unsigned)steps << 32) | (unsigned)(N - red[0]);
+                lastep = lastep_word(steps, N, red[0]);
                 have_lastep = true;
             }
             if (do_reset) c.episode[a] = epi + 1;
@@ -665,12 +585,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         c.pref_x[gq] = pref.x; c.pref_y[gq] = pref.y;
         if (acc_ovf) atomicAdd(reinterpret_cast<unsigned*>(&p.arena_stats[(size_t)a * ST_STRIDE + ST_OVERFLOW]), acc_ovf);
         if (i == 0) {
-            unsigned long long* st = c.arena_stats + (size_t)a * ST_STRIDE;
-            if (acc_coll) st[ST_COLL] += acc_coll;
-            if (acc_wall) st[ST_OBST_COLL] += acc_wall;
-            if (acc_goals) st[ST_GOALS] += acc_goals;
-            if (acc_epis) st[ST_EPISODES] += acc_epis;
-            if (have_lastep) st[ST_LASTEP] = lastep;
+            flush_stats(c.arena_stats + (size_t)a * ST_STRIDE, acc_coll, acc_wall, acc_goals, acc_epis, have_lastep, lastep);
             c.arena_done[a] = adone;
             c.step_count[a] = steps;
             atomicAdd(&c.arena_steps[a], (unsigned long long)acc_steps);

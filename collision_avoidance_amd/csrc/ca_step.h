@@ -4,7 +4,7 @@
 #include "ca_lp.h"
 #include "ca_lines.h"
 #include "ca_nbr.h"
-#include "ca_alan.h"
+#include "ca_rules.h"
 
 namespace ca {
 
@@ -27,7 +27,6 @@ __host__ __device__ inline size_t step_lds_bytes(int BS, int K, int S, int ST = 
 //         LP3 through a small per-wave LDS pool.  Needs S <= ST; ~8 KB of LDS per wave instead of
 //         16 KB; built for 4 waves per SIMD (<= 128 VGPRs), i.e. 16 waves per CU: the 4096 arenas
 //         of the C3 workload are all resident at once instead of taking 1.6 rounds at 10 per CU.
-typedef const __attribute__((address_space(4))) StepCold ColdK;  // the cold block through the constant address space
 
 // An agent with MORE obstacle neighbours than the register-line kernel has obstacle slots (ST): solved apart, by its own
 // lane alone, exactly as the contract says -- every half-plane built in order into an LDS table of its own (the wave's LP3
@@ -86,7 +85,7 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 // four-lanes kernel (ca_quad.h) -- softmax draw and rotated preferred velocity in the prologue (the softmax terms wait in the wave's
 // LP3 pool, which is free then: at most ML actions), reward and the sliding-window update of weights / times (global memory,
 // [A][nA][N]) where the epilogue begins; the goal direction is derived again there from the staged pre-step position instead of
-// living in registers across the solve.  Same arithmetic as ca_alan.h's kernels, which remain the three-launch form of the rest.
+// living in registers across the solve.  The rules are ca_rules.h's, as in ca_alan.h's kernels (the three-launch form of the rest).
 // PER (ALAN instantiation only): AlanArenaSets = an action set per arena (ca_alan_configure_per_arena; ca_common.h
 // alan_count / alan_cs); a trailing pack, empty in every other instantiation, so that those keep their names and their code.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
@@ -139,16 +138,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     if (active) {
         pos = mk(p.pos_x[q], p.pos_y[q]);
         vel = mk(p.vel_x[q], p.vel_y[q]);
-        if (p.actions) {  // env.py:371-383
-            double pf_x, pf_y, sn, cs;
-            pref_dir64(pos.x, pos.y, p.goal_x[q], p.goal_y[q], &pf_x, &pf_y);
-            sincos64((double)p.actions[q], &sn, &cs);
-            const double rl_x = pf_x * cs - pf_y * sn;
-            const double rl_y = pf_x * sn + pf_y * cs;
-            pf32 = mk((float)pf_x, (float)pf_y);
-            pref = mk((float)rl_x, (float)rl_y);
+        if (p.actions) {
+            action_pref(pos, p.goal_x[q], p.goal_y[q], p.actions[q], pf32, pref);
         } else if constexpr (ALAN) {   // ALAN:578-598: softmax over the action weights, one draw, goal direction rotated by the action
-            typedef const __attribute__((address_space(4))) AlanCold AlanK;
             const AlanK& al = *(AlanK*)p.alan;
             const int nA = al.nA, nk = alan_count<AM>(al, a);   // stride | this arena's actions (ALAN = 2: a set per arena)
             // [k][lane] in the wave's LP3 pool (ML doubles per lane), or -- LDS line table -- over the table itself, which is
@@ -157,28 +149,13 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             double* ps = ST > 0 ? reinterpret_cast<double*>(s_lines + (size_t)(tid >> 6) * (2 * ML) * POOL_SLOTS) + (tid & 63)
                                 : reinterpret_cast<double*>(s_lines) + tid;
             const double* w = al.w + (size_t)a * nA * N + i;
-            for (int k = 0; k < nk; ++k) ps[k * PSTR] = exp64(w[(size_t)k * N] / al.temp);
-            const double sum = np_sum(nk, [&](int k) { return ps[k * PSTR]; });
-            double acc = 0.0;
-            for (int k = 0; k < nk; ++k) { const double v = ps[k * PSTR] / sum; ps[k * PSTR] = v; acc += v; }
-            double ui, u1;
-            if (p.alan_u) ui = p.alan_u[q];
-            else {
-                const StepCold* cp = p.cold;
-                rng2(cp->seed, cp->arena_offset + a, i, RNG_ALAN + (cp->episode[a] << 8), (uint32_t)cp->step_count[a], &ui, &u1);
-            }
-            int act_id = nk - 1;
-            double run = 0.0;
-            bool found = false;
-            for (int k = 0; k < nk - 1; ++k) {
-                run += ps[k * PSTR];
-                if (!found && run / acc > ui) { act_id = k; found = true; }
-            }
-            double dgx, dgy;
-            pref_dir64(pos.x, pos.y, p.goal_x[q], p.goal_y[q], &dgx, &dgy);
-            double cs, sn;
-            alan_cs<AM>(al, a, act_id, &cs, &sn);
-            pref = mk((float)(dgx * cs - dgy * sn), (float)(dgx * sn + dgy * cs));
+            auto psk = [&](int k) -> double& { return ps[k * PSTR]; };
+            alan_terms(nk, 0, 1, psk, [&](int k) { return w[(size_t)k * N]; }, al.temp);
+            const StepCold* cp = p.cold;
+            const int act_id = alan_draw(nk, psk, [&] { return alan_uniform(p.alan_u, q, cp->seed, cp->arena_offset, a, i, cp->episode[a], cp->step_count[a]); });
+            double dgx, dgy, dlx, dly;
+            alan_dirs<AM>(al, a, act_id, pos, p.goal_x[q], p.goal_y[q], &dgx, &dgy, &dlx, &dly);
+            pref = mk((float)dlx, (float)dly);
             pf32 = mk(__int_as_float(act_id), 0.0f);   // (the lane's slot of the goal direction carries the action: no action tensor here)
         } else {
             pref = mk(p.pref_x[q], p.pref_y[q]);
@@ -450,33 +427,17 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     if constexpr (PARK_PREF) pref = mk(reinterpret_cast<float*>(s_misc)[tid * 4 + 2], reinterpret_cast<float*>(s_misc)[tid * 4 + 3]);
     float rew_alan = 0.0f;
     if constexpr (ALAN) {   // ALAN:603-628: reward of the executed action, sliding-window update (the staged arena still is the pre-step one)
-        typedef const __attribute__((address_space(4))) AlanCold AlanK;
         const AlanK& al = *(AlanK*)p.alan;
         if (active) {
             const int act_id = __float_as_int(pf32.x), nA = al.nA, nk = alan_count<AM>(al, a);
-            double dgx, dgy;
-            pref_dir64(s_px[tid], s_py[tid], c.goal_x[q], c.goal_y[q], &dgx, &dgy);   // the prologue's values again, bit for bit
-            double cs, sn;
-            alan_cs<AM>(al, a, act_id, &cs, &sn);
-            const double dlx = dgx * cs - dgy * sn, dly = dgx * sn + dgy * cs;
-            {
-                const float scale = (float)al.reward_scale;
-                const float r_goal = vel.x * (float)dgx + vel.y * (float)dgy;
-                const float r_polite = vel.x * (float)dlx + vel.y * (float)dly;
-                rew_alan = scale * r_goal + (1.0f - scale) * r_polite;
-                al.reward[q] = rew_alan;
-            }
-            const double vx = (double)vel.x, vy = (double)vel.y;
-            const double Rw = al.reward_scale * (vx * dgx + vy * dgy) + (1.0 - al.reward_scale) * (vx * dlx + vy * dly);
+            double dgx, dgy, dlx, dly;   // the prologue's values again, bit for bit
+            alan_dirs<AM>(al, a, act_id, mk(s_px[tid], s_py[tid]), c.goal_x[q], c.goal_y[q], &dgx, &dgy, &dlx, &dly);
+            rew_alan = step_reward(al.reward_scale, vel, mk((float)dgx, (float)dgy), mk((float)dlx, (float)dly));
+            al.reward[q] = rew_alan;
             double* w = al.w + (size_t)a * nA * N + i;
             double* t = al.t + (size_t)a * nA * N + i;
-            for (int k = 0; k < nk; ++k) {
-                double tk = t[(size_t)k * N] + al.dt;
-                double wk = w[(size_t)k * N];
-                if (tk >= al.window) { tk = 0.0; wk = 0.0; }
-                if (k == act_id) wk = Rw;
-                t[(size_t)k * N] = tk; w[(size_t)k * N] = wk;
-            }
+            alan_update(al, vel, dgx, dgy, dlx, dly, act_id, nk, 0, 1, [&](int k) -> double& { return w[(size_t)k * N]; },
+                        [&](int k) -> double& { return t[(size_t)k * N]; });
             al.action[q] = act_id;
             c.pref_x[q] = (float)dlx; c.pref_y[q] = (float)dly;   // the agent still holds the velocity it was given at ALAN:598
         }
@@ -552,20 +513,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             if (!(N & 1) && N > 1) { const int h = N >> 1; if (i < h) pairs += near(h); }
         }
         if (active) {
-            bool wall = false;
-            if (p.tab_off == nullptr) {
-                for (int e = 0; e < p.n_obst; ++e) {
-                    const ObstDev o1 = p.obst[e];
-                    if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
-                }
-            } else {
-                const int ne = p.tab_off[a + 1] - p.tab_off[a];
-                for (int e = 0; e < ne; ++e) {
-                    const ObstDev o1 = load_obst(tab, e);
-                    if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
-                }
-            }
             if (pairs) atomicAdd(&red[1], pairs);
+            // (one table for every arena: a loop of one trip count, the records through the argument pointer)
+            const bool wall = p.tab_off == nullptr ? touches_wall(p.obst, p.n_obst, pos, R) : touches_wall(tab, p.tab_off[a + 1] - p.tab_off[a], pos, R);
             if (wall) atomicAdd(&red[2], 1);
         }
     }
@@ -578,15 +528,10 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     if (active) {
         gx = c.goal_x[q]; gy = c.goal_y[q];
         if (p.actions) {
-            const float scale = (float)c.reward_scale;
-            const float r_goal = vel.x * pf32.x + vel.y * pf32.y;
-            const float r_polite = vel.x * pref.x + vel.y * pref.y;  // pref still is the action-rotated direction (env.py:381)
-            rew = scale * r_goal + (1.0f - scale) * r_polite;
+            rew = step_reward(c.reward_scale, vel, pf32, pref);   // pref still is the action-rotated direction (env.py:381)
             c.reward[q] = rew;
         } else {
-            double dx, dy;
-            pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-            pref = mk((float)dx, (float)dy);
+            pref = goal_dir(pos, gx, gy);
         }
     }
 
@@ -597,57 +542,34 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     int done = active ? c.agent_done[q] : 1;
     int steps = active ? c.step_count[a] : 0;
     if (!p.actions && !nodone) ++steps;
-    if (active && !nodone) {
-        bool hit = false;
-        if (c.done_mode == 0) {
-            hit = (done == 0) && (pos.x < c.done_x_thresh);
+    if (active && !nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
+        if (c.done_mode == 2) {
+            const int rc = c.regoal_count[q];
+            regoal_draw(c, a, i, rc, &gx, &gy);
+            c.regoal_count[q] = rc + 1;
         } else {
-            const double dx = (double)pos.x - gx, dy = (double)pos.y - gy;
-            const double lim = 2.0 * (double)p.radius;
-            hit = (dx * dx + dy * dy) < lim * lim;
-            if (c.done_mode == 1) hit = hit && (done == 0);
+            done = 1;
+            c.arrive_step[q] = steps;
+            arrival_goal(c, q, &gx, &gy);
+            c.agent_done[q] = 1;
         }
-        if (hit) {
-            if (c.done_mode == 2) {
-                const int rc = c.regoal_count[q];
-                double u0, u1;
-                rng2(c.seed, c.arena_offset + a, i, RNG_REGOAL, (uint32_t)rc, &u0, &u1);
-                gx = uniform64((double)c.goal_x0, (double)c.goal_x1, u0);
-                gy = uniform64((double)c.goal_y0, (double)c.goal_y1, u1);
-                c.regoal_count[q] = rc + 1;
-            } else {
-                done = 1;
-                c.arrive_step[q] = steps;
-                gx = c.goal2_x[q]; gy = c.goal2_y[q];
-                c.agent_done[q] = 1;
-            }
-            c.goal_x[q] = gx; c.goal_y[q] = gy;
-            goal_changed = true;
-            atomicAdd(&red[3], 1);
-        }
+        c.goal_x[q] = gx; c.goal_y[q] = gy;
+        goal_changed = true;
+        atomicAdd(&red[3], 1);
     }
     if (p.actions) ++steps;
     if (active && done == 0) atomicAdd(&red[0], 1);
     __syncthreads();
 
-    bool all_done = false;
-    if (active) {
-        all_done = !nodone && (red[0] == 0);
-        if (c.max_step > 0 && steps >= c.max_step) all_done = true;
-    }
+    const bool all_done = active && episode_over(c, nodone, red[0], steps);
     const bool do_reset = all_done && (p.flags & 4u);  // CA_F_AUTORESET
     int epi = 0;
     if (do_reset) {  // env.py:461-488 for this arena
         epi = c.episode[a];
-        double u0, u1;
-        rng2(c.seed, c.arena_offset + a, i, RNG_RESET, (uint32_t)epi, &u0, &u1);
-        pos = mk((float)uniform64((double)c.spawn_x0, (double)c.spawn_x1, u0),
-                 (float)uniform64((double)c.spawn_y0, (double)c.spawn_y1, u1));
+        pos = spawn_draw(c, a, i, epi);
         done = 0;
         c.agent_done[q] = 0;
-        double dx, dy;
-        pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-        pref = mk((float)dx, (float)dy);
+        pref = goal_dir(pos, gx, gy);
     }
     // sum of rewards: fixed-shape tree inside the wave, then per-arena in lane order
     if ((p.actions || ALAN) && (p.flags & 2u)) {
@@ -659,15 +581,8 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
         if (active && (i & 63) == 0)
             atomicAdd(reinterpret_cast<double*>(&c.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), r);
     }
-    // orientation of the observation frame (env.py:236): direction to the goal from the final state.
-    // After an ORCA-only step or a reset `pref` already is that vector; otherwise derive it here, once
-    // per agent, instead of in each of the 16 ray lanes of the observation kernel.
-    float ox = pref.x, oy = pref.y;
-    if (active && !do_reset && (p.actions != nullptr || goal_changed)) {
-        double dx, dy;
-        pref_dir64(pos.x, pos.y, gx, gy, &dx, &dy);
-        ox = (float)dx; oy = (float)dy;
-    }
+    const V2 o = obs_frame(pref, active && !do_reset && (p.actions != nullptr || goal_changed), pos, gx, gy);
+    const float ox = o.x, oy = o.y;
     CA_STAMP(10);
     __syncthreads();  // all lanes have read red[] and episode[]
     if (active) {
@@ -683,14 +598,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
         if constexpr (!ALAN) { c.pref_x[q] = pref.x; c.pref_y[q] = pref.y; }   // (ALAN: written above)
 #endif
         if (i == 0) {
-            unsigned long long* st = c.arena_stats + (size_t)a * ST_STRIDE;
-            if (red[1]) st[ST_COLL] += (unsigned)red[1];
-            if (red[2]) st[ST_OBST_COLL] += (unsigned)red[2];
-            if (red[3]) st[ST_GOALS] += (unsigned)red[3];
-            if (all_done) {  // + what a caller that auto-resets wants to know about the episode that ended
-                st[ST_EPISODES] += 1;
-                st[ST_LASTEP] = ((unsigned long long)(unsigned)steps << 32) | (unsigned)(N - red[0]);
-            }
+            flush_stats(c.arena_stats + (size_t)a * ST_STRIDE, red[1], red[2], red[3], all_done ? 1u : 0u, all_done, lastep_word(steps, N, red[0]));
             c.arena_done[a] = all_done ? 1 : 0;
             c.step_count[a] = do_reset ? 0 : steps;
             atomicAdd(&c.arena_steps[a], 1ull);   // (no return value: nothing waits for it at the end of the kernel)
@@ -715,16 +623,12 @@ __global__ void reset_kernel(const StepArgs p) {
     if (p.reset_px) {
         pos = mk(p.reset_px[q], p.reset_py[q]);
     } else {
-        double u0, u1;
-        rng2(c.seed, c.arena_offset + a, i, RNG_RESET, (uint32_t)c.episode[a], &u0, &u1);
-        pos = mk((float)uniform64((double)c.spawn_x0, (double)c.spawn_x1, u0),
-                 (float)uniform64((double)c.spawn_y0, (double)c.spawn_y1, u1));
+        pos = spawn_draw(c, a, i, c.episode[a]);
     }
-    double dx, dy;
-    pref_dir64(pos.x, pos.y, c.goal_x[q], c.goal_y[q], &dx, &dy);
+    const V2 d = goal_dir(pos, c.goal_x[q], c.goal_y[q]);
     c.pos_x[q] = pos.x; c.pos_y[q] = pos.y;
-    c.pref_x[q] = (float)dx; c.pref_y[q] = (float)dy;
-    c.orient_x[q] = (float)dx; c.orient_y[q] = (float)dy;
+    c.pref_x[q] = d.x; c.pref_y[q] = d.y;
+    c.orient_x[q] = d.x; c.orient_y[q] = d.y;
     c.agent_done[q] = 0;
 }
 // orientation from scratch (after the caller overwrote positions or goals through ca_set)
