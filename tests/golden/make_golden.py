@@ -14,10 +14,13 @@ none of its source is copied: the fixtures hold inputs and the outputs the refer
   alan_scenarios.npz  ALAN_true.py scenario generators: start/goal layouts and obstacle polygons.
   alan_online.npz     ALAN_true.py online_step runs (softmax selection, weights, arrival times, TTime).
   alan_orca.npz       ALAN_true.py run_sim(mode=0) episodes (orca_step + counter + done_test).
+  env_n64_k10.npz     the same env loop at the shape the bench times: 64 agents, neighborDist 5, maxNeighbors 10
+  overspeed_n64_k10.npz  agent-steps of a second such run whose ORCA answer leaves the speed disc, once by a factor of 32
+  utils_vectors_k10.npz  comp_laser with the 5.0 ray table on 60-84 segments (ten octagons + walls)
   alan_blocks.npz     three "blocks" worlds as the reference draws them (ALAN_true.py:333-374: four random blocks per
                       simulator, re-drawn by reset()), their polygons, and run_sim(mode=0) in each.
 
-Usage: python tests/golden/make_golden.py
+Usage: python tests/golden/make_golden.py [blocks | round5 | headline]
 """
 import importlib.util
 import os
@@ -121,6 +124,92 @@ def gen_utils_vectors():
     print("utils_vectors.npz: %d line_intersection, %d comp_laser cases" % (len(li_in), len(cases_out)))
 
 
+def gen_utils_vectors_k10():
+    """comp_laser alone at the headline range: the ray table at 5.0 and 60-84 segments per case (ten neighbours'
+    octagons + 0-4 wall segments), among them a neighbour nearer than the octagon's inradius 0.5 cos(pi / 8) = 0.4619
+    (the ray origin inside its octagon), two octagons at the same distance along one ray, and a wall through the origin."""
+    u = load_ref_utils()
+    rng = np.random.RandomState(4321)
+    from math import cos, sin, pi
+    nd, nr = 5.0, 16
+    rays = [((0, 0), (nd * cos(i * 2 * pi / nr), -nd * sin(i * 2 * pi / nr))) for i in range(nr)]
+    cases_segs, cases_orient, cases_out = [], [], []
+
+    def octagon(rel, r=0.5, n=8):
+        pts = [(r * cos(i * 2 * pi / n), -r * sin(i * 2 * pi / n)) for i in range(n)]
+        return [((pts[i][0] + rel[0], pts[i][1] + rel[1]),
+                 (pts[(i + 1) % n][0] + rel[0], pts[(i + 1) % n][1] + rel[1])) for i in range(n)]
+
+    def run_case(centres, walls, orient, same_vel=()):
+        """same_vel: two octagons that tie on a ray carry one velocity -- which of two equal distances the reference's
+        argsort puts first is numpy's choice, so a fixture must not depend on it"""
+        lw, vels = [], [tuple(rng.uniform(-1, 1, 2)) for _ in centres]
+        if same_vel:
+            vels[same_vel[1]] = vels[same_vel[0]]
+        for c, vel in zip(centres, vels):
+            lw += [(s, vel) for s in octagon(c)]
+        lw += [(w, (0, 0)) for w in walls]
+        assert 60 <= len(lw) <= 84 and len(centres) == 10
+        res = u.comp_laser(rays, lw, orient)
+        cases_out.append(np.array([[r[0][0], r[0][1], r[1][0], r[1][1]] for r in res], np.float64))
+        cases_segs.append(np.array([[l[0][0][0], l[0][0][1], l[0][1][0], l[0][1][1], l[1][0], l[1][1]] for l in lw], np.float64))
+        cases_orient.append(orient)
+
+    def polar(dist, ang):
+        return (dist * cos(ang), dist * sin(ang))
+
+    def wall():
+        p = rng.uniform(-5.5, 5.5, 4)
+        return ((p[0], p[1]), (p[2], p[3]))
+
+    for k in range(36):
+        # nearest first, as the simulator lists them; overlapping octagons are what a dense arena gives
+        dist = np.sort(rng.uniform(0.5, 5.0, 10))
+        centres = [polar(d, rng.uniform(0, 2 * pi)) for d in dist]
+        walls = [wall() for _ in range(k % 5)]
+        th = rng.uniform(0, 2 * pi)
+        if k % 4 == 1:      # the ray origin inside the nearest neighbour's octagon (inradius 0.4619)
+            centres[0] = polar(rng.uniform(0.02, 0.45), rng.uniform(0, 2 * pi))
+        elif k % 4 == 2:    # ... and inside two of them
+            centres[0] = polar(rng.uniform(0.02, 0.3), rng.uniform(0, 2 * pi))
+            centres[1] = polar(rng.uniform(0.3, 0.45), rng.uniform(0, 2 * pi))
+        same = ()
+        if k % 4 == 3:      # two octagons at the same distance along ray j and its neighbours: the second a copy of the first
+            j = rng.randint(nr)
+            ang = -j * 2 * pi / nr - th
+            centres[3] = polar(rng.uniform(1.0, 4.0), ang)
+            centres[4] = centres[3]
+            same = (3, 4)
+        orient = (cos(th), sin(th))
+        if k % 6 == 0:
+            # a wall through the origin: t = 0, d = 0, the hit (0, 0) is reported as a miss (utils.py:103) and hides whatever
+            # lies behind -- on the rays that cross it with denom > 0; with denom < 0 the test `(t_numer < 0) == denom_is_positive`
+            # (utils.py:27) lets the ray through.  Which of the two depends on the sign of a t_numer that is zero only if no
+            # rounding touches it: no rotation (orientation (1, 0)) and end points a * u, b * u with few mantissa bits, so that
+            # the case is the same exact zero in fp64 and in fp32.
+            ux, uy = [(1.0, 0.0), (0.0, 1.0), (1.0, 0.5), (-0.5, 1.0), (1.0, 1.0), (0.25, -1.0)][(k // 6) % 6]
+            a, b = 0.5 * rng.randint(2, 9), 0.5 * rng.randint(2, 9)
+            walls = walls[:3] + [((-a * ux, -a * uy), (b * ux, b * uy))]
+            orient = (1.0, 0.0)
+        run_case(centres, walls, orient, same)
+    # the same tie, mirrored: two different octagons whose facing vertices meet ray 0 at one point (x = 2.0)
+    centres = [polar(d, a) for d, a in zip(np.sort(rng.uniform(2.6, 5.0, 8)), rng.uniform(0.5, 5.7, 8))]
+    run_case([(1.5, 0.0), (2.5, 0.0)] + centres, [wall(), wall()], (1.0, 0.0), (0, 1))
+    # two axis-aligned walls through the origin, one along rays 0 and 8 (collinear: denom = 0), ten octagons around them
+    centres = [polar(d, a) for d, a in zip(np.sort(rng.uniform(0.6, 5.0, 10)), rng.uniform(0, 2 * pi, 10))]
+    run_case(centres, [((-3.0, 0.0), (3.0, 0.0)), ((0.0, -2.0), (0.0, 2.0))], (1.0, 0.0))
+    m = max(s.shape[0] for s in cases_segs)
+    segs = np.zeros((len(cases_segs), m, 6)); counts = np.zeros(len(cases_segs), np.int32)
+    for i, s in enumerate(cases_segs):
+        segs[i, :s.shape[0]] = s; counts[i] = s.shape[0]
+    np.savez_compressed(os.path.join(HERE, "utils_vectors_k10.npz"),
+                        rays=np.array([r[1] for r in rays], np.float64), neighbor_dist=np.float64(nd),
+                        cl_segs=segs, cl_counts=counts,
+                        cl_orient=np.array(cases_orient, np.float64),
+                        cl_out=np.array(cases_out, np.float64))
+    print("utils_vectors_k10.npz: %d comp_laser cases of %d..%d segments" % (len(cases_out), counts.min(), counts.max()))
+
+
 # ---------------------------------------------------------------------------------------------
 class _Stream:
     """Seeded replacement for random.uniform; records what it hands out."""
@@ -203,10 +292,16 @@ def obs_array(env, d):
 
 
 def gen_env_fixture(name, n_agents, seed, n_steps, reset_at, obs_every, spawn_squeeze=None, act_scale=None,
-                    orca_every=17, reset_on_done=False, after_reset_steps=0):
+                    orca_every=17, reset_on_done=False, after_reset_steps=0, neighbor_dist=None, max_neighbors=None,
+                    obs_at=None):
     """act_scale: actions ~ U(-act_scale, act_scale) (agents pass the door); reset_on_done: the caller's protocol
     (run_rllib.py's workers): the step after '__all__' comes back True is preceded by env.reset(), and the run ends
-    after_reset_steps steps later -- the END of an episode: env.py:352-365, 404-414, 461-488."""
+    after_reset_steps steps later -- the END of an episode: env.py:352-365, 404-414, 461-488.
+    neighbor_dist / max_neighbors: the reference class has no such arguments; its constructor sets the two constants
+    and then calls _init_comp_laser_rays (env.py:28-29, 59) before it makes the simulator, so that method is wrapped
+    to overwrite them first -- the ray table, the simulator and every agent are then built by the reference's own code
+    at the given range.  The file then also holds neighbor_dist, max_neighbors, step_count and, per step, the
+    simulator's neighbour counts.  obs_at: the steps whose observation is kept, instead of the obs_every rule."""
     import warnings
     warnings.simplefilter("ignore")
     import collision_avoidance.envs.collision_avoidence_env as refenv
@@ -225,7 +320,22 @@ def gen_env_fixture(name, n_agents, seed, n_steps, reset_at, obs_every, spawn_sq
         refenv.uniform = stream
     import io
     import contextlib
-    env = refenv.Collision_Avoidance_Env(numAgents=n_agents)
+    headline = neighbor_dist is not None
+    if headline:
+        cls = refenv.Collision_Avoidance_Env
+        inner = cls._init_comp_laser_rays
+
+        def rays_at_range(self):
+            self.neighborDist, self.maxNeighbors = float(neighbor_dist), int(max_neighbors)
+            inner(self)
+        cls._init_comp_laser_rays = rays_at_range
+        try:
+            env = cls(numAgents=n_agents)
+        finally:
+            cls._init_comp_laser_rays = inner
+        assert env.neighborDist == neighbor_dist and env.maxNeighbors == max_neighbors
+    else:
+        env = refenv.Collision_Avoidance_Env(numAgents=n_agents)
     rng = np.random.RandomState(seed + 1)
     rec = dict(actions=[], pos=[], vel=[], pref=[], tgt=[], reward=[], done_all=[], agents_done=[],
                obs=[], obs_steps=[], reset_steps=[], reset_pos=[], reset_obs=[], kind=[])
@@ -233,6 +343,8 @@ def gen_env_fixture(name, n_agents, seed, n_steps, reset_at, obs_every, spawn_sq
     init = dict(pos0=p, vel0=v, pref0=pf, tgt0=t, obs0=obs_array(env, env.gym_obs))
     pending_reset, last = False, n_steps
     rec["step_count"] = []
+    if headline:
+        rec["nb_count"], rec["obst_count"] = [], []
     for s in range(n_steps):
         if s >= last:
             break
@@ -267,12 +379,18 @@ def gen_env_fixture(name, n_agents, seed, n_steps, reset_at, obs_every, spawn_sq
         rec["kind"].append(kind); rec["actions"].append(act); rec["pos"].append(p); rec["vel"].append(v)
         rec["pref"].append(pf); rec["tgt"].append(t); rec["reward"].append(rew)
         rec["done_all"].append(done_all); rec["agents_done"].append(np.array(env.agents_done, np.int32))
-        if s % obs_every == 0 or s < 24 or kind == 1:
+        if headline:
+            rec["nb_count"].append(np.array([env.sim.getAgentNumAgentNeighbors(i) for i in range(n_agents)], np.uint8))
+            rec["obst_count"].append(np.array([env.sim.getAgentNumObstacleNeighbors(i) for i in range(n_agents)], np.uint8))
+        if (s in obs_at) if obs_at is not None else (s % obs_every == 0 or s < 24 or kind == 1):
             rec["obs"].append(obs_array(env, o)); rec["obs_steps"].append(s)
-    if not reset_on_done:
+    if not reset_on_done and not headline:
         del rec["step_count"]         # the fixtures of rounds 1-4 regenerate byte for byte
     out = {k: np.array(v) for k, v in rec.items()}
     out.update(init)
+    if headline:
+        out["neighbor_dist"] = np.float64(neighbor_dist)
+        out["max_neighbors"] = np.int32(max_neighbors)
     out["n_agents"] = np.int32(n_agents)
     out["step_count_final"] = np.int32(env.step_count)
     np.savez_compressed(os.path.join(HERE, name), **out)
@@ -560,9 +678,47 @@ def gen_round5():
     gen_alan_finished()
 
 
+HEADLINE_OBS_AT = (0, 1, 2, 3, 4, 5, 16, 24, 33, 60, 75, 90, 105, 120, 135, 150, 186, 199, 200, 201, 202, 203, 220, 239)
+
+
+def gen_headline():
+    """The shape the bench times (scenarios.BENCH_CONFIGS["C3"]: 64 agents, neighborDist 5, maxNeighbors 10) through the
+    reference's own constructor / reset / step / orca_step / _get_obs: every neighbour list full, up to 84 segments per
+    agent, 5-long rays, ~100 overlapping pairs per step (64 agents spawn in the 5 x 10 box), a mid-run reset() whose
+    observation is taken on the stale lists.  State every step (the by-value check of the over-speed programmes needs
+    every step's predecessor); 24 observation snapshots: the first steps, orca_steps (16, 33, 135, 186, 203, 220) and the
+    steps around the reset().
+
+    overspeed_n64_k10.npz: the same run with the reset() taken at step 150 instead comes, at step 202, upon a programme
+    whose fp32 answer is 32 maxSpeed (tests/test_oracle_overspeed.py).  A reward of that size cannot be held to the
+    absolute 1e-6 the env-loop replays ask of fp32 (an fp32 ulp at 29 is 1.9e-6), so that run is not the trajectory fixture;
+    what it keeps is, for every agent-step after its reset() with |v| > maxSpeed + 1e-4, the state doStep saw (all 64
+    agents) and the velocity it returned."""
+    gen_utils_vectors_k10()
+    kw = dict(seed=31, obs_every=None, act_scale=0.5, neighbor_dist=5.0, max_neighbors=10)
+    gen_env_fixture("env_n64_k10.npz", 64, n_steps=240, reset_at=(200,), obs_at=HEADLINE_OBS_AT, **kw)
+    tmp = "_overspeed_run.npz"
+    gen_env_fixture(tmp, 64, n_steps=206, reset_at=(150,), obs_at=(), **kw)
+    g = np.load(os.path.join(HERE, tmp))
+    speed = np.hypot(g["vel"][..., 0].astype(np.float64), g["vel"][..., 1].astype(np.float64))
+    at = [(int(s), int(i)) for s, i in np.argwhere(speed > 1.0 + 1e-4) if s > 150]
+    prev_pref = lambda s: g["pref"][s] if g["kind"][s] == 0 else g["pref"][s - 1]     # (an orca_step runs on the one left before)
+    np.savez_compressed(os.path.join(HERE, "overspeed_n64_k10.npz"),
+                        step=np.array([s for s, _ in at], np.int32), agent=np.array([i for _, i in at], np.int32),
+                        pos=np.array([g["pos"][s - 1] for s, _ in at]), vel=np.array([g["vel"][s - 1] for s, _ in at]),
+                        pref=np.array([prev_pref(s) for s, _ in at]), new_vel=np.array([g["vel"][s, i] for s, i in at]),
+                        neighbor_dist=g["neighbor_dist"], max_neighbors=g["max_neighbors"], n_agents=g["n_agents"])
+    os.remove(os.path.join(HERE, tmp))
+    print("overspeed_n64_k10.npz: %d agent-steps, |v| up to %.4f" % (len(at), max(speed[s, i] for s, i in at)))
+
+
 if __name__ == "__main__":
     if not os.path.isdir(REF):
         print("reference not present; nothing to do")
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "headline":   # only the files recorded at the bench's shape
+        install_stubs()
+        gen_headline()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "blocks":   # only the file added in round 2
         install_stubs()
@@ -582,3 +738,4 @@ if __name__ == "__main__":
     gen_alan_orca()
     gen_alan_blocks()
     gen_round5()
+    gen_headline()

@@ -17,6 +17,9 @@ Families (what each is built to provoke):
   crowd     agents only: cut-off circle / left leg / right leg, overlapping pairs (the 1 / dt branch), infeasible rings (LP3)
   mirror    exactly mirrored neighbours on one axis: parallel and anti-parallel agent lines (the |det| <= eps branches of LP1 / LP3)
   hemmed    agents pressed against walls by a crowd: LP3 with obstacle lines as hard constraints
+  dense     (dense_scenes, apart from all_scenes: eleven agents) the bench's regime -- a full list of ten neighbours, three to
+            seven of them overlapping the focus agent, a wall in range; in every other scene two of those on opposite sides of it:
+            LP3 on nearly parallel far-away lines, whose fp32 answer leaves the speed disc (tests/orca_lp.py)
 """
 import math
 
@@ -275,6 +278,32 @@ def hemmed(rng, n):
     return out
 
 
+def dense_overlap(rng, n):
+    out = []
+    for k in range(n):
+        m_over = 3 + k % 5                                         # 3..7 neighbours overlapping the focus agent
+        p0 = rng.uniform(5.0, 7.0, 2)
+        ang = rng.uniform(0, 2 * math.pi, 10)
+        rad = np.concatenate([rng.uniform(0.25, 0.95, m_over), rng.uniform(1.05, 4.5, 10 - m_over)])
+        vel = np.array([_vel(rng, 0, 1.0) for _ in range(11)])
+        if k % 2:
+            # two overlapping neighbours on opposite sides of the focus agent, within 1e-4 .. 1e-2 rad of facing each other (as
+            # in the recorded runs' worst cases): their half-planes, 30 / s from the origin, are nearly anti-parallel, both
+            # are violated whatever the velocity, and LP3 intersects them 1e3 .. 1e5 from the origin (tests/orca_lp.py)
+            ang[1] = ang[0] + math.pi + rng.choice([-1, 1]) * 10.0 ** rng.uniform(-4, -2)
+            vel[1] = vel[0] + rng.uniform(-0.002, 0.002, 2)      # (moving with it: the half-plane's normal is the direction of
+            vel[2] = vel[0] + rng.uniform(-0.002, 0.002, 2)      # relVel - relPos / dt, and a relative speed of 1 turns it by 0.03 rad)
+        pos = np.concatenate([[p0], p0 + np.stack([np.cos(ang), np.sin(ang)], 1) * rad[:, None]])
+        pref = np.array([_vel(rng, 0.5, 1.3) for _ in range(11)])
+        # a free-standing wall in range of the focus agent (tau_obst vmax + r = 2), not touching it
+        u = _unit(rng.uniform(0, 2 * math.pi))
+        c = p0 + rng.uniform(0.6, 1.8) * np.array([-u[1], u[0]]) + rng.uniform(-1.0, 1.0) * u
+        half = rng.uniform(1.0, 3.0)
+        out.append(_scene("dense", [[c - half * u, c + half * u]], pos, vel, pref))
+    return out
+
+
+DENSE = ("dense", dense_overlap, 300, 18)
 FAMILIES = (("walls", walls, 1500, 11), ("convex", convex, 1200, 12), ("notch", notch, 900, 13), ("room", room, 3000, 14),
             ("crowd", crowd, 1600, 15), ("mirror", mirror, 800, 16), ("hemmed", hemmed, 1200, 17))
 
@@ -285,6 +314,12 @@ def all_scenes(scale=1.0):
     for name, fn, n, seed in FAMILIES:
         out += fn(np.random.RandomState(seed), max(6, int(n * scale)))
     return out
+
+
+def dense_scenes(scale=1.0):
+    """The dense-overlap family (eleven agents a scene: its own batch on the GPU), seeded like the others."""
+    name, fn, n, seed = DENSE
+    return fn(np.random.RandomState(seed), max(6, int(n * scale)))
 
 
 def run_oracle_sim(scene, capture=True):

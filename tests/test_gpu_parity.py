@@ -326,7 +326,12 @@ def test_sharding_invariance():
         e.close()
 
 
-def _golden_replay_gpu(golden_dir, name):
+def _golden_replay_gpu(golden_dir, name, arenas=1, max_obst_neighbors=16, switches=None, lanes=None, report=None):
+    """arenas: the recorded run replicated over that many arenas (same start state, actions and resets in each); arena 0
+    is held against the fixture and, at every snapshot step and the last one, every arena against arena 0 bit for bit.
+    switches: environment switches (CA_QUAD, CA_REG_LINES) in force while the handle is created; lanes: the
+    lanes_per_agent the handle must then report.  The range (neighbor_dist, max_neighbors) is the fixture's own where
+    it records one.  report: dict that receives the figures of the run."""
     from collision_avoidance_amd import _lib
     from tests.test_oracle_golden import flip_margins, FLIP_MARGIN
     margins = flip_margins(golden_dir, name)   # fp64 oracle replay: how close each recorded ray is to flipping
@@ -335,29 +340,73 @@ def _golden_replay_gpu(golden_dir, name):
         bad = err.reshape(n, 16, 4).max(axis=2) > 3e-5
         if bad.any():   # fp32 vs the reference's fp64: only rays that graze a segment end / tie two hits may differ
             assert (margins[key][bad] < FLIP_MARGIN).all(), (key, np.argwhere(bad).tolist(), margins[key][bad])
+        worst["obs"] = max(worst["obs"], float(np.where(bad, 0.0, err.reshape(n, 16, 4).max(axis=2)).max()))
         return int(bad.sum())
     g = np.load(os.path.join(golden_dir, name))
     n = int(g["n_agents"])
-    env = H.make_gpu(1, n, "doorway", scenarios.env_params(), max_obst_neighbors=16)
+    A = arenas
+    worst = dict(obs=0.0, reward=0.0)
+    p = scenarios.env_params()
+    if "neighbor_dist" in g.files:
+        p.update(neighbor_dist=float(g["neighbor_dist"]), max_neighbors=int(g["max_neighbors"]))
+    old = {k: os.environ.get(k) for k in (("CA_QUAD", "CA_REG_LINES") if switches is not None else ())}
+    for k in old:                      # (switches given: exactly those, whatever the suite is run with)
+        os.environ.pop(k, None)
+    os.environ.update(switches or {})
+    try:
+        env = H.make_gpu(A, n, "doorway", p, max_obst_neighbors=max_obst_neighbors)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    if lanes is not None:
+        info = env.launch_info()
+        assert info["lanes_per_agent"] == lanes, info
+        # which kernels these are: 16 agents per 256-thread observation workgroup; one lane per agent = one 64-lane workgroup
+        # per 64-agent arena, whose dynamic LDS is the [K + S][lanes] float4 line table + staging (tests/test_worlds.py) only
+        # where the table kernel was asked for -- the register-line kernel keeps no such table
+        assert info["obs_grid"] == A * -(-n // 16), info
+        table = 64 * ((p["max_neighbors"] + max_obst_neighbors) * 16 + 32)
+        if lanes == 1:
+            assert n != 64 or info["grid"] == A, info
+            assert (info["lds_bytes"] == table) == ((switches or {}).get("CA_REG_LINES") == "0"), (info, table)
     assert (env.get(_lib.FLD_GOAL2_X) == -10.0).all() and (env.get(_lib.FLD_GOAL2_Y) == 5.0).all()   # env.py:361: the doorway
-    env.set(_lib.FLD_POS_X, g["pos0"][:, 0]); env.set(_lib.FLD_POS_Y, g["pos0"][:, 1])               # world's own retarget
-    env.set(_lib.FLD_VEL_X, g["vel0"][:, 0]); env.set(_lib.FLD_VEL_Y, g["vel0"][:, 1])
-    env.set(_lib.FLD_PREF_X, g["pref0"][:, 0]); env.set(_lib.FLD_PREF_Y, g["pref0"][:, 1])
-    env.set(_lib.FLD_GOAL_X, g["tgt0"][:, 0]); env.set(_lib.FLD_GOAL_Y, g["tgt0"][:, 1])
+    rep = lambda a: np.ascontiguousarray(np.broadcast_to(a, (A,) + a.shape))                         # world's own retarget
+    env.set(_lib.FLD_POS_X, rep(g["pos0"][:, 0])); env.set(_lib.FLD_POS_Y, rep(g["pos0"][:, 1]))
+    env.set(_lib.FLD_VEL_X, rep(g["vel0"][:, 0])); env.set(_lib.FLD_VEL_Y, rep(g["vel0"][:, 1]))
+    env.set(_lib.FLD_PREF_X, rep(g["pref0"][:, 0])); env.set(_lib.FLD_PREF_Y, rep(g["pref0"][:, 1]))
+    env.set(_lib.FLD_GOAL_X, rep(g["tgt0"][:, 0])); env.set(_lib.FLD_GOAL_Y, rep(g["tgt0"][:, 1]))
     obs_at = {int(s): k for k, s in enumerate(g["obs_steps"])}
     reset_at = {int(s): k for k, s in enumerate(g["reset_steps"])}
+
+    def all_arenas_equal_arena_0(what, ob, rew):
+        for f in ("POS_X", "POS_Y", "VEL_X", "VEL_Y", "PREF_X", "PREF_Y", "GOAL_X", "GOAL_Y", "AGENT_DONE", "STEP_COUNT", "ARENA_DONE"):
+            v = env.get(getattr(_lib, "FLD_" + f))
+            H._eq(v, rep(v[0]), "%s: %s of every arena against arena 0" % (what, f))
+        H._eq(ob, rep(ob[0]), what + ": observation of every arena against arena 0")
+        if rew is not None:
+            H._eq(rew, rep(rew[0]), what + ": reward of every arena against arena 0")
+        for lists, kind in ((env.neighbor_lists(), "agent"), (env.obstacle_neighbor_lists(), "obstacle")):
+            cnt, idx = lists
+            H._eq(cnt, rep(cnt[0]), "%s: %s neighbour counts" % (what, kind))
+            m = np.arange(idx.shape[2])[None, None, :] < cnt[:, :, None]          # (entries beyond the count are not defined)
+            H._eq(np.where(m, idx, -1), rep(np.where(m, idx, -1)[0]), "%s: %s neighbour lists" % (what, kind))
     bad = tot = 0
-    for s in range(len(g["kind"])):
+    steps = len(g["kind"])
+    for s in range(steps):
         if s in reset_at:
             k = reset_at[s]
-            ob = env.reset(g["reset_pos"][k][:, 0], g["reset_pos"][k][:, 1])
+            ob = env.reset(rep(g["reset_pos"][k][:, 0]), rep(g["reset_pos"][k][:, 1]))
             err = np.abs(ob[0].astype(np.float64) - g["reset_obs"][k])
             bad += count_bad(err, ("reset", k)); tot += n * 16
+            if A > 1:
+                all_arenas_equal_arena_0("reset before step %d" % s, ob, None)
+        rew = None
         if g["kind"][s] == 1:
             ob = env.orca_step(with_obs=True, no_done=True)
         else:
-            ob, rew, done, _ = env.step(g["actions"][s])
+            ob, rew, done, _ = env.step(rep(g["actions"][s]))
             np.testing.assert_allclose(rew[0], g["reward"][s], rtol=0, atol=1e-6)
+            worst["reward"] = max(worst["reward"], float(np.abs(rew[0].astype(np.float64) - g["reward"][s]).max()))
             assert bool(done[0]) == bool(g["done_all"][s])
         st = env.state()
         # trajectories: the north-star tolerance is 1e-4; the reference run here shares the ORCA
@@ -376,7 +425,11 @@ def _golden_replay_gpu(golden_dir, name):
         if s in obs_at:
             err = np.abs(ob[0].astype(np.float64) - g["obs"][obs_at[s]])
             bad += count_bad(err, ("step", s)); tot += n * 16
+        if A > 1 and (s in obs_at or s == steps - 1):
+            all_arenas_equal_arena_0("step %d" % s, ob, rew)
     env.close()
+    if report is not None:
+        report.update(rays=tot, beyond=bad, max_obs=worst["obs"], max_reward=worst["reward"])
     return bad, tot
 
 
@@ -388,6 +441,76 @@ def test_gpu_replays_reference_env_loop_golden(golden_dir, name):
     Python loops and the laser observation, not the ORCA solver itself."""
     bad, tot = _golden_replay_gpu(golden_dir, name)
     assert bad <= 2, (bad, tot)        # (observed: 0 of ~46 000 rays; each one that differs must be within FLIP_MARGIN of flipping: count_bad)
+
+
+HEADLINE_CASES = {   # arenas, max_obst_neighbors, switches, lanes per agent
+    # 1032 arenas, no switch: what bench.py's C3 launches, by the library's own choice -- one lane per agent (1032 lane-waves >= 1024),
+    # the register-line solve kernel for 64 lanes with 4 obstacle neighbours, the 256-thread observation kernel, and, the arena count
+    # being a multiple of 8, the observation's workgroup -> arena remap by XCD (ca_env.hip launch_obs: xcd = A % 8 == 0), as at 4096
+    "1032-S4": (1032, 4, {}, 1),
+    # 1030 arenas: the same kernels with the remap off (the observation's other runtime branch), 4 and 16 obstacle neighbours
+    "1030-S4": (1030, 4, {}, 1),
+    "1030-S16": (1030, 16, {}, 1),
+    "3-lane": (3, 4, {"CA_QUAD": "0"}, 1),
+    "3-table": (3, 4, {"CA_QUAD": "0", "CA_REG_LINES": "0"}, 1),     # the LDS line table
+    "3-quad": (3, 4, {"CA_QUAD": "1"}, 4),
+}
+
+
+@pytest.mark.parametrize("case", list(HEADLINE_CASES))
+def test_gpu_replays_reference_env_loop_golden_at_the_headline_shape(golden_dir, case):
+    """The reference's env loop recorded at the shape the bench times (tests/golden/env_n64_k10.npz: 64 agents, neighborDist 5,
+    maxNeighbors 10, every list full, up to 84 segments per agent, ~100 overlapping pairs per step, speeds up to 1.2 maxSpeed),
+    replicated over the arenas of a batch: arena 0 against the recording with the rules of its siblings above, every other
+    arena against arena 0 bit for bit.  With 64 agents every solve workgroup is one whole arena and every observation
+    workgroup a quarter of one, whatever the arena count: what the counts choose is the solve kernel and the observation's
+    remap.  CA_HEADLINE_TABLE=<path> appends the case's figures (profiles/r07_headline_golden_replay.txt)."""
+    A, S, switches, lanes = HEADLINE_CASES[case]
+    rep = {}
+    bad, tot = _golden_replay_gpu(golden_dir, "env_n64_k10.npz", arenas=A, max_obst_neighbors=S, switches=switches, lanes=lanes,
+                                  report=rep)
+    line = "%-9s arenas %5d  max_obst_neighbors %2d  lanes/agent %d  rays compared %6d  beyond 3e-5: %d  max |d obs| among the rest %.3g  max |d reward| %.3g" % (
+        case, A, S, lanes, rep["rays"], rep["beyond"], rep["max_obs"], rep["max_reward"])
+    print(line)
+    if os.environ.get("CA_HEADLINE_TABLE"):
+        with open(os.environ["CA_HEADLINE_TABLE"], "a") as fh:
+            fh.write(line + "\n")
+    # (observed on an MI355X, every case: 0 of 25 600 rays beyond 3e-5, max |d obs| 8.2e-6, max |d reward| 1.1e-7; each ray that differs
+    # must be within FLIP_MARGIN of flipping: count_bad)
+    assert tot >= 20000 and bad <= 2, (bad, tot)
+
+
+@pytest.mark.parametrize("kernel", ["lane", "table", "quad"])
+def test_gpu_returns_the_recorded_velocities_that_leave_the_speed_disc(golden_dir, kernel):
+    """tests/golden/overspeed_n64_k10.npz: 54 agent-steps of a run of the reference's env loop at the bench's shape whose ORCA
+    answer leaves the speed disc -- once by a factor of 32, where LP1's discriminant is fp32 noise and any other order of
+    the same arithmetic gives another answer (tests/test_oracle_overspeed.py has the by-value account).  One arena per
+    recorded state (all 64 agents as doStep saw them), one ORCA step: the agent's new velocity is the recorded one, bit
+    for bit, on every solve kernel."""
+    from collision_avoidance_amd import _lib
+    h = np.load(os.path.join(golden_dir, "overspeed_n64_k10.npz"))
+    A, n = len(h["step"]), int(h["n_agents"])
+    p = scenarios.env_params()
+    p.update(neighbor_dist=float(h["neighbor_dist"]), max_neighbors=int(h["max_neighbors"]))
+    over = {"lane": {"CA_QUAD": "0"}, "table": {"CA_QUAD": "0", "CA_REG_LINES": "0"}, "quad": {"CA_QUAD": "1"}}[kernel]
+    old = {k: os.environ.get(k) for k in ("CA_QUAD", "CA_REG_LINES")}
+    for k in old:
+        os.environ.pop(k, None)
+    os.environ.update(over)
+    try:
+        env = H.make_gpu(A, n, "doorway", p, max_obst_neighbors=4)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    assert env.launch_info()["lanes_per_agent"] == (4 if kernel == "quad" else 1), env.launch_info()
+    for f, v in (("POS", h["pos"]), ("VEL", h["vel"]), ("PREF", h["pref"])):
+        env.set(getattr(_lib, "FLD_%s_X" % f), v[..., 0]); env.set(getattr(_lib, "FLD_%s_Y" % f), v[..., 1])
+    env.orca_step(no_done=True)
+    a, i = np.arange(A), h["agent"]
+    got = np.stack([env.get(_lib.FLD_VEL_X)[a, i], env.get(_lib.FLD_VEL_Y)[a, i]], 1)
+    H._eq(got, h["new_vel"], "recorded over-speed velocities / " + kernel)
+    assert np.hypot(got[:, 0], got[:, 1]).max() > 30.0            # the state that is there for it
+    env.close()
 
 
 @pytest.mark.parametrize("name", ["env_doorway_n6_episode.npz", "env_doorway_n4_all_done.npz"])
@@ -494,7 +617,7 @@ def test_full_size_properties(name, A, N, nd, K, steps):
     # sorted by the distance of the step that built them: after one step of motion still ascending within 4 v dt
     dd = np.where(valid, d, np.inf)
     both = valid[:, :, 1:] & valid[:, :, :-1]
-    assert np.all((dd[:, :, 1:] - dd[:, :, :-1])[both] >= -4 * 1.02 / 60 - 1e-4)
+    assert np.all(dd[:, :, 1:][both] - dd[:, :, :-1][both] >= -4 * 1.02 / 60 - 1e-4)    # (masked first: no inf - inf)
     rng = np.random.RandomState(5)
     for s in range(3):                                                     # full steps: actions in, obs out
         act = rng.uniform(-0.5, 0.5, (A, N)).astype(np.float32)

@@ -19,15 +19,23 @@ def test_line_intersection_matches_reference(golden_dir):
             assert d == ref[0] and p[0] == ref[1] and p[1] == ref[2]  # same fp64 expressions
 
 
-def test_comp_laser_f64_matches_reference(golden_dir):
-    g = np.load(os.path.join(golden_dir, "utils_vectors.npz"))
+def _comp_laser_f64(golden_dir, name):
+    g = np.load(os.path.join(golden_dir, name))
     for segs, n, orient, ref in zip(g["cl_segs"], g["cl_counts"], g["cl_orient"], g["cl_out"]):
         out = o.comp_laser(g["rays"], segs[:n], orient, np.float64)
         np.testing.assert_allclose(out, ref, rtol=0, atol=1e-12)
 
 
+def test_comp_laser_f64_matches_reference(golden_dir):
+    _comp_laser_f64(golden_dir, "utils_vectors.npz")
+
+
 def test_comp_laser_f32_close_to_reference(golden_dir):
-    g = np.load(os.path.join(golden_dir, "utils_vectors.npz"))
+    _comp_laser_f32(golden_dir, "utils_vectors.npz")
+
+
+def _comp_laser_f32(golden_dir, name):
+    g = np.load(os.path.join(golden_dir, name))
     bad = tot = 0
     for segs, n, orient, ref in zip(g["cl_segs"], g["cl_counts"], g["cl_orient"], g["cl_out"]):
         out = o.comp_laser(g["rays"], segs[:n], orient, np.float32)
@@ -46,6 +54,47 @@ def test_ray_and_octagon_tables(golden_dir):
     np.testing.assert_allclose(np.hypot(oct_[:, 0], oct_[:, 1]), 0.5, atol=1e-15)
     np.testing.assert_array_equal(oct_[1:, :2], oct_[:-1, 2:])   # closed chain
     np.testing.assert_array_equal(oct_[-1, 2:], oct_[0, :2])
+
+
+# ---- the same at the range the bench runs at: utils_vectors_k10.npz (ray table at 5.0, ten octagons + walls per case) ----
+def test_comp_laser_k10_f64_matches_reference(golden_dir):
+    _comp_laser_f64(golden_dir, "utils_vectors_k10.npz")
+
+
+def test_comp_laser_k10_f32_close_to_reference(golden_dir):
+    _comp_laser_f32(golden_dir, "utils_vectors_k10.npz")
+
+
+def test_comp_laser_k10_cases_are_what_they_are_for(golden_dir):
+    """60-84 segments per case (ten octagons + 0-4 walls); a neighbour nearer than the octagon's inradius (the ray origin
+    inside it: every ray hits it from within); two octagons at the same distance along a ray; a wall through the origin,
+    reported as a miss on the rays along it (utils.py:103) although an octagon lies behind."""
+    g = np.load(os.path.join(golden_dir, "utils_vectors_k10.npz"), allow_pickle=False)
+    cnt, segs, out = g["cl_counts"], g["cl_segs"], g["cl_out"]
+    assert float(g["neighbor_dist"]) == 5.0 and cnt.min() >= 60 and cnt.max() == 84 and len(cnt) >= 30
+    assert set((cnt - 80).tolist()) == {0, 1, 2, 3, 4}
+    inradius = 0.5 * np.cos(np.pi / 8)
+    inside = tied = through = blinded = 0
+    for c, sg, ot in zip(cnt, segs, out):
+        ctr = sg[:80, :2].reshape(10, 8, 2).mean(axis=1)            # the octagons' centres
+        dist = np.hypot(ctr[:, 0], ctr[:, 1])
+        walls_through = [w for w in sg[80:c] if w[0] * w[3] - w[1] * w[2] == 0.0 and w[0] * w[2] + w[1] * w[3] < 0]
+        through += len(walls_through)                                # cross(a, b) = 0 exactly, a . b < 0
+        if walls_through:
+            blinded += int((ot == 0).all(axis=1).sum())              # rays that end at the origin: reported as a miss
+        elif dist.min() < inradius - 0.01:
+            hit = np.hypot(ot[:, 0], ot[:, 1])
+            assert (hit > 0).all() and (hit <= dist.min() + 0.5 + 1e-12).all()      # every ray ends on an octagon it starts in
+        inside += int(dist.min() < inradius - 0.01)
+        d = np.linalg.norm(ctr[:, None] - ctr[None], axis=2) + np.eye(10) * 9
+        tied += int(d.min() < 1e-12 or np.any(np.abs(d - 1.0) < 1e-12))
+    assert inside >= 10 and tied >= 8 and through >= 6 and blinded >= 3 * through, (inside, tied, through, blinded)
+
+
+def test_ray_table_at_the_headline_range(golden_dir):
+    g = np.load(os.path.join(golden_dir, "utils_vectors_k10.npz"))
+    np.testing.assert_array_equal(o.ray_table(5.0), g["rays"])
+    np.testing.assert_allclose(np.hypot(g["rays"][:, 0], g["rays"][:, 1]), 5.0, atol=1e-15)
 
 
 FLIP_MARGIN = 1e-5   # a ray may differ between fp32 and the reference's fp64 only if it is this close to flipping
@@ -70,7 +119,10 @@ def count_bad(err, tol, margins, key, env, prec, n):
 def _replay(golden_dir, name, prec, margins=None):
     g = np.load(os.path.join(golden_dir, name))
     n = int(g["n_agents"])
-    cfg = o.make_config(n_arenas=1, n_agents=n, max_obst_neighbors=16)
+    at = {}                                   # the range the run was recorded at (default: the env's own 1.5 / 5)
+    if "neighbor_dist" in g.files:
+        at = dict(neighbor_dist=float(g["neighbor_dist"]), max_neighbors=int(g["max_neighbors"]))
+    cfg = o.make_config(n_arenas=1, n_agents=n, max_obst_neighbors=16, **at)
     env = o.OracleEnv(cfg)
     env.set_obstacles(scenarios.obstacles("doorway", n))
     env.set(o.FLD_POS_X, g["pos0"][:, 0]); env.set(o.FLD_POS_Y, g["pos0"][:, 1])
@@ -112,6 +164,9 @@ def _replay(golden_dir, name, prec, margins=None):
         np.testing.assert_array_equal(st["goal_y"][0], g["tgt"][s][:, 1])
         if "step_count" in g.files:          # the episode fixtures of round 5: the counter and its cap, step by step
             assert int(env.get(o.FLD_STEP_COUNT)[0]) == int(g["step_count"][s]), s
+        if "nb_count" in g.files:            # the lists the reference's _get_obs walked (env.py:246-250, 283, 305)
+            np.testing.assert_array_equal(env.get(o.FLD_NB_COUNT)[0], g["nb_count"][s], err_msg="nb_count step %d" % s)
+            np.testing.assert_array_equal(env.get(o.FLD_OBST_COUNT)[0], g["obst_count"][s], err_msg="obst_count step %d" % s)
         if s in obs_at:
             err = np.abs(env.get(obs_fld)[0].astype(np.float64) - g["obs"][obs_at[s]])
             obs_bad += count_bad(err, tol, margins, ("step", s), env, prec, n); obs_tot += n * 16
@@ -160,6 +215,45 @@ def test_env_loop_f32_close_to_reference(golden_dir, name):
     """fp32 observation arithmetic against the reference's fp64: within 3e-5 except rays that graze a segment end
     (counted, bounded, and each one checked to BE such a ray)."""
     bad, tot = _replay(golden_dir, name, o.PREC_F32, flip_margins(golden_dir, name))
+    assert bad <= max(2, tot // 500), (bad, tot)
+
+
+# ---- the shape the bench times: 64 agents, neighborDist 5, maxNeighbors 10 (tests/golden/make_golden.py gen_headline) ----
+HEADLINE = "env_n64_k10.npz"
+
+
+def test_headline_fixture_is_what_it_is_for(golden_dir):
+    """Conditions on the recording, not tolerances: it is there because no other fixture reaches this regime."""
+    g = np.load(os.path.join(golden_dir, HEADLINE), allow_pickle=False)
+    n = int(g["n_agents"])
+    assert n == 64 and float(g["neighbor_dist"]) == 5.0 and int(g["max_neighbors"]) == 10
+    steps = len(g["kind"])
+    assert steps >= 240 and g["pos"].shape == g["vel"].shape == g["pref"].shape == (steps, n, 2)      # state at EVERY step
+    snap = [int(s) for s in g["obs_steps"]]
+    r = int(g["reset_steps"][0])
+    assert len(snap) >= 24 and set(range(6)) <= set(snap) and {r - 1, r, r + 1, r + 2} <= set(snap)
+    assert any(g["kind"][s] == 1 for s in snap) and len(g["reset_obs"]) == 1 and 0 < r < steps - 30
+    nb, ob = g["nb_count"].astype(int), g["obst_count"].astype(int)
+    assert (8 * nb + ob)[snap].max() >= 80                       # segments some agent's observation walks
+    assert (nb == 10).mean() >= 0.9 and ob.max() <= 4            # full lists; the bench's template holds 4 obstacle neighbours
+    d = np.linalg.norm(g["pos"][:, :, None].astype(np.float64) - g["pos"][:, None].astype(np.float64), axis=3)
+    pairs = (d[:, np.triu_indices(n, 1)[0], np.triu_indices(n, 1)[1]] < 1.0).sum(axis=1)
+    assert pairs.max() >= 50, pairs.max()                        # overlapping pairs in one step
+    rays = np.concatenate([g["obs"], g["reset_obs"]]).reshape(-1, 4)
+    hit = (rays[:, 0] != 0) | (rays[:, 1] != 0)
+    assert len(rays) >= 20000 and hit.mean() >= 0.8, (len(rays), hit.mean())
+    assert np.hypot(rays[:, 0], rays[:, 1]).max() > 1.5          # ... and beyond the env's own 1.5 range
+    assert not g["done_all"].any() and g["agents_done"].max() == 0
+
+
+def test_headline_env_loop_f64_matches_reference(golden_dir):
+    bad, tot = _replay(golden_dir, HEADLINE, o.PREC_F64)
+    assert tot >= 20000 and bad == 0, (bad, tot)
+
+
+def test_headline_env_loop_f32_close_to_reference(golden_dir):
+    """The rules of test_env_loop_f32_close_to_reference at the bench's shape (observed: 0 of 25 600 rays beyond 3e-5)."""
+    bad, tot = _replay(golden_dir, HEADLINE, o.PREC_F32, flip_margins(golden_dir, HEADLINE))
     assert bad <= max(2, tot // 500), (bad, tot)
 
 
