@@ -7,10 +7,14 @@
 // Tag of the kernels' per-arena-action-set instantiations (step_kernel / quad_kernel <..., true, AlanArenaSets>).  Declared
 // outside the namespace so that the instantiations' names read like the others' (tools/kernel_resources.py).
 struct AlanArenaSets;
+// Tag of the observation kernel's wide instantiations (obs_kernel<..., WideObstLists>: obstacle-neighbour lists of 17 .. 64).
+struct WideObstLists;
 
 namespace ca {
 
-constexpr int SMAX = 16;      // CA_MAX_OBST_NEIGHBORS (LDS line table; the register-line and quad kernels hold 4)
+constexpr int SMAX = 16;      // obstacle-neighbour lists of up to 16 (LDS line table; the register-line and quad kernels hold 4)
+constexpr int SWIDE = 64;     // CA_MAX_OBST_NEIGHBORS: the wide instantiations of the LDS-line-table kernel and of the observation
+                              // (lists of 17 .. 64; sorted list in the idle line table, ca_nbr.h; LP3 with room for KMAX + 64 lines)
 constexpr float EPS = 0.00001f;
 
 struct ObstDev {  // one obstacle edge (this vertex -> next vertex) with everything ORCA needs about

@@ -85,7 +85,8 @@ struct ca_env {
     // -1 = unset, else the first character's digit
     struct { int reg_lines = -1, pair = -1, alan_fused = -1; } sw;
     int ST = 0, KT = 16;  // solve-kernel variant: ST > 0 = register lines with ST obstacle slots; KT = KMAX
-    int SMX = 4;          // ... and the capacity of its obstacle-neighbour list (4, or 16: agents with more than ST are solved apart)
+    int SMX = 4;          // ... and the capacity of its obstacle-neighbour list (4, or 16: agents with more than ST are solved apart;
+                          // SWIDE = 64 with ST = 0: the wide LDS-table kernel of a handle with max_obst_neighbors > 16)
     int max_edges = 0;    // edges of the largest installed obstacle table (the variant depends on it: pick_variant)
     int n_cus = 256;      // compute units of the device (pick_variant: is the batch resident with the LDS line table?)
     bool pair = false;     // large arenas: two lanes per agent for the whole step (ca_pair.h)
@@ -303,10 +304,16 @@ static const void* quad_fn_for(int BS) {
         default: return fn_ptr(&quad_kernel<KMAX, 512, SQ, ALAN, PER...>);
     }
 }
+// the wide LDS-table kernel (obstacle lists of 17 .. 64): arenas of at most 128 agents, no ALAN form
+template <int KMAX>
+static const void* wide_fn_for(int BS) {
+    return BS == 64 ? fn_ptr(&step_kernel<KMAX, 64, 0, SWIDE>) : fn_ptr(&step_kernel<KMAX, 128, 0, SWIDE>);
+}
 // the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
 // more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
 template <bool ALAN, class... PER>
 static const void* lane_fn_for(const ca_env* e) {
+    if (e->SMX > SMAX) return e->KT == 5 ? wide_fn_for<5>(e->BS) : (e->KT == 16 ? wide_fn_for<16>(e->BS) : wide_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->ST > 0 && e->SMX > 4) return e->KT == 5 ? step_fn_for<5, 4, 16, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 16, ALAN, PER...>(e->BS);
     if (e->ST > 0) return e->KT == 5 ? step_fn_for<5, 4, 4, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 4, ALAN, PER...>(e->BS);
     if (e->KT == 5) return step_fn_for<5, 0, SMAX, ALAN, PER...>(e->BS);
@@ -346,7 +353,9 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
 }
 
 typedef void (*obs_fn_t)(const ObsArgs);
-static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false) {  // workgroup size x width of the stored agent-neighbour ids
+static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = false) {  // workgroup size x width of the stored agent-neighbour ids
+    // (obstacle lists above 16: arenas of at most 128 agents -- 256 lanes, 8-bit ids; ca_create checks that)
+    if (wide) return dense ? obs_kernel<256, false, true, WideObstLists> : obs_kernel<256, false, false, WideObstLists>;
     if (dense) return obs_kernel<256, false, true>;   // (arenas of fewer than 16 agents: 256 lanes, 8-bit ids)
     switch (obs_bs) {
         case 1024: return w16 ? obs_kernel<1024, true> : obs_kernel<1024, false>;
@@ -361,6 +370,8 @@ static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false) {  // workgroup
 // reference env's own 10-agent arenas would otherwise leave 6 of 16 groups idle).  CA_OBS_DENSE=0: one arena per workgroup.
 static bool obs_dense(const ca_env* e) { return e->obs_dense_on; }   // (latched by ca_create)
 static int obs_nstage(const ca_env* e) { return obs_dense(e) ? 16 + 2 * e->cfg.n_agents : e->cfg.n_agents; }
+static bool obs_wide(const ca_env* e) { return e->S > SMAX; }   // more than 16 obstacle ids per agent (ca_obs.h WIDE)
+static size_t obs_lds(const ca_env* e, int obs_bs) { return obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S), obs_wide(e) ? e->S : 16); }
 
 static hipError_t launch_obs(ca_env* e) {
     if (!e->orient_valid) {  // positions or goals were edited from outside: re-derive the frame
@@ -390,9 +401,9 @@ static hipError_t launch_obs(ca_env* e) {
     memcpy(o.rays, e->rays, sizeof o.rays);
     memcpy(o.oct, e->oct, sizeof o.oct);
     const dim3 grid(o.dense ? (unsigned)(((size_t)o.A * o.N + apb - 1) / apb) : (unsigned)((size_t)o.A * o.bpa)), block(obs_bs);
-    const size_t lds = obs_lds_bytes(o.nstage_max, obs_bs, o.paircap);
+    const size_t lds = obs_lds(e, obs_bs);
     ProfScope ps(e, KIND_OBS);
-    launch_k(ps, obs_fn(obs_bs, e->nidx16 != 0, o.dense != 0), grid, block, lds, e->stream, o);
+    launch_k(ps, obs_fn(obs_bs, e->nidx16 != 0, o.dense != 0, obs_wide(e)), grid, block, lds, e->stream, o);
     return hipGetLastError();
 }
 
@@ -517,6 +528,9 @@ static size_t lds_static_bytes(const ca_env* e) {
 //     (ca_step.h solve_many_obstacles), so the list capacity stays RVO2's "every edge in range" --, or
 //   * the LDS line table would not fit (arenas above 256 agents with many obstacle neighbours), or the batch would not be resident
 //     with it (below).
+// max_obst_neighbors > 16 ALWAYS means the wide LDS line table (ST = 0, SMX = SWIDE: lists of up to 64, K + S lines per lane), whatever
+// the switches say: no register lines (not even when the batch is not resident with the table -- it then runs in rounds), no
+// two-lanes and no four-lanes kernel (ca_create) exist for such lists.
 // Else the LDS line table (ST = 0): worlds like the two-way tube ("deadlock": 42 edges, 17 % of the agent-steps with more
 // than four in range).  Called by ca_create (no table yet) and again whenever tables are installed: every variant computes
 // the same bits, so a handle may change variant between steps.
@@ -533,7 +547,8 @@ static void pick_variant(ca_env* e) {
     // deadlock x 50 agents, 1280 arenas 49.6 us (table) / 64.8 us (registers) per ORCA step, 1536 arenas 81.6 / 67.7, 4096 arenas
     // 157.8 / 76.3; blocks x 20 agents, 8192 arenas 126.9 / 75.4; profiles/r04_g_many_edge_worlds.txt)
     const bool table_resident = table_fits && (long)e->grid <= (long)e->n_cus * (long)((160 * 1024) / table_per_wg);
-    if (allow && e->K <= 10 && e->S <= 4) { e->ST = 4; e->SMX = 4; }
+    if (e->S > SMAX) { e->ST = 0; e->SMX = SWIDE; }
+    else if (allow && e->K <= 10 && e->S <= 4) { e->ST = 4; e->SMX = 4; }
     else if (allow && e->K <= 10 && (small_world || force || !table_resident)) { e->ST = 4; e->SMX = 16; }
     else { e->ST = 0; e->SMX = 16; }
     e->lds = step_lds_bytes(e->BS, e->K, e->S, e->ST, e->KT);
@@ -575,7 +590,8 @@ static int alan_pick(ca_env* e) {
     const size_t lq = quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions);
     const bool on = e->sw.alan_fused != 0;   // (CA_ALAN_FUSED=0: the three-launch form everywhere)
     e->alan_fused = on && (e->quad || e->quad_roll) && lq <= 64 * 1024;
-    e->alan_lane = on && !e->quad && !e->pair && e->BS <= 128 && e->K <= 10 &&
+    // (obstacle lists above 16: the wide table kernel has no ALAN instantiation and no four-lanes form -- select -> solve -> update)
+    e->alan_lane = on && !e->quad && !e->pair && e->BS <= 128 && e->K <= 10 && e->S <= SMAX &&
                    e->n_actions <= (e->ST > 0 ? 4 + e->KT : 2 * (e->K + e->S));
     if (e->alan_fused) HIPCHK(e, allow_lds(solve_launch(e, true, true)));   // (the ALAN rollout; on a quad handle the ALAN step too)
     if (e->alan_lane) HIPCHK(e, allow_lds(solve_launch(e, true, false)));
@@ -670,7 +686,8 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         e->SQ = e->S <= 4 ? 4 : 16;
         // (register budget: a 1024-lane workgroup caps the kernel at 128 VGPRs, a 512-lane one at 256 -- the variant with 16
         // obstacle neighbours and K = 10 needs all 256 already at 256 lanes)
-        const bool fits = e->K <= 10 && 4 * P <= ((e->SQ == 16 && e->KT == 10) ? 256 : 512);
+        // (... and it holds obstacle lists of 4 or 16: a handle with max_obst_neighbors > 16 never takes it, CA_QUAD=1 or not)
+        const bool fits = e->S <= SMAX && e->K <= 10 && 4 * P <= ((e->SQ == 16 && e->KT == 10) ? 256 : 512);
         // (counted at P lanes per arena, the layout the crossover was measured with, whatever the packing is now)
         const long lane_waves = (long)((cfg->n_arenas + e->BS / P - 1) / (e->BS / P)) * (e->BS / 64);
         e->quad = fits && (v ? v[0] == '1' : lane_waves < 1024);
@@ -679,6 +696,19 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         const int apbq = (e->BSq / 4) / P;
         e->grid_q = (cfg->n_arenas + apbq - 1) / apbq;
         e->lds_q = quad_lds_bytes(e->BSq, e->KT, e->SQ);
+    }
+    if (e->S > SMAX && (e->lds + lds_static_bytes(e) > LDS_PER_CU || e->BS > 128 || obs_block_threads(cfg->n_agents) != 256)) {
+        // obstacle lists above 16 live in the LDS line table, K + S lines per lane: 64 lanes with K <= 16, 128 lanes with K <= 10 at S = 64
+        if (e->lds + lds_static_bytes(e) > LDS_PER_CU)
+            fail(nullptr, CA_ERANGE, "ca_create: the solve kernel for n_agents=%d, max_neighbors=%d, max_obst_neighbors=%d does not fit the "
+                 "160 KiB of LDS of a CU (%zu B: obstacle lists above %d take the LDS line table, max_neighbors + max_obst_neighbors lines "
+                 "per lane)", cfg->n_agents, e->K, e->S, e->lds + lds_static_bytes(e), SMAX);
+        else
+            fail(nullptr, CA_ERANGE, "ca_create: max_obst_neighbors=%d: obstacle lists above %d are built for arenas of at most 128 agents "
+                 "(n_agents=%d)", e->S, SMAX, cfg->n_agents);
+        if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+        delete e;
+        return CA_ERANGE;
     }
     if (!e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU) {
         fail(nullptr, CA_ERANGE, "ca_create: the solve kernel would need %zu B of LDS (> 160 KiB) for n_agents=%d, "
@@ -719,9 +749,9 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     if (r == hipSuccess) r = apply_variant_attributes(e, &lds_misfit);
     if (r == hipSuccess) {
         const int obs_bs = obs_block_threads(cfg->n_agents);
-        const size_t ol = obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S));
+        const size_t ol = obs_lds(e, obs_bs);
         if (ol > 48 * 1024) {
-            r = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_fn(obs_bs, e->nidx16 != 0, obs_dense(e))),
+            r = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_fn(obs_bs, e->nidx16 != 0, obs_dense(e), obs_wide(e))),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)ol);
         }
     }

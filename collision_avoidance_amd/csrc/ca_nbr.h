@@ -47,7 +47,14 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
 // the K nearest agents, written as the lists [A,S,N] / [A,K,N] that the solve kernel and the
 // observation read.  It runs at the head of the solve kernel (ca_step.h step_kernel).
 // ============================================================================================
-// SM: capacity of the register list of obstacle neighbours (S <= SM): 4 for the register-line solve, SMAX for the LDS table
+// SM: capacity of the register list of obstacle neighbours (S <= SM): 4 for the register-line solve, SMAX for the LDS table.
+// SM > SMAX (the wide LDS-table kernels, lists of up to SWIDE edges): 2 SM registers for the keys do not exist, so the sorted list
+// is built in LDS instead -- in the line table, which is idle until the lines are built after the search: key slot k of lane t
+// is the 64-bit word [k][t] at the head of the kernel's dynamic LDS (S x 8 B per lane, always less than the table's (K + S) x 16 B;
+// the 64-bit words of consecutive lanes are consecutive in LDS, the conflict-free pattern of a ds_read_b64 / ds_write_b64).  Only
+// the lane itself touches its column, and the solve kernel has a barrier between the search and its first line.  The order is
+// sorted_insert's: ascending (distance, index) key.  Cost: a data-dependent shift loop per accepted edge -- edges arrive in index
+// order, not by distance, so an insert is up to S LDS round trips on the slowest lane of the wave.
 template <int KMAX, int BS, int SM>
 __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #ifndef CA_NBR_NO_VGPR_PAD
@@ -76,13 +83,39 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 
     const float INF = __int_as_float(0x7f800000);
     // ---- obstacle neighbours (App. A.2): brute force over the edge table ----
-    const int sofs = SM - S;  // the S-entry list is right-aligned in the register array
+    constexpr bool WIDE = SM > SMAX;
+    constexpr int SR = WIDE ? 1 : SM;   // register slots of the list (wide: none, the list is in LDS)
+    const int sofs = SR - S;  // the S-entry list is right-aligned in the register array
     const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
     const double KEY_DUMMY = __longlong_as_double((long long)0xFFF0000000000000ull);  // -inf: never moves
-    double okey[SM];
+    double okey[SR];
 #pragma unroll
-    for (int k = 0; k < SM; ++k) okey[k] = (k < sofs) ? KEY_DUMMY : KEY_EMPTY;
+    for (int k = 0; k < SR; ++k) okey[k] = (k < sofs) ? KEY_DUMMY : KEY_EMPTY;
     int oin = 0;
+    // (wide) the lane's column of the LDS list, ascending in slots [0, wcnt): a newcomer shifts the larger keys up by one slot;
+    // on a full list the largest key falls off -- the newcomer itself, if it is that
+    unsigned long long* wkey = nullptr;
+    int wcnt = 0;
+    if constexpr (WIDE) {
+        extern __shared__ float4 smem4[];
+        wkey = reinterpret_cast<unsigned long long*>(smem4) + tid;
+    }
+    auto wide_insert = [&](unsigned long long x) __attribute__((always_inline)) {
+        int k = wcnt;
+        if (wcnt == S) {
+            if (wkey[(S - 1) * BS] < x) return;
+            k = S - 1;
+        } else {
+            ++wcnt;
+        }
+        while (k > 0) {
+            const unsigned long long y = wkey[(k - 1) * BS];
+            if (y < x) break;
+            wkey[k * BS] = y;
+            --k;
+        }
+        wkey[k * BS] = x;
+    };
     {
         const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
         auto visit = [&](const ObstDev& o1, int e, bool mine) __attribute__((always_inline)) {
@@ -93,7 +126,8 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
                 const float dsq = distSqPointSegment(a1, a2, pos);
                 if (dsq < rangeSq) {
                     ++oin;
-                    sorted_insert<SM>(okey, make_key(dsq, e));
+                    if constexpr (WIDE) wide_insert(((unsigned long long)__float_as_uint(dsq) << 32) | (unsigned)e);
+                    else sorted_insert<SR>(okey, make_key(dsq, e));
                 }
             }
         };
@@ -108,7 +142,12 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
         }
     }
     const int ocnt = oin < S ? oin : S;
-    if constexpr (SM > 4) {   // a list of 16 keys is 32 registers: it goes to memory now, not after the agent scan
+    if constexpr (WIDE) {     // the LDS list goes to memory before the agent scan (an empty slot reads -1, as in the register form)
+        if (active) {
+            for (int k = 0; k < S; ++k)
+                p.obst_idx[((size_t)a * S + k) * N + i] = k < wcnt ? (unsigned short)(unsigned)wkey[k * BS] : (unsigned short)0xFFFFu;
+        }
+    } else if constexpr (SM > 4) {   // a list of 16 keys is 32 registers: it goes to memory now, not after the agent scan
         if (active) {
 #pragma unroll
             for (int k = 0; k < SM; ++k)

@@ -63,9 +63,10 @@ struct ObsArgs {
 //              | ray and octagon tables [64] | pair counts [2][16] | (source, ray) pairs [16 x 16 (K + S)] u16: the
 //              workgroup's (agent, neighbour, ray) list from the front, every agent's obstacle pairs in a block of its
 //              own from the back
-__host__ __device__ inline size_t obs_lds_bytes(int nstage_max, int obs_bs, int paircap) {
+// (obw: staged obstacle ids per agent -- 16, or S in the wide instantiations, lists of 17 .. 64 edges)
+__host__ __device__ inline size_t obs_lds_bytes(int nstage_max, int obs_bs, int paircap, int obw = 16) {
     const size_t apb = obs_bs / 16;
-    return (size_t)nstage_max * 16 + 2 * apb * 16 * 8 + apb * 16 + apb * 16 * 4 + apb * 16 * 4 + 64 * 4 + 2 * apb * 4 + apb * (size_t)paircap * 2;
+    return (size_t)nstage_max * 16 + 2 * apb * 16 * 8 + apb * 16 + apb * 16 * 4 + apb * (size_t)obw * 4 + 64 * 4 + 2 * apb * 4 + apb * (size_t)paircap * 2;
 }
 #ifndef CA_OBS_BS_MAX
 #define CA_OBS_BS_MAX 256
@@ -107,8 +108,12 @@ __device__ __forceinline__ float ray_dial(float x, float y) {
 // is < 1e-4 and the margin is 0.01 dial units (3.9e-3 rad).  Segments passing (almost) through the
 // origin, where "short way round" is ill-defined, get all 16 rays.  For an agent NEIGHBOUR the
 // window is that of the circle through its octagon's vertices (see the pre-pass).
-template <int OBS_BS, bool NW16, bool DENSE = false>
+// WIDE_TAG = WideObstLists (obstacle-neighbour lists of 17 .. 64 edges, S > 16): an agent's S obstacle ids are staged by its 16
+// lanes in a strided loop instead of one id per lane, S ids per agent in LDS; the pre-pass and build() then run over up to 64
+// edges as they are.  (A trailing pack, empty in every other instantiation, so that those keep their names and their code.)
+template <int OBS_BS, bool NW16, bool DENSE = false, class... WIDE_TAG>
 __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
+    constexpr bool WIDE = sizeof...(WIDE_TAG) > 0;
     constexpr int OBS_APB = OBS_BS / 16;  // agents per workgroup
     extern __shared__ float4 smem4[];
     const int tid = threadIdx.x;
@@ -156,7 +161,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     float4* s_frame = reinterpret_cast<float4*>(s_rel + OBS_APB * 16);           // (cos, sin, pos x, pos y) per agent
     int* s_nb = reinterpret_cast<int*>(s_frame + OBS_APB);
     int* s_ob = s_nb + OBS_APB * 16;
-    float* s_rays = reinterpret_cast<float*>(s_ob + OBS_APB * 16);  // [32] rays then [32] octagon
+    const int OBW = WIDE ? S : 16;   // staged obstacle ids per agent
+    float* s_rays = reinterpret_cast<float*>(s_ob + OBS_APB * OBW);  // [32] rays then [32] octagon
     float* s_oct = s_rays + 32;
     int* s_cnt = reinterpret_cast<int*>(s_oct + 32);                       // [0]: neighbour pairs of the workgroup
     int* s_cnt2 = s_cnt + OBS_APB;                                         // [16] obstacle pairs per agent
@@ -193,7 +199,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             nn = cnts & 0xFF; ns = cnts >> 8;
             c = p.orient_x[q]; s = -p.orient_y[q];  // utils.py:48-51: cos/sin of -atan2(orientation)
             if (r < nn) s_nb[g * 16 + r] = abase + ld_idx_t<NW16>(p.nb_idx, ((size_t)a * K + r) * N + i);  // as an index of the staged arrays
-            if (r < ns) s_ob[g * 16 + r] = (int)p.obst_idx[((size_t)a * S + r) * N + i];
+            if constexpr (WIDE) { for (int t = r; t < ns; t += 16) s_ob[g * OBW + t] = (int)p.obst_idx[((size_t)a * S + t) * N + i]; }
+            else if (r < ns) s_ob[g * 16 + r] = (int)p.obst_idx[((size_t)a * S + r) * N + i];
         } else {
             const int cnts = (p.counts + aoff)[ii];
             nn = cnts & 0xFF; ns = cnts >> 8;
@@ -201,7 +208,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             const unsigned li = (unsigned)r * (unsigned)N + ii;     // inside the arena's [K][N] / [S][N] block: below 16 x 1024
             const char* nbase = (const char*)p.nb_idx + aoff * (size_t)K * (NW16 ? 2 : 1);
             if (r < nn) s_nb[g * 16 + r] = ld_idx_t<NW16>(nbase, li);  // as an index of the staged arrays (GATHER: of the arena)
-            if (r < ns) s_ob[g * 16 + r] = (int)(p.obst_idx + aoff * (size_t)S)[li];
+            if constexpr (WIDE) { for (unsigned t = (unsigned)r; t < (unsigned)ns; t += 16u) s_ob[g * OBW + t] = (int)(p.obst_idx + aoff * (size_t)S)[t * (unsigned)N + ii]; }
+            else if (r < ns) s_ob[g * 16 + r] = (int)(p.obst_idx + aoff * (size_t)S)[li];
         }
     }
     s_key[g * 16 + r] = ~0ull;
@@ -266,7 +274,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         const float dx = s_rays[2 * r], dy = s_rays[2 * r + 1];
         int cnt2 = 0;
         for (int sidx = 0; sidx < ns; ++sidx) {
-            const ObstDev o1 = load_obst(tab, s_ob[g * 16 + sidx]);
+            const ObstDev o1 = load_obst(tab, s_ob[g * OBW + sidx]);
             const float x1 = o1.px - mx, y1 = o1.py - my, x2 = o1.qx - mx, y2 = o1.qy - my;
             const float ax = c * x1 - s * y1, ay = s * x1 + c * y1;
             const float bx = c * x2 - s * y2, by = s * x2 + c * y2;
@@ -297,7 +305,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             x2 = oc.z + rx; y2 = oc.w + ry;
             if (want_vel) { const int nb = s_nb[g * 16 + k]; vx = GATHER ? gvx[nb] : s_vx[nb]; vy = GATHER ? gvy[nb] : s_vy[nb]; }  // env.py:252
         } else {
-            const ObstDev o1 = load_obst(tab, s_ob[g * 16 + (m - 8 * nn)]);
+            const ObstDev o1 = load_obst(tab, s_ob[g * OBW + (m - 8 * nn)]);
             x1 = o1.px - mx; y1 = o1.py - my;
             x2 = o1.qx - mx; y2 = o1.qy - my;
         }

@@ -22,7 +22,9 @@ __host__ __device__ inline size_t step_lds_bytes(int BS, int K, int S, int ST = 
 // ALAN:631-636) followed by the done test of ALAN:118-121 unless CA_F_NODONE.
 // ============================================================================================
 
-// ST = 0: ORCA lines in the LDS table [K+S][BS] (any K <= 16, S <= 8).
+// ST = 0: ORCA lines in the LDS table [K+S][BS] (any K <= 16; S <= 16, or -- SMX = SWIDE, the wide instantiations -- S <= 64: the
+//         same code over a table of K + S lines per lane, the sorted obstacle list built in that table while it is idle
+//         (ca_nbr.h) and LP3's private array with room for KMAX + 64 projected lines).
 // ST > 0: ORCA lines in registers (ST obstacle slots + KMAX neighbour slots), LP2/LP1 fully unrolled,
 //         LP3 through a small per-wave LDS pool.  Needs S <= ST; ~8 KB of LDS per wave instead of
 //         16 KB; built for 4 waves per SIMD (<= 128 VGPRs), i.e. 16 waves per CU: the 4096 arenas
@@ -395,7 +397,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     int fail = nl;
     if (active) fail = lp2(ls, nl, p.max_speed, pref, false, nv);
     CA_STAMP(6);
-    if (active && fail < nl) lp3<KMAX + SMAX>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, p.max_speed, nv);
+    if (active && fail < nl) lp3<KMAX + (SMX > SMAX ? SMX : SMAX)>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, p.max_speed, nv);
     }
     if (active) {  // ---- integrate (App. A.1) ----
         vel = nv;

@@ -45,7 +45,9 @@ _bases = (_EnvBase,) if _MultiAgentEnv is object or _EnvBase is _MultiAgentEnv e
 class Collision_Avoidance_Env(*_bases):
     metadata = {'render.modes': ['human']}
 
-    def __init__(self, numAgents=10, device=0, seed=0):
+    def __init__(self, numAgents=10, device=0, seed=0, max_obst_neighbors=None, allow_obst_overflow=False):
+        # (max_obst_neighbors / allow_obst_overflow: VecCollisionAvoidanceEnv's keywords, no reference counterpart -- the
+        # reference's simulator keeps every obstacle edge in range; the defaults are the vector env's)
         # constants of env.py:27-44
         self.timeStep = 1 / 60.
         self.neighborDist = 1.5
@@ -63,13 +65,15 @@ class Collision_Avoidance_Env(*_bases):
         self.observation_space = box(low=-self.neighborDist, high=self.neighborDist,
                                      shape=(self.laser_num * 4,))                               # env.py:53
         self._device, self._seed = device, seed
+        self._max_obst_neighbors, self._allow_obst_overflow = max_obst_neighbors, allow_obst_overflow
         self._keys = ['agent_' + str(i) for i in range(numAgents)]                              # env.py:275, 373, 400
         self._make()
         self.reset()                                                                            # env.py:74
 
     def _make(self):
         self.vec = VecCollisionAvoidanceEnv(1, self.numAgents, scenario="doorway", device=self._device,
-                                            seed=self._seed, use_torch=False)
+                                            seed=self._seed, use_torch=False, max_obst_neighbors=self._max_obst_neighbors,
+                                            allow_obst_overflow=self._allow_obst_overflow)
 
     @property
     def step_count(self):

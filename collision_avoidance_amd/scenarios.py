@@ -203,3 +203,19 @@ BENCH_CONFIGS = {
     "M128": dict(n_arenas=1024, n_agents=128, neighbor_dist=5.0, max_neighbors=10),
     "M180": dict(n_arenas=512, n_agents=180, neighbor_dist=5.0, max_neighbors=10),
 }
+
+
+def squares_grid(k, x0, y0, pitch, size):
+    """k x k square blocks (counter-clockwise polygons) of side `size`, the lower left one at (x0, y0), `pitch` apart."""
+    return [[(x0 + c * pitch, y0 + r * pitch), (x0 + c * pitch + size, y0 + r * pitch),
+             (x0 + c * pitch + size, y0 + r * pitch + size), (x0 + c * pitch, y0 + r * pitch + size)]
+            for r in range(k) for c in range(k)]
+
+
+def pillar_hall(n_agents, k, pitch, size=0.3, x0=0.4, y0=0.4):
+    """A polyline world that needs obstacle-neighbour lists above 16 (max_obst_neighbors up to 64): the crowd arena's border and
+    the pillars of squares_grid(k, x0, y0, pitch, size) that lie inside it (largest x and y below envsize - 0.2).
+    pillar_hall(64, 14, 1.0): 197 polygons, 788 edges, up to 34 of them in range of an agent."""
+    e = envsize("crowd", n_agents)
+    keep = [q for q in squares_grid(k, x0, y0, pitch, size) if max(v[0] for v in q) < e - 0.2 and max(v[1] for v in q) < e - 0.2]
+    return [[(0.0, 0.0), (0.0, e), (e, e), (e, 0.0)]] + keep

@@ -21,6 +21,10 @@ _I32_FIELDS = {_lib.FLD_AGENT_DONE, _lib.FLD_ARRIVE_STEP, _lib.FLD_NB_COUNT, _li
                _lib.FLD_OBST_COUNT, _lib.FLD_OBST_IDX, _lib.FLD_STEP_COUNT, _lib.FLD_ARENA_DONE,
                _lib.FLD_EPISODE, _lib.FLD_REGOAL_COUNT, _lib.FLD_ALAN_ACTION}
 _ARENA_FIELDS = {_lib.FLD_STEP_COUNT, _lib.FLD_ARENA_DONE, _lib.FLD_EPISODE}
+# VecCollisionAvoidanceEnv's default list capacity is min(this, edges of the world): the reference's own worlds never bring more
+# than 16 edges in range, and lists of up to 16 keep the register-line and four-lanes kernels available.  A polyline world that
+# needs more asks for it: max_obst_neighbors up to _lib.MAX_OBST_NEIGHBORS (64).
+DEFAULT_MAX_OBST_NEIGHBORS = 16
 _F64_FIELDS = {_lib.FLD_GOAL_X, _lib.FLD_GOAL_Y, _lib.FLD_GOAL2_X, _lib.FLD_GOAL2_Y, _lib.FLD_ALAN_WEIGHTS,
                _lib.FLD_ALAN_TIMES}
 
@@ -37,9 +41,14 @@ class VecCollisionAvoidanceEnv:
     use_torch: hand observations/rewards out as torch tensors on the device (zero-copy for the
                observation) and accept device tensors as actions.  False: numpy in/out.
     allow_obst_overflow: the reference's simulator keeps every obstacle edge in range of an agent (env.py:249, 301-318); the
-               lists here hold max_obst_neighbors (<= 16).  False (default): an agent with more edges in range makes the step
+               lists here hold max_obst_neighbors.  False (default): an agent with more edges in range makes the step
                calls raise (CA_ERANGE, naming arena and agent); True: the nearest max_obst_neighbors are kept and the event is
                only counted (stats()["obst_overflow"]).
+    max_obst_neighbors: capacity of the obstacle-neighbour lists, 1 .. 64 (_lib.MAX_OBST_NEIGHBORS); None (default):
+               min(16, edges of the world).  Above 16 the handle takes the wide LDS-table solve kernel and the wide observation
+               (launch_info()): arenas of at most 128 agents (at 64: 64 agents with any max_neighbors, 128 with max_neighbors <= 10;
+               other shapes raise CA_ERANGE at construction).  A world of subdivided walls or many pillars that raises the overflow
+               error wants this raised, not allow_obst_overflow.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
@@ -60,7 +69,7 @@ class VecCollisionAvoidanceEnv:
             polys = list(obstacles or [])
         n_edges = max(sum(len(q) for q in w) for w in worlds) if worlds else sum(len(q) for q in polys)
         if max_obst_neighbors is None:
-            max_obst_neighbors = max(1, min(_lib.MAX_OBST_NEIGHBORS, n_edges))
+            max_obst_neighbors = max(1, min(DEFAULT_MAX_OBST_NEIGHBORS, n_edges))
         self.cfg = _lib.Config(n_arenas=self.A, n_agents=self.N, arena_offset=arena_offset, seed=seed,
                                max_obst_neighbors=max_obst_neighbors, **p)
         self.K, self.S = self.cfg.max_neighbors, self.cfg.max_obst_neighbors

@@ -30,8 +30,12 @@ extern "C" {
 #define CA_OBS_DIM 64 /* env.py:34,53: 16 rays x (hit x, hit y, vel x, vel y) */
 #define CA_N_RAYS 16
 #define CA_MAX_NEIGHBORS 16      /* largest supported max_neighbors       */
-#define CA_MAX_OBST_NEIGHBORS 16 /* largest supported max_obst_neighbors: RVO2 keeps every edge in range (env.py:249,
-                                    301-318); 16 covers the reference's own worlds.  A list that meets more edges in range
+#define CA_MAX_OBST_NEIGHBORS 64 /* largest supported max_obst_neighbors: RVO2 keeps every edge in range (env.py:249,
+                                    301-318); 16 covers the reference's own worlds, 64 polyline worlds (subdivided walls,
+                                    pillar halls).  Lists above 16 take a kernel of their own (ca_solver_info) and need
+                                    n_agents <= 128 and max_neighbors + max_obst_neighbors lines per lane in a CU's LDS:
+                                    at 64, n_agents <= 64 with any max_neighbors, n_agents <= 128 with max_neighbors <= 10.
+                                    A list that meets more edges in range
                                     than it holds drops the farthest, counts it (ca_stats.obst_overflow) AND makes every
                                     later step call fail with CA_ERANGE: see ca_allow_obstacle_overflow */
 #define CA_MAX_AGENTS 1024       /* one workgroup owns one arena; above 256 agents max_neighbors <= 10
@@ -133,7 +137,9 @@ typedef struct ca_config {
     float time_horizon_obst;    /* env.py:130                                                 */
     float radius;               /* env.py:31                                                  */
     float max_speed;            /* env.py:32                                                  */
-    int32_t max_obst_neighbors; /* capacity of the obstacle-neighbour list, 1..CA_MAX_OBST_NEIGHBORS;
+    int32_t max_obst_neighbors; /* capacity of the obstacle-neighbour list, 1..CA_MAX_OBST_NEIGHBORS (64);
+                                   above 16: ca_create returns CA_ERANGE for shapes whose line table
+                                   does not fit a CU's LDS (see CA_MAX_OBST_NEIGHBORS);
                                    overflow is counted in ca_stats.obst_overflow and is an error
                                    (CA_ERANGE) unless ca_allow_obstacle_overflow accepted it    */
     int32_t max_step;           /* env.py:44; <= 0: no cap                                    */
@@ -277,7 +283,9 @@ int ca_alan_rollout(ca_env* env, int32_t steps, uint32_t flags);
  * the agent and the number of edges) -- asynchronously, like a device fault: the first call made after the kernel that
  * overflowed has finished reports it, calls that synchronise report it at once -- until ca_reset_stats clears it.
  * ca_allow_obstacle_overflow(env, 1) accepts the truncation (nearest max_obst_neighbors edges kept, counted in
- * ca_stats.obst_overflow and per arena); 0 restores the default.  ca_get / ca_get_stats always work. */
+ * ca_stats.obst_overflow and per arena); 0 restores the default.  ca_get / ca_get_stats always work.
+ * The cure is a larger list: max_obst_neighbors up to CA_MAX_OBST_NEIGHBORS = 64 (a 9 x 9 grid of small squares at a pitch of
+ * 0.65 puts 62 edges in range of an agent); the solve and the observation then carry every one of them, bit for bit RVO2's. */
 int ca_allow_obstacle_overflow(ca_env* env, int32_t allow);
 
 /* Blocks until the stream is idle, then returns the counters accumulated so far. */
@@ -319,6 +327,10 @@ int ca_launch_info(ca_env* env, int32_t* block, int32_t* grid, int32_t* lds_byte
  * lines live in registers when max_neighbors <= 10 and either max_obst_neighbors <= 4 or the installed world has at most 16
  * edges per arena (the reference env's own doorway world: an agent with more than four edges in range is solved apart,
  * exactly), else in an LDS table; the choice is re-made when obstacle tables are installed.
+ * max_obst_neighbors > 16 always means one lane per agent on the wide LDS table (max_neighbors + max_obst_neighbors lines per
+ * lane; *lanes_per_agent = 1, *rollout_one_launch = 0, ca_launch_info's lds_bytes = block x (16 (K + S) + 32)), whatever the
+ * world and the batch size: no register lines, no two- or four-lanes kernel (CA_QUAD / CA_REG_LINES are ignored), a batch
+ * that is not resident with the table runs in rounds, and ca_alan_step is three launches (select, solve, update).
  * *rollout_one_launch = 1: ca_rollout(env, T, flags without CA_F_OBS) is ONE kernel launch that keeps every arena in
  * registers / LDS for its T steps (the four-lanes kernel; chosen up to 1024 waves inclusive); 0: it is T launches. */
 int ca_solver_info(ca_env* env, int32_t* lanes_per_agent, int32_t* rollout_one_launch);
