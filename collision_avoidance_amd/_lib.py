@@ -24,7 +24,8 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_get_stats", "ca_reset_stats", "ca_sync", "ca_debug_math", "ca_profile", "ca_profile_read", "ca_launch_info",
            "ca_alan_configure", "ca_alan_step", "ca_alan_rollout", "ca_reset_masked", "ca_get_obstacles",
            "ca_set_obstacles_per_arena", "ca_get_obstacles_arena", "ca_solver_info", "ca_source_sha", "ca_host_alloc", "ca_host_free",
-           "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena")
+           "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
+           "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info")
 
 
 class Config(C.Structure):
@@ -108,6 +109,9 @@ def load():
     L.ca_profile_read.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_float)]
     L.ca_launch_info.argtypes = [vp] + [C.POINTER(i32)] * 4
     L.ca_solver_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.ca_set_agent_params.argtypes = [vp, vp, vp, vp, vp, sz, i32]
+    L.ca_get_agent_params.argtypes = [vp, vp, vp, vp, vp, sz, i32]
+    L.ca_agent_params_info.argtypes = [vp, C.POINTER(i32)]
     L.ca_source_sha.argtypes = []
     L.ca_source_sha.restype = C.c_char_p
     for name in EXPORTS:

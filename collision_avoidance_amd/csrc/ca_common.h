@@ -2,6 +2,7 @@
 // Part of the HIP kernels of libcaenv.so (see ca_kernels.h for the overview and the numerics contract).
 #pragma once
 #include "ca_math.h"
+#include <type_traits>
 #include <utility>
 
 // Tag of the kernels' per-arena-action-set instantiations (step_kernel / quad_kernel <..., true, AlanArenaSets>).  Declared
@@ -9,8 +10,15 @@
 struct AlanArenaSets;
 // Tag of the observation kernel's wide instantiations (obs_kernel<..., WideObstLists>: obstacle-neighbour lists of 17 .. 64).
 struct WideObstLists;
+// Tag of the per-agent-parameter instantiations (step_kernel<KMAX, BS, 0, SMAX, false, AgentParams>, obs_kernel<..., AgentParams>):
+// radius, max_speed, time_horizon and time_horizon_obst of every agent come from [A,N] arrays (ca_set_agent_params) instead of
+// the handle's four constants.
+struct AgentParams;
 
 namespace ca {
+
+// is the tag T among a kernel's trailing tag pack?  (an empty pack: no)
+template <class T, class... P> constexpr bool has_tag = (std::is_same_v<T, P> || ...);
 
 constexpr int SMAX = 16;      // obstacle-neighbour lists of up to 16 (LDS line table; the register-line and quad kernels hold 4)
 constexpr int SWIDE = 64;     // CA_MAX_OBST_NEIGHBORS: the wide instantiations of the LDS-line-table kernel and of the observation
@@ -57,6 +65,9 @@ struct StepCold {
     int max_step, done_mode;
     float done_x_thresh;
     float spawn_x0, spawn_x1, spawn_y0, spawn_y1, goal_x0, goal_x1, goal_y0, goal_y1;
+    // per-agent ORCA parameters [A*N] (ca_set_agent_params; null on a handle with uniform parameters): read by the AgentParams
+    // instantiations only.  At the end of the block: nothing the other kernels load moves.
+    const float *ap_radius, *ap_max_speed, *ap_time_horizon, *ap_time_horizon_obst;
 };
 
 // ALAN online learning inside the four-lanes kernel (ca_quad.h): the bandit's arguments, in device memory like StepCold

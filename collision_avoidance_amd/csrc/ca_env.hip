@@ -96,6 +96,13 @@ struct ca_env {
     int BSq = 64, grid_q = 1, SQ = 4;   // SQ: obstacle-neighbour capacity of the quad variant (4 or 16)
     size_t lds_q = 0;
     size_t lds = 0;
+    // per-agent ORCA parameters (ca_set_agent_params): configuration, like the obstacle tables.  ap = the handle runs the
+    // AgentParams instantiations (one lane per agent on the LDS line table, the observation with an octagon per neighbour);
+    // quad_cfg / quad_roll_cfg keep what ca_create chose for uniform parameters, to return to when the parameters are cleared.
+    bool ap = false, quad_cfg = false, quad_roll_cfg = false;
+    float* d_ap[4] = {nullptr, nullptr, nullptr, nullptr};   // [A*N] radius | max_speed | time_horizon | time_horizon_obst
+    float* d_ap_oct = nullptr;                               // [A*N][8] float2: every agent's octagon (ca_obs.h ObsArgs::ap_oct)
+    std::vector<float> h_ap[4];                              // host copies (ca_get_agent_params)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
     // opt-in per-kernel timing (ca_profile): event pairs recorded around launches, drained on read
@@ -250,6 +257,8 @@ static void fill_cold(const ca_env* e, StepCold& c) {
     c.max_step = g.max_step; c.done_mode = g.done_mode; c.done_x_thresh = g.done_x_thresh;
     c.spawn_x0 = g.spawn_x0; c.spawn_x1 = g.spawn_x1; c.spawn_y0 = g.spawn_y0; c.spawn_y1 = g.spawn_y1;
     c.goal_x0 = g.goal_x0; c.goal_x1 = g.goal_x1; c.goal_y0 = g.goal_y0; c.goal_y1 = g.goal_y1;
+    c.ap_radius = e->ap ? e->d_ap[0] : nullptr; c.ap_max_speed = e->ap ? e->d_ap[1] : nullptr;
+    c.ap_time_horizon = e->ap ? e->d_ap[2] : nullptr; c.ap_time_horizon_obst = e->ap ? e->d_ap[3] : nullptr;
 }
 
 static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t flags) {
@@ -309,10 +318,22 @@ template <int KMAX>
 static const void* wide_fn_for(int BS) {
     return BS == 64 ? fn_ptr(&step_kernel<KMAX, 64, 0, SWIDE>) : fn_ptr(&step_kernel<KMAX, 128, 0, SWIDE>);
 }
+// per-agent parameters (ca_set_agent_params): the LDS line table with lists of up to 16, any arena size that fits; no ALAN form
+template <int KMAX>
+static const void* ap_fn_for(int BS) {
+    switch (BS) {
+        case 64: return fn_ptr(&step_kernel<KMAX, 64, 0, SMAX, false, AgentParams>);
+        case 128: return fn_ptr(&step_kernel<KMAX, 128, 0, SMAX, false, AgentParams>);
+        case 256: return fn_ptr(&step_kernel<KMAX, 256, 0, SMAX, false, AgentParams>);
+        case 512: return fn_ptr(&step_kernel<KMAX, 512, 0, SMAX, false, AgentParams>);
+        default: return fn_ptr(&step_kernel<KMAX, 1024, 0, SMAX, false, AgentParams>);
+    }
+}
 // the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
 // more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
 template <bool ALAN, class... PER>
 static const void* lane_fn_for(const ca_env* e) {
+    if (e->ap) return e->KT == 5 ? ap_fn_for<5>(e->BS) : (e->KT == 16 ? ap_fn_for<16>(e->BS) : ap_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->SMX > SMAX) return e->KT == 5 ? wide_fn_for<5>(e->BS) : (e->KT == 16 ? wide_fn_for<16>(e->BS) : wide_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->ST > 0 && e->SMX > 4) return e->KT == 5 ? step_fn_for<5, 4, 16, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 16, ALAN, PER...>(e->BS);
     if (e->ST > 0) return e->KT == 5 ? step_fn_for<5, 4, 4, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 4, ALAN, PER...>(e->BS);
@@ -353,7 +374,9 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
 }
 
 typedef void (*obs_fn_t)(const ObsArgs);
-static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = false) {  // workgroup size x width of the stored agent-neighbour ids
+static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = false, bool ap = false) {  // workgroup size x width of the stored agent-neighbour ids
+    // (per-agent parameters: 256 lanes, what obs_block_threads gives every arena size; never with obstacle lists above 16)
+    if (ap) return dense ? obs_kernel<256, false, true, AgentParams> : (w16 ? obs_kernel<256, true, false, AgentParams> : obs_kernel<256, false, false, AgentParams>);
     // (obstacle lists above 16: arenas of at most 128 agents -- 256 lanes, 8-bit ids; ca_create checks that)
     if (wide) return dense ? obs_kernel<256, false, true, WideObstLists> : obs_kernel<256, false, false, WideObstLists>;
     if (dense) return obs_kernel<256, false, true>;   // (arenas of fewer than 16 agents: 256 lanes, 8-bit ids)
@@ -371,7 +394,16 @@ static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = fal
 static bool obs_dense(const ca_env* e) { return e->obs_dense_on; }   // (latched by ca_create)
 static int obs_nstage(const ca_env* e) { return obs_dense(e) ? 16 + 2 * e->cfg.n_agents : e->cfg.n_agents; }
 static bool obs_wide(const ca_env* e) { return e->S > SMAX; }   // more than 16 obstacle ids per agent (ca_obs.h WIDE)
-static size_t obs_lds(const ca_env* e, int obs_bs) { return obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S), obs_wide(e) ? e->S : 16); }
+static size_t obs_lds(const ca_env* e, int obs_bs) {
+    if (e->ap) return obs_lds_bytes_ap(obs_nstage(e), obs_bs, 16 * (e->K + e->S));
+    return obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S), obs_wide(e) ? e->S : 16);
+}
+static obs_fn_t obs_fn_of(const ca_env* e) { return obs_fn(obs_block_threads(e->cfg.n_agents), e->nidx16 != 0, obs_dense(e), obs_wide(e), e->ap); }
+// (above the 48 KiB that every kernel may take, the observation kernel's dynamic LDS needs its limit raised before the launch)
+static hipError_t allow_obs_lds(const ca_env* e) {
+    const size_t ol = obs_lds(e, obs_block_threads(e->cfg.n_agents));
+    return ol > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(obs_fn_of(e)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ol) : hipSuccess;
+}
 
 static hipError_t launch_obs(ca_env* e) {
     if (!e->orient_valid) {  // positions or goals were edited from outside: re-derive the frame
@@ -400,10 +432,11 @@ static hipError_t launch_obs(ca_env* e) {
     o.radius = e->cfg.radius;
     memcpy(o.rays, e->rays, sizeof o.rays);
     memcpy(o.oct, e->oct, sizeof o.oct);
+    o.ap_oct = e->ap ? e->d_ap_oct : nullptr;
     const dim3 grid(o.dense ? (unsigned)(((size_t)o.A * o.N + apb - 1) / apb) : (unsigned)((size_t)o.A * o.bpa)), block(obs_bs);
     const size_t lds = obs_lds(e, obs_bs);
     ProfScope ps(e, KIND_OBS);
-    launch_k(ps, obs_fn(obs_bs, e->nidx16 != 0, o.dense != 0, obs_wide(e)), grid, block, lds, e->stream, o);
+    launch_k(ps, obs_fn_of(e), grid, block, lds, e->stream, o);
     return hipGetLastError();
 }
 
@@ -548,10 +581,11 @@ static void pick_variant(ca_env* e) {
     // 157.8 / 76.3; blocks x 20 agents, 8192 arenas 126.9 / 75.4; profiles/r04_g_many_edge_worlds.txt)
     const bool table_resident = table_fits && (long)e->grid <= (long)e->n_cus * (long)((160 * 1024) / table_per_wg);
     if (e->S > SMAX) { e->ST = 0; e->SMX = SWIDE; }
+    else if (e->ap) { e->ST = 0; e->SMX = SMAX; }   // per-agent parameters: always the LDS line table, whatever the switches, the world and the batch say
     else if (allow && e->K <= 10 && e->S <= 4) { e->ST = 4; e->SMX = 4; }
     else if (allow && e->K <= 10 && (small_world || force || !table_resident)) { e->ST = 4; e->SMX = 16; }
     else { e->ST = 0; e->SMX = 16; }
-    e->lds = step_lds_bytes(e->BS, e->K, e->S, e->ST, e->KT);
+    e->lds = e->ap ? step_lds_bytes_ap(e->BS, e->K, e->S) : step_lds_bytes(e->BS, e->K, e->S, e->ST, e->KT);
     // two lanes per agent for the whole step (ca_pair.h), arenas of 129 .. 512 agents on register lines: a 512-agent arena is 8
     // waves of one lane per agent on its CU -- two per SIMD, each a long dependent chain; 16 waves with half the chain each fill it
     // (CA_PAIR=0: the one-lane register-line kernel; arenas of 65 .. 128 agents, two waves, measured faster on it: ca_pair.h)
@@ -591,7 +625,8 @@ static int alan_pick(ca_env* e) {
     const bool on = e->sw.alan_fused != 0;   // (CA_ALAN_FUSED=0: the three-launch form everywhere)
     e->alan_fused = on && (e->quad || e->quad_roll) && lq <= 64 * 1024;
     // (obstacle lists above 16: the wide table kernel has no ALAN instantiation and no four-lanes form -- select -> solve -> update)
-    e->alan_lane = on && !e->quad && !e->pair && e->BS <= 128 && e->K <= 10 && e->S <= SMAX &&
+    // (per-agent parameters: the same -- quad and quad_roll are off there, and the AgentParams kernel has no ALAN instantiation)
+    e->alan_lane = on && !e->ap && !e->quad && !e->pair && e->BS <= 128 && e->K <= 10 && e->S <= SMAX &&
                    e->n_actions <= (e->ST > 0 ? 4 + e->KT : 2 * (e->K + e->S));
     if (e->alan_fused) HIPCHK(e, allow_lds(solve_launch(e, true, true)));   // (the ALAN rollout; on a quad handle the ALAN step too)
     if (e->alan_lane) HIPCHK(e, allow_lds(solve_launch(e, true, false)));
@@ -696,6 +731,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         const int apbq = (e->BSq / 4) / P;
         e->grid_q = (cfg->n_arenas + apbq - 1) / apbq;
         e->lds_q = quad_lds_bytes(e->BSq, e->KT, e->SQ);
+        e->quad_cfg = e->quad; e->quad_roll_cfg = e->quad_roll;
     }
     if (e->S > SMAX && (e->lds + lds_static_bytes(e) > LDS_PER_CU || e->BS > 128 || obs_block_threads(cfg->n_agents) != 256)) {
         // obstacle lists above 16 live in the LDS line table, K + S lines per lane: 64 lanes with K <= 16, 128 lanes with K <= 10 at S = 64
@@ -747,14 +783,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
 #endif
     bool lds_misfit = false;
     if (r == hipSuccess) r = apply_variant_attributes(e, &lds_misfit);
-    if (r == hipSuccess) {
-        const int obs_bs = obs_block_threads(cfg->n_agents);
-        const size_t ol = obs_lds(e, obs_bs);
-        if (ol > 48 * 1024) {
-            r = hipFuncSetAttribute(reinterpret_cast<const void*>(obs_fn(obs_bs, e->nidx16 != 0, obs_dense(e), obs_wide(e))),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)ol);
-        }
-    }
+    if (r == hipSuccess) r = allow_obs_lds(e);
     if (r == hipSuccess) {
         r = hipHostMalloc((void**)&e->ovf_host, sizeof(unsigned long long), hipHostMallocDefault);
         if (r == hipSuccess) *e->ovf_host = 0ull;
@@ -791,7 +820,7 @@ int ca_destroy(ca_env* e) {
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
-                    e->d_act_tab, e->d_act_n};
+                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -974,7 +1003,139 @@ int ca_get_obstacles_arena(ca_env* e, int32_t arena, float* verts_xy, int32_t* n
     return get_table(e, arena, verts_xy, next, convex, cap, n_out);
 }
 
-}  // extern "C" (the scenario generators below are plain C++)
+}  // extern "C" (the per-agent parameters and the scenario generators below are plain C++ around their entry points)
+
+// ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133; setAgentRadius / setAgentMaxSpeed /
+// setAgentTimeHorizon / setAgentTimeHorizonObst) ----
+// every agent's octagon as the observation sees it (env.py:335-350): vertex e = (r cos(e pi/4), -(r sin(e pi/4))) in fp64 from the
+// fp32 radius, rounded once to fp32 -- host_tables' chain, per agent; cos / sin are libm's, as there
+static void agent_octagons(const std::vector<float>& radius, std::vector<float>& oct) {
+    double cs[8], sn[8];
+    for (int i = 0; i < 8; ++i) { const double th = i * (2.0 * M_PI / 8); cs[i] = std::cos(th); sn[i] = std::sin(th); }
+    oct.resize(radius.size() * 16);
+    for (size_t q = 0; q < radius.size(); ++q) {
+        const double r = (double)radius[q];
+        for (int i = 0; i < 8; ++i) { oct[q * 16 + 2 * i] = (float)(r * cs[i]); oct[q * 16 + 2 * i + 1] = (float)(-r * sn[i]); }
+    }
+}
+
+// the handle's variant state that per-agent parameters change (saved before a prospective pick_variant, restored on failure)
+struct VariantState { bool ap, quad, quad_roll, pair; int ST, SMX, KT; size_t lds, lds_p; };
+static VariantState save_variant(const ca_env* e) { return {e->ap, e->quad, e->quad_roll, e->pair, e->ST, e->SMX, e->KT, e->lds, e->lds_p}; }
+static void restore_variant(ca_env* e, const VariantState& v) {
+    e->ap = v.ap; e->quad = v.quad; e->quad_roll = v.quad_roll; e->pair = v.pair; e->ST = v.ST; e->SMX = v.SMX; e->KT = v.KT;
+    e->lds = v.lds; e->lds_p = v.lds_p;
+}
+// switch the handle to (on) or away from (off) the AgentParams kernels: variant and dynamic-LDS limits, checked against the CU's
+// LDS before anything is swapped (as install_tables does).  *misfit: the kernel does not fit; the handle is then left as it was.
+static hipError_t switch_agent_params(ca_env* e, bool on, bool* misfit) {
+    const VariantState old_v = save_variant(e);
+    e->ap = on;
+    e->quad = on ? false : e->quad_cfg;
+    e->quad_roll = on ? false : e->quad_roll_cfg;
+    pick_variant(e);
+    hipError_t r = apply_variant_attributes(e, misfit);
+    if (r == hipSuccess && !*misfit) r = allow_obs_lds(e);
+    if (r != hipSuccess || *misfit) {
+        restore_variant(e, old_v);
+        bool dummy = false;
+        (void)apply_variant_attributes(e, &dummy);   // (the previous variant's limits again: the attribute calls are idempotent)
+    }
+    return r;
+}
+
+extern "C" {
+
+int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, const float* time_horizon,
+                        const float* time_horizon_obst, size_t bytes_each, int32_t src_is_device) {
+    if (!e) return CA_EINVAL;
+    const float* src[4] = {radius, max_speed, time_horizon, time_horizon_obst};
+    static const char* const names[4] = {"radius", "max_speed", "time_horizon", "time_horizon_obst"};
+    const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
+    const bool any = radius || max_speed || time_horizon || time_horizon_obst;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (!any) {   // back to the handle's four constants and to the kernels it used with them
+        if (!e->ap) return CA_OK;
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        bool misfit = false;
+        const hipError_t r = switch_agent_params(e, false, &misfit);
+        if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the per-agent parameters stay)", hipGetErrorString(r));
+        if (misfit) return fail(e, CA_ERANGE, "ca_set_agent_params: the uniform solve kernel does not fit the 160 KiB of LDS of a CU (the per-agent parameters stay)");
+        StepCold hc;
+        fill_cold(e, hc);
+        HIPCHK(e, upload(e, e->d_cold, &hc, sizeof hc));
+        for (auto& h : e->h_ap) h.clear();
+        return alan_pick(e);
+    }
+    if (e->S > SMAX)
+        return fail(e, CA_EINVAL, "ca_set_agent_params: not together with wide obstacle lists (max_obst_neighbors=%d > %d)", e->S, SMAX);
+    const size_t an = AN(e);
+    if (bytes_each != an * 4) return fail(e, CA_ESIZE, "ca_set_agent_params: each array holds %zu bytes, got %zu", an * 4, bytes_each);
+    // a configuration call: every value is checked (a device array is copied back for it)
+    std::vector<float> h[4];
+    for (int k = 0; k < 4; ++k) {
+        h[k].assign(an, defaults[k]);
+        if (!src[k]) continue;
+        if (src_is_device) HIPCHK(e, download(e, h[k].data(), src[k], an * 4));
+        else memcpy(h[k].data(), src[k], an * 4);
+        for (size_t q = 0; q < an; ++q)
+            if (!(h[k][q] >= CA_MIN_LENGTH && h[k][q] <= CA_MAX_LENGTH))   // (also false for NaN)
+                return fail(e, CA_ERANGE, "ca_set_agent_params: %s=%g of arena %zu, agent %zu is outside the supported range [%g, %g] or not a number",
+                            names[k], (double)h[k][q], q / (size_t)e->cfg.n_agents, q % (size_t)e->cfg.n_agents, (double)CA_MIN_LENGTH, (double)CA_MAX_LENGTH);
+    }
+    std::vector<float> oct;
+    agent_octagons(h[0], oct);
+    // the buffers exist before anything changes (the first call allocates them; they stay until ca_destroy)
+    for (int k = 0; k < 4; ++k) if (!e->d_ap[k]) HIPCHK(e, hipMalloc((void**)&e->d_ap[k], an * 4));
+    if (!e->d_ap_oct) HIPCHK(e, hipMalloc((void**)&e->d_ap_oct, an * 64));
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous values
+    if (!e->ap) {   // the prospective variant is chosen and checked against the CU's LDS before anything is swapped
+        bool misfit = false;
+        const hipError_t r = switch_agent_params(e, true, &misfit);
+        if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the handle keeps its uniform parameters)", hipGetErrorString(r));
+        if (misfit)
+            return fail(e, CA_ERANGE, "ca_set_agent_params: the per-agent solve kernel (LDS line table, max_neighbors + max_obst_neighbors lines per lane) "
+                        "does not fit the 160 KiB of LDS of a CU for n_agents=%d, max_neighbors=%d, max_obst_neighbors=%d; the handle keeps its "
+                        "uniform parameters", e->cfg.n_agents, e->K, e->S);
+    }
+    hipError_t r = hipSuccess;
+    for (int k = 0; k < 4 && r == hipSuccess; ++k) r = hipMemcpyAsync(e->d_ap[k], h[k].data(), an * 4, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(e->d_ap_oct, oct.data(), an * 64, hipMemcpyHostToDevice, e->stream);
+    StepCold hc;
+    fill_cold(e, hc);
+    if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);   // (synchronises: the host vectors above may go)
+    if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r));
+    for (int k = 0; k < 4; ++k) e->h_ap[k].swap(h[k]);
+    return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
+}
+
+int ca_get_agent_params(ca_env* e, float* radius, float* max_speed, float* time_horizon, float* time_horizon_obst,
+                        size_t bytes_each, int32_t dst_is_device) {
+    if (!e) return CA_EINVAL;
+    float* dst[4] = {radius, max_speed, time_horizon, time_horizon_obst};
+    const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
+    const size_t an = AN(e);
+    if (bytes_each != an * 4) return fail(e, CA_ESIZE, "ca_get_agent_params: each array holds %zu bytes, got %zu", an * 4, bytes_each);
+    HIPCHK(e, hipSetDevice(e->device));
+    for (int k = 0; k < 4; ++k) {
+        if (!dst[k]) continue;
+        std::vector<float> uni;
+        if (!e->ap) uni.assign(an, defaults[k]);   // uniform parameters: the handle's constant for every agent
+        const float* s = e->ap ? e->h_ap[k].data() : uni.data();
+        if (dst_is_device) { HIPCHK(e, upload(e, dst[k], s, an * 4)); }
+        else memcpy(dst[k], s, an * 4);
+    }
+    return CA_OK;
+}
+
+int ca_agent_params_info(ca_env* e, int32_t* per_agent) {
+    if (!e) return CA_EINVAL;
+    if (per_agent) *per_agent = e->ap ? 1 : 0;
+    return CA_OK;
+}
+
+}  // extern "C"
+
 
 // The scenario generators (env.py:86-97, ALAN:175-457) on the host, for arenas [0, An): An = n_arenas for the one scenario
 // whose draws are sequential per arena (rejection-sampled starts), An = 1 for the per-agent TABLE of the others -- their

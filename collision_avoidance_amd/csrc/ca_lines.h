@@ -5,7 +5,7 @@
 
 namespace ca {
 
-// App. A.4: the half-plane induced by one neighbouring agent (both agents have radius R).
+// App. A.4: the half-plane induced by one neighbouring agent.
 // Branch-free: a wave of 64 agents takes all three cases of the contract (cut-off circle, legs, collision) for nearly
 // every neighbour slot anyway, and as branches they cost 179 vector instructions per line, 39 of them register copies
 // at the joins.  Here the cut-off circle and the collision case share their arithmetic (the same formulas on the time
@@ -14,11 +14,12 @@ namespace ca {
 //   * right leg:  -( (rp.x leg + rp.y cr, -rp.x cr + rp.y leg) / d2 )  is evaluated as  -( (rp.x leg - rp.y c, rp.x c +
 //     rp.y leg) / d2 ) with c = -cr: x - (-y) = x + y and (-x) y = x (-y) are exact identities of IEEE arithmetic;
 //   * lanes on the other side of a select compute NaN / inf at worst (sqrt of a negative, 1/0), which is dropped.
-__device__ __forceinline__ Line agent_orca_line(V2 pos, V2 vel, V2 opos, V2 ovel, float R, float invT, float invDt) {
+// R: the agent's own radius, oR: the neighbour's -- combinedRadius = R + oR, own radius first, as the contract adds them.
+__device__ __forceinline__ Line agent_orca_line(V2 pos, V2 vel, V2 opos, V2 ovel, float R, float oR, float invT, float invDt) {
     const V2 rp = opos - pos;
     const V2 rv = vel - ovel;
     const float distSq = absSq(rp);
-    const float cr = R + R;
+    const float cr = R + oR;
     const float crSq = sqr(cr);
     const bool coll = !(distSq > crSq);
     const float invX = coll ? invDt : invT;
@@ -43,6 +44,11 @@ __device__ __forceinline__ Line agent_orca_line(V2 pos, V2 vel, V2 opos, V2 ovel
     const V2 u = circle ? uC : uL;
     line.point = vel + 0.5f * u;
     return line;
+}
+
+// one radius for both agents (every kernel of a handle with uniform parameters)
+__device__ __forceinline__ Line agent_orca_line(V2 pos, V2 vel, V2 opos, V2 ovel, float R, float invT, float invDt) {
+    return agent_orca_line(pos, vel, opos, ovel, R, R, invT, invDt);
 }
 
 // App. A.3: the half-plane induced by the obstacle edge e.  Returns false when the edge yields no

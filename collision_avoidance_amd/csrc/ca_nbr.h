@@ -55,7 +55,9 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
 // the lane itself touches its column, and the solve kernel has a barrier between the search and its first line.  The order is
 // sorted_insert's: ascending (distance, index) key.  Cost: a data-dependent shift loop per accepted edge -- edges arrive in index
 // order, not by distance, so an insert is up to S LDS round trips on the slowest lane of the wave.
-template <int KMAX, int BS, int SM>
+// AP (the AgentParams instantiation of the solve kernel): the range of the obstacle search is the agent's own,
+// sqr(time_horizon_obst_i * max_speed_i + radius_i), from the per-agent arrays of the cold block.
+template <int KMAX, int BS, int SM, bool AP = false>
 __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #ifndef CA_NBR_NO_VGPR_PAD
     // Claim 128 VGPRs (the kernel needs 56): at most 4 waves then fit on a SIMD, so a launch that brings one
@@ -117,7 +119,11 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
         wkey[k * BS] = x;
     };
     {
-        const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
+        float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
+        if constexpr (AP) {
+            const StepCold* cp = p.cold;
+            rangeSq = active ? sqr(cp->ap_time_horizon_obst[q] * cp->ap_max_speed[q] + cp->ap_radius[q]) : 0.0f;
+        }
         auto visit = [&](const ObstDev& o1, int e, bool mine) __attribute__((always_inline)) {
             const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
             const float alol = leftOf(a1, a2, pos);

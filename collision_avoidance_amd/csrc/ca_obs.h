@@ -41,6 +41,10 @@ struct ObsArgs {
     float radius;         // of the octagon = agent radius (env.py:31,338)
     float rays[32];       // env.py:321-332
     float oct[32];        // env.py:335-350
+    const float* ap_oct;  // AgentParams instantiations only: [A*N][8] float2, every agent's octagon vertices (radius r_j: vertex e =
+                          // ((float)(r_j cos(e pi/4)), (float)(-(r_j sin(e pi/4)))) in fp64 from the fp32 radius, made on the host by
+                          // ca_set_agent_params; chord e runs from vertex e to vertex (e + 1) mod 8, env.py:335-350).  Last member:
+                          // nothing the other instantiations read moves.
 };
 
 #ifdef CA_STAMPS
@@ -67,6 +71,11 @@ struct ObsArgs {
 __host__ __device__ inline size_t obs_lds_bytes(int nstage_max, int obs_bs, int paircap, int obw = 16) {
     const size_t apb = obs_bs / 16;
     return (size_t)nstage_max * 16 + 2 * apb * 16 * 8 + apb * 16 + apb * 16 * 4 + apb * (size_t)obw * 4 + 64 * 4 + 2 * apb * 4 + apb * (size_t)paircap * 2;
+}
+// the AgentParams instantiations: ... | the octagons of the agents' neighbours [16][16][8] float2 (64 B per neighbour slot), behind the
+// pair list rounded up to 16 bytes
+__host__ __device__ inline size_t obs_lds_bytes_ap(int nstage_max, int obs_bs, int paircap) {
+    return ((obs_lds_bytes(nstage_max, obs_bs, paircap) + 15) & ~(size_t)15) + (size_t)(obs_bs / 16) * 16 * 64;
 }
 #ifndef CA_OBS_BS_MAX
 #define CA_OBS_BS_MAX 256
@@ -111,9 +120,15 @@ __device__ __forceinline__ float ray_dial(float x, float y) {
 // WIDE_TAG = WideObstLists (obstacle-neighbour lists of 17 .. 64 edges, S > 16): an agent's S obstacle ids are staged by its 16
 // lanes in a strided loop instead of one id per lane, S ids per agent in LDS; the pre-pass and build() then run over up to 64
 // edges as they are.  (A trailing pack, empty in every other instantiation, so that those keep their names and their code.)
+// AgentParams in the pack (per-agent radii, ca_set_agent_params; never together with WideObstLists): neighbour j is seen as the
+// octagon of ITS radius -- the lane that owns neighbour slot k copies j's eight vertices from the per-agent table into LDS, the
+// chords are built from them, and the pre-pass circle, the tolerance of phase A and its world-frame filter take that radius
+// (= vertex 0's x, exactly: (float)((double)r cos 0) = r).
 template <int OBS_BS, bool NW16, bool DENSE = false, class... WIDE_TAG>
 __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
-    constexpr bool WIDE = sizeof...(WIDE_TAG) > 0;
+    constexpr bool WIDE = has_tag<WideObstLists, WIDE_TAG...>;
+    constexpr bool AP = has_tag<AgentParams, WIDE_TAG...>;
+    static_assert(!(WIDE && AP), "per-agent parameters go with obstacle lists of up to 16");
     constexpr int OBS_APB = OBS_BS / 16;  // agents per workgroup
     extern __shared__ float4 smem4[];
     const int tid = threadIdx.x;
@@ -168,6 +183,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     int* s_cnt2 = s_cnt + OBS_APB;                                         // [16] obstacle pairs per agent
     unsigned short* s_pair = reinterpret_cast<unsigned short*>(s_cnt2 + OBS_APB);  // [16 * paircap]
     const int SPAIRS = 16 * S;  // an agent's block of obstacle pairs
+    // (AP) vertex e of the octagon of neighbour slot k of agent g: s_noct[(g * 16 + k) * 8 + e]
+    float2* s_noct = reinterpret_cast<float2*>(reinterpret_cast<char*>(smem4) + ((obs_lds_bytes(NST, OBS_BS, PAIRCAP) + 15) & ~(size_t)15));
     CA_OSTAMP(0);
     if (tid < 32) { s_rays[tid] = p.rays[tid]; s_oct[tid] = p.oct[tid]; }
 
@@ -237,7 +254,16 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             const int nb = s_nb[g * 16 + k];
             const float rx = (GATHER ? gpx[nb] : s_px[nb]) - mx, ry = (GATHER ? gpy[nb] : s_py[nb]) - my;
             s_rel[g * 16 + k] = make_float2(rx, ry);  // (env.py:288-289) for the pair trips and the winners
-            const float d2 = rx * rx + ry * ry, R = p.radius;
+            float Rk = p.radius;
+            if constexpr (AP) {   // the neighbour's own octagon, from the per-agent table (its index in the batch: the staged arenas are contiguous)
+                const size_t nq = (DENSE ? (size_t)a_lo * N : aoff) + (size_t)nb;
+                const float2* src = reinterpret_cast<const float2*>(p.ap_oct) + nq * 8;
+                float2* dst = s_noct + (g * 16 + k) * 8;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dst[e] = src[e];
+                Rk = src[0].x;
+            }
+            const float d2 = rx * rx + ry * ry, R = Rk;
             const float ax = c * rx - s * ry, ay = s * rx + c * ry;
             const bool all = !(d2 > 1.0404f * R * R);  // the agent is inside (or within 2 % of) that circle
             const float ua = ray_dial(ax, ay);
@@ -300,9 +326,15 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             const int k = m >> 3, e = m & 7;
             const float2 rel = s_rel[g * 16 + k];
             const float rx = rel.x, ry = rel.y;
-            const float4 oc = reinterpret_cast<const float4*>(s_oct)[e];
-            x1 = oc.x + rx; y1 = oc.y + ry;
-            x2 = oc.z + rx; y2 = oc.w + ry;
+            if constexpr (AP) {   // chord e of the neighbour's own octagon: vertex e -> vertex (e + 1) mod 8
+                const float2 va = s_noct[(g * 16 + k) * 8 + e], vb = s_noct[(g * 16 + k) * 8 + ((e + 1) & 7)];
+                x1 = va.x + rx; y1 = va.y + ry;
+                x2 = vb.x + rx; y2 = vb.y + ry;
+            } else {
+                const float4 oc = reinterpret_cast<const float4*>(s_oct)[e];
+                x1 = oc.x + rx; y1 = oc.y + ry;
+                x2 = oc.z + rx; y2 = oc.w + ry;
+            }
             if (want_vel) { const int nb = s_nb[g * 16 + k]; vx = GATHER ? gvx[nb] : s_vx[nb]; vy = GATHER ? gvy[nb] : s_vy[nb]; }  // env.py:252
         } else {
             const ObstDev o1 = load_obst(tab, s_ob[g * OBW + (m - 8 * nn)]);
@@ -321,9 +353,16 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         }
     };
     // chord e of a neighbour at (rx, ry) from its agent, in the agent's frame fr = (cos, sin)
-    auto build_nb = [&](const float2& fr, float rx, float ry, int e, SegGeom& sg) {
-        const float4 oc = reinterpret_cast<const float4*>(s_oct)[e];
-        const float x1 = oc.x + rx, y1 = oc.y + ry, x2 = oc.z + rx, y2 = oc.w + ry;
+    // (slot = ga * 16 + k: AP reads that neighbour's own vertices)
+    auto build_nb = [&](const float2& fr, float rx, float ry, int e, SegGeom& sg, int slot) {
+        float x1, y1, x2, y2;
+        if constexpr (AP) {
+            const float2 va = s_noct[slot * 8 + e], vb = s_noct[slot * 8 + ((e + 1) & 7)];
+            x1 = va.x + rx; y1 = va.y + ry; x2 = vb.x + rx; y2 = vb.y + ry;
+        } else {
+            const float4 oc = reinterpret_cast<const float4*>(s_oct)[e];
+            x1 = oc.x + rx; y1 = oc.y + ry; x2 = oc.z + rx; y2 = oc.w + ry;
+        }
         sg.r1x = fr.x * x1 - fr.y * y1; sg.r1y = fr.y * x1 + fr.x * y1;  // utils.py:59
         sg.r2x = fr.x * x2 - fr.y * y2; sg.r2y = fr.y * x2 + fr.x * y2;  // utils.py:60
         sg.s32x = sg.r2x - sg.r1x; sg.s32y = sg.r2y - sg.r1y;
@@ -366,7 +405,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // bit for bit (env.py:335-350 builds them as a chain), so the 8 rotated vertices are computed once
     // per pair and every chord is accept-tested against the pair's single ray.  Only accepted chords
     // (about two per pair) are re-derived through build()/hit() for the exact hit distance.
-    const float tol = 2e-5f * p.rays[0] * (p.rays[0] + 2.0f * p.radius + 1.0f);  // rays[0] = neighbor_dist (env.py:321-332)
+    const float tol_u = 2e-5f * p.rays[0] * (p.rays[0] + 2.0f * p.radius + 1.0f);  // rays[0] = neighbor_dist (env.py:321-332)
     auto merge = [&](int ga, int ray, float best, int best_m) {
         if (best_m >= 0)
             atomicMin(&s_key[ga * 16 + ray], ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)best_m);
@@ -399,7 +438,12 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         // so the eight cross products are four, each added to and subtracted from the ray x centre term.
         const float wx = fr.x * s10x + fr.y * s10y, wy = fr.x * s10y - fr.y * s10x;
         const float wb = wx * ry - wy * rx;
-        const float R = p.radius, Rh = 0.70710678f * R;
+        float Rp = p.radius, tol = tol_u;
+        if constexpr (AP) {   // the source's radius, in the filter and in its tolerance
+            Rp = s_noct[(pr >> 4) * 8].x;
+            tol = 2e-5f * p.rays[0] * (p.rays[0] + 2.0f * Rp + 1.0f);
+        }
+        const float R = Rp, Rh = 0.70710678f * R;
         const float c0 = R * wy, c2 = R * wx, c1 = Rh * (wx + wy), c3 = Rh * (wy - wx);
         const float cr[8] = {wb - c0, wb - c1, wb - c2, wb + c3, wb + c0, wb + c1, wb + c2, wb - c3};
         unsigned acc = 0;
@@ -418,8 +462,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             const int e2 = two ? __ffs(acc) - 1 : e1;
             acc &= acc - 1;  // (0 & anything stays 0)
             SegGeom g1, g2;
-            build_nb(fr, rx, ry, e1, g1);
-            build_nb(fr, rx, ry, e2, g2);
+            build_nb(fr, rx, ry, e1, g1, pr >> 4);
+            build_nb(fr, rx, ry, e2, g2, pr >> 4);
             float dn1, dn2;
             const bool ok1 = accept_nb(g1, s10x, s10y, dn1), ok2 = accept_nb(g2, s10x, s10y, dn2) && two;
             // Both accepted (the ray enters through one chord and leaves through the other): the distance is monotone

@@ -15,6 +15,8 @@ __host__ __device__ inline size_t step_lds_bytes(int BS, int K, int S, int ST = 
     if (ST > 0) return (size_t)(BS / 64) * (2 * (ST + KMAX)) * POOL_SLOTS * 16 + (size_t)BS * 32;
     return (size_t)BS * ((size_t)(K + S) * 16 + 16 + 16);
 }
+// the AgentParams instantiation (LDS line table): ... | radii [BS], the arena's radii staged behind the misc ints
+__host__ __device__ inline size_t step_lds_bytes_ap(int BS, int K, int S) { return step_lds_bytes(BS, K, S) + (size_t)BS * 4; }
 
 // ============================================================================================
 // One environment step for every arena (SURVEY.md A5/A6 -> A10-A15 -> A16-A18 + A20).
@@ -88,13 +90,19 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 // LP3 pool, which is free then: at most ML actions), reward and the sliding-window update of weights / times (global memory,
 // [A][nA][N]) where the epilogue begins; the goal direction is derived again there from the staged pre-step position instead of
 // living in registers across the solve.  The rules are ca_rules.h's, as in ca_alan.h's kernels (the three-launch form of the rest).
-// PER (ALAN instantiation only): AlanArenaSets = an action set per arena (ca_alan_configure_per_arena; ca_common.h
-// alan_count / alan_cs); a trailing pack, empty in every other instantiation, so that those keep their names and their code.
+// PER: a trailing pack of tags, empty in every other instantiation, so that those keep their names and their code.
+//   AlanArenaSets (ALAN instantiations only) = an action set per arena (ca_alan_configure_per_arena; ca_common.h alan_count / alan_cs);
+//   AgentParams (LDS line table, ST = 0, no ALAN form) = radius, max_speed, time_horizon and time_horizon_obst per agent
+//   (ca_set_agent_params): the four values are loaded per lane from the cold block's [A*N] arrays, the arena's radii are staged in
+//   LDS behind the misc ints (a neighbour's radius enters combinedRadius = r_i + r_j and the pair count), and the pair count
+//   scans the arena instead of the neighbour lists, whose shortcut assumes one radius.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
-    constexpr int AM = !ALAN ? 0 : (sizeof...(PER) > 0 ? 2 : 1);   // the set mode of alan_count / alan_cs
+    constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
+    constexpr bool AP = has_tag<AgentParams, PER...>;
+    static_assert(!AP || (ST == 0 && !ALAN && SMX <= SMAX), "per-agent parameters: the LDS line table with lists of up to 16, no ALAN form");
     extern __shared__ float4 smem4[];
-    constexpr bool LISTP = BS > 64;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
+    constexpr bool LISTP = BS > 64 && !AP;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
     //                                   scan of the staged arena is as fast -- round 5 measured the lists there: 57.7 against 57.3 us)
     __shared__ unsigned s_vmax2;   // (LISTP) the largest squared speed of the workgroup's arenas in this step, as float bits: see the pair count
     if constexpr (LISTP) { if (threadIdx.x == 0) s_vmax2 = 0u; }   // (barriers follow before its first use)
@@ -102,7 +110,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // The neighbour search runs at the head of this kernel (one drain/fill less per step than a launch of its own, and its
     // dispatch skew overlaps useful work).  A lane later reads back only the lists of its own agent, which it wrote itself;
     // the search's LDS arrays are not used again.
-    nbr_body<KMAX, BS, SMX>(p);
+    nbr_body<KMAX, BS, SMX, AP>(p);
     constexpr int ML = ST + KMAX;  // register slots (ST > 0)
     const int tid = threadIdx.x;
     const int P = p.P;
@@ -124,6 +132,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     float* s_vx = s_py + BS;
     float* s_vy = s_vx + BS;
     int* s_misc = reinterpret_cast<int*>(s_vy + BS);            // [BS][4]
+    float* s_rad = reinterpret_cast<float*>(s_misc + 4 * BS);   // [BS] (AP only: step_lds_bytes_ap) the arenas' radii, kept to the end
     LdsLines ls; ls.base = s_lines + tid; ls.stride = BS;       // (ST = 0 only)
 
     CA_STAMP(0);
@@ -163,6 +172,15 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             pref = mk(p.pref_x[q], p.pref_y[q]);
         }
     }
+    // the agent's own ORCA parameters: the handle's, or -- AP -- its entries of the per-agent arrays
+    float r_own = p.radius, ms = p.max_speed, th = p.time_horizon, tho = p.time_horizon_obst;
+    if constexpr (AP) {
+        if (active) {
+            const StepCold* cp = p.cold;
+            r_own = cp->ap_radius[q]; ms = cp->ap_max_speed[q]; th = cp->ap_time_horizon[q]; tho = cp->ap_time_horizon_obst[q];
+        }
+        s_rad[tid] = r_own;
+    }
     s_px[tid] = pos.x; s_py[tid] = pos.y; s_vx[tid] = vel.x; s_vy[tid] = vel.y;
     reinterpret_cast<float*>(s_misc)[tid * 4 + 0] = pf32.x; reinterpret_cast<float*>(s_misc)[tid * 4 + 1] = pf32.y;
     // workgroups of more than one wave carry more per-lane state: there the preferred velocity waits in the lane's LDS
@@ -189,7 +207,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     CA_STAMP(2);
     CA_STAMP(3);
 #endif
-    const float R = p.radius;
+    const float R = AP ? r_own : p.radius;
     V2 nv = mk(0.0f, 0.0f);
     if constexpr (ST > 0) {
         // ================= register path =================
@@ -353,7 +371,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
         // ================= LDS-table path =================
         int nl = 0;
     {
-        const float invTO = 1.0f / p.time_horizon_obst;
+        const float invTO = 1.0f / tho;
         int e_next = (ocnt > 0) ? ld_idx_t<true>(obst_idx_s, ((size_t)a * S + 0) * N + i) : 0;
         for (int s = 0; s < S; ++s) {
             if (s < ocnt) {
@@ -378,14 +396,16 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     const int numObstLines = nl;
     CA_STAMP(4);
     {
-        const float invT = 1.0f / p.time_horizon;
+        const float invT = 1.0f / th;
         const float invDt = 1.0f / p.time_step;
         int j_next = (ncnt > 0) ? ld_idx_t<CA_NBW16(BS)>(nb_idx_s, ((size_t)a * K + 0) * N + i) : 0;
         for (int k = 0; k < K; ++k) {
             if (k < ncnt) {
                 const int j = lbase + j_next;
                 if (k + 1 < ncnt) j_next = ld_idx_t<CA_NBW16(BS)>(nb_idx_s, ((size_t)a * K + (k + 1)) * N + i);
-                const Line line = agent_orca_line(pos, vel, mk(s_px[j], s_py[j]), mk(s_vx[j], s_vy[j]), R, invT, invDt);
+                Line line;
+                if constexpr (AP) line = agent_orca_line(pos, vel, mk(s_px[j], s_py[j]), mk(s_vx[j], s_vy[j]), R, s_rad[j], invT, invDt);
+                else line = agent_orca_line(pos, vel, mk(s_px[j], s_py[j]), mk(s_vx[j], s_vy[j]), R, invT, invDt);
                 ls.put(nl, line);
                 ++nl;
             }
@@ -395,9 +415,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     CA_STAMP(5);
     // ---- 2-D linear program (App. A.5) ----
     int fail = nl;
-    if (active) fail = lp2(ls, nl, p.max_speed, pref, false, nv);
+    if (active) fail = lp2(ls, nl, ms, pref, false, nv);
     CA_STAMP(6);
-    if (active && fail < nl) lp3<KMAX + (SMX > SMAX ? SMX : SMAX)>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, p.max_speed, nv);
+    if (active && fail < nl) lp3<KMAX + (SMX > SMAX ? SMX : SMAX)>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, ms, nv);
     }
     if (active) {  // ---- integrate (App. A.1) ----
         vel = nv;
@@ -454,7 +474,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // arena -- entries [2 lbase + i] and [2 lbase + N + i] of the float2 view of the four staged arrays --, so that the balanced
     // scan reads "agent (i + d) mod N" as entry i + d without a wrap
     float2* s_xy2 = reinterpret_cast<float2*>(s_px);
-    if constexpr (LISTP) { s_px[tid] = pos.x; s_py[tid] = pos.y; }
+    if constexpr (LISTP || AP) { s_px[tid] = pos.x; s_py[tid] = pos.y; }
     else if (i < p.N && la < apb) { s_xy2[2 * lbase + i] = make_float2(pos.x, pos.y); s_xy2[2 * lbase + i + p.N] = make_float2(pos.x, pos.y); }
     s_misc[tid * 4 + 0] = 0; s_misc[tid * 4 + 1] = 0; s_misc[tid * 4 + 2] = 0; s_misc[tid * 4 + 3] = 0;
     __syncthreads();
@@ -495,7 +515,22 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             });
             scan_all = (ncnt == K) && !(far2 > sqr(R + R + 2.0f * m2));
         }
-        if constexpr (LISTP) {
+        if constexpr (AP) {
+            // Mixed radii: a pair overlaps within sqr(r_i + r_j) (the oracle's arena_collisions), which the lists' shortcut above --
+            // one radius, neighbor_dist >= 2 R + 2 m -- does not bound.  The arena is scanned, balanced as below: every unordered
+            // pair once, agent i against the agents (i + d) mod N for d = 1 .. (N - 1) / 2 and, N even, the lower half against its
+            // antipode; positions and radii from the staged arena.
+            if (active) {
+                const int H = (N - 1) >> 1;
+                auto near = [&](int d) __attribute__((always_inline)) {
+                    int j = i + d;
+                    j = j >= N ? j - N : j;
+                    return absSq(pos - mk(s_px[lbase + j], s_py[lbase + j])) < sqr(R + s_rad[lbase + j]) ? 1 : 0;   // (R: the agent's own)
+                };
+                for (int d = 1; d <= H; ++d) pairs += near(d);
+                if (!(N & 1) && N > 1) { const int h = N >> 1; if (i < h) pairs += near(h); }
+            }
+        } else if constexpr (LISTP) {
             if (__ballot(scan_all) != 0ull && scan_all) {
                 pairs = 0;
                 for (int j = i + 1; j < N; ++j)
@@ -544,7 +579,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     int done = active ? c.agent_done[q] : 1;
     int steps = active ? c.step_count[a] : 0;
     if (!p.actions && !nodone) ++steps;
-    if (active && !nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
+    if (active && !nodone && goal_hit(c, pos, gx, gy, AP ? R : p.radius, done)) {
         if (c.done_mode == 2) {
             const int rc = c.regoal_count[q];
             regoal_draw(c, a, i, rc, &gx, &gy);

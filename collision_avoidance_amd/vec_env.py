@@ -49,10 +49,13 @@ class VecCollisionAvoidanceEnv:
                (launch_info()): arenas of at most 128 agents (at 64: 64 agents with any max_neighbors, 128 with max_neighbors <= 10;
                other shapes raise CA_ERANGE at construction).  A world of subdivided walls or many pillars that raises the overflow
                error wants this raised, not allow_obst_overflow.
+    agent_params: dict(radius=, max_speed=, time_horizon=, time_horizon_obst=) handed to set_agent_params() once the handle
+               exists: ORCA parameters per agent instead of the four constants of `params`.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
-                 arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False):
+                 arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
+                 agent_params=None):
         self.L = _lib.load()
         self.A, self.N = int(n_arenas), int(n_agents)
         p = scenarios.env_params()
@@ -101,6 +104,8 @@ class VecCollisionAvoidanceEnv:
             self.set_obstacles(polys)
         if scenario is not None:
             self.init_scenario(scenario)
+        if agent_params:
+            self.set_agent_params(**agent_params)
 
     # ---- plumbing -------------------------------------------------------------------------------
     def _call(self, name, *args):
@@ -334,8 +339,49 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_launch_info", self.h, *[C.byref(x) for x in v])
         lanes, roll = C.c_int32(), C.c_int32()
         self._call("ca_solver_info", self.h, C.byref(lanes), C.byref(roll))
+        per = C.c_int32()
+        self._call("ca_agent_params_info", self.h, C.byref(per))
         return dict(block=v[0].value, grid=v[1].value, lds_bytes=v[2].value, obs_grid=v[3].value,
-                    lanes_per_agent=lanes.value, rollout_one_launch=roll.value)
+                    lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value))
+
+    # ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133) ---------------
+    _AGENT_PARAMS = ("radius", "max_speed", "time_horizon", "time_horizon_obst")
+
+    def set_agent_params(self, radius=None, max_speed=None, time_horizon=None, time_horizon_obst=None):
+        """radius, max_speed, time_horizon and time_horizon_obst per agent (ca_set_agent_params): each a numpy array or torch
+        tensor of shape [A,N] -- a scalar or an [A] array (one value per arena) is broadcast --, or None: every agent keeps the
+        value of `params`.  Configuration like the obstacles: it survives reset() and init_scenario() and is not part of
+        get_state().  The handle then runs the per-agent kernels (launch_info()["agent_params"]); all four None returns it to
+        uniform parameters, like clear_agent_params().  neighbor_dist and max_neighbors stay per handle."""
+        keep, ptrs = [], []
+        for name, v in zip(self._AGENT_PARAMS, (radius, max_speed, time_horizon, time_horizon_obst)):
+            if v is None:
+                ptrs.append(None)
+                continue
+            if torch is not None and isinstance(v, torch.Tensor):   # a configuration call: the library checks every value on the host anyway
+                v = v.detach().cpu().numpy()
+            a = np.asarray(v, np.float32)
+            if a.ndim == 1 and a.shape[0] == self.A:   # one value per arena (also where A == N)
+                a = a[:, None]
+            try:
+                full = np.ascontiguousarray(np.broadcast_to(a, (self.A, self.N)), np.float32)
+            except ValueError:
+                raise ValueError("set_agent_params: %s must be a scalar, an [A] array or an [A,N] array (A=%d, N=%d), got shape %s"
+                                 % (name, self.A, self.N, a.shape))
+            keep.append(full)
+            ptrs.append(_ptr(full))
+        self._call("ca_set_agent_params", self.h, ptrs[0], ptrs[1], ptrs[2], ptrs[3], self.A * self.N * 4, 0)
+
+    def clear_agent_params(self):
+        """Back to the uniform parameters of `params` and to the kernels the handle used with them."""
+        self._call("ca_set_agent_params", self.h, None, None, None, None, 0, 0)
+
+    def agent_params(self):
+        """dict(radius, max_speed, time_horizon, time_horizon_obst) of [A,N] float32 arrays: what the kernels use (the value of
+        `params` everywhere on a handle with uniform parameters)."""
+        out = {k: np.empty((self.A, self.N), np.float32) for k in self._AGENT_PARAMS}
+        self._call("ca_get_agent_params", self.h, *[_ptr(out[k]) for k in self._AGENT_PARAMS], self.A * self.N * 4, 0)
+        return out
 
     # ---- the environment API ----------------------------------------------------------------------
     def _on_device(self, t, dtype):

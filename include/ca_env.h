@@ -190,6 +190,34 @@ int ca_set_obstacles_per_arena(ca_env* env, const float* verts_xy, const int32_t
 int ca_get_obstacles_arena(ca_env* env, int32_t arena, float* verts_xy, int32_t* next, int32_t* convex, int32_t cap,
                            int32_t* n_out);
 
+/* Replaces the per-agent arguments of sim.addAgent (env.py:126-133; ALAN:81-87) / setAgentRadius, setAgentMaxSpeed,
+ * setAgentTimeHorizon, setAgentTimeHorizonObst: a crowd of large and small, slow and fast agents, or arenas that differ in these
+ * values (domain randomisation).  Each array: f32 [A,N] (host or device), or NULL = every agent keeps the handle's ca_config value
+ * for that parameter.  All four NULL: the handle returns to uniform parameters and to the kernels it used before.
+ *   - Configuration, like the obstacle tables, not state: the values persist across ca_reset, ca_reset_masked, CA_F_AUTORESET and
+ *     ca_init_scenario, and are not a ca_field.  The scenario generators and the spawn boxes keep using ca_config.radius.
+ *   - neighbor_dist and max_neighbors stay per handle: they size the neighbour-key image, the search grid, the ray table of the
+ *     observation and the kernels' K classes.
+ *   - Every value is checked (a device array is copied back for the check): a value that is not finite or lies outside
+ *     [CA_MIN_LENGTH, CA_MAX_LENGTH] -> CA_ERANGE (ca_last_error names the parameter, the arena and the agent);
+ *     bytes_each != A*N*4 -> CA_ESIZE; a handle with max_obst_neighbors > 16 -> CA_EINVAL (not together with wide obstacle lists);
+ *     a shape whose LDS line table does not fit a CU (lanes x (16 (max_neighbors + max_obst_neighbors) + 36) bytes plus the
+ *     neighbour search's arrays > 160 KiB: e.g. 512 agents with max_neighbors 10 and lists of 16) -> CA_ERANGE.  On any failure the
+ *     handle keeps its previous parameters and kernels.
+ *   - While the parameters are set the handle runs one lane per agent on the LDS line table, an instantiation of its own, whatever
+ *     the world and the batch size (CA_QUAD / CA_PAIR / CA_REG_LINES are ignored): ca_solver_info reports lanes_per_agent = 1,
+ *     rollout_one_launch = 0, ca_rollout is T launches, ca_alan_step / ca_alan_rollout take the three-launch form (select, solve,
+ *     update; one action set or one per arena).  The observation sees neighbour j as the octagon of radius r_j (env.py:335-350).
+ *     Results are the CPU oracle's with these values per agent, bit for bit; arrays equal to the ca_config values give the
+ *     uniform handle's bits. */
+int ca_set_agent_params(ca_env* env, const float* radius, const float* max_speed, const float* time_horizon,
+                        const float* time_horizon_obst, size_t bytes_each, int32_t src_is_device);
+/* The four arrays as the kernels use them (the ca_config value for every agent on a handle with uniform parameters); any may be NULL. */
+int ca_get_agent_params(ca_env* env, float* radius, float* max_speed, float* time_horizon,
+                        float* time_horizon_obst, size_t bytes_each, int32_t dst_is_device);
+/* *per_agent = 1 while per-agent parameters are set (the AgentParams kernels run), else 0. */
+int ca_agent_params_info(ca_env* env, int32_t* per_agent);
+
 /* Replaces _init_world's agent loop (env.py:86-97) / ALAN's scenario generators (ALAN:175-457).  Runs on the device: every
  * agent's heading, start and targets come from the handle's counter-based streams (keyed by the global arena id) or, for
  * the layouts that do not depend on the arena, from a per-agent table made once on the host (its cos / sin / sqrt are
