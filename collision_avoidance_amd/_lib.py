@@ -25,7 +25,8 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_alan_configure", "ca_alan_step", "ca_alan_rollout", "ca_reset_masked", "ca_get_obstacles",
            "ca_set_obstacles_per_arena", "ca_get_obstacles_arena", "ca_solver_info", "ca_source_sha", "ca_host_alloc", "ca_host_free",
            "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
-           "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info")
+           "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info",
+           "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info")
 
 
 class Config(C.Structure):
@@ -112,6 +113,9 @@ def load():
     L.ca_set_agent_params.argtypes = [vp, vp, vp, vp, vp, sz, i32]
     L.ca_get_agent_params.argtypes = [vp, vp, vp, vp, vp, sz, i32]
     L.ca_agent_params_info.argtypes = [vp, C.POINTER(i32)]
+    L.ca_set_agent_counts.argtypes = [vp, vp, sz, i32]
+    L.ca_get_agent_counts.argtypes = [vp, vp, sz, i32]
+    L.ca_agent_counts_info.argtypes = [vp, C.POINTER(i32)]
     L.ca_source_sha.argtypes = []
     L.ca_source_sha.restype = C.c_char_p
     for name in EXPORTS:

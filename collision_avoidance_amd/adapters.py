@@ -56,11 +56,17 @@ def _spaces(vec, batch):
 
 
 def _episode_info(st, ended, n_agents):
-    """Per finished arena: length, arrivals, whether the cap cut it (env.py:408-410)."""
+    """Per finished arena: length, arrivals, whether the cap cut it (env.py:408-410).  n_agents: a number, or [A] agents per arena."""
     idx = np.nonzero(ended)[0]
     steps = st["last_episode_steps"][idx]
     arrived = st["last_episode_arrived"][idx]
-    return dict(arena=idx, length=steps, arrived=arrived, truncated=arrived < n_agents)
+    return dict(arena=idx, length=steps, arrived=arrived, truncated=arrived < np.broadcast_to(n_agents, ended.shape)[idx])
+
+
+def _agent_counts(vec):
+    """[A] agents per arena of a vector env (N everywhere where it has no per-arena counts, set_agent_counts)."""
+    get = getattr(vec, "agent_counts", None)
+    return np.asarray(get(), np.int64) if get is not None else np.full(vec.A, vec.N, np.int64)
 
 
 class AgentVectorEnv(object):
@@ -74,6 +80,8 @@ class AgentVectorEnv(object):
 
     infos (arrays over arenas unless noted):
       "agent_arrived" [A*N]  the per-agent flag the reference never reports (its gym_dones['agent_i'])
+      "agent_active" [A*N]   False for the absent slots of an env with per-arena agent counts (set_agent_counts): num_envs stays
+                             A * N, such a slot carries a zero observation and reward and its arena's done, and its action is ignored
       "collisions", "obst_collisions", "goals_reached"  counted during this step, per arena
       "episode"  dict(arena, length, arrived, truncated) for the arenas that finished in this step
     """
@@ -112,10 +120,11 @@ class AgentVectorEnv(object):
                 infos[k] = (st[k] - self._prev[k]).astype(np.int64)
             self._prev = st
             infos["agent_arrived"] = self.vec.get(_lib.FLD_AGENT_DONE).reshape(self.num_envs) != 0
-            infos["episode"] = _episode_info(st, ended, self.N)
+            infos["episode"] = _episode_info(st, ended, _agent_counts(self.vec))
             trunc = np.zeros(self.A, bool)
             trunc[infos["episode"]["arena"]] = infos["episode"]["truncated"]
             trunc_agents = np.repeat(trunc, self.N)
+        infos["agent_active"] = (np.arange(self.N)[None, :] < _agent_counts(self.vec)[:, None]).reshape(self.num_envs)
         obs, rew = self._flat(obs, (_lib.OBS_DIM,)), self._flat(rew)
         if not self.new_step_api:
             return obs, rew, done_agents, infos
@@ -140,6 +149,8 @@ class MultiAgentVectorEnv(object):
                             RLlib expects of a finished agent); it keeps walking to its second target
                             with a zero heading offset, as a policy-free ORCA agent.
     infos[env]['__common__'] carries the arena's collision counters of the step (common_info=True).
+    On an env with per-arena agent counts (set_agent_counts) the dictionaries of sub-environment e hold agent_0 .. agent_{n_e-1}
+    only, and an action dictionary need not contain the absent ids.
     """
 
     def __init__(self, vec, per_agent_dones=True, common_info=True):
@@ -158,14 +169,15 @@ class MultiAgentVectorEnv(object):
         return x.detach().cpu().numpy() if torch is not None and isinstance(x, torch.Tensor) else np.asarray(x)
 
     def _obs_dict(self, obs, e):
-        live = ~self._reported[e]
+        live = ~self._reported[e] & (np.arange(self.N) < _agent_counts(self.vec)[e])
         return {self.agent_ids[i]: obs[e, i] for i in range(self.N) if live[i]}
 
     def _actions(self, action_dicts):
         act = np.zeros((self.num_envs, self.N), np.float32)
         items = action_dicts.items() if isinstance(action_dicts, dict) else enumerate(action_dicts)
+        counts = _agent_counts(self.vec)
         for e, d in items:
-            for i, aid in enumerate(self.agent_ids):
+            for i, aid in enumerate(self.agent_ids[:counts[e]]):
                 if self._reported[e, i]:
                     continue
                 act[e, i] = float(np.asarray(d[aid]).reshape(-1)[0])   # KeyError like env.py:373
@@ -193,9 +205,11 @@ class MultiAgentVectorEnv(object):
         obs, rew, done = self._host(obs), self._host(rew), self._host(done) != 0
         arrived = self.vec.get(_lib.FLD_AGENT_DONE) != 0
         st = self.vec.arena_stats()
+        counts = _agent_counts(self.vec)
         obs_b, rew_b, done_b, info_b = [], [], [], []
         for e in range(self.num_envs):
             was = self._reported[e].copy()
+            was[counts[e]:] = True          # absent rows: in no dictionary
             newly = arrived[e] & ~was if self.per_agent_dones else np.zeros(self.N, bool)
             dd = {'__all__': bool(done[e])}
             od, rd, idd = {}, {}, {}
@@ -204,6 +218,7 @@ class MultiAgentVectorEnv(object):
                     continue
                 od[aid], rd[aid], idd[aid] = obs[e, i], float(rew[e, i]), {}
                 dd[aid] = bool(newly[i]) or (self.per_agent_dones and bool(done[e]))
+            newly[counts[e]:] = False
             if self.per_agent_dones:
                 self._reported[e] |= newly
             if self.common_info:
@@ -211,7 +226,7 @@ class MultiAgentVectorEnv(object):
                     collisions=int(st["collisions"][e] - self._prev["collisions"][e]),
                     obst_collisions=int(st["obst_collisions"][e] - self._prev["obst_collisions"][e]),
                     goals_reached=int(st["goals_reached"][e] - self._prev["goals_reached"][e]),
-                    truncated=bool(done[e]) and not bool(arrived[e].all()))
+                    truncated=bool(done[e]) and not bool(arrived[e, :counts[e]].all()))
             obs_b.append(od); rew_b.append(rd); done_b.append(dd); info_b.append(idd)
         self._prev, self._obs = st, obs
         return obs_b, rew_b, done_b, info_b

@@ -14,6 +14,12 @@ struct WideObstLists;
 // radius, max_speed, time_horizon and time_horizon_obst of every agent come from [A,N] arrays (ca_set_agent_params) instead of
 // the handle's four constants.
 struct AgentParams;
+// Tag of the per-arena-agent-count instantiations (step_kernel<KMAX, BS, 0, SMAX, false, ArenaCounts>, obs_kernel<..., ArenaCounts>):
+// arena a consists of agents 0 .. counts[a] - 1 (ca_set_agent_counts); n_agents stays the stride of every array, rows beyond the
+// count are absent.  The tag INCLUDES AgentParams -- these are the per-agent-parameter kernels with a count per arena (a handle
+// without parameters of the caller's has the arrays filled with its constants) -- and stands alone in the pack, so that
+// "AgentParams" keeps naming exactly the instantiations it named before.
+struct ArenaCounts;
 
 namespace ca {
 
@@ -68,6 +74,9 @@ struct StepCold {
     // per-agent ORCA parameters [A*N] (ca_set_agent_params; null on a handle with uniform parameters): read by the AgentParams
     // instantiations only.  At the end of the block: nothing the other kernels load moves.
     const float *ap_radius, *ap_max_speed, *ap_time_horizon, *ap_time_horizon_obst;
+    // agents per arena [A] (ca_set_agent_counts; null on a handle whose arenas all hold N agents): read by the ArenaCounts
+    // instantiations and by reset_counts_kernel only.  Last member: nothing the other kernels load moves.
+    const int* agent_counts;
 };
 
 // ALAN online learning inside the four-lanes kernel (ca_quad.h): the bandit's arguments, in device memory like StepCold

@@ -103,6 +103,13 @@ struct ca_env {
     float* d_ap[4] = {nullptr, nullptr, nullptr, nullptr};   // [A*N] radius | max_speed | time_horizon | time_horizon_obst
     float* d_ap_oct = nullptr;                               // [A*N][8] float2: every agent's octagon (ca_obs.h ObsArgs::ap_oct)
     std::vector<float> h_ap[4];                              // host copies (ca_get_agent_params)
+    // per-arena agent counts (ca_set_agent_counts): configuration too.  ac = the handle runs the ArenaCounts instantiations, which
+    // are AgentParams kernels: ap = ap_user || ac, and without parameters of the caller's (ap_user) the per-agent arrays hold the
+    // ca_config values.
+    bool ac = false, ap_user = false;
+    int* d_counts = nullptr;                                 // [A]
+    std::vector<int> h_counts;                               // host copy (ca_get_agent_counts, ca_get_stats); empty while !ac
+    uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
     // opt-in per-kernel timing (ca_profile): event pairs recorded around launches, drained on read
@@ -259,6 +266,7 @@ static void fill_cold(const ca_env* e, StepCold& c) {
     c.goal_x0 = g.goal_x0; c.goal_x1 = g.goal_x1; c.goal_y0 = g.goal_y0; c.goal_y1 = g.goal_y1;
     c.ap_radius = e->ap ? e->d_ap[0] : nullptr; c.ap_max_speed = e->ap ? e->d_ap[1] : nullptr;
     c.ap_time_horizon = e->ap ? e->d_ap[2] : nullptr; c.ap_time_horizon_obst = e->ap ? e->d_ap[3] : nullptr;
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
 }
 
 static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t flags) {
@@ -329,10 +337,22 @@ static const void* ap_fn_for(int BS) {
         default: return fn_ptr(&step_kernel<KMAX, 1024, 0, SMAX, false, AgentParams>);
     }
 }
+// ... and agent counts per arena (ca_set_agent_counts): the same kernel under the ArenaCounts tag, which includes AgentParams
+template <int KMAX>
+static const void* ac_fn_for(int BS) {
+    switch (BS) {
+        case 64: return fn_ptr(&step_kernel<KMAX, 64, 0, SMAX, false, ArenaCounts>);
+        case 128: return fn_ptr(&step_kernel<KMAX, 128, 0, SMAX, false, ArenaCounts>);
+        case 256: return fn_ptr(&step_kernel<KMAX, 256, 0, SMAX, false, ArenaCounts>);
+        case 512: return fn_ptr(&step_kernel<KMAX, 512, 0, SMAX, false, ArenaCounts>);
+        default: return fn_ptr(&step_kernel<KMAX, 1024, 0, SMAX, false, ArenaCounts>);
+    }
+}
 // the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
 // more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
 template <bool ALAN, class... PER>
 static const void* lane_fn_for(const ca_env* e) {
+    if (e->ac) return e->KT == 5 ? ac_fn_for<5>(e->BS) : (e->KT == 16 ? ac_fn_for<16>(e->BS) : ac_fn_for<10>(e->BS));   // (refused by the ALAN calls)
     if (e->ap) return e->KT == 5 ? ap_fn_for<5>(e->BS) : (e->KT == 16 ? ap_fn_for<16>(e->BS) : ap_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->SMX > SMAX) return e->KT == 5 ? wide_fn_for<5>(e->BS) : (e->KT == 16 ? wide_fn_for<16>(e->BS) : wide_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->ST > 0 && e->SMX > 4) return e->KT == 5 ? step_fn_for<5, 4, 16, ALAN, PER...>(e->BS) : step_fn_for<10, 4, 16, ALAN, PER...>(e->BS);
@@ -374,7 +394,9 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
 }
 
 typedef void (*obs_fn_t)(const ObsArgs);
-static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = false, bool ap = false) {  // workgroup size x width of the stored agent-neighbour ids
+static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = false, bool ap = false, bool ac = false) {  // workgroup size x width of the stored agent-neighbour ids
+    // (agent counts per arena: the per-agent-parameter kernel under the ArenaCounts tag)
+    if (ac) return dense ? obs_kernel<256, false, true, ArenaCounts> : (w16 ? obs_kernel<256, true, false, ArenaCounts> : obs_kernel<256, false, false, ArenaCounts>);
     // (per-agent parameters: 256 lanes, what obs_block_threads gives every arena size; never with obstacle lists above 16)
     if (ap) return dense ? obs_kernel<256, false, true, AgentParams> : (w16 ? obs_kernel<256, true, false, AgentParams> : obs_kernel<256, false, false, AgentParams>);
     // (obstacle lists above 16: arenas of at most 128 agents -- 256 lanes, 8-bit ids; ca_create checks that)
@@ -398,7 +420,7 @@ static size_t obs_lds(const ca_env* e, int obs_bs) {
     if (e->ap) return obs_lds_bytes_ap(obs_nstage(e), obs_bs, 16 * (e->K + e->S));
     return obs_lds_bytes(obs_nstage(e), obs_bs, 16 * (e->K + e->S), obs_wide(e) ? e->S : 16);
 }
-static obs_fn_t obs_fn_of(const ca_env* e) { return obs_fn(obs_block_threads(e->cfg.n_agents), e->nidx16 != 0, obs_dense(e), obs_wide(e), e->ap); }
+static obs_fn_t obs_fn_of(const ca_env* e) { return obs_fn(obs_block_threads(e->cfg.n_agents), e->nidx16 != 0, obs_dense(e), obs_wide(e), e->ap, e->ac); }
 // (above the 48 KiB that every kernel may take, the observation kernel's dynamic LDS needs its limit raised before the launch)
 static hipError_t allow_obs_lds(const ca_env* e) {
     const size_t ol = obs_lds(e, obs_block_threads(e->cfg.n_agents));
@@ -433,6 +455,7 @@ static hipError_t launch_obs(ca_env* e) {
     memcpy(o.rays, e->rays, sizeof o.rays);
     memcpy(o.oct, e->oct, sizeof o.oct);
     o.ap_oct = e->ap ? e->d_ap_oct : nullptr;
+    o.agent_counts = e->ac ? e->d_counts : nullptr;
     const dim3 grid(o.dense ? (unsigned)(((size_t)o.A * o.N + apb - 1) / apb) : (unsigned)((size_t)o.A * o.bpa)), block(obs_bs);
     const size_t lds = obs_lds(e, obs_bs);
     ProfScope ps(e, KIND_OBS);
@@ -445,7 +468,7 @@ static hipError_t launch_reset(ca_env* e, const StepArgs& a) {
     const unsigned an = (unsigned)AN(e);
     {
         ProfScope ps(e, KIND_RESET);
-        launch_k(ps, reset_kernel, dim3((an + 255) / 256), dim3(256), 0, e->stream, a);
+        launch_k(ps, e->ac ? reset_counts_kernel : reset_kernel, dim3((an + 255) / 256), dim3(256), 0, e->stream, a);
     }
     hipError_t r = hipGetLastError();
     if (r != hipSuccess) return r;
@@ -820,7 +843,7 @@ int ca_destroy(ca_env* e) {
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
-                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct};
+                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1020,17 +1043,19 @@ static void agent_octagons(const std::vector<float>& radius, std::vector<float>&
 }
 
 // the handle's variant state that per-agent parameters change (saved before a prospective pick_variant, restored on failure)
-struct VariantState { bool ap, quad, quad_roll, pair; int ST, SMX, KT; size_t lds, lds_p; };
-static VariantState save_variant(const ca_env* e) { return {e->ap, e->quad, e->quad_roll, e->pair, e->ST, e->SMX, e->KT, e->lds, e->lds_p}; }
+struct VariantState { bool ap, ap_user, ac, quad, quad_roll, pair; int ST, SMX, KT; size_t lds, lds_p; };
+static VariantState save_variant(const ca_env* e) { return {e->ap, e->ap_user, e->ac, e->quad, e->quad_roll, e->pair, e->ST, e->SMX, e->KT, e->lds, e->lds_p}; }
 static void restore_variant(ca_env* e, const VariantState& v) {
-    e->ap = v.ap; e->quad = v.quad; e->quad_roll = v.quad_roll; e->pair = v.pair; e->ST = v.ST; e->SMX = v.SMX; e->KT = v.KT;
+    e->ap = v.ap; e->ap_user = v.ap_user; e->ac = v.ac; e->quad = v.quad; e->quad_roll = v.quad_roll; e->pair = v.pair; e->ST = v.ST; e->SMX = v.SMX; e->KT = v.KT;
     e->lds = v.lds; e->lds_p = v.lds_p;
 }
-// switch the handle to (on) or away from (off) the AgentParams kernels: variant and dynamic-LDS limits, checked against the CU's
+// switch the handle to the kernels of (parameters of the caller's: ap_user, agent counts per arena: ac) -- the AgentParams kernels
+// if either is set, with the ArenaCounts tag if ac, else the uniform ones: variant and dynamic-LDS limits, checked against the CU's
 // LDS before anything is swapped (as install_tables does).  *misfit: the kernel does not fit; the handle is then left as it was.
-static hipError_t switch_agent_params(ca_env* e, bool on, bool* misfit) {
+static hipError_t switch_agent_params(ca_env* e, bool ap_user, bool ac, bool* misfit) {
     const VariantState old_v = save_variant(e);
-    e->ap = on;
+    const bool on = ap_user || ac;
+    e->ap = on; e->ap_user = ap_user; e->ac = ac;
     e->quad = on ? false : e->quad_cfg;
     e->quad_roll = on ? false : e->quad_roll_cfg;
     pick_variant(e);
@@ -1044,7 +1069,129 @@ static hipError_t switch_agent_params(ca_env* e, bool on, bool* misfit) {
     return r;
 }
 
+// the device arrays of the AgentParams kernels (the first call allocates them; they stay until ca_destroy)
+static int alloc_agent_params(ca_env* e) {
+    const size_t an = AN(e);
+    for (int k = 0; k < 4; ++k) if (!e->d_ap[k]) HIPCHK(e, hipMalloc((void**)&e->d_ap[k], an * 4));
+    if (!e->d_ap_oct) HIPCHK(e, hipMalloc((void**)&e->d_ap_oct, an * 64));
+    return CA_OK;
+}
+// the four arrays and the octagons of their radii into them; complete on return (the host vectors may go)
+static hipError_t push_agent_params(ca_env* e, const std::vector<float> (&h)[4]) {
+    const size_t an = AN(e);
+    std::vector<float> oct;
+    agent_octagons(h[0], oct);
+    hipError_t r = hipSuccess;
+    for (int k = 0; k < 4 && r == hipSuccess; ++k) r = hipMemcpyAsync(e->d_ap[k], h[k].data(), an * 4, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(e->d_ap_oct, oct.data(), an * 64, hipMemcpyHostToDevice, e->stream);
+    return r != hipSuccess ? r : hipStreamSynchronize(e->stream);
+}
+
+// ---- agents per arena (the reference's one constructor argument, Collision_Avoidance_Env(numAgents), env.py:23-60, per arena) ----
+// ca_stats.agent_steps = steps an arena was advanced x its agents: the kernels count the steps (arena_steps), so the product so far
+// is folded into a host counter whenever the agents per arena change
+static int fold_agent_steps(ca_env* e) {
+    const size_t A = e->cfg.n_arenas;
+    std::vector<unsigned long long> hs(A);
+    HIPCHK(e, download(e, hs.data(), e->arena_steps, A * 8));
+    for (size_t a = 0; a < A; ++a) e->agent_steps_base += hs[a] * (uint64_t)(e->ac ? e->h_counts[a] : e->cfg.n_agents);
+    HIPCHK(e, hipMemsetAsync(e->arena_steps, 0, A * 8, e->stream));
+    return CA_OK;
+}
+// what an absent row shows from the call on: a reward of 0 and an observation row of zeros
+__global__ void clear_absent_kernel(const int* counts, int A, int N, float* reward, float* obs) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // one lane per (row, ray)
+    const size_t q = t >> 4;
+    if (q >= (size_t)A * N) return;
+    const int a = (int)(q / N), i = (int)(q - (size_t)a * N), r = (int)(t & 15);
+    if (i < counts[a]) return;
+    reinterpret_cast<float4*>(obs)[q * 16 + r] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (r == 0) reward[q] = 0.0f;
+}
+
 extern "C" {
+
+int ca_set_agent_counts(ca_env* e, const int32_t* counts, size_t bytes, int32_t src_is_device) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    const int A = e->cfg.n_arenas, N = e->cfg.n_agents;
+    const size_t an = AN(e);
+    std::vector<int> h;
+    if (counts) {
+        if (e->S > SMAX)
+            return fail(e, CA_EINVAL, "ca_set_agent_counts: not together with wide obstacle lists (max_obst_neighbors=%d > %d)", e->S, SMAX);
+        if (bytes != (size_t)A * 4) return fail(e, CA_ESIZE, "ca_set_agent_counts: the array holds %zu bytes, got %zu", (size_t)A * 4, bytes);
+        h.resize(A);
+        if (src_is_device) HIPCHK(e, download(e, h.data(), counts, (size_t)A * 4));
+        else memcpy(h.data(), counts, (size_t)A * 4);
+        for (int a = 0; a < A; ++a)
+            if (h[a] < 1 || h[a] > N)
+                return fail(e, CA_ERANGE, "ca_set_agent_counts: arena %d has a count of %d, outside [1, n_agents=%d]", a, h[a], N);
+        if (!e->d_counts) HIPCHK(e, hipMalloc((void**)&e->d_counts, (size_t)A * 4));
+        { const int rc = alloc_agent_params(e); if (rc) return rc; }
+    } else if (!e->ac) {
+        return CA_OK;
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous counts
+    if (e->ac != (counts != nullptr)) {   // the prospective kernels are chosen and checked against the CU's LDS before anything is swapped
+        bool misfit = false;
+        const hipError_t r = switch_agent_params(e, e->ap_user, counts != nullptr, &misfit);
+        if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_counts: %s (the handle keeps its previous counts)", hipGetErrorString(r));
+        if (misfit)
+            return fail(e, CA_ERANGE, "ca_set_agent_counts: the %s solve kernel does not fit the 160 KiB of LDS of a CU for n_agents=%d, max_neighbors=%d, "
+                        "max_obst_neighbors=%d (with counts: the LDS line table, max_neighbors + max_obst_neighbors lines per lane); the handle keeps "
+                        "its previous counts", counts ? "per-arena-count" : "uniform", N, e->K, e->S);
+        e->ac = !e->ac;   // (the steps counted so far belong to the previous counts)
+        const int rc = fold_agent_steps(e);
+        e->ac = !e->ac;
+        if (rc) return rc;
+    } else {
+        const int rc = fold_agent_steps(e);
+        if (rc) return rc;
+    }
+    hipError_t r = hipSuccess;
+    if (counts) {
+        r = hipMemcpyAsync(e->d_counts, h.data(), (size_t)A * 4, hipMemcpyHostToDevice, e->stream);
+        if (r == hipSuccess && !e->ap_user) {   // no parameters of the caller's: the per-agent arrays hold the ca_config values
+            const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
+            std::vector<float> hp[4];
+            for (int k = 0; k < 4; ++k) hp[k].assign(an, defaults[k]);
+            r = push_agent_params(e, hp);
+        }
+    }
+    // the lists of the last step may name agents that are gone, and a fresh simulator has none: both counts of every row read 0
+    if (r == hipSuccess) r = hipMemsetAsync(e->counts, 0, an * sizeof(unsigned short), e->stream);
+    if (r == hipSuccess && counts) {
+        hipLaunchKernelGGL(clear_absent_kernel, dim3((unsigned)((an * 16 + 255) / 256)), dim3(256), 0, e->stream, e->d_counts, A, N, e->reward, e->obs);
+        r = hipGetLastError();
+    }
+    e->h_counts.swap(h);
+    e->lists_trusted = false;
+    StepCold hc;
+    fill_cold(e, hc);
+    if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);   // (synchronises)
+    if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_counts: %s", hipGetErrorString(r));
+    return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
+}
+
+int ca_get_agent_counts(ca_env* e, int32_t* counts, size_t bytes, int32_t dst_is_device) {
+    if (!e || !counts) return fail(e, CA_EINVAL, "ca_get_agent_counts: null argument");
+    const size_t A = e->cfg.n_arenas;
+    if (bytes != A * 4) return fail(e, CA_ESIZE, "ca_get_agent_counts: the array holds %zu bytes, got %zu", A * 4, bytes);
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<int> uni;
+    if (!e->ac) uni.assign(A, e->cfg.n_agents);
+    const int* s = e->ac ? e->h_counts.data() : uni.data();
+    if (dst_is_device) { HIPCHK(e, upload(e, counts, s, A * 4)); }
+    else memcpy(counts, s, A * 4);
+    return CA_OK;
+}
+
+int ca_agent_counts_info(ca_env* e, int32_t* per_arena) {
+    if (!e) return CA_EINVAL;
+    if (per_arena) *per_arena = e->ac ? 1 : 0;
+    return CA_OK;
+}
 
 int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, const float* time_horizon,
                         const float* time_horizon_obst, size_t bytes_each, int32_t src_is_device) {
@@ -1055,10 +1202,19 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     const bool any = radius || max_speed || time_horizon || time_horizon_obst;
     HIPCHK(e, hipSetDevice(e->device));
     if (!any) {   // back to the handle's four constants and to the kernels it used with them
-        if (!e->ap) return CA_OK;
+        if (!e->ap_user) return CA_OK;
         HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (e->ac) {   // agent counts stay set: their kernels stay, the per-agent arrays return to the ca_config values
+            std::vector<float> h[4];
+            for (int k = 0; k < 4; ++k) h[k].assign(AN(e), defaults[k]);
+            const hipError_t r = push_agent_params(e, h);
+            if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r));
+            e->ap_user = false;
+            for (auto& v : e->h_ap) v.clear();
+            return alan_pick(e);
+        }
         bool misfit = false;
-        const hipError_t r = switch_agent_params(e, false, &misfit);
+        const hipError_t r = switch_agent_params(e, false, false, &misfit);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the per-agent parameters stay)", hipGetErrorString(r));
         if (misfit) return fail(e, CA_ERANGE, "ca_set_agent_params: the uniform solve kernel does not fit the 160 KiB of LDS of a CU (the per-agent parameters stay)");
         StepCold hc;
@@ -1083,29 +1239,25 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
                 return fail(e, CA_ERANGE, "ca_set_agent_params: %s=%g of arena %zu, agent %zu is outside the supported range [%g, %g] or not a number",
                             names[k], (double)h[k][q], q / (size_t)e->cfg.n_agents, q % (size_t)e->cfg.n_agents, (double)CA_MIN_LENGTH, (double)CA_MAX_LENGTH);
     }
-    std::vector<float> oct;
-    agent_octagons(h[0], oct);
     // the buffers exist before anything changes (the first call allocates them; they stay until ca_destroy)
-    for (int k = 0; k < 4; ++k) if (!e->d_ap[k]) HIPCHK(e, hipMalloc((void**)&e->d_ap[k], an * 4));
-    if (!e->d_ap_oct) HIPCHK(e, hipMalloc((void**)&e->d_ap_oct, an * 64));
+    { const int rc = alloc_agent_params(e); if (rc) return rc; }
     HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous values
     if (!e->ap) {   // the prospective variant is chosen and checked against the CU's LDS before anything is swapped
         bool misfit = false;
-        const hipError_t r = switch_agent_params(e, true, &misfit);
+        const hipError_t r = switch_agent_params(e, true, false, &misfit);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the handle keeps its uniform parameters)", hipGetErrorString(r));
         if (misfit)
             return fail(e, CA_ERANGE, "ca_set_agent_params: the per-agent solve kernel (LDS line table, max_neighbors + max_obst_neighbors lines per lane) "
                         "does not fit the 160 KiB of LDS of a CU for n_agents=%d, max_neighbors=%d, max_obst_neighbors=%d; the handle keeps its "
                         "uniform parameters", e->cfg.n_agents, e->K, e->S);
     }
-    hipError_t r = hipSuccess;
-    for (int k = 0; k < 4 && r == hipSuccess; ++k) r = hipMemcpyAsync(e->d_ap[k], h[k].data(), an * 4, hipMemcpyHostToDevice, e->stream);
-    if (r == hipSuccess) r = hipMemcpyAsync(e->d_ap_oct, oct.data(), an * 64, hipMemcpyHostToDevice, e->stream);
+    hipError_t r = push_agent_params(e, h);
     StepCold hc;
     fill_cold(e, hc);
-    if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);   // (synchronises: the host vectors above may go)
+    if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);
     if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r));
     for (int k = 0; k < 4; ++k) e->h_ap[k].swap(h[k]);
+    e->ap_user = true;   // (a handle with agent counts ran these kernels already, on the ca_config values)
     return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
 }
 
@@ -1120,8 +1272,8 @@ int ca_get_agent_params(ca_env* e, float* radius, float* max_speed, float* time_
     for (int k = 0; k < 4; ++k) {
         if (!dst[k]) continue;
         std::vector<float> uni;
-        if (!e->ap) uni.assign(an, defaults[k]);   // uniform parameters: the handle's constant for every agent
-        const float* s = e->ap ? e->h_ap[k].data() : uni.data();
+        if (!e->ap_user) uni.assign(an, defaults[k]);   // uniform parameters: the handle's constant for every agent
+        const float* s = e->ap_user ? e->h_ap[k].data() : uni.data();
         if (dst_is_device) { HIPCHK(e, upload(e, dst[k], s, an * 4)); }
         else memcpy(dst[k], s, an * 4);
     }
@@ -1130,7 +1282,7 @@ int ca_get_agent_params(ca_env* e, float* radius, float* max_speed, float* time_
 
 int ca_agent_params_info(ca_env* e, int32_t* per_agent) {
     if (!e) return CA_EINVAL;
-    if (per_agent) *per_agent = e->ap ? 1 : 0;
+    if (per_agent) *per_agent = e->ap_user ? 1 : 0;
     return CA_OK;
 }
 
@@ -1283,6 +1435,9 @@ int ca_init_scenario(ca_env* e, int32_t scenario) {
     if (!e) return CA_EINVAL;
     if (scenario < 0 || scenario > CA_SCN_CROWD_SEPARATED)
         return fail(e, CA_EINVAL, "ca_init_scenario: unknown scenario %d", scenario);
+    if (e->ac && scenario != CA_SCN_DOORWAY)
+        return fail(e, CA_EINVAL, "ca_init_scenario: scenario %d is not supported while per-arena agent counts are set (its geometry is a function "
+                    "of the number of agents; CA_SCN_DOORWAY is not)", scenario);
     const ca_config& c = e->cfg;
     const int A = c.n_arenas, N = c.n_agents;
     const size_t an = AN(e);
@@ -1603,6 +1758,7 @@ static int alan_install(ca_env* e, int nA, double temp, double timewindow, doubl
 int ca_alan_configure(ca_env* e, const double* actions_xy, int32_t n_actions, double temp, double timewindow,
                       double time_step) {
     if (!e || !actions_xy) return fail(e, CA_EINVAL, "ca_alan_configure: null argument");
+    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_configure: ALAN is not supported while per-arena agent counts are set");
     if (n_actions < 1 || n_actions > CA_ALAN_MAX_ACTIONS)
         return fail(e, CA_ERANGE, "ca_alan_configure: n_actions=%d out of range 1..%d", n_actions, CA_ALAN_MAX_ACTIONS);
     if (!(temp > 0.0) || !(timewindow > 0.0) || !(time_step > 0.0))
@@ -1618,6 +1774,7 @@ int ca_alan_configure(ca_env* e, const double* actions_xy, int32_t n_actions, do
 int ca_alan_configure_per_arena(ca_env* e, const double* actions_xy, const int32_t* n_actions, double temp, double timewindow,
                                 double time_step) {
     if (!e || !actions_xy || !n_actions) return fail(e, CA_EINVAL, "ca_alan_configure_per_arena: null argument");
+    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_configure_per_arena: ALAN is not supported while per-arena agent counts are set");
     const int A = e->cfg.n_arenas;
     int nmax = 0;
     for (int a = 0; a < A; ++a) {
@@ -1664,6 +1821,7 @@ int ca_alan_actions_arena(ca_env* e, int32_t arena, double* cs_xy, int32_t cap, 
 
 int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags) {
     if (!e) return CA_EINVAL;
+    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_step: ALAN is not supported while per-arena agent counts are set");
     if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_step: call ca_alan_configure first");
     if (flags & (CA_F_AUTORESET | CA_F_NODONE))
         return fail(e, CA_EINVAL, "ca_alan_step: CA_F_AUTORESET / CA_F_NODONE do not apply (ALAN:106-123)");
@@ -1721,6 +1879,7 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
 
 int ca_alan_rollout(ca_env* e, int32_t steps, uint32_t flags) {
     if (!e || steps < 0) return fail(e, CA_EINVAL, "ca_alan_rollout: bad argument");
+    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_rollout: ALAN is not supported while per-arena agent counts are set");
     { const int rs = overflow_status(e, "ca_alan_rollout"); if (rs) return rs; }
     if (e->n_actions > 0 && e->alan_fused && e->quad_roll && !(flags & (CA_F_OBS | CA_F_AUTORESET | CA_F_NODONE)) && steps > 1) {
         // run_sim(mode=1) (ALAN:106-123) as ONE launch per CA_ROLLOUT_MAX_T steps: select -> doStep -> update for every step
@@ -1818,8 +1977,8 @@ int ca_get_stats(ca_env* e, ca_stats* out) {
     HIPCHK(e, hipMemcpyAsync(hs.data(), e->arena_steps, A * 8, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     unsigned long long arena_steps = 0;
-    for (size_t a = 0; a < A; ++a) arena_steps += hs[a];
-    s.agent_steps = arena_steps * (uint64_t)e->cfg.n_agents;
+    for (size_t a = 0; a < A; ++a) arena_steps += hs[a] * (uint64_t)(e->ac ? e->h_counts[a] : e->cfg.n_agents);   // x the arena's agents
+    s.agent_steps = e->agent_steps_base + arena_steps;
     *out = s;
     return CA_OK;
 }
@@ -1830,6 +1989,7 @@ int ca_reset_stats(ca_env* e) {
     HIPCHK(e, hipMemsetAsync(e->arena_stats, 0, (size_t)e->cfg.n_arenas * ST_STRIDE * 8, e->stream));
     HIPCHK(e, hipMemsetAsync(e->arena_steps, 0, (size_t)e->cfg.n_arenas * 8, e->stream));
     e->steps_done = 0;
+    e->agent_steps_base = 0;
     if (e->ovf_host && (*(volatile unsigned long long*)e->ovf_host >> 63)) {   // the sticky overflow status goes with the counters; a step
         HIPCHK(e, hipStreamSynchronize(e->stream));                              // still in flight must not set it again behind the clear
         *(volatile unsigned long long*)e->ovf_host = 0ull;

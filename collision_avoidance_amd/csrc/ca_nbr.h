@@ -57,7 +57,11 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
 // order, not by distance, so an insert is up to S LDS round trips on the slowest lane of the wave.
 // AP (the AgentParams instantiation of the solve kernel): the range of the obstacle search is the agent's own,
 // sqr(time_horizon_obst_i * max_speed_i + radius_i), from the per-agent arrays of the cold block.
-template <int KMAX, int BS, int SM, bool AP = false>
+// AC (the ArenaCounts instantiation): arena a holds n_a = agent_counts[a] agents.  A lane is active for i < n_a, and a candidate j
+// counts for j < n_a: the loops over candidates keep their wave-uniform trip count N (several arenas of different counts may share
+// a wave) and the count joins the accept test, so the staged position of an absent lane is never taken, whatever it holds.  The
+// grid scan sorts the present agents only.
+template <int KMAX, int BS, int SM, bool AP = false, bool AC = false>
 __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #ifndef CA_NBR_NO_VGPR_PAD
     // Claim 128 VGPRs (the kernel needs 56): at most 4 waves then fit on a SIMD, so a launch that brings one
@@ -73,7 +77,9 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     lane_slot(p, tid, la, i);
     const int apb = p.apb;
     const int a = p.a0 + work_block(p) * apb + la;
-    const bool active = (a < p.a1) && (i < p.N) && (la < apb) && !arena_frozen(p, a);
+    int n_a = p.N;   // agents of this lane's arena
+    if constexpr (AC) n_a = ((a < p.a1) && (la < apb)) ? p.cold->agent_counts[a] : 0;
+    const bool active = (a < p.a1) && (i < n_a) && (la < apb) && !arena_frozen(p, a);
     const int N = p.N, K = p.K, S = p.S;
     const int q = active ? a * N + i : 0;
     const int lbase = tid - i;
@@ -188,7 +194,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             if (tid >= 2 && tid < 4) s_box[tid] = 0u;
             for (int cidx = tid; cidx < GMAX * GMAX; cidx += BS) s_ccnt[cidx] = 0;
             __syncthreads();
-            const bool in_arena = (a < p.a1) && (i < N);  // frozen arenas skip the scan but keep the barriers
+            const bool in_arena = (a < p.a1) && (i < n_a);  // frozen arenas skip the scan but keep the barriers
             {  // the arena's bounding box: a reduction per wave, then one atomic per wave and corner
                 const unsigned ox = ord(pos.x), oy = ord(pos.y);
                 const unsigned bx0 = wave_min_u32(in_arena ? ox : 0xFFFFFFFFu), by0 = wave_min_u32(in_arena ? oy : 0xFFFFFFFFu);
@@ -320,7 +326,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
         for (int k = 0; k <= KMAX; ++k) ck[k] = (k < kofs) ? 0u : 0xFFFFFFFFu;
         auto visit = [&](int j, V2 o) __attribute__((always_inline)) {
             const float dsq = absSq(pos - o);
-            const bool pass = active && j != i && dsq < rangeSq0;
+            const bool pass = active && j != i && (!AC || j < n_a) && dsq < rangeSq0;
             const unsigned u = __float_as_uint(dsq);
             unsigned key = (((u > u0 ? u : u0) - u0) << p.logP) | (unsigned)j;
             asm volatile("" : "+v"(key));   // (computed for every lane: left to itself the compiler branches around these three
@@ -361,7 +367,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             const V2 o = o_next;  // the next candidate's position is in flight while this one is inserted
             if (j + 1 < N) o_next = mk(s_px[lbase + j + 1], s_py[lbase + j + 1]);
             const float dsq = absSq(pos - o);
-            if (active && j != i && dsq < rangeSq) {
+            if (active && j != i && (!AC || j < n_a) && dsq < rangeSq) {
                 sorted_insert<KMAX>(nkey, make_key(dsq, j));
                 if (ncnt < K) ++ncnt;
                 if (ncnt == K) rangeSq = key_dist(nkey[KMAX - 1]);

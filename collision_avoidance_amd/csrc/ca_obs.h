@@ -45,6 +45,7 @@ struct ObsArgs {
                           // ((float)(r_j cos(e pi/4)), (float)(-(r_j sin(e pi/4)))) in fp64 from the fp32 radius, made on the host by
                           // ca_set_agent_params; chord e runs from vertex e to vertex (e + 1) mod 8, env.py:335-350).  Last member:
                           // nothing the other instantiations read moves.
+    const int* agent_counts;  // ArenaCounts instantiations only: [A] agents per arena (ca_set_agent_counts).  Behind ap_oct for the same reason.
 };
 
 #ifdef CA_STAMPS
@@ -124,10 +125,13 @@ __device__ __forceinline__ float ray_dial(float x, float y) {
 // octagon of ITS radius -- the lane that owns neighbour slot k copies j's eight vertices from the per-agent table into LDS, the
 // chords are built from them, and the pre-pass circle, the tolerance of phase A and its world-frame filter take that radius
 // (= vertex 0's x, exactly: (float)((double)r cos 0) = r).
+// ArenaCounts in the pack (includes AgentParams): a row i >= agent_counts[a] is absent -- its list counts are taken as 0 whatever the
+// memory holds, so its observation row is written as zeros; nobody's list names it, so it casts no octagon either.
 template <int OBS_BS, bool NW16, bool DENSE = false, class... WIDE_TAG>
 __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     constexpr bool WIDE = has_tag<WideObstLists, WIDE_TAG...>;
-    constexpr bool AP = has_tag<AgentParams, WIDE_TAG...>;
+    constexpr bool AC = has_tag<ArenaCounts, WIDE_TAG...>;
+    constexpr bool AP = has_tag<AgentParams, WIDE_TAG...> || AC;   // (ArenaCounts includes AgentParams)
     static_assert(!(WIDE && AP), "per-agent parameters go with obstacle lists of up to 16");
     constexpr int OBS_APB = OBS_BS / 16;  // agents per workgroup
     extern __shared__ float4 smem4[];
@@ -214,6 +218,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         if constexpr (DENSE) {
             const int cnts = p.counts[q];
             nn = cnts & 0xFF; ns = cnts >> 8;
+            if constexpr (AC) { if (i >= p.agent_counts[a]) { nn = 0; ns = 0; } }   // an absent row: no sources, a row of zeros
             c = p.orient_x[q]; s = -p.orient_y[q];  // utils.py:48-51: cos/sin of -atan2(orientation)
             if (r < nn) s_nb[g * 16 + r] = abase + ld_idx_t<NW16>(p.nb_idx, ((size_t)a * K + r) * N + i);  // as an index of the staged arrays
             if constexpr (WIDE) { for (int t = r; t < ns; t += 16) s_ob[g * OBW + t] = (int)p.obst_idx[((size_t)a * S + t) * N + i]; }
@@ -221,6 +226,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         } else {
             const int cnts = (p.counts + aoff)[ii];
             nn = cnts & 0xFF; ns = cnts >> 8;
+            if constexpr (AC) { if (i >= p.agent_counts[a]) { nn = 0; ns = 0; } }   // an absent row: no sources, a row of zeros
             c = (p.orient_x + aoff)[ii]; s = -(p.orient_y + aoff)[ii];  // utils.py:48-51: cos/sin of -atan2(orientation)
             const unsigned li = (unsigned)r * (unsigned)N + ii;     // inside the arena's [K][N] / [S][N] block: below 16 x 1024
             const char* nbase = (const char*)p.nb_idx + aoff * (size_t)K * (NW16 ? 2 : 1);

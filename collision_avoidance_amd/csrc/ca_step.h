@@ -96,10 +96,14 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 //   (ca_set_agent_params): the four values are loaded per lane from the cold block's [A*N] arrays, the arena's radii are staged in
 //   LDS behind the misc ints (a neighbour's radius enters combinedRadius = r_i + r_j and the pair count), and the pair count
 //   scans the arena instead of the neighbour lists, whose shortcut assumes one radius.
+//   ArenaCounts (includes AgentParams) = arena a holds agent_counts[a] of its N rows (ca_set_agent_counts): lanes i >= n_a are
+//   idle like the lanes beyond N, the neighbour search and the pair count take candidates j < n_a (ca_nbr.h), and the done test,
+//   the last-episode word and the in-kernel reset see the arena's n_a agents.  Nothing of an absent row is loaded or stored.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
-    constexpr bool AP = has_tag<AgentParams, PER...>;
+    constexpr bool AC = has_tag<ArenaCounts, PER...>;
+    constexpr bool AP = has_tag<AgentParams, PER...> || AC;   // (ArenaCounts includes AgentParams: one tag names the instantiation)
     static_assert(!AP || (ST == 0 && !ALAN && SMX <= SMAX), "per-agent parameters: the LDS line table with lists of up to 16, no ALAN form");
     extern __shared__ float4 smem4[];
     constexpr bool LISTP = BS > 64 && !AP;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // The neighbour search runs at the head of this kernel (one drain/fill less per step than a launch of its own, and its
     // dispatch skew overlaps useful work).  A lane later reads back only the lists of its own agent, which it wrote itself;
     // the search's LDS arrays are not used again.
-    nbr_body<KMAX, BS, SMX, AP>(p);
+    nbr_body<KMAX, BS, SMX, AP, AC>(p);
     constexpr int ML = ST + KMAX;  // register slots (ST > 0)
     const int tid = threadIdx.x;
     const int P = p.P;
@@ -119,7 +123,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     const int apb = p.apb;
     const int a = p.a0 + work_block(p) * apb + la;
     const bool frozen = arena_frozen(p, a);  // CA_F_FREEZE: the episode of this arena is over
-    const bool active = (a < p.a1) && (i < p.N) && (la < apb) && !frozen;
+    int n_a = p.N;   // agents of this lane's arena (AC: its entry of the counts)
+    if constexpr (AC) n_a = ((a < p.a1) && (la < apb)) ? p.cold->agent_counts[a] : 0;
+    const bool active = (a < p.a1) && (i < n_a) && (la < apb) && !frozen;
     if (frozen && i == 0) p.arena_stats[(size_t)a * ST_STRIDE + ST_FROZEN] += 1;
     const int N = p.N, K = p.K, S = p.S;
     const int q = active ? a * N + i : 0;
@@ -444,6 +450,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     const int a = p.a0 + work_block(p) * apb + la;
     const int q = active ? a * N + i : 0;
     const int lbase = tid - i;
+    // agents of the arena (AC: read again where the epilogue needs it, not kept across the solve; an idle lane never uses it)
+    int NA = N;
+    if constexpr (AC) NA = active ? c.agent_counts[a] : 1;
     const ObstDev* tab = p.obst + ((p.tab_off != nullptr && active) ? p.tab_off[a] : 0);
     pf32 = mk(reinterpret_cast<float*>(s_misc)[tid * 4 + 0], reinterpret_cast<float*>(s_misc)[tid * 4 + 1]);
     if constexpr (PARK_PREF) pref = mk(reinterpret_cast<float*>(s_misc)[tid * 4 + 2], reinterpret_cast<float*>(s_misc)[tid * 4 + 3]);
@@ -519,8 +528,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             // Mixed radii: a pair overlaps within sqr(r_i + r_j) (the oracle's arena_collisions), which the lists' shortcut above --
             // one radius, neighbor_dist >= 2 R + 2 m -- does not bound.  The arena is scanned, balanced as below: every unordered
             // pair once, agent i against the agents (i + d) mod N for d = 1 .. (N - 1) / 2 and, N even, the lower half against its
-            // antipode; positions and radii from the staged arena.
+            // antipode; positions and radii from the staged arena.  (AC: N here is the arena's own count -- absent lanes are never a j.)
             if (active) {
+                const int N = NA;
                 const int H = (N - 1) >> 1;
                 auto near = [&](int d) __attribute__((always_inline)) {
                     int j = i + d;
@@ -635,7 +645,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
         if constexpr (!ALAN) { c.pref_x[q] = pref.x; c.pref_y[q] = pref.y; }   // (ALAN: written above)
 #endif
         if (i == 0) {
-            flush_stats(c.arena_stats + (size_t)a * ST_STRIDE, red[1], red[2], red[3], all_done ? 1u : 0u, all_done, lastep_word(steps, N, red[0]));
+            flush_stats(c.arena_stats + (size_t)a * ST_STRIDE, red[1], red[2], red[3], all_done ? 1u : 0u, all_done, lastep_word(steps, NA, red[0]));
             c.arena_done[a] = all_done ? 1 : 0;
             c.step_count[a] = do_reset ? 0 : steps;
             atomicAdd(&c.arena_steps[a], 1ull);   // (no return value: nothing waits for it at the end of the kernel)
@@ -650,12 +660,15 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
 // reset() for every arena (env.py:461-488): new positions only; velocities, targets and the
 // neighbour lists of the last step stay.
 // ============================================================================================
-__global__ void reset_kernel(const StepArgs p) {
+// AC (reset_counts_kernel, a handle with per-arena agent counts): rows i >= agent_counts[a] are absent and stay as they are.
+template <bool AC>
+__device__ __forceinline__ void reset_body(const StepArgs& p) {
     const ColdK& c = *(ColdK*)p.cold;
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= p.A * p.N) return;
     const int a = q / p.N, i = q - a * p.N;
     if (p.reset_mask && p.reset_mask[a] == 0) return;
+    if constexpr (AC) { if (i >= c.agent_counts[a]) return; }
     V2 pos;
     if (p.reset_px) {
         pos = mk(p.reset_px[q], p.reset_py[q]);
@@ -668,6 +681,8 @@ __global__ void reset_kernel(const StepArgs p) {
     c.orient_x[q] = d.x; c.orient_y[q] = d.y;
     c.agent_done[q] = 0;
 }
+__global__ void reset_kernel(const StepArgs p) { reset_body<false>(p); }
+__global__ void reset_counts_kernel(const StepArgs p) { reset_body<true>(p); }
 // orientation from scratch (after the caller overwrote positions or goals through ca_set)
 __global__ void orient_kernel(const StepArgs p) {
     const ColdK& c = *(ColdK*)p.cold;

@@ -51,11 +51,16 @@ class VecCollisionAvoidanceEnv:
                error wants this raised, not allow_obst_overflow.
     agent_params: dict(radius=, max_speed=, time_horizon=, time_horizon_obst=) handed to set_agent_params() once the handle
                exists: ORCA parameters per agent instead of the four constants of `params`.
+    agent_counts: [A] ints handed to set_agent_counts() before the scenario is initialised: arena a holds agent_counts[a] of its
+               n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None):
+                 agent_params=None, agent_counts=None):
+        if agent_counts is not None and scenario not in (None, "doorway"):
+            raise ValueError("agent_counts: scenario %r lays its agents out as a function of n_agents; only 'doorway' or None "
+                             "go with per-arena agent counts" % (scenario,))
         self.L = _lib.load()
         self.A, self.N = int(n_arenas), int(n_agents)
         p = scenarios.env_params()
@@ -102,6 +107,8 @@ class VecCollisionAvoidanceEnv:
             self.set_obstacles_per_arena(worlds)
         else:
             self.set_obstacles(polys)
+        if agent_counts is not None:
+            self.set_agent_counts(agent_counts)
         if scenario is not None:
             self.init_scenario(scenario)
         if agent_params:
@@ -339,10 +346,12 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_launch_info", self.h, *[C.byref(x) for x in v])
         lanes, roll = C.c_int32(), C.c_int32()
         self._call("ca_solver_info", self.h, C.byref(lanes), C.byref(roll))
-        per = C.c_int32()
+        per, cnt = C.c_int32(), C.c_int32()
         self._call("ca_agent_params_info", self.h, C.byref(per))
+        self._call("ca_agent_counts_info", self.h, C.byref(cnt))
         return dict(block=v[0].value, grid=v[1].value, lds_bytes=v[2].value, obs_grid=v[3].value,
-                    lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value))
+                    lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value),
+                    agent_counts=bool(cnt.value))
 
     # ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133) ---------------
     _AGENT_PARAMS = ("radius", "max_speed", "time_horizon", "time_horizon_obst")
@@ -382,6 +391,35 @@ class VecCollisionAvoidanceEnv:
         out = {k: np.empty((self.A, self.N), np.float32) for k in self._AGENT_PARAMS}
         self._call("ca_get_agent_params", self.h, *[_ptr(out[k]) for k in self._AGENT_PARAMS], self.A * self.N * 4, 0)
         return out
+
+    # ---- agents per arena (the reference's constructor argument numAgents, env.py:23-60, per arena) ---
+    def set_agent_counts(self, counts):
+        """Arena a holds counts[a] agents, rows 0 .. counts[a]-1 of its N (ca_set_agent_counts): an [A] int array or torch
+        tensor, every entry in [1, N].  Shapes stay [A,N,...]; absent rows show a zero observation and reward and are left alone
+        otherwise (agent_mask()).  Configuration like the obstacles: it survives reset() and init_scenario("doorway") and is
+        not part of get_state().  Clears the neighbour lists of every arena.  The handle then runs the per-arena-count kernels
+        (launch_info()["agent_counts"]); the other scenario generators and the ALAN calls raise while counts are set."""
+        if torch is not None and isinstance(counts, torch.Tensor):   # a configuration call: the library checks every value on the host
+            counts = counts.detach().cpu().numpy()
+        c = np.asarray(counts)
+        if c.shape != (self.A,) or c.dtype.kind not in "iu":
+            raise ValueError("set_agent_counts: counts must be an [A] integer array (A=%d), got shape %s, dtype %s" % (self.A, c.shape, c.dtype))
+        c = np.ascontiguousarray(np.clip(c, -2 ** 31, 2 ** 31 - 1), np.int32)   # (out of range stays out of range for the library's check)
+        self._call("ca_set_agent_counts", self.h, _ptr(c), c.nbytes, 0)
+
+    def clear_agent_counts(self):
+        """Every arena holds N agents again; back to the kernels the handle used before."""
+        self._call("ca_set_agent_counts", self.h, None, 0, 0)
+
+    def agent_counts(self):
+        """int32 [A]: the agents of every arena (N everywhere on a handle without counts)."""
+        out = np.empty(self.A, np.int32)
+        self._call("ca_get_agent_counts", self.h, _ptr(out), out.nbytes, 0)
+        return out
+
+    def agent_mask(self):
+        """bool [A,N]: True for the rows that are agents of their arena."""
+        return np.arange(self.N)[None, :] < self.agent_counts()[:, None]
 
     # ---- the environment API ----------------------------------------------------------------------
     def _on_device(self, t, dtype):

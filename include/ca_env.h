@@ -150,7 +150,7 @@ typedef struct ca_config {
 } ca_config;
 
 typedef struct ca_stats {
-    uint64_t agent_steps;     /* counted IN the solve kernels: per arena, the steps it was really advanced, x n_agents */
+    uint64_t agent_steps;     /* counted IN the solve kernels: per arena, the steps it was really advanced, x its agents */
     uint64_t episodes;
     uint64_t collisions;      /* overlapping agent pairs after the update, summed over steps  */
     uint64_t obst_collisions; /* agents overlapping an obstacle edge, summed over steps       */
@@ -217,6 +217,42 @@ int ca_get_agent_params(ca_env* env, float* radius, float* max_speed, float* tim
                         float* time_horizon_obst, size_t bytes_each, int32_t dst_is_device);
 /* *per_agent = 1 while per-agent parameters are set (the AgentParams kernels run), else 0. */
 int ca_agent_params_info(ca_env* env, int32_t* per_agent);
+
+/* Arenas of different crowd sizes in one batch: the reference's one constructor argument, Collision_Avoidance_Env(numAgents)
+ * (env.py:23-60), per arena.  counts: i32 [A], host or device; NULL = every arena holds n_agents again and the handle returns to
+ * the kernels it used before.
+ *   - Layout: every array keeps its shape and strides ([A,N], [A,K,N], [A,N,64]; N = ca_config.n_agents, now a capacity).  Arena a
+ *     consists of agents 0 .. counts[a]-1; rows i >= counts[a] are absent.
+ *   - An absent agent is nobody's neighbour and casts no octagon into anybody's observation.  It is not in the done test (an
+ *     arena's episode is over when all of its counts[a] agents are done, or at the step cap) and in no statistic:
+ *     ca_stats.agent_steps grows by counts[a] per step of arena a, and the "agents that arrived" half of the last-episode word is
+ *     out of counts[a].
+ *   - From the call on the observation row and the reward of an absent row read 0, and its two list counts read 0.  No kernel
+ *     writes any other field of an absent row -- not ca_step / ca_orca_step / ca_rollout, not ca_reset (the caller's position
+ *     arrays included), ca_reset_masked or CA_F_AUTORESET: an absent row keeps what the caller last put there.
+ *   - Configuration, like the agent parameters and the obstacle tables, not state: the counts persist across ca_reset*,
+ *     CA_F_AUTORESET and ca_init_scenario, and are not a ca_field.
+ *   - The call drains the stream and clears the agent- and obstacle-neighbour counts of EVERY arena (the old lists may name agents
+ *     that are gone; a fresh simulator has empty lists).  It touches nothing else.  counts[a] == n_agents for every arena is
+ *     allowed and still selects the kernels described below.
+ *   - bytes != A*4 -> CA_ESIZE; a count outside [1, n_agents] -> CA_ERANGE (ca_last_error names the arena and the value); a handle
+ *     with max_obst_neighbors > 16 -> CA_EINVAL; a shape whose LDS line table does not fit a CU -> CA_ERANGE (as for
+ *     ca_set_agent_params).  On any failure the handle keeps its previous counts and kernels.
+ *   - Not supported while counts are set (CA_EINVAL, the message says so): ca_init_scenario for every scenario but CA_SCN_DOORWAY
+ *     (the other generators' geometry is a function of the number of agents; the doorway's is not and works unchanged, for all N
+ *     rows), ca_alan_configure*, ca_alan_step and ca_alan_rollout.
+ *   - Composes with ca_set_agent_params, in either order; clearing one keeps the other.
+ *   - While counts are set the handle runs one lane per agent on the LDS line table (the per-agent-parameter kernels with a count
+ *     per arena; without parameters of the caller's the per-agent arrays hold the ca_config values, whose bits are the uniform
+ *     handle's): ca_solver_info reports lanes_per_agent = 1, rollout_one_launch = 0, ca_rollout is T launches.  An arena keeps its
+ *     N-lane slot and absent lanes idle.  CA_F_FREEZE, ca_step_packed and the overflow error work as before.  Arena a computes
+ *     what a handle of one arena with n_agents = counts[a] and arena_offset + a computes, bit for bit (no random stream is keyed
+ *     by n_agents); sum_reward is added in another order (1e-9 relative). */
+int ca_set_agent_counts(ca_env* env, const int32_t* counts, size_t bytes, int32_t src_is_device);
+/* The counts as the kernels use them (n_agents everywhere on a uniform handle). */
+int ca_get_agent_counts(ca_env* env, int32_t* counts, size_t bytes, int32_t dst_is_device);
+/* *per_arena = 1 while counts are set (the ArenaCounts kernels run), else 0. */
+int ca_agent_counts_info(ca_env* env, int32_t* per_arena);
 
 /* Replaces _init_world's agent loop (env.py:86-97) / ALAN's scenario generators (ALAN:175-457).  Runs on the device: every
  * agent's heading, start and targets come from the handle's counter-based streams (keyed by the global arena id) or, for
