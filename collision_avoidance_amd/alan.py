@@ -72,7 +72,8 @@ class Collision_Avoidance_Sim(object):
         # are the global arenas [r * n_arenas, (r + 1) * n_arenas) of this seed
         self.vec = VecCollisionAvoidanceEnv(self.n_arenas, self.numAgents, scenario=self.scenario, params=p,
                                             device=self._device, seed=self._seed, use_torch=False,
-                                            arena_offset=self._resets * self.n_arenas)
+                                            arena_offset=self._resets * self.n_arenas,
+                                            tiled=self.numAgents > _lib.MAX_AGENTS)   # (any numAgents, like the reference's)
         self._resets += 1
         if self.arena_actions is not None:
             self.vec.alan_configure_per_arena(self.arena_actions, self.online_temp, self.timewindow, self.timeStep)

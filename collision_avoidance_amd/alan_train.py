@@ -132,7 +132,7 @@ class MCMC_trainer(object):
         """One episode set of n_chains * num arenas; chain c's set on arenas c*num .. c*num+num-1 (:55-67)."""
         from .alan import Collision_Avoidance_Sim
         arena_sets = [list(s) for s in action_sets for _ in range(self.num)]
-        if self._sim is None:
+        if self._sim is None:   # (any numAgents: above 1024 the simulator asks for a tiled handle on its own, alan.py)
             self._sim = Collision_Avoidance_Sim(numAgents=self.numAgents, scenario=self.scenario, device=self.device,
                                                 seed=self.seed, n_arenas=self.n_chains * self.num, arena_actions=arena_sets)
         else:

@@ -109,6 +109,12 @@ struct ca_env {
     bool ac = false, ap_user = false;
     int* d_counts = nullptr;                                 // [A]
     std::vector<int> h_counts;                               // host copy (ca_get_agent_counts, ca_get_stats); empty while !ac
+    // the tiled solve path (ca_create_ex, CA_CREATE_TILED; ca_tiled.h): an arena spans `tiles` workgroups of TILE lanes, a step is
+    // three launches (solve, advance, close)
+    bool tiled = false;
+    int TILE = 128, tiles = 1;
+    float *nv_x = nullptr, *nv_y = nullptr;   // [A*N] new velocity, then the copy of the post-step position (ca_tiled.h TiledArgs)
+    unsigned* tscr = nullptr;                 // [A][TS_STRIDE] per-arena scratch of the three launches
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -153,7 +159,9 @@ static int overflow_status(ca_env* e, const char* where) {
                 "max_obst_neighbors=%d, so the farthest were dropped (RVO2 keeps every edge in range: collision_avoidence_env.py:249, "
                 "301-318).  Raise max_obst_neighbors (at most %d), coarsen the world's polylines, or accept the truncation with "
                 "ca_allow_obstacle_overflow(env, 1); ca_reset_stats clears this status", where,
-                (long long)((v >> 20) & 0xFFFFFFFFFFull), (int)((v >> 8) & 0x7FF), (int)(v & 0xFF), (v & 0xFF) == 255 ? "+" : "",
+                // (a tiled handle's word has a wider agent field: ca_tiled.h note_overflow_tiled)
+                (long long)(e->tiled ? (v >> 24) & 0xFFFFFFFFFull : (v >> 20) & 0xFFFFFFFFFFull),
+                (int)(e->tiled ? (v >> 8) & 0xFFFF : (v >> 8) & 0x7FF), (int)(v & 0xFF), (v & 0xFF) == 255 ? "+" : "",
                 e->S, CA_MAX_OBST_NEIGHBORS);
 }
 
@@ -367,7 +375,19 @@ static const void* quad_fn_for(const ca_env* e) {   // (K <= 10)
     return e->KT == 5 ? quad_fn_for<5, 4, ALAN, PER...>(e->BSq) : quad_fn_for<10, 4, ALAN, PER...>(e->BSq);
 }
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
+// the tiled path's first launch (ca_tiled.h): KMAX class x TILE
+template <int KMAX>
+static const void* tiled_fn_for(int TILE) {
+    switch (TILE) {
+        case 64: return fn_ptr(&tiled_solve_kernel<KMAX, 64>);
+        case 256: return fn_ptr(&tiled_solve_kernel<KMAX, 256>);
+        default: return fn_ptr(&tiled_solve_kernel<KMAX, 128>);
+    }
+}
 static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout) {
+    if (e->tiled)   // (the first of the three launches of a step; no ALAN and no rollout form)
+        return {e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE)),
+                dim3(e->grid), dim3(e->TILE), e->lds};
     const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
     if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
         const void* f = per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e));
@@ -386,6 +406,20 @@ static hipError_t allow_lds(const SolveLaunch& s) {
 static hipError_t launch_step(ca_env* e, const StepArgs& a) {
     const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1);
     if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
+    if (e->tiled) {   // solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
+        TiledArgs ta;
+        ta.s = a; ta.nv_x = e->nv_x; ta.nv_y = e->nv_y; ta.scr = e->tscr; ta.tiles = e->tiles;
+        void* params[] = {&ta};
+        const void* fns[3] = {s.fn, fn_ptr(&tiled_advance_kernel), fn_ptr(&tiled_close_kernel)};
+        const size_t lds[3] = {s.lds, 0, (size_t)e->TILE * 8};
+        for (int k = 0; k < 3; ++k) {   // (each launch timed on its own dispatch, kind 1)
+            ProfScope ps(e, KIND_STEP);
+            const hipError_t r = ps.t0 ? hipExtLaunchKernel(fns[k], s.grid, s.block, params, lds[k], e->stream, ps.t0, ps.t1, 0)
+                                       : hipLaunchKernel(fns[k], s.grid, s.block, params, lds[k], e->stream);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    }
     ProfScope ps(e, KIND_STEP, a.T > 1 ? a.T : 1);
     StepArgs arg = a;
     void* params[] = {&arg};
@@ -414,7 +448,9 @@ static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = fal
 // Arenas of fewer than 16 agents: the 16 agent groups of an observation workgroup take 16 consecutive agents of the batch (the
 // reference env's own 10-agent arenas would otherwise leave 6 of 16 groups idle).  CA_OBS_DENSE=0: one arena per workgroup.
 static bool obs_dense(const ca_env* e) { return e->obs_dense_on; }   // (latched by ca_create)
-static int obs_nstage(const ca_env* e) { return obs_dense(e) ? 16 + 2 * e->cfg.n_agents : e->cfg.n_agents; }
+// (a tiled handle: obs_kernel<256, true> gathers its neighbours from global memory and never touches the staged arrays -- none are
+// carved out, at 16384 agents they would be 256 KB)
+static int obs_nstage(const ca_env* e) { return e->tiled ? 0 : (obs_dense(e) ? 16 + 2 * e->cfg.n_agents : e->cfg.n_agents); }
 static bool obs_wide(const ca_env* e) { return e->S > SMAX; }   // more than 16 obstacle ids per agent (ca_obs.h WIDE)
 static size_t obs_lds(const ca_env* e, int obs_bs) {
     if (e->ap) return obs_lds_bytes_ap(obs_nstage(e), obs_bs, 16 * (e->K + e->S));
@@ -594,6 +630,11 @@ static void pick_variant(ca_env* e) {
     // (CA_REG_LINES, latched by ca_create: 0 forces the LDS line table, 1 the register lines wherever they exist)
     const bool allow = e->sw.reg_lines != 0, force = e->sw.reg_lines == 1;
     e->KT = e->K <= 5 ? 5 : (e->K <= 10 ? 10 : 16);
+    if (e->tiled) {   // one kernel family whatever the world: the LDS line table of a tile, lists of up to 16
+        e->ST = 0; e->SMX = SMAX; e->pair = false;
+        e->lds = tiled_lds_bytes(e->TILE, e->K, e->S);
+        return;
+    }
     const size_t table_per_wg = step_lds_bytes(e->BS, e->K, e->S, 0, e->KT) + lds_static_bytes(e);
     const bool table_fits = table_per_wg <= 160 * 1024;
     const bool small_world = e->max_edges <= 16;
@@ -624,6 +665,7 @@ static void pick_variant(ca_env* e) {
 static const size_t LDS_PER_CU = 160 * 1024;
 static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
     const SolveLaunch plain = solve_launch(e, false, false);
+    if (e->tiled) { *misfit = false; return allow_lds(plain); }   // (at most 256 lanes x (32 lines x 16 B + 8 B) = 130 KiB)
     *misfit = !e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU;
     hipError_t r = hipSuccess;
     if (e->pair) {
@@ -643,7 +685,7 @@ static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
 // per lane), else select -> solve -> update.
 static int alan_pick(ca_env* e) {
     e->alan_fused = e->alan_lane = false;
-    if (e->n_actions <= 0) return CA_OK;
+    if (e->n_actions <= 0 || e->tiled) return CA_OK;   // (a tiled handle: select -> tiled solve -> update)
     const size_t lq = quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions);
     const bool on = e->sw.alan_fused != 0;   // (CA_ALAN_FUSED=0: the three-launch form everywhere)
     e->alan_fused = on && (e->quad || e->quad_roll) && lq <= 64 * 1024;
@@ -660,12 +702,20 @@ extern "C" {
 
 const char* ca_last_error(const ca_env* env) { return env ? env->err.c_str() : g_create_err.c_str(); }
 
-int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
+int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) { return ca_create_ex(cfg, 0u, device, stream, out); }
+
+int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out) {
     if (!cfg || !out) return fail(nullptr, CA_EINVAL, "ca_create: null argument");
     *out = nullptr;
-    if (cfg->n_arenas <= 0 || cfg->n_agents <= 0 || cfg->n_agents > CA_MAX_AGENTS)
+    if (create_flags & ~CA_CREATE_TILED) return fail(nullptr, CA_EINVAL, "ca_create_ex: unknown create_flags 0x%x", create_flags);
+    const bool tiled = (create_flags & CA_CREATE_TILED) != 0;
+    const int max_agents = tiled ? CA_MAX_AGENTS_LARGE : CA_MAX_AGENTS;
+    if (cfg->n_arenas <= 0 || cfg->n_agents <= 0 || cfg->n_agents > max_agents)
         return fail(nullptr, CA_ERANGE, "ca_create: n_arenas=%d n_agents=%d out of range (agents 1..%d)",
-                    cfg->n_arenas, cfg->n_agents, CA_MAX_AGENTS);
+                    cfg->n_arenas, cfg->n_agents, max_agents);
+    if (tiled && cfg->max_obst_neighbors > SMAX)
+        return fail(nullptr, CA_ERANGE, "ca_create_ex: max_obst_neighbors=%d: wide obstacle lists (above %d) have no tiled form",
+                    cfg->max_obst_neighbors, SMAX);
     if (cfg->max_neighbors < 0 || cfg->max_neighbors > CA_MAX_NEIGHBORS)
         return fail(nullptr, CA_ERANGE, "ca_create: max_neighbors=%d out of range 0..%d", cfg->max_neighbors,
                     CA_MAX_NEIGHBORS);
@@ -705,6 +755,13 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         auto digit = [](const char* name) { const char* v = getenv(name); return (v && v[0] >= '0' && v[0] <= '9') ? v[0] - '0' : -1; };
         e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.pair = digit("CA_PAIR"); e->sw.alan_fused = digit("CA_ALAN_FUSED");
     }
+    e->tiled = tiled;
+    if (tiled) {   // CA_TILE = 64 | 128 | 256 (diagnostic switch, tools/tiled_cost.py): the tile of the tiled path; anything else: 128
+        const char* v = getenv("CA_TILE");
+        const int want = v ? atoi(v) : 0;
+        e->TILE = (want == 64 || want == 256) ? want : 128;
+        e->tiles = (cfg->n_agents + e->TILE - 1) / e->TILE;
+    }
     // launch geometry: P lanes per arena (power of two >= N), one or more whole arenas per block
     int P = 1, logP = 0;
     while (P < cfg->n_agents) { P <<= 1; ++logP; }
@@ -712,15 +769,25 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     e->BS = P > 64 ? P : 64;
     e->LS = P; e->apb = e->BS / P; e->linv = 65536 / P; e->dense = 0;   // (P a power of two: exact)
     e->grid = (cfg->n_arenas + e->apb - 1) / e->apb;
+    if (tiled) {   // a workgroup is a tile: the lane -> (arena, agent) fields of StepArgs are not read by the tiled kernels
+        if ((size_t)cfg->n_arenas * e->tiles > (size_t)0x7FFFFFFF) {
+            fail(nullptr, CA_ERANGE, "ca_create_ex: n_arenas=%d x %d tiles per arena is more workgroups than a launch holds", cfg->n_arenas, e->tiles);
+            if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+            delete e;
+            return CA_ERANGE;
+        }
+        e->BS = e->TILE; e->LS = e->TILE; e->apb = 1; e->linv = 65536 / e->TILE;
+        e->grid = cfg->n_arenas * e->tiles;
+    }
     {
         const char* v = getenv("CA_OBS_DENSE");  // diagnostic switch: 0 = one arena per observation workgroup
-        e->obs_dense_on = cfg->n_agents < 16 && !(v && v[0] == '0');
+        e->obs_dense_on = !tiled && cfg->n_agents < 16 && !(v && v[0] == '0');
     }
     {   // arenas within one wave whose N is no power of two: N lanes each, back to back, where that packs more arenas into the
         // wave than P lanes each (the reference env's own 10-agent arenas: six per wave instead of four)
         const char* v = getenv("CA_DENSE");  // diagnostic switch: 0 = P lanes per arena
         const int N = cfg->n_agents;
-        if (!(v && v[0] == '0') && e->BS == 64 && P < 64 && 64 / N > 64 / P) {
+        if (!tiled && !(v && v[0] == '0') && e->BS == 64 && P < 64 && 64 / N > 64 / P) {
             const int linv = (65536 + N - 1) / N;
             bool exact = true;
             for (int t = 0; t < 64; ++t) exact = exact && ((t * linv) >> 16) == t / N;
@@ -745,9 +812,9 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         // (register budget: a 1024-lane workgroup caps the kernel at 128 VGPRs, a 512-lane one at 256 -- the variant with 16
         // obstacle neighbours and K = 10 needs all 256 already at 256 lanes)
         // (... and it holds obstacle lists of 4 or 16: a handle with max_obst_neighbors > 16 never takes it, CA_QUAD=1 or not)
-        const bool fits = e->S <= SMAX && e->K <= 10 && 4 * P <= ((e->SQ == 16 && e->KT == 10) ? 256 : 512);
+        const bool fits = !tiled && e->S <= SMAX && e->K <= 10 && 4 * P <= ((e->SQ == 16 && e->KT == 10) ? 256 : 512);
         // (counted at P lanes per arena, the layout the crossover was measured with, whatever the packing is now)
-        const long lane_waves = (long)((cfg->n_arenas + e->BS / P - 1) / (e->BS / P)) * (e->BS / 64);
+        const long lane_waves = tiled ? 0 : (long)((cfg->n_arenas + e->BS / P - 1) / (e->BS / P)) * (e->BS / 64);   // (tiled: BS is a tile, fits is false)
         e->quad = fits && (v ? v[0] == '1' : lane_waves < 1024);
         e->quad_roll = fits && (v ? v[0] == '1' : lane_waves <= 1024);  // T steps per launch: ahead at 1024 lane-waves too
         e->BSq = 4 * P > 64 ? 4 * P : 64;
@@ -769,7 +836,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
         delete e;
         return CA_ERANGE;
     }
-    if (!e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU) {
+    if (!tiled && !e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU) {
         fail(nullptr, CA_ERANGE, "ca_create: the solve kernel would need %zu B of LDS (> 160 KiB) for n_agents=%d, "
              "max_neighbors=%d, max_obst_neighbors=%d: arenas above 256 agents need max_neighbors <= 10 "
              "(register-line variant)", e->lds + lds_static_bytes(e), cfg->n_agents, e->K, e->S);
@@ -786,7 +853,12 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) {
     for (auto p : f64s) if (r == hipSuccess) r = dalloc(e, p, an);
     int** i32s[] = {&e->agent_done, &e->arrive_step, &e->regoal_count};
     for (auto p : i32s) if (r == hipSuccess) r = dalloc(e, p, an);
-    e->nidx16 = CA_NBW16(e->BS) ? 1 : 0;  // u8 indices address 256 agents (BS = max(64, pow2 >= N): the kernels' compile-time test)
+    if (tiled) {
+        if (r == hipSuccess) r = dalloc(e, &e->nv_x, an);
+        if (r == hipSuccess) r = dalloc(e, &e->nv_y, an);
+        if (r == hipSuccess) r = dalloc(e, &e->tscr, A * (size_t)TS_STRIDE);
+    }
+    e->nidx16 = (tiled || CA_NBW16(e->BS)) ? 1 : 0;  // u8 indices address 256 agents (BS = max(64, pow2 >= N): the kernels' compile-time test)
     if (r == hipSuccess) r = dalloc(e, &e->counts, an);
     if (r == hipSuccess) r = dalloc(e, reinterpret_cast<unsigned char**>(&e->nb_idx),
                                     an * (size_t)(e->K > 0 ? e->K : 1) * (e->nidx16 ? 2 : 1));
@@ -843,7 +915,8 @@ int ca_destroy(ca_env* e) {
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
-                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts};
+                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
+                    e->nv_x, e->nv_y, e->tscr};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1113,6 +1186,8 @@ extern "C" {
 
 int ca_set_agent_counts(ca_env* e, const int32_t* counts, size_t bytes, int32_t src_is_device) {
     if (!e) return CA_EINVAL;
+    if (e->tiled)
+        return fail(e, CA_EINVAL, "ca_set_agent_counts: not on a tiled handle (CA_CREATE_TILED): the tiled kernels have no per-arena-count form");
     HIPCHK(e, hipSetDevice(e->device));
     const int A = e->cfg.n_arenas, N = e->cfg.n_agents;
     const size_t an = AN(e);
@@ -1200,6 +1275,8 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     static const char* const names[4] = {"radius", "max_speed", "time_horizon", "time_horizon_obst"};
     const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
     const bool any = radius || max_speed || time_horizon || time_horizon_obst;
+    if (e->tiled)
+        return fail(e, CA_EINVAL, "ca_set_agent_params: not on a tiled handle (CA_CREATE_TILED): the tiled kernels have no per-agent-parameter form");
     HIPCHK(e, hipSetDevice(e->device));
     if (!any) {   // back to the handle's four constants and to the kernels it used with them
         if (!e->ap_user) return CA_OK;
@@ -2174,6 +2251,15 @@ int ca_solver_info(ca_env* e, int32_t* lanes_per_agent, int32_t* rollout_one_lau
     if (!e) return CA_EINVAL;
     if (lanes_per_agent) *lanes_per_agent = e->quad ? 4 : (e->pair ? 2 : 1);
     if (rollout_one_launch) *rollout_one_launch = e->quad_roll ? 1 : 0;
+    return CA_OK;
+}
+
+int ca_tiled_info(ca_env* e, int32_t* tiled, int32_t* tile_agents, int32_t* tiles_per_arena, int32_t* launches_per_step) {
+    if (!e) return CA_EINVAL;
+    if (tiled) *tiled = e->tiled ? 1 : 0;
+    if (tile_agents) *tile_agents = e->tiled ? e->TILE : 0;
+    if (tiles_per_arena) *tiles_per_arena = e->tiled ? e->tiles : 0;
+    if (launches_per_step) *launches_per_step = e->tiled ? 3 : 0;
     return CA_OK;
 }
 

@@ -13,6 +13,8 @@
 //   * pair kernel (ca_pair.h): TWO lanes per agent for large arenas (192 .. 512 agents: one arena per workgroup is otherwise
 //     two waves per SIMD, each a long dependent chain): grid-scan candidates, half-planes and LP1 clips dealt over the pair,
 //     lines in registers (slot m of the even / odd lane = neighbour 2 m / 2 m + 1), merges by DPP.
+//   * tiled kernels (ca_tiled.h): arenas of up to 16384 agents on a handle made with CA_CREATE_TILED -- one lane per agent, an arena
+//     spread over workgroups of TILE agents, a step in three launches (solve, advance, close) whose boundaries are the barriers.
 //   * obs_kernel (ca_obs.h): 16 lanes per agent, one lane per (source, ray) pair, ds_min_u64 merge per ray.
 // Arenas are independent, so there is no inter-workgroup traffic; the grids are arena-major, and the observation workgroups of
 // an arena are indexed so that they run on the XCD whose solve workgroup wrote the arena's state (ca_obs.h).
@@ -33,6 +35,7 @@
 #include "ca_step.h"
 #include "ca_quad.h"
 #include "ca_pair.h"
+#include "ca_tiled.h"
 #include "ca_alan.h"
 #include "ca_obs.h"
 

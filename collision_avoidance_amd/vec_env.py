@@ -53,11 +53,19 @@ class VecCollisionAvoidanceEnv:
                exists: ORCA parameters per agent instead of the four constants of `params`.
     agent_counts: [A] ints handed to set_agent_counts() before the scenario is initialised: arena a holds agent_counts[a] of its
                n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
+    tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
+               arena spread over several workgroups, a step in three launches (tiled_info()); max_obst_neighbors <= 16, no
+               agent_params / agent_counts (ValueError).  Results are the ordinary handle's bit for bit.  False (default): one
+               workgroup per arena, n_agents <= 1024.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None, agent_counts=None):
+                 agent_params=None, agent_counts=None, tiled=False):
+        if tiled and (agent_params or agent_counts is not None):
+            raise ValueError("tiled=True: the tiled kernels have no per-agent-parameter and no per-arena-count form "
+                             "(agent_params= / agent_counts= go with tiled=False)")
+        self.tiled = bool(tiled)
         if agent_counts is not None and scenario not in (None, "doorway"):
             raise ValueError("agent_counts: scenario %r lays its agents out as a function of n_agents; only 'doorway' or None "
                              "go with per-arena agent counts" % (scenario,))
@@ -84,8 +92,11 @@ class VecCollisionAvoidanceEnv:
         self.device = int(device)
         self.use_torch = (torch is not None and torch.cuda.is_available()) if use_torch is None else bool(use_torch)
         h = C.c_void_p()
-        rc = self.L.ca_create(C.byref(self.cfg), self.device, None, C.byref(h))
-        _lib.check(self.L, None, rc, "ca_create")
+        if self.tiled:
+            rc = self.L.ca_create_ex(C.byref(self.cfg), _lib.CREATE_TILED, self.device, None, C.byref(h))
+        else:
+            rc = self.L.ca_create(C.byref(self.cfg), self.device, None, C.byref(h))
+        _lib.check(self.L, None, rc, "ca_create_ex" if self.tiled else "ca_create")
         self.h = h
         if allow_obst_overflow:
             self._call("ca_allow_obstacle_overflow", self.h, 1)
@@ -352,6 +363,13 @@ class VecCollisionAvoidanceEnv:
         return dict(block=v[0].value, grid=v[1].value, lds_bytes=v[2].value, obs_grid=v[3].value,
                     lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value),
                     agent_counts=bool(cnt.value))
+
+    def tiled_info(self):
+        """dict(tiled, tile_agents, tiles_per_arena, launches_per_step) of the tiled solve path (ca_tiled_info); zeros on an
+        ordinary handle."""
+        v = [C.c_int32() for _ in range(4)]
+        self._call("ca_tiled_info", self.h, *[C.byref(x) for x in v])
+        return dict(tiled=bool(v[0].value), tile_agents=v[1].value, tiles_per_arena=v[2].value, launches_per_step=v[3].value)
 
     # ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133) ---------------
     _AGENT_PARAMS = ("radius", "max_speed", "time_horizon", "time_horizon_obst")

@@ -40,6 +40,11 @@ extern "C" {
                                     later step call fail with CA_ERANGE: see ca_allow_obstacle_overflow */
 #define CA_MAX_AGENTS 1024       /* one workgroup owns one arena; above 256 agents max_neighbors <= 10
                                     is required (LDS capacity: the register-line solve kernels)         */
+#define CA_MAX_AGENTS_LARGE 16384 /* agents per arena on a tiled handle (ca_create_ex, CA_CREATE_TILED): an arena
+                                    spread over several workgroups                                       */
+
+/* create flags for ca_create_ex */
+#define CA_CREATE_TILED 1u /* the tiled solve path: n_agents 1..CA_MAX_AGENTS_LARGE, see ca_create_ex */
 
 /* error codes */
 #define CA_OK 0
@@ -165,6 +170,22 @@ typedef struct ca_env ca_env;
  * device: HIP device ordinal.  stream: a hipStream_t to run on (e.g. PyTorch's current stream),
  * or NULL to let the handle create its own. */
 int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
+/* ca_create with create flags; ca_create(cfg, ...) is ca_create_ex(cfg, 0, ...).  Unknown flag bits -> CA_EINVAL.
+ * CA_CREATE_TILED: one large crowd in one world (the reference's Collision_Avoidance_Env(numAgents) / Collision_Avoidance_Sim(numAgents)
+ * take any number).  n_agents may be 1..CA_MAX_AGENTS_LARGE (above -> CA_ERANGE, "out of range"); max_obst_neighbors <= 16 (above ->
+ * CA_ERANGE: wide lists have no tiled form); max_neighbors 0..16 at any size.
+ *   - The handle runs the tiled kernels whatever its size (below 1025 agents: for comparison and tests): one lane per agent, an
+ *     arena spread over ceil(n_agents / tile) workgroups, a step in three launches on the handle's stream -- solve (neighbour
+ *     search over the whole arena, N^2 per arena; lines; LP), advance (integration, reward, goal / wall tests), close (pair count,
+ *     end of episode, in-kernel reset) -- ca_tiled_info.  Results are the CPU oracle's and the ordinary handle's bit for bit;
+ *     ca_stats.sum_reward is added in another order (1e-9 relative).
+ *   - Every step, reset, scenario, field, obstacle-table and ALAN call works as on an ordinary handle, with all step flags and the
+ *     sticky overflow error; ca_rollout is T times the three launches, ca_alan_step / ca_alan_rollout take the three-launch form
+ *     around them (select, solve, update); neighbour ids are 16 bits on the device.
+ *   - ca_set_agent_params and ca_set_agent_counts -> CA_EINVAL (no tiled form); the handle keeps working.
+ *   - ca_solver_info reports lanes_per_agent = 1, rollout_one_launch = 0; ca_launch_info the first of the three launches;
+ *     ca_profile counts each of the three launches on its own under kind 1. */
+int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out);
 int ca_destroy(ca_env* env);
 const char* ca_last_error(const ca_env* env);
 /* Run on the caller's stream from now on (hipStream_t; NULL = the device's default stream).
@@ -375,7 +396,8 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * returns, per kernel kind, the number of sampled launches and their mean duration in milliseconds since the last read
  * (kinds: 0 nbr_kernel -- always 0: the neighbour search is the head of step_kernel, with no launch of its own; the
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
- * duration / T --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
+ * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
+ * is three launches and its time three times the mean --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
  * launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
@@ -398,6 +420,9 @@ int ca_launch_info(ca_env* env, int32_t* block, int32_t* grid, int32_t* lds_byte
  * *rollout_one_launch = 1: ca_rollout(env, T, flags without CA_F_OBS) is ONE kernel launch that keeps every arena in
  * registers / LDS for its T steps (the four-lanes kernel; chosen up to 1024 waves inclusive); 0: it is T launches. */
 int ca_solver_info(ca_env* env, int32_t* lanes_per_agent, int32_t* rollout_one_launch);
+/* The tiled solve path of a handle made with CA_CREATE_TILED: *tiled = 1, *tile_agents = agents per workgroup, *tiles_per_arena =
+ * workgroups an arena spans, *launches_per_step = kernel launches of one solve (3).  All zeros on an ordinary handle. */
+int ca_tiled_info(ca_env* env, int32_t* tiled, int32_t* tile_agents, int32_t* tiles_per_arena, int32_t* launches_per_step);
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
 const char* ca_source_sha(void);
