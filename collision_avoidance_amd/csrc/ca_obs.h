@@ -10,12 +10,18 @@ namespace ca {
 //
 // A workgroup (256 lanes) owns 16 agents of ONE arena; 16 lanes per agent.  The arena's
 // positions/velocities are staged in LDS once (the neighbour gathers then never leave the CU).
+// The 16 lanes of an agent stage it and write its row; in between, work is dealt over the WORKGROUP, whichever
+// agent it belongs to (the agents' frames, list lengths and neighbour offsets are in LDS for that):
+// Pre-pass -- lane per agent NEIGHBOUR: the workgroup's first 16 K lanes (lane L: agent L / K, slot L % K) each
+//   turn one neighbour into its window of rays, so at K = 10 three waves run that body and the fourth skips it.
+//   An obstacle neighbour only becomes an (agent, edge slot) item of one list per workgroup.
 // Phase A -- lane per (source, ray) pair (8 octagon chords per ORCA agent neighbour, one segment per ORCA
-//   obstacle neighbour): the segment is rotated into the goal-aligned frame and tested only against the
-//   rays that can possibly reach it: the rays inside its angular span as seen from the origin (a
-//   conservative superset, see the pre-pass).  The (neighbour, ray) pairs of the workgroup's 16 agents
-//   form ONE list walked by all its lanes, so a wave takes a second trip only for what does not fit the
-//   whole workgroup.  The ray/segment test itself is the reference's arithmetic, so culling never
+//   obstacle neighbour): the segment is rotated into the goal-aligned frame; a neighbour is tested only against
+//   the rays inside its angular span as seen from the origin (a conservative superset, see the pre-pass), a
+//   wall item against all 16 rays, lane per (item, ray).  The (neighbour, ray) pairs of the workgroup's 16
+//   agents form ONE list walked by all its lanes, and so do the wall items: a wave takes a trip only for
+//   what the waves before it do not hold (a settled crowd has three wall items per workgroup: one wave, once).
+//   The ray/segment test itself is the reference's arithmetic, so neither culling nor dealing ever
 //   changes a result.  A hit is merged into the ray's slot with one LDS ds_min_u64 on the key
 //   (distance bits << 32 | segment index): the minimum distance wins and equal distances resolve
 //   to the first segment, exactly like a serial first-minimum scan.
@@ -64,14 +70,27 @@ struct ObsArgs {
 // The observation workgroup: OBS_BS lanes = OBS_BS/16 agents of ONE arena (template parameter: 256,
 // 512 or 1024 lanes, so that a workgroup can own a whole arena of up to 64 agents and stage it once).
 
+// The two dealings, each behind a switch for A/B builds (tools/ab_variants.sh; 0 = the per-agent form it replaced):
+// CA_OBS_DEAL_WINDOWS -- the neighbour windows of the pre-pass over the workgroup's first 16 K lanes;
+// CA_OBS_DEAL_WALLS -- the obstacle neighbours as one item list per workgroup, tested lane per (item, ray).
+#ifndef CA_OBS_DEAL_WINDOWS
+#define CA_OBS_DEAL_WINDOWS 1
+#endif
+#ifndef CA_OBS_DEAL_WALLS
+#define CA_OBS_DEAL_WALLS 1
+#endif
+
 // LDS (bytes): arena px,py,vx,vy [N] | keys [16][16] u64 | neighbour positions relative to the agent [16][16] float2 | agent frames [16] float4 | nb idx [16][16] | obstacle idx [16][16]
-//              | ray and octagon tables [64] | pair counts [2][16] | (source, ray) pairs [16 x 16 (K + S)] u16: the
-//              workgroup's (agent, neighbour, ray) list from the front, every agent's obstacle pairs in a block of its
-//              own from the back
+//              | ray and octagon tables [64] | counts [16]: [0] neighbour pairs, [1] wall items of the workgroup | agent-neighbour
+//              list lengths nn [16] | (source, ray) pairs [16 x 16 (K + S)] u16: the workgroup's (agent, neighbour, ray) list from
+//              the front, its (agent, edge slot) wall items in the last 16 S entries
+// (CA_OBS_DEAL_WALLS=0: the nn slots are the agents' obstacle pair counts, and every agent's obstacle pairs fill a block of its
+//  own from the back of the list; with CA_OBS_DEAL_WINDOWS=1 the nn then follow the list.)
 // (obw: staged obstacle ids per agent -- 16, or S in the wide instantiations, lists of 17 .. 64 edges)
 __host__ __device__ inline size_t obs_lds_bytes(int nstage_max, int obs_bs, int paircap, int obw = 16) {
     const size_t apb = obs_bs / 16;
-    return (size_t)nstage_max * 16 + 2 * apb * 16 * 8 + apb * 16 + apb * 16 * 4 + apb * (size_t)obw * 4 + 64 * 4 + 2 * apb * 4 + apb * (size_t)paircap * 2;
+    return (size_t)nstage_max * 16 + 2 * apb * 16 * 8 + apb * 16 + apb * 16 * 4 + apb * (size_t)obw * 4 + 64 * 4 + 2 * apb * 4 + apb * (size_t)paircap * 2 +
+           ((CA_OBS_DEAL_WINDOWS && !CA_OBS_DEAL_WALLS) ? apb * 4 : 0);
 }
 // the AgentParams instantiations: ... | the octagons of the agents' neighbours [16][16][8] float2 (64 B per neighbour slot), behind the
 // pair list rounded up to 16 bytes
@@ -144,7 +163,9 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // read sits in that XCD's L2 (C3: obs_kernel 62.2 -> 61.5 us).
     int bid = blockIdx.x;
     if (p.xcd) { const int x = bid & 7, idx = bid >> 3, q8 = idx / p.bpa; bid = (x + 8 * q8) * p.bpa + (idx - q8 * p.bpa); }
+    constexpr bool DEAL_WINDOWS = CA_OBS_DEAL_WINDOWS != 0, DEAL_WALLS = CA_OBS_DEAL_WALLS != 0;
     int a, i, a_lo, nstage;   // this group's arena and agent; first arena and number of agents the workgroup stages
+    int sbase;                // group 0's agent as an index of the staged arrays (GATHER: of the arena); group gw's is sbase + gw
     bool active;
     if constexpr (DENSE) {   // groups = consecutive agents of the batch
         const int first = bid * OBS_APB, gi = first + g;
@@ -152,12 +173,14 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         const int ga = active ? gi : p.A * N - 1;
         a = p.a0 + ga / N; i = ga - (ga / N) * N;
         a_lo = p.a0 + first / N;
+        sbase = first - (first / N) * N;
         const int last = min(first + OBS_APB - 1, p.A * N - 1);
         nstage = (last / N - first / N + 1) * N;
     } else {
         const int ab = bid / p.bpa;
         a = p.a0 + ab;
-        i = (bid - ab * p.bpa) * OBS_APB + g;
+        sbase = (bid - ab * p.bpa) * OBS_APB;
+        i = sbase + g;
         active = i < N;
         a_lo = a; nstage = N;
     }
@@ -168,7 +191,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // and no lane does 64-bit address arithmetic (it was 35 of the wave's ~575 vector instructions).
     const size_t aoff = (size_t)a * N;
     const unsigned ii = active ? (unsigned)i : 0u;
-    const ObstDev* tab = p.obst + (p.tab_off ? p.tab_off[a] : 0);  // this arena's edge table
+    const int toff = p.tab_off ? p.tab_off[a] : 0;  // this arena's edge table: staged obstacle ids are indices of p.obst, so that
+                                                    // a lane working on another group's edge needs nothing of that group's arena
 
     const int NST = p.nstage_max;   // agents staged at most (N; dense: up to 16 + 2 N)
     float* s_px = reinterpret_cast<float*>(smem4);
@@ -183,10 +207,13 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     const int OBW = WIDE ? S : 16;   // staged obstacle ids per agent
     float* s_rays = reinterpret_cast<float*>(s_ob + OBS_APB * OBW);  // [32] rays then [32] octagon
     float* s_oct = s_rays + 32;
-    int* s_cnt = reinterpret_cast<int*>(s_oct + 32);                       // [0]: neighbour pairs of the workgroup
-    int* s_cnt2 = s_cnt + OBS_APB;                                         // [16] obstacle pairs per agent
+    int* s_cnt = reinterpret_cast<int*>(s_oct + 32);                       // [0]: neighbour pairs, [1]: wall items of the workgroup
+    int* s_cnt2 = s_cnt + OBS_APB;                                         // [16] nn per agent (!DEAL_WALLS: obstacle pairs per agent)
     unsigned short* s_pair = reinterpret_cast<unsigned short*>(s_cnt2 + OBS_APB);  // [16 * paircap]
-    const int SPAIRS = 16 * S;  // an agent's block of obstacle pairs
+    const int SPAIRS = 16 * S;  // (!DEAL_WALLS) an agent's block of obstacle pairs
+    // wall item (agent group << 6 | edge slot): at most S per agent, behind the at most 16 K neighbour pairs per agent
+    unsigned short* s_item = s_pair + OBS_APB * PAIRCAP - OBS_APB * S;
+    int* s_nn = DEAL_WALLS ? s_cnt2 : reinterpret_cast<int*>(s_pair + OBS_APB * PAIRCAP);
     // (AP) vertex e of the octagon of neighbour slot k of agent g: s_noct[(g * 16 + k) * 8 + e]
     float2* s_noct = reinterpret_cast<float2*>(reinterpret_cast<char*>(smem4) + ((obs_lds_bytes(NST, OBS_BS, PAIRCAP) + 15) & ~(size_t)15));
     CA_OSTAMP(0);
@@ -221,8 +248,8 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             if constexpr (AC) { if (i >= p.agent_counts[a]) { nn = 0; ns = 0; } }   // an absent row: no sources, a row of zeros
             c = p.orient_x[q]; s = -p.orient_y[q];  // utils.py:48-51: cos/sin of -atan2(orientation)
             if (r < nn) s_nb[g * 16 + r] = abase + ld_idx_t<NW16>(p.nb_idx, ((size_t)a * K + r) * N + i);  // as an index of the staged arrays
-            if constexpr (WIDE) { for (int t = r; t < ns; t += 16) s_ob[g * OBW + t] = (int)p.obst_idx[((size_t)a * S + t) * N + i]; }
-            else if (r < ns) s_ob[g * 16 + r] = (int)p.obst_idx[((size_t)a * S + r) * N + i];
+            if constexpr (WIDE) { for (int t = r; t < ns; t += 16) s_ob[g * OBW + t] = toff + (int)p.obst_idx[((size_t)a * S + t) * N + i]; }
+            else if (r < ns) s_ob[g * 16 + r] = toff + (int)p.obst_idx[((size_t)a * S + r) * N + i];
         } else {
             const int cnts = (p.counts + aoff)[ii];
             nn = cnts & 0xFF; ns = cnts >> 8;
@@ -231,12 +258,19 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             const unsigned li = (unsigned)r * (unsigned)N + ii;     // inside the arena's [K][N] / [S][N] block: below 16 x 1024
             const char* nbase = (const char*)p.nb_idx + aoff * (size_t)K * (NW16 ? 2 : 1);
             if (r < nn) s_nb[g * 16 + r] = ld_idx_t<NW16>(nbase, li);  // as an index of the staged arrays (GATHER: of the arena)
-            if constexpr (WIDE) { for (unsigned t = (unsigned)r; t < (unsigned)ns; t += 16u) s_ob[g * OBW + t] = (int)(p.obst_idx + aoff * (size_t)S)[t * (unsigned)N + ii]; }
-            else if (r < ns) s_ob[g * 16 + r] = (int)(p.obst_idx + aoff * (size_t)S)[li];
+            if constexpr (WIDE) { for (unsigned t = (unsigned)r; t < (unsigned)ns; t += 16u) s_ob[g * OBW + t] = toff + (int)(p.obst_idx + aoff * (size_t)S)[t * (unsigned)N + ii]; }
+            else if (r < ns) s_ob[g * 16 + r] = toff + (int)(p.obst_idx + aoff * (size_t)S)[li];
         }
     }
     s_key[g * 16 + r] = ~0ull;
-    if (r == 0) { s_cnt[g] = 0; s_cnt2[g] = 0; }
+    // what a lane working for another group's agent needs of it: the frame's rotation and the list length now, the
+    // position (read from the staged arena) behind the barrier
+    if (r == 0) {
+        s_cnt[g] = 0;
+        if constexpr (!DEAL_WALLS) s_cnt2[g] = 0;
+        s_frame[g] = make_float4(c, s, 0.0f, 0.0f);
+        if constexpr (DEAL_WINDOWS || DEAL_WALLS) s_nn[g] = nn;
+    }
     CA_OSTAMP(1);
     __syncthreads();
     CA_OSTAMP(2);
@@ -244,7 +278,24 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     const int M = 8 * nn + ns;
     float mx = 0.0f, my = 0.0f;
     if (M > 0) { mx = GATHER ? gpx[i] : s_px[abase + i]; my = GATHER ? gpy[i] : s_py[abase + i]; }
-    if (r == 0) s_frame[g] = make_float4(c, s, mx, my);  // phase A lanes also work for the workgroup's other agents
+    if (r == 0) reinterpret_cast<float2*>(&s_frame[g])[1] = make_float2(mx, my);  // (read behind the next barrier only)
+    // Obstacle neighbours: every (agent, edge slot) becomes an item of the workgroup's list -- rank from the wave's ballot, ONE
+    // atomic per wave (list order is irrelevant, as for the pairs below).  A settled crowd has three items per workgroup
+    // (an agent in five has a wall in range), so phase A's wall loop is one trip of one wave instead of a trip of every
+    // wave that holds such an agent.
+    if constexpr (DEAL_WALLS) {
+        for (int t = r; ; t += 16) {
+            const bool has = t < ns;
+            const unsigned long long bal = __ballot(has);
+            if (bal == 0ull) break;
+            int base = 0;
+            if ((tid & 63) == 0) base = atomicAdd(&s_cnt[1], __popcll(bal));
+            base = __builtin_amdgcn_readfirstlane(base);
+            const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+            if (has) s_item[base + rank] = (unsigned short)((g << 6) | t);
+            if constexpr (!WIDE) break;   // (at most 16 obstacle neighbours: slot r of lane r)
+        }
+    }
     // ---- pre-pass: which (source, ray) pairs are worth the exact test?  Supersets only; never results. ----
     // (1) lane per agent NEIGHBOUR: all 8 octagon vertices lie on the circle of radius R around it, so the
     // rays within asin(R/d) of its direction are a superset for each of its 8 chords.  asin(t) <= t + t^3 / 6 +
@@ -252,11 +303,29 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // sums to c at t = 1): within 2e-3 rad of asin for t <= 1/2, i.e. for neighbours that do not overlap the agent.
     // The margin of 0.002 dial units = 7.8e-4 rad covers the dial's 1e-4 and the approximate reciprocal square root.
     // The pairs go to the workgroup's list at a position from the wave's prefix sum of the window widths and ONE atomic
-    // per wave (at most 16 neighbours, CA_MAX_NEIGHBORS, so lane r < nn of an agent owns neighbour slot r).
-    {
-        const int k = r;
+    // per wave.  The neighbour slots are dealt over the workgroup's first 16 K lanes: lane L works for slot L % K of agent
+    // group L / K, whose frame, list length and position it reads from LDS.  Lane r < nn of every agent owning slot r
+    // (at most 16 neighbours, CA_MAX_NEIGHBORS) would leave 6 of 16 lanes idle at K = 10 and send all four waves through
+    // this body for three waves' worth of slots; a wave without slots skips it whole (the prefix sum needs full waves).
+    // L / K for L < 1024, K <= 16 as a multiplication by floor(65536 / K) + 1.
+    static constexpr unsigned RCP_K[17] = {0, 65537, 32769, 21846, 16385, 13108, 10923, 9363, 8193, 7282, 6554, 5958, 5462, 5042, 4682, 4370, 4097};
+    if (!DEAL_WINDOWS || __builtin_amdgcn_readfirstlane(tid & ~63) < OBS_APB * K) {
+        int gw = g, k = r;           // the agent group and the neighbour slot this lane works for
+        bool live = r < nn;
+        float wc = c, ws = s, wmx = mx, wmy = my;
+        if constexpr (DEAL_WINDOWS) {
+            gw = (int)(((unsigned)tid * RCP_K[K]) >> 16); k = tid - gw * K;
+            live = tid < OBS_APB * K && k < s_nn[tid < OBS_APB * K ? gw : 0];
+            if (live) {
+                const float2 cs = *reinterpret_cast<const float2*>(&s_frame[gw]);
+                wc = cs.x; ws = cs.y;
+                wmx = GATHER ? gpx[sbase + gw] : s_px[sbase + gw]; wmy = GATHER ? gpy[sbase + gw] : s_py[sbase + gw];
+            }
+        }
+        const float c = wc, s = ws, mx = wmx, my = wmy;   // (of the agent worked for, from here to the end of the block)
+        const int g = gw;
         int i0 = 0, w = 0;
-        if (k < nn) {
+        if (live) {
             const int nb = s_nb[g * 16 + k];
             const float rx = (GATHER ? gpx[nb] : s_px[nb]) - mx, ry = (GATHER ? gpy[nb] : s_py[nb]) - my;
             s_rel[g * 16 + k] = make_float2(rx, ry);  // (env.py:288-289) for the pair trips and the winners
@@ -302,11 +371,13 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // separates the edge's end points and the crossing is not behind the origin, i.e. (up to rounding, covered
     // by tolE = 50x the error of these products) the two end points are not on the same side of the line and
     // not both behind.  Obstacle pairs fill the agent's block at the back of the list.
-    {
+    // (The per-agent form: with the walls dealt, an item meets all 16 rays in phase A and this filter, which could only
+    // save the wave a hit() that no lane of it accepts, is not run.)
+    if constexpr (!DEAL_WALLS) {
         const float dx = s_rays[2 * r], dy = s_rays[2 * r + 1];
         int cnt2 = 0;
         for (int sidx = 0; sidx < ns; ++sidx) {
-            const ObstDev o1 = load_obst(tab, s_ob[g * OBW + sidx]);
+            const ObstDev o1 = load_obst(p.obst, s_ob[g * OBW + sidx]);
             const float x1 = o1.px - mx, y1 = o1.py - my, x2 = o1.qx - mx, y2 = o1.qy - my;
             const float ax = c * x1 - s * y1, ay = s * x1 + c * y1;
             const float bx = c * x2 - s * y2, by = s * x2 + c * y2;
@@ -343,7 +414,7 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             }
             if (want_vel) { const int nb = s_nb[g * 16 + k]; vx = GATHER ? gvx[nb] : s_vx[nb]; vy = GATHER ? gvy[nb] : s_vy[nb]; }  // env.py:252
         } else {
-            const ObstDev o1 = load_obst(tab, s_ob[g * OBW + (m - 8 * nn)]);
+            const ObstDev o1 = load_obst(p.obst, s_ob[g * OBW + (m - 8 * nn)]);
             x1 = o1.px - mx; y1 = o1.py - my;
             x2 = o1.qx - mx; y2 = o1.qy - my;
         }
@@ -495,16 +566,40 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         }
         merge(ga, ray, best, best_m);
     }
-    const int no = s_cnt2[g];
-    for (int pi = r; pi < no; pi += 16) {
-        const int pr = s_pair[OBS_APB * PAIRCAP - 1 - (g * SPAIRS + pi)];
-        const int k = pr >> 4, ray = pr & 15;
-        const float s10x = s_rays[2 * ray] - 0.0f, s10y = s_rays[2 * ray + 1] - 0.0f;
-        SegGeom sg;
-        float dum0, dum1, d, hx, hy;
-        const int m = 8 * nn + (k - nn);
-        build(m, sg, dum0, dum1, false);
-        if (hit(sg, s10x, s10y, d, hx, hy)) merge(g, ray, d, m);
+    if constexpr (DEAL_WALLS) {
+        // lane per (wall item, ray) of the workgroup: the edge in the item's agent's frame -- build()'s expressions on that
+        // agent's (cos, sin, position), so build()'s values -- and the reference's test.  16 lanes per item and a stride
+        // that is a multiple of 16: a lane always takes its own ray r.
+        const int nlanes = 16 * s_cnt[1];
+        for (int t = tid; t < nlanes; t += OBS_BS) {
+            const int it = s_item[t >> 4];
+            const int ga = it >> 6, sl = it & 63;
+            const float4 fr = s_frame[ga];
+            const int m = 8 * s_nn[ga] + sl;
+            const ObstDev o1 = load_obst(p.obst, s_ob[ga * OBW + sl]);
+            const float x1 = o1.px - fr.z, y1 = o1.py - fr.w, x2 = o1.qx - fr.z, y2 = o1.qy - fr.w;
+            SegGeom sg;
+            sg.r1x = fr.x * x1 - fr.y * y1; sg.r1y = fr.y * x1 + fr.x * y1;  // utils.py:59
+            sg.r2x = fr.x * x2 - fr.y * y2; sg.r2y = fr.y * x2 + fr.x * y2;  // utils.py:60
+            sg.s32x = sg.r2x - sg.r1x; sg.s32y = sg.r2y - sg.r1y;
+            sg.s02x = 0.0f - sg.r1x; sg.s02y = 0.0f - sg.r1y;
+            sg.t_numer = sg.s32x * sg.s02y - sg.s32y * sg.s02x;
+            const float s10x = s_rays[2 * r] - 0.0f, s10y = s_rays[2 * r + 1] - 0.0f;
+            float d, hx, hy;
+            if (hit(sg, s10x, s10y, d, hx, hy)) merge(ga, r, d, m);
+        }
+    } else {
+        const int no = s_cnt2[g];
+        for (int pi = r; pi < no; pi += 16) {
+            const int pr = s_pair[OBS_APB * PAIRCAP - 1 - (g * SPAIRS + pi)];
+            const int k = pr >> 4, ray = pr & 15;
+            const float s10x = s_rays[2 * ray] - 0.0f, s10y = s_rays[2 * ray + 1] - 0.0f;
+            SegGeom sg;
+            float dum0, dum1, d, hx, hy;
+            const int m = 8 * nn + (k - nn);
+            build(m, sg, dum0, dum1, false);
+            if (hit(sg, s10x, s10y, d, hx, hy)) merge(g, ray, d, m);
+        }
     }
     CA_OSTAMP(5);
     __syncthreads();  // a ray's key takes hits from every wave of the workgroup
