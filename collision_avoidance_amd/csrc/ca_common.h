@@ -179,6 +179,18 @@ __device__ __forceinline__ bool arena_frozen(const StepArgs& p, int a) {
     return (p.flags & 16u) != 0 && a < p.a1 && p.arena_done[a] != 0;
 }
 
+// This arena's edge table: its first record, where it begins in p.obst, its edge count.  One table for every arena (tab_off null):
+// p.obst and p.n_obst.  A table per arena: arena a's slice of the offsets -- or, for a lane that has no arena to ask for
+// (have = false: a is out of range), offset 0 and no edge.
+struct ArenaEdges { const ObstDev* tab; int off, n; };
+__device__ __forceinline__ ArenaEdges arena_edges(const StepArgs& p, int a, bool have) {
+    ArenaEdges E;
+    E.off = (p.tab_off != nullptr && have) ? p.tab_off[a] : 0;
+    E.n = (p.tab_off != nullptr) ? (have ? p.tab_off[a + 1] - E.off : 0) : p.n_obst;
+    E.tab = p.obst + E.off;
+    return E;
+}
+
 // Orders the LDS traffic of ONE wave: LDS executes a wave's instructions in issue order, so lanes of
 // the same wave only need the compiler not to move accesses across this point and the earlier
 // operations to have been issued and returned (s_waitcnt lgkmcnt(0)).

@@ -374,7 +374,6 @@ static const void* quad_fn_for(const ca_env* e) {   // (K <= 10)
     if (e->SQ > 4) return e->KT == 5 ? quad_fn_for<5, 16, ALAN, PER...>(e->BSq) : quad_fn_for<10, 16, ALAN, PER...>(e->BSq);
     return e->KT == 5 ? quad_fn_for<5, 4, ALAN, PER...>(e->BSq) : quad_fn_for<10, 4, ALAN, PER...>(e->BSq);
 }
-// alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
 // the tiled path's first launch (ca_tiled.h): KMAX class x TILE
 template <int KMAX>
 static const void* tiled_fn_for(int TILE) {
@@ -384,6 +383,7 @@ static const void* tiled_fn_for(int TILE) {
         default: return fn_ptr(&tiled_solve_kernel<KMAX, 128>);
     }
 }
+// alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
 static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout) {
     if (e->tiled)   // (the first of the three launches of a step; no ALAN and no rollout form)
         return {e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE)),

@@ -26,10 +26,12 @@
 // operation order of SURVEY.md Appendix A.  The CPU oracle (oracle/) obeys the same contract, so
 // trajectories agree bit for bit.
 //
-// Files: ca_common.h (types, launch arguments), ca_lp.h (LP1/LP2/LP3), ca_lines.h (ORCA half-planes),
-// ca_nbr.h (neighbour search), ca_rules.h (the environment's per-agent rules: actions, reward, done test, goals, resets,
-// ALAN's draw and update), ca_step.h (solve + reset kernels), ca_alan.h (ALAN bandit kernels), ca_obs.h (laser
-// observation).
+// Files: ca_math.h (fp32 / fp64 primitives of the contract), ca_common.h (types, launch arguments, arena_edges),
+// ca_lp.h (LP1/LP2/LP3), ca_lines.h (ORCA half-planes; the `covered` test line_covers / table_covers),
+// ca_nbr.h (neighbour search; key_empty / key_dummy, edge_in_range), ca_rules.h (the environment's per-agent rules: actions,
+// reward, done test, goals, resets, the wall test and the pair count's shortcut, ALAN's draw and update), ca_step.h (lane solve +
+// reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
+// ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"

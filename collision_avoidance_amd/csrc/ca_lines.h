@@ -169,5 +169,17 @@ __device__ __forceinline__ bool obst_orca_line(const ObstDev* __restrict__ tab, 
     return ok;
 }
 
+// App. A.3 step 1, the test every `covered` is made of: the earlier obstacle line M already excludes both scaled end points c1, c2 of
+// an edge.  (The product stays where it is used: formed ahead, as an argument, it moved pair_kernel's instructions; ca_quad.h keeps its own form.)
+__device__ __forceinline__ bool line_covers(const Line& M, V2 c1, V2 c2, float invTO, float R) {
+    return det(c1 - M.point, M.dir) - invTO * R >= -EPS && det(c2 - M.point, M.dir) - invTO * R >= -EPS;
+}
+// ... against the first nl lines of a line table (the register-slot kernels wrap line_covers in a static_for over their slots)
+template <class Lines>
+__device__ __forceinline__ bool table_covers(const Lines& lines, int nl, V2 c1, V2 c2, float invTO, float R) {
+    for (int j = 0; j < nl; ++j)
+        if (line_covers(lines.get(j), c1, c2, invTO, R)) return true;
+    return false;
+}
 
 }  // namespace ca

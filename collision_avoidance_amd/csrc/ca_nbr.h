@@ -28,6 +28,9 @@ __device__ __forceinline__ double key_max(double a, double b) {
 __device__ __forceinline__ double make_key(float d, int idx) {
     return __longlong_as_double((long long)(((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx));
 }
+// the two keys that are no candidate: an empty slot (+inf, -1) sorts behind every candidate; a dummy slot (-inf) never moves
+__device__ __forceinline__ double key_empty() { return __longlong_as_double(0x7F800000FFFFFFFFll); }
+__device__ __forceinline__ double key_dummy() { return __longlong_as_double((long long)0xFFF0000000000000ull); }
 __device__ __forceinline__ float key_dist(double k) { return __uint_as_float((unsigned)((unsigned long long)__double_as_longlong(k) >> 32)); }
 __device__ __forceinline__ int key_index(double k) { return (int)(unsigned)(unsigned long long)__double_as_longlong(k); }
 __device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) {
@@ -40,6 +43,19 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
 #pragma unroll
     for (int k = MAXN - 1; k >= 1; --k) key[k] = key_max(key[k - 1], key_min(key[k], x));
     key[0] = key_min(key[0], x);
+}
+
+// App. A.2, the range test of the obstacle-neighbour list: the agent at pos is on the outer side of edge o1, within range of its line and -- only then
+// computed, into dsq -- of the segment.  `mine`: this lane really has such an edge (inside, and the statements in this order: the kernels' text depends on it).
+__device__ __forceinline__ bool edge_in_range(const ObstDev& o1, V2 pos, float rangeSq, bool mine, float& dsq) {
+    const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
+    const float alol = leftOf(a1, a2, pos);
+    const float dsl = div_ir(sqr(alol), absSq(a2 - a1));   // (an edge has a length; the quotient is only compared with the range)
+    if (mine && dsl < rangeSq && alol < 0.0f) {
+        dsq = distSqPointSegment(a1, a2, pos);
+        if (dsq < rangeSq) return true;
+    }
+    return false;
 }
 
 // ============================================================================================
@@ -94,11 +110,9 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     constexpr bool WIDE = SM > SMAX;
     constexpr int SR = WIDE ? 1 : SM;   // register slots of the list (wide: none, the list is in LDS)
     const int sofs = SR - S;  // the S-entry list is right-aligned in the register array
-    const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
-    const double KEY_DUMMY = __longlong_as_double((long long)0xFFF0000000000000ull);  // -inf: never moves
     double okey[SR];
 #pragma unroll
-    for (int k = 0; k < SR; ++k) okey[k] = (k < sofs) ? KEY_DUMMY : KEY_EMPTY;
+    for (int k = 0; k < SR; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
     int oin = 0;
     // (wide) the lane's column of the LDS list, ascending in slots [0, wcnt): a newcomer shifts the larger keys up by one slot;
     // on a full list the largest key falls off -- the newcomer itself, if it is that
@@ -131,25 +145,20 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             rangeSq = active ? sqr(cp->ap_time_horizon_obst[q] * cp->ap_max_speed[q] + cp->ap_radius[q]) : 0.0f;
         }
         auto visit = [&](const ObstDev& o1, int e, bool mine) __attribute__((always_inline)) {
-            const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
-            const float alol = leftOf(a1, a2, pos);
-            const float dsl = div_ir(sqr(alol), absSq(a2 - a1));   // (an edge has a length; the quotient is only compared with the range)
-            if (mine && dsl < rangeSq && alol < 0.0f) {
-                const float dsq = distSqPointSegment(a1, a2, pos);
-                if (dsq < rangeSq) {
-                    ++oin;
-                    if constexpr (WIDE) wide_insert(((unsigned long long)__float_as_uint(dsq) << 32) | (unsigned)e);
-                    else sorted_insert<SR>(okey, make_key(dsq, e));
-                }
+            float dsq;
+            if (edge_in_range(o1, pos, rangeSq, mine, dsq)) {
+                ++oin;
+                if constexpr (WIDE) wide_insert(((unsigned long long)__float_as_uint(dsq) << 32) | (unsigned)e);
+                else sorted_insert<SR>(okey, make_key(dsq, e));
             }
         };
         if (p.tab_off == nullptr) {  // one table for every arena: uniform loop, scalar loads of the edge records
             for (int e = 0; e < p.n_obst; ++e) visit(p.obst[e], e, active);
         } else {                     // a table per arena (several arenas may share this wave): ids are local to it
-            const int t0 = active ? p.tab_off[a] : 0, ne = active ? p.tab_off[a + 1] - t0 : 0;
-            for (int e = 0; __ballot(e < ne) != 0ull; ++e) {
-                const bool mine = e < ne;
-                visit(load_obst(p.obst, mine ? t0 + e : 0), e, mine);
+            const ArenaEdges E = arena_edges(p, a, active);
+            for (int e = 0; __ballot(e < E.n) != 0ull; ++e) {
+                const bool mine = e < E.n;
+                visit(load_obst(p.obst, mine ? E.off + e : 0), e, mine);
             }
         }
     }
@@ -172,7 +181,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     const int kofs = KMAX - K;  // the K-entry list is right-aligned in the register array
     double nkey[KMAX];
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? KEY_DUMMY : KEY_EMPTY;
+    for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? key_dummy() : key_empty();
     int ncnt = 0;
     bool scanned = false;
     if constexpr (BS >= 256) {
@@ -356,7 +365,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             ncnt = cnt;
 #pragma unroll
             for (int k = 0; k < KMAX; ++k)  // hand the indices over in the key array the store below reads
-                nkey[k] = (k < kofs) ? KEY_DUMMY : make_key(0.0f, (ck[k] == 0xFFFFFFFFu) ? -1 : (int)(ck[k] & lowmask));
+                nkey[k] = (k < kofs) ? key_dummy() : make_key(0.0f, (ck[k] == 0xFFFFFFFFu) ? -1 : (int)(ck[k] & lowmask));
             scanned = true;
         }
     }

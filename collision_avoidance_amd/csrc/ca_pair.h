@@ -282,30 +282,25 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
     V2 pf32 = mk(1.0f, 0.0f);
     CA_PSTAMP(2);
     // ---- obstacle neighbours (App. A.2): brute force over the edge table, both lanes alike ----
-    const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
-    const ObstDev* tab = p.obst + ((p.tab_off != nullptr && active) ? p.tab_off[a] : 0);  // this arena's edge table
+    // (this arena's edge table, written out; arena_edges below for the count only: held from here on it grew this kernel, asked here for the pointer it moved a compare)
+    const ObstDev* tab = p.obst + ((p.tab_off != nullptr && active) ? p.tab_off[a] : 0);
     double okey[ST];
 #pragma unroll
-    for (int k = 0; k < ST; ++k) okey[k] = KEY_EMPTY;
+    for (int k = 0; k < ST; ++k) okey[k] = key_empty();
     int oin = 0;
     {
         const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
         auto visit = [&](const ObstDev& o1, int e, bool mine) __attribute__((always_inline)) {
-            const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
-            const float alol = leftOf(a1, a2, pos);
-            const float dsl = div_ir(sqr(alol), absSq(a2 - a1));   // (an edge has a length; the quotient is only compared with the range)
-            if (mine && dsl < rangeSq && alol < 0.0f) {
-                const float dsq = distSqPointSegment(a1, a2, pos);
-                if (dsq < rangeSq) {
-                    ++oin;
-                    sorted_insert_n<ST>(okey, make_key(dsq, e));
-                }
+            float dsq;
+            if (edge_in_range(o1, pos, rangeSq, mine, dsq)) {
+                ++oin;
+                sorted_insert_n<ST>(okey, make_key(dsq, e));
             }
         };
         if (p.tab_off == nullptr) {  // one table for every arena: uniform loop, scalar loads of the edge records
             for (int e = 0; e < p.n_obst; ++e) visit(p.obst[e], e, active);
         } else {                     // a table per arena: ids are local to it
-            const int ne = active ? p.tab_off[a + 1] - p.tab_off[a] : 0;
+            const int ne = arena_edges(p, a, active).n;
             for (int e = 0; __ballot(e < ne) != 0ull; ++e) {
                 const bool mine = e < ne;
                 visit(load_obst(tab, mine ? e : 0), e, mine);
@@ -317,7 +312,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
     // ---- agent neighbours (App. A.2): the candidates of every cell row dealt to the two lanes alternately ----
     double nkey[M];
 #pragma unroll
-    for (int k = 0; k < M; ++k) nkey[k] = KEY_EMPTY;
+    for (int k = 0; k < M; ++k) nkey[k] = key_empty();
     {
         CA_PSTAMP(3);
         if (K > 0) {
@@ -371,7 +366,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
                     if (t < hi) { jn = s_sorted[t]; on = s_sxy[t]; }  // the next candidate is in flight during this one
                     const float dsq = absSq(pos - o);
                     const bool ok = j != i && dsq < rangeSq0;
-                    sorted_insert_n<KMAX>(nkey, ok ? make_key(dsq, j) : KEY_EMPTY);
+                    sorted_insert_n<KMAX>(nkey, ok ? make_key(dsq, j) : key_empty());
                 }
             }
             merge_with_partner<M, 0xB1>(nkey);   // both lanes: the KMAX smallest keys of the two lists, ascending
@@ -412,10 +407,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
                     bool c = false;
                     static_for<ST>([&](auto jc) __attribute__((always_inline)) {
                         constexpr int j = decltype(jc)::value;
-                        const Line Mj = unpack_line(OB[j]);
-                        if (j < no && det(c1 - Mj.point, Mj.dir) - invTO * R >= -EPS &&
-                            det(c2 - Mj.point, Mj.dir) - invTO * R >= -EPS)
-                            c = true;
+                        if (j < no && line_covers(unpack_line(OB[j]), c1, c2, invTO, R)) c = true;
                     });
                     return c;
                 };
@@ -519,12 +511,11 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
     int* red = s_red;  // [0] not-done agents, [1] pairs, [2] wall hits, [3] goals (cleared at the head of the kernel)
     __syncthreads();
 
-    if (p.flags & 2u) {  // CA_F_STATS: see ca_step.h for why K distances replace the scan of the arena
+    if (p.flags & 2u) {  // CA_F_STATS: see ca_rules.h pair_reach for why K distances replace the scan of the arena
         int pairs = 0;
         const float crSq = sqr(R + R);
-        // (2 m of ca_step.h's argument, m = the arena's largest speed of this step x dt, measured: a bound from max_speed is not safe)
-        const float m2 = 2.0002f * __builtin_sqrtf(__uint_as_float(s_vmax2)) * p.time_step;
-        bool scan_all = active && !(p.neighbor_dist >= R + R + m2);
+        const float m2 = pair_reach(s_vmax2, p.time_step);
+        bool scan_all = active && !(p.neighbor_dist >= R + R + m2);   // (lists_bound_pairs, written out as in ca_step.h)
         if (active && !scan_all) {
             float far2 = 0.0f;
             int jn[KH];  // this lane's list entries, read back (the lane wrote them itself): not kept in registers across the solve
@@ -543,7 +534,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
             });
             const float of = quad_xor<0xB1>(far2);
             far2 = of > far2 ? of : far2;
-            scan_all = (ncnt == K) && !(far2 > sqr(R + R + 2.0f * m2));
+            scan_all = list_misses_pairs(ncnt, K, far2, R, m2);
         }
         if (__ballot(scan_all) != 0ull && scan_all) {
             pairs = 0;
@@ -552,7 +543,7 @@ __global__ __launch_bounds__(2 * BS, 4) void pair_kernel(const StepArgs p) {
         }
         pairs = pair_sum(pairs);
         if (active) {
-            const bool wall = p.tab_off == nullptr ? touches_wall(p.obst, p.n_obst, pos, R) : touches_wall(tab, p.tab_off[a + 1] - p.tab_off[a], pos, R);
+            const bool wall = p.tab_off == nullptr ? touches_wall(p.obst, p.n_obst, pos, R) : touches_wall(tab, p.tab_off[a + 1] - p.tab_off[a], pos, R);   // (written out: see ca_step.h)
             if (h == 0) {
                 if (pairs) atomicAdd(&red[1], pairs);
                 if (wall) atomicAdd(&red[2], 1);

@@ -225,9 +225,10 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         epi = c.episode[a];
         rc = c.regoal_count[gq];
     }
+    // (this arena's edge table; written out: through ca_common.h arena_edges the text of the 16 kernels without ALAN moved)
     const int tab0 = (p.tab_off != nullptr && in_arena) ? p.tab_off[a] : 0;
     const int nedge = (p.tab_off != nullptr) ? (in_arena ? p.tab_off[a + 1] - tab0 : 0) : p.n_obst;
-    const ObstDev* tab = p.obst + tab0;  // this arena's edge table
+    const ObstDev* tab = p.obst + tab0;
     const float R = p.radius;
     const bool nodone = (p.flags & 8u) != 0;  // CA_F_NODONE
     // per-arena counters of the launch (meaningful in the lanes of agent 0), flushed once at the end
@@ -235,7 +236,6 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     unsigned long long lastep = 0;
     bool have_lastep = false;
     float ox = pref.x, oy = pref.y;
-    const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);  // (+inf, -1)
 
     int nA = 0, nk = 0, last_id = 0;
     float last_rew = 0.0f;
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         // ---- obstacle neighbours (App. A.2): edges e = q, q + 4, ... ----
         double okey[SQ];
 #pragma unroll
-        for (int k = 0; k < SQ; ++k) okey[k] = KEY_EMPTY;
+        for (int k = 0; k < SQ; ++k) okey[k] = key_empty();
         int oin = 0;
         {
             const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
@@ -300,11 +300,11 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                 const ObstDev o1 = load_obst(tab, mine ? e : 0);
                 const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
                 const float alol = leftOf(a1, a2, pos);
-                const float dsl = div_ir(sqr(alol), absSq(a2 - a1));   // (an edge has a length; the quotient is only compared with the range)
+                const float dsl = div_ir(sqr(alol), absSq(a2 - a1));   // (ca_nbr.h edge_in_range, branch-free: through the helper a vector instruction more)
                 const float dsq = distSqPointSegment(a1, a2, pos);
                 const bool in = mine && dsl < rangeSq && alol < 0.0f && dsq < rangeSq;
                 oin += in ? 1 : 0;
-                sorted_insert_n<SQ>(okey, in ? make_key(dsq, e) : KEY_EMPTY);
+                sorted_insert_n<SQ>(okey, in ? make_key(dsq, e) : key_empty());
             }
         }
         merge_quad<SQ>(okey);
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         // ---- agent neighbours (App. A.2): candidates j = q, q + 4, ... ----
         double nkey[M];
 #pragma unroll
-        for (int k = 0; k < M; ++k) nkey[k] = KEY_EMPTY;
+        for (int k = 0; k < M; ++k) nkey[k] = key_empty();
         if (K > 0) {
             const float rangeSq0 = sqr(p.neighbor_dist);
             const int trips = (N + 3) >> 2;
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                 if (tr + 1 < trips) { const int jn = (j + 4 < P) ? j + 4 : 0; o_next = mk(s_px[lbase + jn], s_py[lbase + jn]); }
                 const float dsq = absSq(pos - o);
                 const bool ok = active && j < N && j != i && dsq < rangeSq0;
-                sorted_insert_n<KMAX>(nkey, ok ? make_key(dsq, j) : KEY_EMPTY);
+                sorted_insert_n<KMAX>(nkey, ok ? make_key(dsq, j) : key_empty());
             }
             merge_quad<M>(nkey);
         }
@@ -380,10 +380,10 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                     if constexpr (r > 0) {
                         for (int j = 0; j < no; ++j) {
                             const Line Mj = ls.get(j);
-                            if (det(c1 - Mj.point, Mj.dir) - thr >= -EPS && det(c2 - Mj.point, Mj.dir) - thr >= -EPS) alive = 0;
+                            if (det(c1 - Mj.point, Mj.dir) - thr >= -EPS && det(c2 - Mj.point, Mj.dir) - thr >= -EPS) alive = 0;   // (ca_lines.h line_covers, written out: through it the branch became a select)
                         }
                     }
-                    // ... and those of the lanes before this one in this round, resolved in list order
+                    // ... and those of the lanes before this one in this round, resolved in list order (line_covers written out: through it the ALAN forms grew by an instruction)
                     bool cov0, cov1, cov2;
                     {
                         const V2 pt = mk(quad_bcast<0>(lpx), quad_bcast<0>(lpy)), dr = mk(quad_bcast<0>(ldx), quad_bcast<0>(ldy));

@@ -1,10 +1,11 @@
 // ca_rules.h -- the reference environment's per-agent rules, stated once for every kernel that applies them
 // Part of the HIP kernels of libcaenv.so (see ca_kernels.h for the overview and the numerics contract).
 //
-// The solve kernels (ca_step.h one lane, ca_pair.h two lanes, ca_quad.h four lanes per agent), the reset kernel and the
-// three-launch ALAN kernels (ca_alan.h) call these.  They work on values: what lane writes, barriers, LDS staging and the
-// reward sums stay in the kernels, and storage that differs by kernel (the softmax terms, the ALAN weights and times) is
-// reached through an accessor that returns a reference.  Every fp32 / fp64 operation is in the order the oracle uses.
+// Callers: the solve kernels -- ca_step.h (one lane per agent), ca_pair.h (two lanes), ca_quad.h (four lanes), ca_tiled.h (the tiled
+// path's three launches) --, the reset kernels (ca_step.h) and the three-launch ALAN kernels (ca_alan.h).  The rules work on values:
+// what lane writes, barriers, LDS staging and the reward sums stay in the kernels, and storage that differs by kernel (the softmax
+// terms, the ALAN weights and times, the lists of the pair count) is reached through an accessor or stays in the kernel's loop.
+// Every fp32 / fp64 operation is in the order the oracle uses.  (The solve's geometry: ca_lines.h, ca_nbr.h, ca_common.h arena_edges.)
 #pragma once
 #include "ca_common.h"
 
@@ -95,6 +96,25 @@ __device__ __forceinline__ bool touches_wall(const ObstDev* tab, int ne, V2 pos,
         if (distSqPointSegment(mk(o1.px, o1.py), mk(o1.qx, o1.qy), pos) < sqr(R)) wall = true;
     }
     return wall;
+}
+
+// SURVEY A20, the overlapping pairs (i < j, distance < 2 R after the step) counted through the neighbour lists instead of a scan of
+// the arena.  Nobody moves farther than m = the arena's largest speed of this step x dt (measured, not assumed: two agents that a
+// reset drops onto the same spot can leave the linear programs at hundreds of times max_speed -- the oracle does the same -- and a
+// bound of 1.01 max_speed dt then misses a pair: one in 2.8e7 agent-steps of the soak with auto-reset,
+// profiles/r04_soak_parity.txt), so an agent that overlaps this one now was within 2R + 2m of it when the neighbour list was built:
+// if the list is not full it holds every agent within neighbor_dist (>= 2R + 2m required), and if it is full and its farthest
+// member is still beyond 2R + 4m now, its K-th distance then was beyond 2R + 2m -- either way every candidate is in the list and K
+// distances replace the scan.  The kernels (ca_step.h above 64 agents, ca_pair.h, ca_tiled.h's close launch) keep their own loops
+// over their own storage: they measure far2, the largest squared distance to a list member now, and scan for the lanes that cannot
+// conclude.  One radius for all: the AgentParams instantiations scan.  m2 = 2 m, a hair wide for the rounding of the update
+// (vmax2: the largest squared speed as float bits; NaN / infinite speeds fail every test below: full scan)
+__device__ __forceinline__ float pair_reach(unsigned vmax2, float dt) { return 2.0002f * __builtin_sqrtf(__uint_as_float(vmax2)) * dt; }
+// the lists can bound the pairs at all: they reach as far as an agent that overlaps now was when they were built
+__device__ __forceinline__ bool lists_bound_pairs(float neighbor_dist, float R, float m2) { return neighbor_dist >= R + R + m2; }
+// this agent's list of ncnt members (capacity K) did not: it is full and its farthest member is not beyond 2R + 4m
+__device__ __forceinline__ bool list_misses_pairs(int ncnt, int K, float far2, float R, float m2) {
+    return (ncnt == K) && !(far2 > sqr(R + R + 2.0f * m2));
 }
 
 // the ST_LASTEP word of an ended episode: its steps, and how many agents reached their goal

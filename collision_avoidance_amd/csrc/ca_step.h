@@ -55,16 +55,10 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
     const float *ax = arena, *ay = arena + bs, *avx = arena + 2 * bs, *avy = arena + 3 * bs;  // the staged arena: px | py | vx | vy
     LdsLines ls; ls.base = tbl; ls.stride = TS;
     int nl = 0;
-    for (int s = 0; s < ocnt; ++s) {
+    for (int s = 0; s < ocnt; ++s) {   // (this loop again in ca_tiled.h and, reading ahead over S trips, below: one helper for the three moved the text of two)
         const int e = ld_idx_t<true>(oidx, (size_t)s * (size_t)stride);
         Line line;
-        auto covered = [&](V2 c1, V2 c2) {
-            for (int j = 0; j < nl; ++j) {
-                const Line M = ls.get(j);
-                if (det(c1 - M.point, M.dir) - invTO * R >= -EPS && det(c2 - M.point, M.dir) - invTO * R >= -EPS) return true;
-            }
-            return false;
-        };
+        auto covered = [&](V2 c1, V2 c2) { return table_covers(ls, nl, c1, c2, invTO, R); };
         if (obst_orca_line(tab, e, pos, vel, R, invTO, covered, line)) { ls.put(nl, line); ++nl; }
     }
     const int numObst = nl;
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     asm volatile("" : "+s"(nb_idx_s), "+s"(obst_idx_s));
     const int cnts = active ? (int)p.counts[q] : 0;
     const int ocnt = cnts >> 8, ncnt = cnts & 0xFF;
-    const ObstDev* tab = p.obst + ((p.tab_off != nullptr && active) ? p.tab_off[a] : 0);  // this arena's edge table
+    const ObstDev* tab = arena_edges(p, a, active).tab;  // this arena's edge table
 #if defined(CA_STAMPS) && CA_STAMPS == 3
     CA_STAMP_HWID();
 #else
@@ -235,10 +229,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
                         bool c = false;
                         static_for<ST>([&](auto jc) __attribute__((always_inline)) {
                             constexpr int j = decltype(jc)::value;
-                            const Line M = unpack_line(L[j]);
-                            if (j < no && det(c1 - M.point, M.dir) - invTO * R >= -EPS &&
-                                det(c2 - M.point, M.dir) - invTO * R >= -EPS)
-                                c = true;
+                            if (j < no && line_covers(unpack_line(L[j]), c1, c2, invTO, R)) c = true;
                         });
                         return c;
                     };
@@ -348,6 +339,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
                     const int rank = __popcll(om & below_o);
                     const bool mine = need_o && rank < GX;
                     if (mine) {
+                        // (written out, not arena_edges: through the helper the register allocation of these kernels, at the 128-VGPR limit, moved)
                         const ObstDev* tab_o = p.obst + (p.tab_off != nullptr ? p.tab_off[a_o] : 0);
                         solve_many_obstacles<CA_NBW16(BS), GX>((CA_AS(3) char*)(pool + rank), MLX, (const CA_AS(1) char*)tab_o,
                                                                (const CA_AS(1) char*)(obst_idx_s + (size_t)a_o * S * N + i_o),
@@ -384,18 +376,8 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
                 const int e = e_next;
                 if (s + 1 < ocnt) e_next = ld_idx_t<true>(obst_idx_s, ((size_t)a * S + (s + 1)) * N + i);
                 Line line;
-                auto covered = [&](V2 c1, V2 c2) {
-                    for (int j = 0; j < nl; ++j) {
-                        const Line M = ls.get(j);
-                        if (det(c1 - M.point, M.dir) - invTO * R >= -EPS && det(c2 - M.point, M.dir) - invTO * R >= -EPS)
-                            return true;
-                    }
-                    return false;
-                };
-                if (obst_orca_line(tab, e, pos, vel, R, invTO, covered, line)) {
-                    ls.put(nl, line);
-                    ++nl;
-                }
+                auto covered = [&](V2 c1, V2 c2) { return table_covers(ls, nl, c1, c2, invTO, R); };
+                if (obst_orca_line(tab, e, pos, vel, R, invTO, covered, line)) { ls.put(nl, line); ++nl; }
             }
         }
     }
@@ -453,7 +435,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // agents of the arena (AC: read again where the epilogue needs it, not kept across the solve; an idle lane never uses it)
     int NA = N;
     if constexpr (AC) NA = active ? c.agent_counts[a] : 1;
-    const ObstDev* tab = p.obst + ((p.tab_off != nullptr && active) ? p.tab_off[a] : 0);
+    const ObstDev* tab = arena_edges(p, a, active).tab;
     pf32 = mk(reinterpret_cast<float*>(s_misc)[tid * 4 + 0], reinterpret_cast<float*>(s_misc)[tid * 4 + 1]);
     if constexpr (PARK_PREF) pref = mk(reinterpret_cast<float*>(s_misc)[tid * 4 + 2], reinterpret_cast<float*>(s_misc)[tid * 4 + 3]);
     float rew_alan = 0.0f;
@@ -490,21 +472,14 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     int* red = s_misc + la * 4;  // per-arena: [0] not-done agents, [1] pairs, [2] wall hits, [3] goals
 
     if (p.flags & 2u) {  // CA_F_STATS
-        // Overlapping pairs (i < j, distance < 2R after the step).  Nobody moves farther than m = the arena's largest speed of
-        // this step x dt (measured, not assumed: two agents that a reset drops onto the same spot can leave the linear programs
-        // at hundreds of times max_speed -- the oracle does the same -- and a bound of 1.01 max_speed dt then misses a pair: one
-        // in 2.8e7 agent-steps of the soak with auto-reset, profiles/r04_soak_parity.txt),
-        // so an agent that overlaps this one now was within 2R + 2m of it when the neighbour list was built: if the
-        // list is not full it holds every agent within neighbor_dist (>= 2R + 2m required), and if it is full and
-        // its farthest member is still beyond 2R + 4m now, its K-th distance then was beyond 2R + 2m -- either way
-        // every candidate is in the list and K distances replace the scan of the arena (worth it above 64 agents:
-        // C5 80 -> 73 us).  A wave in which some lane cannot conclude that (a clump of more than K agents) scans the
-        // arena for those lanes.
+        // Overlapping pairs (i < j, distance < 2R after the step): through the neighbour lists where they bound them (ca_rules.h
+        // pair_reach; worth it above 64 agents: C5 80 -> 73 us).  A wave in which some lane cannot conclude that (a clump of more
+        // than K agents) scans the arena for those lanes.
         int pairs = 0;
         const float crSq = sqr(R + R);
-        float m2 = 0.0f;   // 2 m, a hair wide for the rounding of the update (NaN / infinite speeds fail every test below: full scan)
-        if constexpr (LISTP) m2 = 2.0002f * __builtin_sqrtf(__uint_as_float(s_vmax2)) * p.time_step;
-        bool scan_all = active && !(LISTP && p.neighbor_dist >= R + R + m2);
+        float m2 = 0.0f;
+        if constexpr (LISTP) m2 = pair_reach(s_vmax2, p.time_step);
+        bool scan_all = active && !(LISTP && p.neighbor_dist >= R + R + m2);   // (ca_rules.h lists_bound_pairs, written out: through it two operands of one scalar instruction changed places)
         if constexpr (LISTP) if (active && !scan_all) {
             float far2 = 0.0f;
             const int ncnt = (int)(p.counts[q] & 0xFFu);  // read again (this lane wrote it): not kept in a register across the solve
@@ -522,7 +497,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
                     if (j > i && d2 < crSq) ++pairs;
                 }
             });
-            scan_all = (ncnt == K) && !(far2 > sqr(R + R + 2.0f * m2));
+            scan_all = list_misses_pairs(ncnt, K, far2, R, m2);
         }
         if constexpr (AP) {
             // Mixed radii: a pair overlaps within sqr(r_i + r_j) (the oracle's arena_collisions), which the lists' shortcut above --
@@ -561,7 +536,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
         }
         if (active) {
             if (pairs) atomicAdd(&red[1], pairs);
-            // (one table for every arena: a loop of one trip count, the records through the argument pointer)
+            // (one table: one trip count, records through the argument pointer.  Written out here and in ca_pair.h: as an overload it moved an instruction of that loop)
             const bool wall = p.tab_off == nullptr ? touches_wall(p.obst, p.n_obst, pos, R) : touches_wall(tab, p.tab_off[a + 1] - p.tab_off[a], pos, R);
             if (wall) atomicAdd(&red[2], 1);
         }

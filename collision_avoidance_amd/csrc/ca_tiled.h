@@ -92,9 +92,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
         }
     }
 
-    // ---- obstacle neighbours (App. A.2; ca_nbr.h's visit and key) ----
-    const double KEY_EMPTY = __longlong_as_double(0x7F800000FFFFFFFFll);                // (+inf, -1)
-    const double KEY_DUMMY = __longlong_as_double((long long)0xFFF0000000000000ull);    // -inf: never moves
+    // ---- obstacle neighbours (App. A.2; ca_nbr.h's keys; its edge_in_range and ca_common.h arena_edges written out: through them this kernel's text moved) ----
     const ObstDev* tab = p.obst + ((p.tab_off != nullptr) ? p.tab_off[a] : 0);          // this arena's edge table
     const int n_edges = p.tab_off != nullptr ? p.tab_off[a + 1] - p.tab_off[a] : p.n_obst;
     int oin = 0;
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
         const int sofs = SMAX - S;   // the S-entry list is right-aligned in the register array
         double okey[SMAX];
 #pragma unroll
-        for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? KEY_DUMMY : KEY_EMPTY;
+        for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
         const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
         for (int e = 0; e < n_edges; ++e) {   // (uniform: scalar loads of the edge records)
             const ObstDev& o1 = tab[e];
@@ -130,7 +128,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
     const int kofs = KMAX - K;
     double nkey[KMAX];
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? KEY_DUMMY : KEY_EMPTY;
+    for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? key_dummy() : key_empty();
     int ncnt = 0;
     if (K > 0) {
         float rangeSq = sqr(p.neighbor_dist);
@@ -174,12 +172,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
             const int e = ld_idx_t<true>(p.obst_idx, ((size_t)a * S + s) * N + i);   // (this lane wrote it)
             Line line;
             auto covered = [&](V2 c1, V2 c2) {
-                for (int j = 0; j < nl; ++j) {
-                    const Line M = ls.get(j);
-                    if (det(c1 - M.point, M.dir) - invTO * R >= -EPS && det(c2 - M.point, M.dir) - invTO * R >= -EPS)
-                        return true;
-                }
-                return false;
+                return table_covers(ls, nl, c1, c2, invTO, R);
             };
             if (obst_orca_line(tab, e, pos, vel, R, invTO, covered, line)) {
                 ls.put(nl, line);
@@ -313,10 +306,10 @@ __global__ __launch_bounds__(256) void tiled_close_kernel(const TiledArgs t) {
         int pairs = 0;
         const float R = p.radius;
         const float crSq = sqr(R + R);
-        const float m2 = 2.0002f * __builtin_sqrtf(__uint_as_float(sc[TS_VMAX2])) * p.time_step;
+        const float m2 = pair_reach(sc[TS_VMAX2], p.time_step);
         V2 pos = mk(0.0f, 0.0f);
         if (active) pos = mk(t.nv_x[q], t.nv_y[q]);
-        bool scan_all = active && !(p.neighbor_dist >= R + R + m2);
+        bool scan_all = active && !lists_bound_pairs(p.neighbor_dist, R, m2);
         if (active && !scan_all) {
             float far2 = 0.0f;
             const int ncnt = (int)(p.counts[q] & 0xFFu);
@@ -326,7 +319,7 @@ __global__ __launch_bounds__(256) void tiled_close_kernel(const TiledArgs t) {
                 far2 = d2 > far2 ? d2 : far2;
                 if (j > i && d2 < crSq) ++pairs;
             }
-            scan_all = (ncnt == K) && !(far2 > sqr(R + R + 2.0f * m2));
+            scan_all = list_misses_pairs(ncnt, K, far2, R, m2);
         }
         if (__syncthreads_or(scan_all ? 1 : 0)) {   // (workgroup-uniform: the barriers below are met by every lane)
             if (scan_all) pairs = 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registers, scratch and code size of every kernel of libcaenv.so, read from the compiler's own metadata.
 
-  python tools/kernel_resources.py [--check] [--filter SUBSTR] [extra hipcc flags ...]
+  python tools/kernel_resources.py [--check] [--filter SUBSTR] [--against OTHER.s] [extra hipcc flags ...]
 
 Compiles collision_avoidance_amd/csrc/ca_env.hip for gfx950 with the product flags plus -save-temps into build/isa/
 (hipcc cross-compiles without a GPU), parses the `amdhsa.kernels` metadata of the device assembly and prints one row
@@ -9,6 +9,13 @@ per kernel: VGPRs, SGPRs, scratch bytes per lane (`.private_segment_fixed_size`)
 code bytes, vector-instruction count.  --check exits non-zero if a step / quad / observation kernel uses scratch: a
 spill at the 128-VGPR limit turns into HBM traffic (round 1: 19 MB per launch) and must not come back silently
 (tests/test_host_cpu.py runs this check when the assembly is already there).
+
+--against OTHER.s: the before / after table of a change that must not move the code.  OTHER.s is the device assembly of another
+tree (this tool's build/isa/*.s there, copied aside).  One row per function with both sets of figures (OTHER's first), and
+`identical` where the instruction text is the same after normalisation: comments and blank lines dropped, local labels numbered
+in order of appearance.  It counts and compares; --check then fails when a name is on one side only, when a kernel's VGPRs, SGPRs,
+scratch, spilled VGPRs or static LDS differ, when a function whose text differs has more vector instructions or code bytes than
+OTHER's, or when a hot kernel uses scratch (as without --against).
 """
 import os
 import re
@@ -64,6 +71,65 @@ def parse(asm_path=ASM):
     return rows
 
 
+def functions(asm_path):
+    """{symbol: normalised instruction text} of every function of the assembly file: comments and blank lines dropped, white space
+    collapsed, local labels (.LBB<function>_<block>, .Ltmp<n>, ...) renamed in order of appearance."""
+    text = open(asm_path).read()
+    out = {}
+    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
+        lines, labels = [], {}
+        for ln in m.group(2).splitlines():
+            ln = " ".join(ln.split(";", 1)[0].split())
+            if ln:
+                lines.append(ln)
+        body = "\n".join(lines)
+        for lab in re.findall(r"\.L\w+", body):
+            labels.setdefault(lab, ".L%d" % len(labels))
+        out[m.group(1)] = re.sub(r"\.L\w+", lambda mm: labels[mm.group(0)], body)
+    return out
+
+
+def short(name):
+    return name.replace("void ca::", "").replace("ca::", "").replace("(ca::StepArgs)", "").replace("(ca::ObsArgs)", "")
+
+
+FIGS = ("vgpr", "sgpr", "scratch", "vgpr_spill", "lds")   # what decides occupancy and scratch traffic: must not move
+
+
+def against(other, flt=None):
+    """Prints the before / after table; returns the number of rows that break the bars: a name on one side only, a figure of FIGS
+    moved, or differing text with more vector instructions or code bytes than the other side's."""
+    new_f, old_f = functions(ASM), functions(other)
+    new_k = {r["sym"]: r for r in parse(ASM)}
+    old_k = {r["sym"]: r for r in parse(other)}
+    syms = sorted(set(new_f) | set(old_f))
+    names = dict(zip(syms, (short(n) for n in demangle(syms))))
+    size = lambda body: len(re.findall(r"^v_", body, re.M))
+    bad = same = 0
+    print("%-52s %11s %11s %11s %9s %11s %15s %13s  %s" % ("function (other -> this)", "VGPR", "SGPR", "scratch", "v-spill", "LDS", "code B", "VALU", "text"))
+    for s in sorted(syms, key=lambda s: names[s]):
+        if flt and flt not in names[s]:
+            continue
+        if s not in new_f or s not in old_f:
+            print("%-52s only in %s" % (names[s][:52], "this tree" if s in new_f else "the other"))
+            bad += 1
+            continue
+        o, n = old_k.get(s), new_k.get(s)
+        pair = lambda k, w: ("%d -> %d" % (o[k], n[k])).rjust(w) if o and n else "-".rjust(w)
+        ident = new_f[s] == old_f[s]
+        same += ident
+        moved = bool(o and n) and any(o[k] != n[k] for k in FIGS)
+        grew = not ident and (size(new_f[s]) > size(old_f[s]) or bool(o and n) and n["code_bytes"] > o["code_bytes"])
+        bad += moved or grew
+        valu = ("%d -> %d" % (size(old_f[s]), size(new_f[s]))).rjust(13)
+        print("%-52s %s %s %s %s %s %s %s  %s" % (names[s][:52], pair("vgpr", 11), pair("sgpr", 11), pair("scratch", 11), pair("vgpr_spill", 9),
+                                                 pair("lds", 11), pair("code_bytes", 15), valu,
+                                                 "identical" if ident else ("differs, FIGURES MOVED" if moved else ("differs, GREW" if grew else "differs"))))
+    print("\n%d functions, %d with identical instruction text, %d differ; %d break a bar (a name on one side only; VGPRs / SGPRs / scratch / "
+          "spilled VGPRs / static LDS moved; differing text with more vector instructions or code bytes)" % (len(syms), same, len(syms) - same, bad))
+    return bad
+
+
 def by_design(name):
     """The LDS-line-table variant step_kernel<K, BS, 0, SMX, ...> keeps LP3's projected lines in a private array (ca_lp.h lp3:
     only the few lanes whose LP2 is infeasible touch it); every other hot kernel must run without scratch memory."""
@@ -91,8 +157,17 @@ def main():
     flt = None
     if "--filter" in args:
         flt = args[args.index("--filter") + 1]
-    extra = [a for a in args if a.startswith("-") and a not in ("--check", "--filter")]
+    other = args[args.index("--against") + 1] if "--against" in args else None
+    extra = [a for a in args if a.startswith("-") and a not in ("--check", "--filter", "--against")]
     ensure_asm(extra)
+    if other:
+        bad = against(other, flt)
+        spills = spilling(parse())
+        for r in spills:
+            print("hot-path kernel with scratch memory: %s: %d B per lane, %d VGPRs spilled" % (r["name"], r["scratch"], r["vgpr_spill"]))
+        if check and (bad or spills):
+            raise SystemExit(1)
+        return
     rows = parse()
     print("%-52s %5s %5s %8s %7s %7s %7s %9s %7s" % ("kernel", "VGPR", "SGPR", "scratch", "v-spill", "s-spill", "LDS", "code B", "VALU"))
     for r in sorted(rows, key=lambda r: r["name"]):
