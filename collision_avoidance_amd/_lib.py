@@ -12,6 +12,7 @@ OBS_DIM = 64
 MAX_NEIGHBORS, MAX_OBST_NEIGHBORS, MAX_AGENTS = 16, 64, 1024
 MAX_AGENTS_LARGE = 16384   # on a tiled handle (ca_create_ex with CREATE_TILED)
 CREATE_TILED = 1
+CREATE_TILED_GRID = 4   # only together with CREATE_TILED: the uniform-grid neighbour search of the tiled path
 DONE_XLESS, DONE_GOAL, DONE_REGOAL = 0, 1, 2
 F_OBS, F_STATS, F_AUTORESET, F_NODONE, F_FREEZE = 1, 2, 4, 8, 16
 SCN_CROWD, SCN_CIRCLE, SCN_DOORWAY, SCN_CONGESTED, SCN_INCOMING, SCN_BLOCKS, SCN_DEADLOCK, SCN_CROWD_SEPARATED = range(8)
@@ -28,7 +29,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_set_obstacles_per_arena", "ca_get_obstacles_arena", "ca_solver_info", "ca_source_sha", "ca_host_alloc", "ca_host_free",
            "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
            "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info",
-           "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info")
+           "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info")
 
 
 class Config(C.Structure):
@@ -77,6 +78,7 @@ def load():
     L.ca_create.argtypes = [C.POINTER(Config), C.c_int, vp, C.POINTER(vp)]
     L.ca_create_ex.argtypes = [C.POINTER(Config), u32, C.c_int, vp, C.POINTER(vp)]
     L.ca_tiled_info.argtypes = [vp] + [C.POINTER(i32)] * 4
+    L.ca_tiled_grid_info.argtypes = [vp] + [C.POINTER(i32)] * 3 + [C.POINTER(C.c_float), C.POINTER(i32)]
     L.ca_destroy.argtypes = [vp]
     L.ca_last_error.argtypes = [vp]
     L.ca_last_error.restype = C.c_char_p

@@ -115,6 +115,13 @@ struct ca_env {
     int TILE = 128, tiles = 1;
     float *nv_x = nullptr, *nv_y = nullptr;   // [A*N] new velocity, then the copy of the post-step position (ca_tiled.h TiledArgs)
     unsigned* tscr = nullptr;                 // [A][TS_STRIDE] per-arena scratch of the three launches
+    // ... with the uniform grid (CA_CREATE_TILED_GRID; ca_tiled.h TiledGridArgs): three launches of a counting sort in front of them
+    bool tgrid = false;
+    int tgx = 0, tgy = 0;                     // the wrapped cell table's sides: powers of two, 8 .. 128
+    float tcs = 0.0f, tics = 0.0f;            // cell size = neighbor_dist / 2, and its reciprocal
+    unsigned *tg_count = nullptr, *tg_start = nullptr, *tg_key = nullptr;   // [A][cells] | [A][cells + 1] | [A*N]
+    float *tg_sx = nullptr, *tg_sy = nullptr; // [A*N] positions in cell order
+    unsigned short* tg_sidx = nullptr;        // [A*N] agent ids in cell order
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -383,11 +390,24 @@ static const void* tiled_fn_for(int TILE) {
         default: return fn_ptr(&tiled_solve_kernel<KMAX, 128>);
     }
 }
+// ... and the solve launch of a grid handle (CA_CREATE_TILED_GRID)
+template <int KMAX>
+static const void* tiled_grid_fn_for(int TILE) {
+    switch (TILE) {
+        case 64: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 64>);
+        case 256: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 256>);
+        default: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 128>);
+    }
+}
+enum { TILED_SORT_LAUNCHES = 3 };   // bin, scan, scatter
+static const void* tiled_solve_fn(const ca_env* e) {
+    if (e->tgrid) return e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE));
+    return e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE));
+}
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
 static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout) {
-    if (e->tiled)   // (the first of the three launches of a step; no ALAN and no rollout form)
-        return {e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE)),
-                dim3(e->grid), dim3(e->TILE), e->lds};
+    if (e->tiled)   // (the solve launch of a step's sequence; no ALAN and no rollout form)
+        return {tiled_solve_fn(e), dim3(e->grid), dim3(e->TILE), e->lds};
     const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
     if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
         const void* f = per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e));
@@ -406,6 +426,30 @@ static hipError_t allow_lds(const SolveLaunch& s) {
 static hipError_t launch_step(ca_env* e, const StepArgs& a) {
     const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1);
     if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
+    if (e->tiled && e->tgrid) {   // bin -> scan -> scatter -> solve -> advance -> close (ca_tiled.h)
+        TiledGridArgs ga;
+        ga.s = a; ga.nv_x = e->nv_x; ga.nv_y = e->nv_y; ga.scr = e->tscr; ga.tiles = e->tiles;
+        ga.cell_count = e->tg_count; ga.cell_start = e->tg_start; ga.key = e->tg_key;
+        ga.sx = e->tg_sx; ga.sy = e->tg_sy; ga.sidx = e->tg_sidx;
+        ga.gx = e->tgx; ga.gy = e->tgy; ga.ics = e->tics;
+        TiledArgs ta = ga;   // (the advance and close launches take the plain arguments)
+        void* gparams[] = {&ga};
+        void* params[] = {&ta};
+        struct { const void* fn; dim3 grid, block; size_t lds; void** args; } seq[TILED_SORT_LAUNCHES + 3] = {
+            {fn_ptr(&tiled_bin_kernel), s.grid, s.block, 0, gparams},
+            {fn_ptr(&tiled_scan_kernel), dim3(e->cfg.n_arenas), dim3(1024), 0, gparams},
+            {fn_ptr(&tiled_scatter_kernel), s.grid, s.block, 0, gparams},
+            {s.fn, s.grid, s.block, s.lds, gparams},
+            {fn_ptr(&tiled_advance_kernel), s.grid, s.block, 0, params},
+            {fn_ptr(&tiled_close_kernel), s.grid, s.block, (size_t)e->TILE * 8, params}};
+        for (const auto& k : seq) {   // (each launch timed on its own dispatch, kind 1)
+            ProfScope ps(e, KIND_STEP);
+            const hipError_t r = ps.t0 ? hipExtLaunchKernel(k.fn, k.grid, k.block, k.args, k.lds, e->stream, ps.t0, ps.t1, 0)
+                                       : hipLaunchKernel(k.fn, k.grid, k.block, k.args, k.lds, e->stream);
+            if (r != hipSuccess) return r;
+        }
+        return hipSuccess;
+    }
     if (e->tiled) {   // solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
         TiledArgs ta;
         ta.s = a; ta.nv_x = e->nv_x; ta.nv_y = e->nv_y; ta.scr = e->tscr; ta.tiles = e->tiles;
@@ -707,8 +751,13 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) { re
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out) {
     if (!cfg || !out) return fail(nullptr, CA_EINVAL, "ca_create: null argument");
     *out = nullptr;
-    if (create_flags & ~CA_CREATE_TILED) return fail(nullptr, CA_EINVAL, "ca_create_ex: unknown create_flags 0x%x", create_flags);
+    if (create_flags & ~(CA_CREATE_TILED | CA_CREATE_TILED_GRID))
+        return fail(nullptr, CA_EINVAL, "ca_create_ex: unknown create_flags 0x%x", create_flags);
     const bool tiled = (create_flags & CA_CREATE_TILED) != 0;
+    const bool tgrid = (create_flags & CA_CREATE_TILED_GRID) != 0;
+    if (tgrid && !tiled)
+        return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_GRID (create_flags 0x%x) without CA_CREATE_TILED: the uniform grid "
+                    "is the tiled path's neighbour search", create_flags);
     const int max_agents = tiled ? CA_MAX_AGENTS_LARGE : CA_MAX_AGENTS;
     if (cfg->n_arenas <= 0 || cfg->n_agents <= 0 || cfg->n_agents > max_agents)
         return fail(nullptr, CA_ERANGE, "ca_create: n_arenas=%d n_agents=%d out of range (agents 1..%d)",
@@ -761,6 +810,19 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         const int want = v ? atoi(v) : 0;
         e->TILE = (want == 64 || want == 256) ? want : 128;
         e->tiles = (cfg->n_agents + e->TILE - 1) / e->TILE;
+    }
+    e->tgrid = tgrid;
+    if (tgrid) {   // the cell table: g x g cells, g the power of two with n_agents / 2 <= g^2 (about one agent per cell where the arena
+                   // is as wide as the table), 8 <= g <= 128: the scan launch sums 128 x 128 cells in one workgroup.
+                   // CA_TILED_CELLS = 8 | 16 | 32 | 64 | 128 (diagnostic switch, tests): that side; anything else: the rule
+        int g = 8;
+        while (g < 128 && 2 * g * g < cfg->n_agents) g <<= 1;
+        const char* v = getenv("CA_TILED_CELLS");
+        const int want = v ? atoi(v) : 0;
+        if (want == 8 || want == 16 || want == 32 || want == 64 || want == 128) g = want;
+        e->tgx = e->tgy = g;
+        e->tcs = 0.5f * cfg->neighbor_dist;
+        e->tics = 1.0f / e->tcs;
     }
     // launch geometry: P lanes per arena (power of two >= N), one or more whole arenas per block
     int P = 1, logP = 0;
@@ -858,6 +920,15 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         if (r == hipSuccess) r = dalloc(e, &e->nv_y, an);
         if (r == hipSuccess) r = dalloc(e, &e->tscr, A * (size_t)TS_STRIDE);
     }
+    if (tgrid) {   // (all zero-filled: the counts must be, and the sorted arrays hold ids below n_agents from the first step on)
+        const size_t cells = (size_t)e->tgx * e->tgy;
+        if (r == hipSuccess) r = dalloc(e, &e->tg_count, A * cells);
+        if (r == hipSuccess) r = dalloc(e, &e->tg_start, A * (cells + 1));
+        if (r == hipSuccess) r = dalloc(e, &e->tg_key, an);
+        if (r == hipSuccess) r = dalloc(e, &e->tg_sx, an);
+        if (r == hipSuccess) r = dalloc(e, &e->tg_sy, an);
+        if (r == hipSuccess) r = dalloc(e, &e->tg_sidx, an);
+    }
     e->nidx16 = (tiled || CA_NBW16(e->BS)) ? 1 : 0;  // u8 indices address 256 agents (BS = max(64, pow2 >= N): the kernels' compile-time test)
     if (r == hipSuccess) r = dalloc(e, &e->counts, an);
     if (r == hipSuccess) r = dalloc(e, reinterpret_cast<unsigned char**>(&e->nb_idx),
@@ -916,7 +987,7 @@ int ca_destroy(ca_env* e) {
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
-                    e->nv_x, e->nv_y, e->tscr};
+                    e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -2233,7 +2304,7 @@ int ca_launch_info(ca_env* e, int32_t* block, int32_t* grid, int32_t* lds_bytes,
     const SolveLaunch s = solve_launch(e, false, false);   // (what a plain ca_step launches)
     if (block) *block = (int32_t)s.block.x;
     if (grid) *grid = (int32_t)s.grid.x;
-    if (lds_bytes) *lds_bytes = (int32_t)s.lds;
+    if (lds_bytes) *lds_bytes = e->tgrid ? 0 : (int32_t)s.lds;   // (a grid handle: the bin launch, the solve launch's geometry without its LDS)
     if (obs_grid) {
         const int apb = obs_block_threads(e->cfg.n_agents) / 16;
         *obs_grid = obs_dense(e) ? (int32_t)(((size_t)e->cfg.n_arenas * e->cfg.n_agents + apb - 1) / apb)
@@ -2259,7 +2330,17 @@ int ca_tiled_info(ca_env* e, int32_t* tiled, int32_t* tile_agents, int32_t* tile
     if (tiled) *tiled = e->tiled ? 1 : 0;
     if (tile_agents) *tile_agents = e->tiled ? e->TILE : 0;
     if (tiles_per_arena) *tiles_per_arena = e->tiled ? e->tiles : 0;
-    if (launches_per_step) *launches_per_step = e->tiled ? 3 : 0;
+    if (launches_per_step) *launches_per_step = e->tiled ? (e->tgrid ? TILED_SORT_LAUNCHES + 3 : 3) : 0;
+    return CA_OK;
+}
+
+int ca_tiled_grid_info(ca_env* e, int32_t* grid, int32_t* cells_x, int32_t* cells_y, float* cell_size, int32_t* sort_launches) {
+    if (!e) return CA_EINVAL;
+    if (grid) *grid = e->tgrid ? 1 : 0;
+    if (cells_x) *cells_x = e->tgrid ? e->tgx : 0;
+    if (cells_y) *cells_y = e->tgrid ? e->tgy : 0;
+    if (cell_size) *cell_size = e->tgrid ? e->tcs : 0.0f;
+    if (sort_launches) *sort_launches = e->tgrid ? TILED_SORT_LAUNCHES : 0;
     return CA_OK;
 }
 

@@ -53,152 +53,116 @@ __host__ __device__ inline size_t tiled_lds_bytes(int TILE, int K, int S) { retu
 __device__ __forceinline__ int tiled_steps_arrive(int steps0, bool actions, bool nodone) { return steps0 + ((!actions && !nodone) ? 1 : 0); }
 __device__ __forceinline__ int tiled_steps_after(int steps0, bool actions, bool nodone) { return steps0 + ((actions || !nodone) ? 1 : 0); }
 
+// ---- the uniform grid of a handle made with CA_CREATE_TILED_GRID ----------------------------------------------------------------
+// The solve launch above tests every agent of the arena against every other.  A grid handle sorts the arena's agents by cell first
+// -- a counting sort that crosses workgroups, so its phases are launches too -- and the solve launch tests only the cells an agent's
+// range touches.  A step is then
+//   tiled_bin_kernel      one lane per agent: its bucket, and its rank in the bucket by an integer atomic on the arena's cell counts
+//                         (zero when the launch starts);
+//   tiled_scan_kernel     one workgroup per arena: the exclusive prefix sum of the counts into cell_start[cells + 1], and the counts
+//                         back to zero -- this workgroup is their only reader after the bin launch, and the next bin launch is a
+//                         kernel boundary away;
+//   tiled_scatter_kernel  one lane per agent: its PRE-step position and its id into slot cell_start[bucket] + rank of sx / sy / sidx;
+//   tiled_grid_solve_kernel<KMAX, TILE>, tiled_advance_kernel, tiled_close_kernel.
+// The table is fixed and wrapped: cell c(v) = floor(v * ics) of a coordinate, bucket (c(y) & (GY - 1)) * GX + (c(x) & (GX - 1)), GX and
+// GY powers of two.  No bounding box (it would be one more arena-wide reduction, one more launch): wrapping only aliases far cells
+// into near ones, and an aliased stranger fails the distance test.  The mask keeps every index inside the table whatever the
+// position arrays hold.  The order inside a cell comes from the atomics and differs from run to run; the lists do not depend on it
+// (tiled_solve_body).  Frozen arenas (CA_F_FREEZE) are skipped by all three: arena_done was last written by the close launch of
+// the step before, which is complete.
+struct TiledGridArgs : TiledArgs {
+    unsigned* cell_count;        // [A][cells]: zero between steps
+    unsigned* cell_start;        // [A][cells + 1]
+    unsigned* key;               // [A*N] bucket << 16 | rank in the bucket (both below 2^14)
+    float *sx, *sy;              // [A*N] the arena's pre-step positions in cell order
+    unsigned short* sidx;        // [A*N] ... and whose they are
+    int gx, gy;                  // the table's sides: powers of two, 8 .. 128
+    float ics;                   // 1 / cell size, computed once by the host
+};
+
+// the unwrapped cell coordinate: monotone in v (a product with a positive constant, floor, and a clamp that also gives NaN a value),
+// which is all the choice of cells below needs
+__device__ __forceinline__ int grid_cell(float v, float ics) {
+    return (int)fminf(fmaxf(floorf(v * ics), -1073741824.0f), 1073741824.0f);
+}
+
+__global__ __launch_bounds__(256) void tiled_bin_kernel(const TiledGridArgs t) {
+    const StepArgs& p = t.s;
+    const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
+    const int i = tile * (int)blockDim.x + (int)threadIdx.x;
+    if (i >= p.N || arena_frozen(p, a)) return;
+    const size_t q = (size_t)a * p.N + i;
+    const int bucket = (grid_cell(p.pos_y[q], t.ics) & (t.gy - 1)) * t.gx + (grid_cell(p.pos_x[q], t.ics) & (t.gx - 1));
+    const unsigned rank = atomicAdd(&t.cell_count[(size_t)a * (t.gx * t.gy) + bucket], 1u);
+    t.key[q] = ((unsigned)bucket << 16) | (rank & 0xFFFFu);
+}
+
+// (1024 lanes, one workgroup per arena: at most 128 x 128 cells, 16 consecutive cells per lane)
+__global__ __launch_bounds__(1024) void tiled_scan_kernel(const TiledGridArgs t) {
+    const StepArgs& p = t.s;
+    __shared__ unsigned s_wave[16];
+    const int a = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (arena_frozen(p, a)) return;   // (the whole workgroup)
+    const int cells = t.gx * t.gy;
+    const int cpl = (cells + 1023) >> 10;
+    unsigned* cnt = t.cell_count + (size_t)a * cells;
+    unsigned* start = t.cell_start + (size_t)a * (cells + 1);
+    const int c0 = tid * cpl;
+    unsigned sum = 0u;
+    for (int k = 0; k < cpl; ++k) sum += (c0 + k < cells) ? cnt[c0 + k] : 0u;
+    unsigned incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned v = __shfl_up(incl, off, 64);
+        if ((tid & 63) >= off) incl += v;
+    }
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    unsigned b = incl - sum;
+    for (int w = 0; w < (tid >> 6); ++w) b += s_wave[w];
+    for (int k = 0; k < cpl; ++k) {
+        if (c0 + k < cells) {
+            const unsigned c = cnt[c0 + k];
+            start[c0 + k] = b;
+            b += c;
+            cnt[c0 + k] = 0u;
+        }
+    }
+    if (tid == 1023) start[cells] = b;
+}
+
+__global__ __launch_bounds__(256) void tiled_scatter_kernel(const TiledGridArgs t) {
+    const StepArgs& p = t.s;
+    const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
+    const int i = tile * (int)blockDim.x + (int)threadIdx.x;
+    if (i >= p.N || arena_frozen(p, a)) return;
+    const size_t abase = (size_t)a * p.N;
+    const unsigned k = t.key[abase + i];
+    const unsigned bucket = min(k >> 16, (unsigned)(t.gx * t.gy - 1));
+    const unsigned dst = t.cell_start[(size_t)a * (t.gx * t.gy + 1) + bucket] + (k & 0xFFFFu);
+    if (dst < (unsigned)p.N) {   // (always, on consistent counts: the guard keeps a step that follows a failed launch inside the arrays)
+        t.sx[abase + dst] = p.pos_x[abase + i];
+        t.sy[abase + dst] = p.pos_y[abase + i];
+        t.sidx[abase + dst] = (unsigned short)i;
+    }
+}
+
 // ---- launch 1: neighbour search, ORCA lines, LP2 / LP3 ------------------------------------------------------------------------
+// The solve launch has two kernels with one body (ca_tiled_solve.inl).
+// Grid (tiled_grid_solve_kernel, a handle made with CA_CREATE_TILED_GRID): lane tile * TILE + tid works for SORTED POSITION s of the
+// arena, its agent is i = sidx[s] -- the lanes of a wave then stand in the same few cells and walk the same runs -- and everything
+// else addresses by i as before.
 template <int KMAX, int TILE>
 __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
-    const StepArgs& p = t.s;
-    extern __shared__ float4 smem4[];
-    const int tid = threadIdx.x;
-    const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
-    const int N = p.N, K = p.K, S = p.S;
-    const int i = tile * TILE + tid;
-    const bool frozen = arena_frozen(p, a);   // (the whole workgroup: one arena)
-    if (tile == 0 && tid == 0) {
-        unsigned* sc = t.scr + (size_t)a * TS_STRIDE;
-        sc[TS_NOTDONE] = 0u; sc[TS_VMAX2] = 0u; sc[TS_LIVE] = frozen ? 0u : 1u;
-        sc[TS_STEPS0] = (unsigned)p.cold->step_count[a]; sc[TS_EPI] = (unsigned)p.cold->episode[a];
-        if (frozen) p.arena_stats[(size_t)a * ST_STRIDE + ST_FROZEN] += 1;
-    }
-    if (frozen) return;
-    const bool active = i < N;
-    const size_t abase = (size_t)a * N;
-    const size_t q = abase + (active ? i : 0);
-
-    float4* s_lines = smem4;                                                   // [(K + S)][TILE]
-    float* s_px = reinterpret_cast<float*>(smem4 + (size_t)(K + S) * TILE);    // the candidate tile
-    float* s_py = s_px + TILE;
-    LdsLines ls; ls.base = s_lines + tid; ls.stride = TILE;
-
-    // ---- own state, preferred velocity (step_kernel's prologue) ----
-    V2 pos = mk(0.0f, 0.0f), vel = mk(0.0f, 0.0f), pref = mk(0.0f, 0.0f);
-    if (active) {
-        pos = mk(p.pos_x[q], p.pos_y[q]);
-        vel = mk(p.vel_x[q], p.vel_y[q]);
-        if (p.actions) {
-            V2 pf32;
-            action_pref(pos, p.goal_x[q], p.goal_y[q], p.actions[q], pf32, pref);
-        } else {
-            pref = mk(p.pref_x[q], p.pref_y[q]);
-        }
-    }
-
-    // ---- obstacle neighbours (App. A.2; ca_nbr.h's keys; its edge_in_range and ca_common.h arena_edges written out: through them this kernel's text moved) ----
-    const ObstDev* tab = p.obst + ((p.tab_off != nullptr) ? p.tab_off[a] : 0);          // this arena's edge table
-    const int n_edges = p.tab_off != nullptr ? p.tab_off[a + 1] - p.tab_off[a] : p.n_obst;
-    int oin = 0;
-    {
-        const int sofs = SMAX - S;   // the S-entry list is right-aligned in the register array
-        double okey[SMAX];
-#pragma unroll
-        for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
-        const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
-        for (int e = 0; e < n_edges; ++e) {   // (uniform: scalar loads of the edge records)
-            const ObstDev& o1 = tab[e];
-            const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
-            const float alol = leftOf(a1, a2, pos);
-            const float dsl = div_ir(sqr(alol), absSq(a2 - a1));
-            if (active && dsl < rangeSq && alol < 0.0f) {
-                const float dsq = distSqPointSegment(a1, a2, pos);
-                if (dsq < rangeSq) {
-                    ++oin;
-                    sorted_insert<SMAX>(okey, make_key(dsq, e));
-                }
-            }
-        }
-        if (active) {
-#pragma unroll
-            for (int k = 0; k < SMAX; ++k)
-                if (k >= sofs) p.obst_idx[((size_t)a * S + (k - sofs)) * N + i] = (unsigned short)key_index(okey[k]);
-        }
-    }
-    const int ocnt = oin < S ? oin : S;
-
-    // ---- agent neighbours: the K smallest (distance, index) keys below neighbor_dist^2, candidates in index order, a tile at a time
-    // through LDS -- the oracle's scan, so the shrinking range is its strict one ----
-    const int kofs = KMAX - K;
-    double nkey[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? key_dummy() : key_empty();
-    int ncnt = 0;
-    if (K > 0) {
-        float rangeSq = sqr(p.neighbor_dist);
-        for (int ct = 0; ct < t.tiles; ++ct) {
-            const int j0 = ct * TILE;
-            const int nj = min(TILE, N - j0);
-            __syncthreads();   // (the previous tile has been read by every lane)
-            if (tid < nj) { s_px[tid] = p.pos_x[abase + j0 + tid]; s_py[tid] = p.pos_y[abase + j0 + tid]; }
-            __syncthreads();
-            V2 o_next = mk(s_px[0], s_py[0]);
-            for (int jj = 0; jj < nj; ++jj) {
-                const V2 o = o_next;   // the next candidate's position is in flight while this one is inserted
-                if (jj + 1 < nj) o_next = mk(s_px[jj + 1], s_py[jj + 1]);
-                const int j = j0 + jj;
-                const float dsq = absSq(pos - o);
-                if (active && j != i && dsq < rangeSq) {
-                    sorted_insert<KMAX>(nkey, make_key(dsq, j));
-                    if (ncnt < K) ++ncnt;
-                    if (ncnt == K) rangeSq = key_dist(nkey[KMAX - 1]);
-                }
-            }
-        }
-    }
-    if (active) {
-        if (__builtin_expect(oin > S, 0)) {
-            atomicAdd(reinterpret_cast<int*>(&p.arena_stats[(size_t)a * ST_STRIDE + ST_OVERFLOW]), 1);
-            note_overflow_tiled(p.cold, a, i, oin);
-        }
-        p.counts[q] = (unsigned short)(ncnt | (ocnt << 8));
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k)
-            if (k >= kofs) st_idx_t<true>(p.nb_idx, ((size_t)a * K + (k - kofs)) * N + i, key_index(nkey[k]));
-    }
-
-    // ---- ORCA lines into the LDS table (step_kernel's LDS-table path; the neighbours' state gathered from global memory) ----
-    int nl = 0;
-    {
-        const float invTO = 1.0f / p.time_horizon_obst;
-        const float R = p.radius;
-        for (int s = 0; s < ocnt; ++s) {
-            const int e = ld_idx_t<true>(p.obst_idx, ((size_t)a * S + s) * N + i);   // (this lane wrote it)
-            Line line;
-            auto covered = [&](V2 c1, V2 c2) {
-                return table_covers(ls, nl, c1, c2, invTO, R);
-            };
-            if (obst_orca_line(tab, e, pos, vel, R, invTO, covered, line)) {
-                ls.put(nl, line);
-                ++nl;
-            }
-        }
-    }
-    const int numObstLines = nl;
-    {
-        const float invT = 1.0f / p.time_horizon;
-        const float invDt = 1.0f / p.time_step;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-            if (k >= kofs && k - kofs < ncnt) {
-                const size_t j = abase + (size_t)key_index(nkey[k]);
-                ls.put(nl, agent_orca_line(pos, vel, mk(p.pos_x[j], p.pos_y[j]), mk(p.vel_x[j], p.vel_y[j]), p.radius, invT, invDt));
-                ++nl;
-            }
-        }
-    }
-    // ---- 2-D linear program (App. A.5), LP3 where it is infeasible ----
-    V2 nv = mk(0.0f, 0.0f);
-    int fail = nl;
-    if (active) fail = lp2(ls, nl, p.max_speed, pref, false, nv);
-    if (active && fail < nl) lp3<KMAX + SMAX>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, p.max_speed, nv);
-    if (active) { t.nv_x[q] = nv.x; t.nv_y[q] = nv.y; }
+#define CA_TILED_SOLVE_GRID 0
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
+}
+template <int KMAX, int TILE>
+__global__ __launch_bounds__(TILE) void tiled_grid_solve_kernel(const TiledGridArgs t) {
+#define CA_TILED_SOLVE_GRID 1
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
 }
 
 // ---- launch 2: integrate, reward, wall / goal tests, the arena's partial results ---------------------------------------------------

@@ -56,16 +56,20 @@ class VecCollisionAvoidanceEnv:
     tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
                arena spread over several workgroups, a step in three launches (tiled_info()); max_obst_neighbors <= 16, no
                agent_params / agent_counts (ValueError).  Results are the ordinary handle's bit for bit.  False (default): one
-               workgroup per arena, n_agents <= 1024.
+               workgroup per arena, n_agents <= 1024.  "grid": the tiled path with its uniform-grid neighbour search
+               (CA_CREATE_TILED | CA_CREATE_TILED_GRID): the arena's agents are sorted by cell in three more launches per step and an
+               agent tests the cells its range touches instead of the whole arena (tiled_grid_info()); the same results.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
                  agent_params=None, agent_counts=None, tiled=False):
+        if tiled not in (False, True, "grid", None, 0, 1):
+            raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
         if tiled and (agent_params or agent_counts is not None):
-            raise ValueError("tiled=True: the tiled kernels have no per-agent-parameter and no per-arena-count form "
-                             "(agent_params= / agent_counts= go with tiled=False)")
-        self.tiled = bool(tiled)
+            raise ValueError("tiled=%r: the tiled kernels have no per-agent-parameter and no per-arena-count form "
+                             "(agent_params= / agent_counts= go with tiled=False)" % (tiled,))
+        self.tiled = "grid" if tiled == "grid" else bool(tiled)
         if agent_counts is not None and scenario not in (None, "doorway"):
             raise ValueError("agent_counts: scenario %r lays its agents out as a function of n_agents; only 'doorway' or None "
                              "go with per-arena agent counts" % (scenario,))
@@ -93,7 +97,8 @@ class VecCollisionAvoidanceEnv:
         self.use_torch = (torch is not None and torch.cuda.is_available()) if use_torch is None else bool(use_torch)
         h = C.c_void_p()
         if self.tiled:
-            rc = self.L.ca_create_ex(C.byref(self.cfg), _lib.CREATE_TILED, self.device, None, C.byref(h))
+            flags = _lib.CREATE_TILED | (_lib.CREATE_TILED_GRID if self.tiled == "grid" else 0)
+            rc = self.L.ca_create_ex(C.byref(self.cfg), flags, self.device, None, C.byref(h))
         else:
             rc = self.L.ca_create(C.byref(self.cfg), self.device, None, C.byref(h))
         _lib.check(self.L, None, rc, "ca_create_ex" if self.tiled else "ca_create")
@@ -370,6 +375,13 @@ class VecCollisionAvoidanceEnv:
         v = [C.c_int32() for _ in range(4)]
         self._call("ca_tiled_info", self.h, *[C.byref(x) for x in v])
         return dict(tiled=bool(v[0].value), tile_agents=v[1].value, tiles_per_arena=v[2].value, launches_per_step=v[3].value)
+
+    def tiled_grid_info(self):
+        """dict(grid, cells_x, cells_y, cell_size, sort_launches) of the uniform grid of a tiled="grid" handle (ca_tiled_grid_info):
+        the wrapped cell table's sides, the width of a cell, the launches in front of the solve launch; zeros on every other handle."""
+        v = [C.c_int32() for _ in range(3)] + [C.c_float(), C.c_int32()]
+        self._call("ca_tiled_grid_info", self.h, *[C.byref(x) for x in v])
+        return dict(grid=bool(v[0].value), cells_x=v[1].value, cells_y=v[2].value, cell_size=v[3].value, sort_launches=v[4].value)
 
     # ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133) ---------------
     _AGENT_PARAMS = ("radius", "max_speed", "time_horizon", "time_horizon_obst")

@@ -45,6 +45,9 @@ extern "C" {
 
 /* create flags for ca_create_ex */
 #define CA_CREATE_TILED 1u /* the tiled solve path: n_agents 1..CA_MAX_AGENTS_LARGE, see ca_create_ex */
+#define CA_CREATE_TILED_GRID 4u /* with CA_CREATE_TILED only (flags == 5): the tiled path finds the agent neighbours through a uniform
+                                   grid sorted across workgroups, see ca_create_ex.  Bit 2u is NOT a flag: it stays unknown
+                                   (CA_EINVAL), as does every other bit */
 
 /* error codes */
 #define CA_OK 0
@@ -184,7 +187,19 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
  *     around them (select, solve, update); neighbour ids are 16 bits on the device.
  *   - ca_set_agent_params and ca_set_agent_counts -> CA_EINVAL (no tiled form); the handle keeps working.
  *   - ca_solver_info reports lanes_per_agent = 1, rollout_one_launch = 0; ca_launch_info the first of the three launches;
- *     ca_profile counts each of the three launches on its own under kind 1. */
+ *     ca_profile counts each of the three launches on its own under kind 1.
+ * CA_CREATE_TILED | CA_CREATE_TILED_GRID (flags == 5; CA_CREATE_TILED_GRID alone -> CA_EINVAL: the grid is the tiled path's): a tiled
+ * handle in every respect above -- limits, refusals, 16-bit ids, step flags, sticky overflow error, ALAN in the three-launch form
+ * around the solve, ca_rollout = T times the launches of a step -- that differs in three ways:
+ *   - the agent-neighbour list is found through a uniform grid instead of the scan of the whole arena: a fixed, wrapped table of
+ *     cells_x x cells_y cells (powers of two chosen from n_agents), cells half a neighbour range wide (ca_tiled_grid_info), the
+ *     arena's agents counting-sorted by cell every step, an agent testing the cells its range touches.  The lists it leaves
+ *     (CA_FLD_NB_*, CA_FLD_OBST_*) are the same, order included: the same K smallest (distance, index) keys;
+ *   - a step is sort_launches more launches in front of the solve (bin, scan, scatter): ca_tiled_info reports
+ *     launches_per_step = sort_launches + 3, and ca_profile counts each under kind 1;
+ *   - ca_launch_info reports the first launch of the sequence (the bin launch: no dynamic LDS).
+ *   The sort's buffers belong to the handle and are no part of its state (no field reads them).  CA_TILED_CELLS=<g> (a power of
+ *   two, 8 .. 128; diagnostic switch latched here, like CA_TILE) forces a g x g table. */
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out);
 int ca_destroy(ca_env* env);
 const char* ca_last_error(const ca_env* env);
@@ -397,7 +412,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * (kinds: 0 nbr_kernel -- always 0: the neighbour search is the head of step_kernel, with no launch of its own; the
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
- * is three launches and its time three times the mean --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
+ * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
  * launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
@@ -421,8 +436,13 @@ int ca_launch_info(ca_env* env, int32_t* block, int32_t* grid, int32_t* lds_byte
  * registers / LDS for its T steps (the four-lanes kernel; chosen up to 1024 waves inclusive); 0: it is T launches. */
 int ca_solver_info(ca_env* env, int32_t* lanes_per_agent, int32_t* rollout_one_launch);
 /* The tiled solve path of a handle made with CA_CREATE_TILED: *tiled = 1, *tile_agents = agents per workgroup, *tiles_per_arena =
- * workgroups an arena spans, *launches_per_step = kernel launches of one solve (3).  All zeros on an ordinary handle. */
+ * workgroups an arena spans, *launches_per_step = kernel launches of one solve (3; with CA_CREATE_TILED_GRID the launches of the
+ * sort in front of them as well: sort_launches + 3).  All zeros on an ordinary handle. */
 int ca_tiled_info(ca_env* env, int32_t* tiled, int32_t* tile_agents, int32_t* tiles_per_arena, int32_t* launches_per_step);
+/* The uniform grid of a handle made with CA_CREATE_TILED | CA_CREATE_TILED_GRID: *grid = 1, *cells_x / *cells_y = the sides of the
+ * wrapped cell table (powers of two, at least 8), *cell_size = the width of a cell (half of neighbor_dist), *sort_launches = kernel
+ * launches in front of the solve launch.  All zeros on every handle without the flag. */
+int ca_tiled_grid_info(ca_env* env, int32_t* grid, int32_t* cells_x, int32_t* cells_y, float* cell_size, int32_t* sort_launches);
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
 const char* ca_source_sha(void);
