@@ -15,6 +15,7 @@ CREATE_TILED = 1
 CREATE_TILED_GRID = 4   # only together with CREATE_TILED: the uniform-grid neighbour search of the tiled path
 DONE_XLESS, DONE_GOAL, DONE_REGOAL = 0, 1, 2
 F_OBS, F_STATS, F_AUTORESET, F_NODONE, F_FREEZE = 1, 2, 4, 8, 16
+TRACE_POS, TRACE_VEL = 1, 2   # channels of a recording rollout (struct ca_trace)
 SCN_CROWD, SCN_CIRCLE, SCN_DOORWAY, SCN_CONGESTED, SCN_INCOMING, SCN_BLOCKS, SCN_DEADLOCK, SCN_CROWD_SEPARATED = range(8)
 
 (FLD_POS_X, FLD_POS_Y, FLD_VEL_X, FLD_VEL_Y, FLD_PREF_X, FLD_PREF_Y, FLD_GOAL_X, FLD_GOAL_Y,
@@ -29,7 +30,8 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_set_obstacles_per_arena", "ca_get_obstacles_arena", "ca_solver_info", "ca_source_sha", "ca_host_alloc", "ca_host_free",
            "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
            "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info",
-           "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info")
+           "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info",
+           "ca_rollout_trace", "ca_alan_rollout_trace")
 
 
 class Config(C.Structure):
@@ -54,6 +56,12 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Trace(C.Structure):
+    """struct ca_trace (include/ca_env.h): the caller's buffers of a recording rollout."""
+    _fields_ = [("agents", C.c_void_p), ("agents_bytes", C.c_size_t), ("arenas", C.c_void_p), ("arenas_bytes", C.c_size_t),
+                ("every", C.c_int32), ("channels", C.c_uint32)]
 
 
 _lib = None
@@ -107,6 +115,8 @@ def load():
     L.ca_alan_actions_arena.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.ca_alan_step.argtypes = [vp, vp, i32, u32]
     L.ca_alan_rollout.argtypes = [vp, i32, u32]
+    L.ca_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
+    L.ca_alan_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]

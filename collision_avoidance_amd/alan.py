@@ -85,23 +85,43 @@ class Collision_Avoidance_Sim(object):
         self._min_ttimes = np.array([min_ttime(start[a], goal[a], self.maxSpeed) for a in range(self.n_arenas)])
         self.min_TTime = float(self._min_ttimes[0])
 
-    def run_sim(self, mode=1):
+    def run_sim(self, mode=1, trace_every=None):
         """mode 1: ALAN online learning, 0: plain ORCA (ALAN_true.py:106-131).
         Returns (success, total_time, TTime, min_TTime); arrays of length n_arenas when n_arenas > 1.
         Every arena stops at its own last arrival (or at max_step) on the device, like the `break` at
-        ALAN_true.py:121-123; the host only looks at the flags every POLL steps."""
+        ALAN_true.py:121-123; the host only looks at the flags every POLL steps.
+        trace_every=k: keep the positions after every k-th step of this call (what the reference draws, ALAN_true.py:689-699) in
+        self.trajectory, a numpy array [R, n_arenas, N, 2] ([R, N, 2] for one arena), recorded inside the rollouts (the trace= of
+        VecCollisionAvoidanceEnv.alan_rollout).  An arena's records end with the last one at or before its last advanced step:
+        self.trajectory_records [n_arenas] counts them, R is the largest count, and an arena that stopped earlier repeats its final
+        state in the rows beyond its own.  1 <= k <= POLL; the polled chunks are cut to a multiple of k, so records fall on
+        multiples of k whatever POLL is (ValueError otherwise)."""
         from . import _lib
+        chunk, records, steps0 = self.POLL, [], None
+        if trace_every is not None:
+            k = int(trace_every)
+            if k != trace_every or k < 1 or k > self.POLL:
+                raise ValueError("run_sim: trace_every=%r must be a whole number of steps in 1 .. POLL=%d" % (trace_every, self.POLL))
+            chunk = self.POLL - self.POLL % k
+            trace = dict(every=k, channels=("pos",), arenas=False)
+            steps0 = self.vec.get(_lib.FLD_STEP_COUNT)
         left = self.max_step - self.step_count
         while left > 0:
-            n = min(self.POLL, left)
-            if mode == 0:
-                self.vec.rollout(n, freeze=True)
+            n = min(chunk, left)
+            roll = self.vec.rollout if mode == 0 else self.vec.alan_rollout
+            if trace_every is None:
+                roll(n, freeze=True)
             else:
-                self.vec.alan_rollout(n, freeze=True)
+                records.append(roll(n, freeze=True, trace=trace)["agents"].cpu().numpy())
             left -= n
             if self.vec.get(_lib.FLD_ARENA_DONE).all():
                 break
         steps = self.vec.get(_lib.FLD_STEP_COUNT)
+        if trace_every is not None:
+            self.trajectory_records = (steps - steps0) // int(trace_every)
+            traj = np.concatenate(records, 0) if records else np.zeros((0, 2, self.n_arenas, self.numAgents), np.float32)
+            traj = np.ascontiguousarray(np.transpose(traj[:int(self.trajectory_records.max())], (0, 2, 3, 1)))   # [R, A, N, 2]
+            self.trajectory = traj[:, 0] if self.n_arenas == 1 else traj
         done = self.vec.get(_lib.FLD_AGENT_DONE)
         arrive = self.vec.get(_lib.FLD_ARRIVE_STEP)
         self.step_count = int(steps[0])

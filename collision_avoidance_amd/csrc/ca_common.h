@@ -20,6 +20,10 @@ struct AgentParams;
 // without parameters of the caller's has the arrays filled with its constants) -- and stands alone in the pack, so that
 // "AgentParams" keeps naming exactly the instantiations it named before.
 struct ArenaCounts;
+// Tag of the four-lanes kernel's recording instantiations (quad_kernel<KMAX, BS, SQ, ALAN, Trace>: ca_rollout_trace /
+// ca_alan_rollout_trace): inside the T-step loop the selected planes of the state and the arena's three words go to the caller's
+// trace buffer whenever the rollout's step count reaches a multiple of `every` (TraceDev below).
+struct Trace;
 
 namespace ca {
 
@@ -52,6 +56,7 @@ struct Line {
 // from call to call; everything the EPILOGUE needs -- the pointers it stores through, the done / reset / re-goal
 // constants -- sits in a per-handle block in device memory (StepCold, written once by ca_create) and is loaded, as
 // scalar loads, where the epilogue begins.
+struct TraceDev;   // (below)
 struct StepCold {
     float *pos_x, *pos_y, *vel_x, *vel_y, *pref_x, *pref_y;
     double *goal_x, *goal_y;        // targets stay fp64 like the reference's Python floats
@@ -77,6 +82,26 @@ struct StepCold {
     // agents per arena [A] (ca_set_agent_counts; null on a handle whose arenas all hold N agents): read by the ArenaCounts
     // instantiations and by reset_counts_kernel only.  Last member: nothing the other kernels load moves.
     const int* agent_counts;
+    // the trace block of the handle (ca_rollout_trace): read by the Trace instantiations of the four-lanes kernel only.  Last
+    // member again.
+    const TraceDev* trace;
+};
+
+// The trace of a recording rollout (include/ca_env.h ca_trace), as the Trace instantiations of the four-lanes kernel read it: a
+// block of the handle's in device memory behind StepCold::trace, rewritten on the stream in front of every such launch
+// (trace_setup_kernel).  Record r holds the state after (r + 1) * every steps of the rollout: agents f32 [R][C][A*N] with the planes
+// pos_x, pos_y, vel_x, vel_y of the selected channels in this order, arenas i32 [R][3][A] = step_count, arena_done, episode (or null).
+struct TraceDev {
+    float* agents;
+    int* arenas;
+    unsigned an;        // A * N: the stride of a plane
+    int A;
+    int R;              // records the buffers hold: the kernel stores record r only if r < R
+    int C;              // planes per record: 2 per channel
+    unsigned channels;  // CA_TRACE_POS = 1 | CA_TRACE_VEL = 2
+    int every;
+    int next;           // the record the next store of this launch fills: (steps the rollout did before the launch) / every
+    int countdown;      // steps of this launch until that store: every - (steps before the launch) % every
 };
 
 // ALAN online learning inside the four-lanes kernel (ca_quad.h): the bandit's arguments, in device memory like StepCold

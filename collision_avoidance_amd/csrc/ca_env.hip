@@ -72,6 +72,8 @@ struct ca_env {
     std::vector<int> h_tab_off;      // empty: one table for all arenas; else [A + 1] offsets into h_obst
     int* d_tab_off = nullptr;
     StepCold* d_cold = nullptr;      // the epilogue's arguments (ca_common.h)
+    TraceDev* d_trace = nullptr;     // the trace block behind StepCold::trace, rewritten in front of every Trace launch of the four-lanes kernel
+    bool trace_on = false;           // ca_rollout_trace / ca_alan_rollout_trace: the T-step launch in flight is a Trace instantiation
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -282,6 +284,7 @@ static void fill_cold(const ca_env* e, StepCold& c) {
     c.ap_radius = e->ap ? e->d_ap[0] : nullptr; c.ap_max_speed = e->ap ? e->d_ap[1] : nullptr;
     c.ap_time_horizon = e->ap ? e->d_ap[2] : nullptr; c.ap_time_horizon_obst = e->ap ? e->d_ap[3] : nullptr;
     c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.trace = e->d_trace;
 }
 
 static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t flags) {
@@ -404,13 +407,16 @@ static const void* tiled_solve_fn(const ca_env* e) {
     if (e->tgrid) return e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE));
     return e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE));
 }
-// alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps
-static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout) {
+// alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps;
+// trace: ... and records them (the Trace instantiations of the four-lanes kernel: the ORCA-only rollout and the fused ALAN rollout with
+// one action set; the callers ask for nothing else)
+static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout, bool trace = false) {
     if (e->tiled)   // (the solve launch of a step's sequence; no ALAN and no rollout form)
         return {tiled_solve_fn(e), dim3(e->grid), dim3(e->TILE), e->lds};
     const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
     if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
-        const void* f = per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e));
+        const void* f = trace ? (alan ? quad_fn_for<true, Trace>(e) : quad_fn_for<false, Trace>(e))
+                              : (per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e)));
         return {f, dim3(e->grid_q), dim3(e->BSq), alan ? quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions) : e->lds_q};
     }
     if (e->pair)   // two lanes per agent (ca_pair.h): one arena per workgroup of 2 P lanes
@@ -424,7 +430,7 @@ static hipError_t allow_lds(const SolveLaunch& s) {
 }
 // neighbour search + lines + LP + integration + reward/done (+ the ALAN bandit), a.T steps
 static hipError_t launch_step(ca_env* e, const StepArgs& a) {
-    const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1);
+    const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1, e->trace_on && a.T > 1);
     if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
     if (e->tiled && e->tgrid) {   // bin -> scan -> scatter -> solve -> advance -> close (ca_tiled.h)
         TiledGridArgs ga;
@@ -954,6 +960,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         r = hipHostMalloc((void**)&e->ovf_host, sizeof(unsigned long long), hipHostMallocDefault);
         if (r == hipSuccess) *e->ovf_host = 0ull;
     }
+    if (r == hipSuccess) r = dalloc(e, &e->d_trace, (size_t)1);
     if (r == hipSuccess) r = hipMalloc((void**)&e->d_cold, sizeof(StepCold));
     if (r == hipSuccess) {
         StepCold hc;
@@ -983,7 +990,7 @@ int ca_destroy(ca_env* e) {
     void* bufs[] = {e->pos_x, e->pos_y, e->vel_x, e->vel_y, e->pref_x, e->pref_y, e->goal_x, e->goal_y,
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
-                    e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_order,
+                    e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
@@ -2086,6 +2093,129 @@ int ca_rollout(ca_env* e, int32_t steps, uint32_t flags) {
     for (int s = 0; s < steps; ++s) {
         const int rc = do_step(e, nullptr, flags);
         if (rc) return rc;
+    }
+    return CA_OK;
+}
+
+// ---- recording rollouts (include/ca_env.h ca_trace) -------------------------------------------------------------------------
+struct TracePlan { int R, C; };
+// every refusal of the two calls, before anything is launched
+static int trace_check(ca_env* e, const char* who, int32_t steps, const ca_trace* tr, TracePlan* pl) {
+    if (!e || steps < 0) return fail(e, CA_EINVAL, "%s: bad argument", who);
+    if (!tr || !tr->agents) return fail(e, CA_EINVAL, "%s: the trace or its agents buffer is null", who);
+    if (tr->every < 1) return fail(e, CA_EINVAL, "%s: every=%d, must be at least 1", who, tr->every);
+    if (tr->channels == 0u || (tr->channels & ~(CA_TRACE_POS | CA_TRACE_VEL)) != 0u)
+        return fail(e, CA_EINVAL, "%s: channels=0x%x, must be CA_TRACE_POS (1), CA_TRACE_VEL (2) or both", who, tr->channels);
+    pl->R = steps / tr->every;
+    pl->C = ((tr->channels & CA_TRACE_POS) ? 2 : 0) + ((tr->channels & CA_TRACE_VEL) ? 2 : 0);
+    const size_t need_ag = (size_t)pl->R * (size_t)pl->C * AN(e) * 4, need_ar = (size_t)pl->R * 3 * (size_t)e->cfg.n_arenas * 4;
+    if (tr->agents_bytes < need_ag)
+        return fail(e, CA_ESIZE, "%s: the agents buffer needs %zu bytes (f32 [R=%d, C=%d, A=%d, N=%d]), got %zu", who, need_ag, pl->R, pl->C,
+                    e->cfg.n_arenas, e->cfg.n_agents, tr->agents_bytes);
+    if (tr->arenas && tr->arenas_bytes < need_ar)
+        return fail(e, CA_ESIZE, "%s: the arenas buffer needs %zu bytes (i32 [R=%d, 3, A=%d]), got %zu", who, need_ar, pl->R, e->cfg.n_arenas,
+                    tr->arenas_bytes);
+    return CA_OK;
+}
+// record r by the record kernel: behind the launches of a step (kind 3 for ca_profile)
+static hipError_t launch_trace_record(ca_env* e, const ca_trace* tr, const TracePlan& pl, int r) {
+    if (r >= pl.R) return hipSuccess;
+    TraceRecArgs t;
+    int c = 0;
+    for (int k = 0; k < 4; ++k) t.src[k] = nullptr;
+    if (tr->channels & CA_TRACE_POS) { t.src[c++] = e->pos_x; t.src[c++] = e->pos_y; }
+    if (tr->channels & CA_TRACE_VEL) { t.src[c++] = e->vel_x; t.src[c++] = e->vel_y; }
+    t.words[0] = e->step_count; t.words[1] = e->arena_done; t.words[2] = e->episode;
+    t.an = (unsigned)AN(e); t.A = e->cfg.n_arenas; t.C = pl.C;
+    t.agents = (float*)tr->agents + (size_t)r * pl.C * t.an;
+    t.arenas = tr->arenas ? (int*)tr->arenas + (size_t)r * 3 * t.A : nullptr;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, trace_record_kernel, dim3((t.an + 255) / 256), dim3(256), 0, e->stream, t);
+    return hipGetLastError();
+}
+// the cursor of a Trace launch of the four-lanes kernel that follows `done` steps of the rollout
+static hipError_t launch_trace_setup(ca_env* e, const ca_trace* tr, const TracePlan& pl, int done) {
+    TraceDev v;
+    v.agents = (float*)tr->agents; v.arenas = (int*)tr->arenas; v.an = (unsigned)AN(e); v.A = e->cfg.n_arenas;
+    v.R = pl.R; v.C = pl.C; v.channels = tr->channels; v.every = tr->every;
+    v.next = done / tr->every; v.countdown = tr->every - done % tr->every;
+    hipLaunchKernelGGL(trace_setup_kernel, dim3(1), dim3(64), 0, e->stream, e->d_trace, v);
+    return hipGetLastError();
+}
+// a T-step launch of the four-lanes kernel that records (a.T > 1)
+static hipError_t launch_step_traced(ca_env* e, const StepArgs& a, const ca_trace* tr, const TracePlan& pl, int done) {
+    hipError_t r = allow_lds(solve_launch(e, a.alan != nullptr, true, true));
+    if (r == hipSuccess) r = launch_trace_setup(e, tr, pl, done);
+    if (r != hipSuccess) return r;
+    e->trace_on = true;
+    r = launch_step(e, a);
+    e->trace_on = false;
+    return r;
+}
+
+int ca_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr) {
+    TracePlan pl;
+    { const int rc = trace_check(e, "ca_rollout_trace", steps, tr, &pl); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, "ca_rollout_trace"); if (rs) return rs; }
+    if (e->quad_roll && !(flags & CA_F_OBS) && steps > 1) {   // ca_rollout's one-launch form, its Trace instantiation
+        StepArgs a;
+        fill_args(e, a, nullptr, flags);
+        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
+            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
+            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
+            if (a.T == 1) {   // (a lone last step is the launch ca_rollout makes, and the record kernel behind it)
+                HIPCHK(e, launch_step(e, a));
+                if ((done + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (done + 1) / tr->every - 1));
+            } else {
+                HIPCHK(e, launch_step_traced(e, a, tr, pl, done));
+            }
+            e->steps_done += (uint64_t)a.T;
+        }
+        e->orient_valid = true;
+        return CA_OK;
+    }
+    for (int s = 0; s < steps; ++s) {   // a sequence of launches per step: the record kernel behind those of every `every`-th
+        const int rc = do_step(e, nullptr, flags);
+        if (rc) return rc;
+        if ((s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
+    }
+    return CA_OK;
+}
+
+int ca_alan_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr) {
+    TracePlan pl;
+    { const int rc = trace_check(e, "ca_alan_rollout_trace", steps, tr, &pl); if (rc) return rc; }
+    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_rollout_trace: ALAN is not supported while per-arena agent counts are set");
+    if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_rollout_trace: call ca_alan_configure first");
+    if (flags & (CA_F_AUTORESET | CA_F_NODONE))
+        return fail(e, CA_EINVAL, "ca_alan_rollout_trace: CA_F_AUTORESET / CA_F_NODONE do not apply (ALAN:106-123)");
+    { const int rs = overflow_status(e, "ca_alan_rollout_trace"); if (rs) return rs; }
+    // (an action set per arena records in the per-step form: no Trace twin of the AlanArenaSets instantiations)
+    if (e->alan_fused && e->quad_roll && !e->alan_per && !(flags & CA_F_OBS) && steps > 1) {
+        HIPCHK(e, hipSetDevice(e->device));
+        StepArgs a;
+        fill_args(e, a, nullptr, flags);
+        a.alan = e->d_alan;
+        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
+            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
+            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
+            if (a.T == 1) {   // (a lone last step: what ca_alan_rollout does with it, and the record kernel behind it)
+                if (!e->quad) { const int rc = ca_alan_step(e, nullptr, 0, flags); if (rc) return rc; }
+                else { HIPCHK(e, launch_step(e, a)); e->steps_done += 1; }
+                if ((done + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (done + 1) / tr->every - 1));
+                continue;
+            }
+            HIPCHK(e, launch_step_traced(e, a, tr, pl, done));
+            e->steps_done += (uint64_t)a.T;
+        }
+        e->orient_valid = true;
+        return CA_OK;
+    }
+    for (int s = 0; s < steps; ++s) {
+        const int rc = ca_alan_step(e, nullptr, 0, flags);
+        if (rc) return rc;
+        if ((s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
     }
     return CA_OK;
 }

@@ -31,7 +31,7 @@
 // ca_nbr.h (neighbour search; key_empty / key_dummy, edge_in_range), ca_rules.h (the environment's per-agent rules: actions,
 // reward, done test, goals, resets, the wall test and the pair count's shortcut, ALAN's draw and update), ca_step.h (lane solve +
 // reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
-// ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation).
+// ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -40,6 +40,7 @@
 #include "ca_tiled.h"
 #include "ca_alan.h"
 #include "ca_obs.h"
+#include "ca_trace.h"
 
 namespace ca {
 

@@ -171,9 +171,18 @@ __host__ __device__ inline size_t quad_lds_bytes(int BS, int KMAX, int SQ, int n
 // PER (ALAN instantiation only): AlanArenaSets = an action set per arena -- the loops run over the arena's own count (nk), the
 // LDS rows keep the stride of the largest set (nA); a trailing pack, empty in every other instantiation (names and code as
 // they were).
+// Trace in the pack (ca_rollout_trace / ca_alan_rollout_trace; with or without ALAN): at the end of every step whose number in the
+// rollout is a multiple of `every` the quad stores its agent's planes and the arena's owner its three words into the caller's
+// trace (ca_common.h TraceDev).  It stands at the very end of the step -- behind the in-kernel reset's update of pos, vel, steps,
+// adone and epi --, so a record is what ca_get would read had the launch ended there; a frozen arena's registers hold the state it
+// was loaded with, and are stored like any other.
+#ifndef CA_TRACE_STORE   // 0: lane q of a quad stores plane q (one store per wave and record, every lane busy); 1: lane 0 stores
+#define CA_TRACE_STORE 0 // the four planes; 2: as 0 with non-temporal stores.  tools/trace_cost.py measures them: DESIGN.md 7f
+#endif
 template <int KMAX, int BS, int SQ, bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
-    constexpr int AM = !ALAN ? 0 : (sizeof...(PER) > 0 ? 2 : 1);   // the set mode of alan_count / alan_cs
+    constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
+    constexpr bool TR = has_tag<Trace, PER...>;
     static_assert(POOL_SLOTS == 16, "a wave holds 16 quads: one line-table slot each");
     static_assert(SQ == 4 || SQ == 16, "obstacle lists of 4 or 16");
     static_assert(!CA_NBW16(BS / 4), "the quad kernel stores 8-bit agent-neighbour ids: at most 256 agent slots per workgroup "
@@ -252,6 +261,10 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     }
     double* s_t = s_w + nA * NS;
     double* s_ps = s_t + nA * NS;
+
+    // the trace's cursor: wave-uniform, a countdown carried through the loop
+    int tr_next = 0, tr_cd = 0;
+    if constexpr (TR) { const TraceK& td = *(TraceK*)c.trace; tr_next = td.next; tr_cd = td.countdown; }
 
     const int T = p.actions ? 1 : (p.T > 0 ? p.T : 1);
     for (int t = 0; t < T; ++t) {
@@ -557,6 +570,37 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         if (active) {
             adone = all_done ? 1 : 0;
             if (do_reset) { steps = 0; epi += 1; }
+        }
+        if constexpr (TR) {   // ---- record (ca_common.h TraceDev): the state as the launch would write it back here ----
+            if (--tr_cd == 0) {
+                const TraceK& td = *(TraceK*)c.trace;   // (scalar loads, like the cold block)
+                tr_cd = td.every;
+                if (tr_next < td.R) {   // (no host mistake makes the kernel store outside the buffers)
+                    const unsigned ch = td.channels;
+#if CA_TRACE_STORE == 1
+                    if (in_arena && q == 0) {
+                        float* rec = td.agents + (size_t)tr_next * td.C * td.an + gq;
+                        if (ch & 1u) { rec[0] = pos.x; rec[td.an] = pos.y; rec += 2 * (size_t)td.an; }
+                        if (ch & 2u) { rec[0] = vel.x; rec[td.an] = vel.y; }
+                    }
+#else
+                    // lane q holds plane q of (pos_x, pos_y, vel_x, vel_y); it lies (q - 2) planes in when positions are left out
+                    const float v = q == 0 ? pos.x : (q == 1 ? pos.y : (q == 2 ? vel.x : vel.y));
+                    const int pl = (ch & 1u) ? q : q - 2;
+                    if (in_arena && ((ch >> (q >> 1)) & 1u)) {
+                        float* dst = td.agents + ((size_t)tr_next * td.C + pl) * td.an + gq;
+#if CA_TRACE_STORE == 2
+                        __builtin_nontemporal_store(v, dst);
+#else
+                        *dst = v;
+#endif
+                    }
+#endif
+                    if (in_arena && i == 0 && q < 3 && td.arenas != nullptr)
+                        td.arenas[((size_t)tr_next * 3 + q) * td.A + a] = q == 0 ? steps : (q == 1 ? adone : epi);
+                }
+                tr_next += 1;
+            }
         }
         // (the next step's first barrier separates these reads of red[] from its clearing)
         CA_STAMP(11);

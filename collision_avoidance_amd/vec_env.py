@@ -33,6 +33,40 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+_TRACE_CHANNELS = {"pos": _lib.TRACE_POS, "vel": _lib.TRACE_VEL}
+
+
+def _trace_channels(channels):
+    """The channel mask of struct ca_trace for ("pos", "vel"), a single name, or a mask."""
+    if isinstance(channels, (int, np.integer)):
+        mask = int(channels)
+    else:
+        names = (channels,) if isinstance(channels, str) else tuple(channels)
+        unknown = [c for c in names if c not in _TRACE_CHANNELS]
+        if unknown:
+            raise ValueError("trace: unknown channel %r (known: 'pos', 'vel')" % (unknown[0],))
+        mask = 0
+        for c in names:
+            mask |= _TRACE_CHANNELS[c]
+    if mask == 0 or mask & ~(_lib.TRACE_POS | _lib.TRACE_VEL):
+        raise ValueError("trace: channels must name 'pos', 'vel' or both, got %r" % (channels,))
+    return mask
+
+
+def trace_shape(steps, every, channels, A, N):
+    """Shapes of the two arrays of a recording rollout (rollout(..., trace=...) / alan_rollout(..., trace=...)), without a
+    device: ((R, C, A, N), (R, 3, A)) with R = steps // every records and C = 2 planes per channel, in the order pos_x, pos_y,
+    vel_x, vel_y; the second is step_count, arena_done, episode per arena."""
+    every = int(every)
+    if every < 1:
+        raise ValueError("trace: every=%d, must be at least 1" % every)
+    if int(steps) < 0:
+        raise ValueError("trace: steps=%d" % int(steps))
+    mask = _trace_channels(channels)
+    R, Cn = int(steps) // every, 2 * bin(mask).count("1")
+    return (R, Cn, int(A), int(N)), (R, 3, int(A))
+
+
 class VecCollisionAvoidanceEnv:
     """A arenas x N agents advanced per call.
 
@@ -556,9 +590,40 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_observe", self.h)
         return self._obs_out()
 
-    def rollout(self, steps, with_obs=False, stats=False, autoreset=False, freeze=False):
+    def _traced(self, name, steps, flags, trace):
+        """ca_rollout_trace / ca_alan_rollout_trace into torch tensors on the handle's device; returns dict(agents, arenas)."""
+        if torch is None or not torch.cuda.is_available():
+            raise RuntimeError("trace= needs PyTorch with a device: the records are written into device tensors")
+        unknown = set(trace) - {"every", "channels", "arenas"}
+        if unknown:
+            raise ValueError("trace: unknown key %r (known: every, channels, arenas)" % sorted(unknown)[0])
+        every, channels = int(trace.get("every", 1)), trace.get("channels", ("pos", "vel"))
+        ag_shape, ar_shape = trace_shape(steps, every, channels, self.A, self.N)
+        dev = torch.device("cuda", self.device)
+        agents = torch.empty(ag_shape, dtype=torch.float32, device=dev)
+        arenas = torch.empty(ar_shape, dtype=torch.int32, device=dev) if trace.get("arenas", True) else None
+        if ag_shape[0] == 0:   # fewer steps than `every`: no record, and an empty tensor has no address to hand over
+            self._call(name[:-len("_trace")], self.h, int(steps), flags)
+        else:
+            tr = _lib.Trace(agents=agents.data_ptr(), agents_bytes=agents.numel() * 4,
+                            arenas=arenas.data_ptr() if arenas is not None else None,
+                            arenas_bytes=arenas.numel() * 4 if arenas is not None else 0,
+                            every=every, channels=_trace_channels(channels))
+            self._call(name, self.h, int(steps), flags, C.byref(tr))
+        if not self.use_torch:   # the handle runs on a stream of its own: the records are complete before torch's stream reads them
+            self.sync()
+        return dict(agents=agents, arenas=arenas)
+
+    def rollout(self, steps, with_obs=False, stats=False, autoreset=False, freeze=False, trace=None):
+        """`steps` ORCA-only steps without returning to the host (ca_rollout).  trace=dict(every=1, channels=("pos", "vel"),
+        arenas=True): also record the state after every `every`-th step (ca_rollout_trace) and return
+        dict(agents=[R, C, A, N] float32, arenas=[R, 3, A] int32 or None) of torch tensors on the handle's device (shapes:
+        trace_shape); record r is the state after (r + 1) * every steps.  The tensors are filled on the handle's stream (torch's
+        current stream of construction with use_torch=True; else the call waits for them)."""
         flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | \
                 (_lib.F_AUTORESET if autoreset else 0) | (_lib.F_FREEZE if freeze else 0)
+        if trace is not None:
+            return self._traced("ca_rollout_trace", steps, flags, trace)
         self._call("ca_rollout", self.h, int(steps), flags)
 
     # ---- ALAN online learning (ALAN_true.py:569-628) -----------------------------------------------
@@ -609,10 +674,12 @@ class VecCollisionAvoidanceEnv:
             self._call("ca_alan_step", self.h, _ptr(uh), 0, flags)
         return self._obs_out() if with_obs else None
 
-    def alan_rollout(self, steps, stats=False, freeze=True):
+    def alan_rollout(self, steps, stats=False, freeze=True, trace=None):
         """run_sim(mode=1) (ALAN_true.py:106-123) for every arena at once: each arena stops at the end of
-        its own episode (freeze) or after `steps` steps."""
+        its own episode (freeze) or after `steps` steps.  trace: as for rollout() (ca_alan_rollout_trace)."""
         flags = (_lib.F_STATS if stats else 0) | (_lib.F_FREEZE if freeze else 0)
+        if trace is not None:
+            return self._traced("ca_alan_rollout_trace", steps, flags, trace)
         self._call("ca_alan_rollout", self.h, int(steps), flags)
 
     def state(self):

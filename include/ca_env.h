@@ -375,6 +375,47 @@ int ca_alan_step(ca_env* env, const double* u, int32_t u_is_device, uint32_t fla
  * resident in LDS --, and a single ca_alan_step is one launch instead of three (select, solve, update). */
 int ca_alan_rollout(ca_env* env, int32_t steps, uint32_t flags);
 
+/* Recording rollouts: ca_rollout / ca_alan_rollout that also write the states in between into buffers of the caller's -- what the
+ * reference shows by drawing every step (ALAN:639-699 draw_world / draw_update), demonstration trajectories, and on a tiled handle the product of
+ * the simulation itself -- without giving up the one-launch rollout and without a host round trip per step.
+ *   R = steps / every records.  Record r holds what ca_get of those fields would return had the rollout been (r + 1) * every
+ *   steps long:
+ *     agents : DEVICE f32 [R, C, A, N], C = 2 per channel bit, the planes in the order pos_x, pos_y, vel_x, vel_y (CA_TRACE_POS
+ *              alone: pos_x, pos_y; CA_TRACE_VEL alone: vel_x, vel_y)
+ *     arenas : DEVICE i32 [R, 3, A] = step_count, arena_done, episode; or NULL: not recorded
+ *   It follows that
+ *     - an arena frozen under CA_F_FREEZE repeats its unchanged state in every later record;
+ *     - under CA_F_AUTORESET the record taken at the step that ended an episode holds the respawned positions, step_count 0 and the
+ *       bumped episode;
+ *     - on a handle with per-arena agent counts an absent row holds what the field holds (what the caller last put there).
+ *   Steps beyond R * every are advanced and not recorded.  The final state, the statistics and every other field are bit for bit
+ *   those of the same call without a trace (one exception, in the last place of one sum: ca_alan_rollout_trace with an action set
+ *   per arena and CA_F_STATS adds ca_stats.sum_reward step by step where ca_alan_rollout adds it per launch).
+ * Asynchronous on the handle's stream like ca_rollout: the buffers are the caller's and must stay alive, and unread, until the
+ * stream has passed the call (ca_sync, or work ordered behind it on the same stream).  The ca_trace struct itself is read before the
+ * call returns.  Flags are those of ca_rollout / ca_alan_rollout; CA_F_OBS is allowed and takes the per-step form.  The sticky
+ * overflow error works as in ca_rollout.
+ * Where ca_rollout / ca_alan_rollout are one launch per 256 steps (ca_solver_info: rollout_one_launch) so are these: the four-lanes
+ * kernel stores the records from its registers, and records continue across launches whatever `every` is.  (ca_alan_rollout_trace
+ * with an action set per arena takes the per-step form.)  Everywhere else -- one- and two-lanes kernels, per-agent parameters,
+ * per-arena counts, wide lists, tiled handles, the three-launch ALAN step, any rollout with CA_F_OBS -- a small record kernel runs
+ * behind the launches of every `every`-th step; ca_profile counts it under kind 3.
+ * Errors, all checked before anything is launched (a failure advances nothing): tr or tr->agents NULL, every < 1, channels zero or
+ * with unknown bits -> CA_EINVAL; agents_bytes, or a non-NULL arenas' arenas_bytes, smaller than the layout -> CA_ESIZE
+ * (ca_last_error names the needed size). */
+#define CA_TRACE_POS 1u   /* pos_x, pos_y */
+#define CA_TRACE_VEL 2u   /* vel_x, vel_y */
+typedef struct ca_trace {
+    void*    agents;        /* DEVICE f32 [R, C, A, N]: C = 2 per channel bit, planes in the order pos_x, pos_y, vel_x, vel_y */
+    size_t   agents_bytes;
+    void*    arenas;        /* DEVICE i32 [R, 3, A]: step_count, arena_done, episode; or NULL */
+    size_t   arenas_bytes;
+    int32_t  every;         /* >= 1 */
+    uint32_t channels;      /* CA_TRACE_POS | CA_TRACE_VEL, at least one */
+} ca_trace;
+int ca_rollout_trace(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
+int ca_alan_rollout_trace(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
+
 /* The reference's simulator keeps EVERY obstacle edge within range of an agent (sim.getAgentNumObstacleNeighbors /
  * getAgentObstacleNeighbor, env.py:249, 301-318, iterate them all); this library's lists hold max_obst_neighbors and drop the
  * farthest edges beyond that.  So that such a deviation cannot pass unnoticed, an overflow is a sticky error of the handle:
