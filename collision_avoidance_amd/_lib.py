@@ -13,6 +13,7 @@ MAX_NEIGHBORS, MAX_OBST_NEIGHBORS, MAX_AGENTS = 16, 64, 1024
 MAX_AGENTS_LARGE = 16384   # on a tiled handle (ca_create_ex with CREATE_TILED)
 CREATE_TILED = 1
 CREATE_TILED_GRID = 4   # only together with CREATE_TILED: the uniform-grid neighbour search of the tiled path
+EDGE_GRID_MAX_EDGES, EDGE_GRID_MAX_ENTRIES = 65535, 1 << 22   # per table of the static edge grid (ca_tiled_edge_grid)
 DONE_XLESS, DONE_GOAL, DONE_REGOAL = 0, 1, 2
 F_OBS, F_STATS, F_AUTORESET, F_NODONE, F_FREEZE = 1, 2, 4, 8, 16
 TRACE_POS, TRACE_VEL = 1, 2   # channels of a recording rollout (struct ca_trace)
@@ -31,7 +32,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
            "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info",
            "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info",
-           "ca_rollout_trace", "ca_alan_rollout_trace")
+           "ca_rollout_trace", "ca_alan_rollout_trace", "ca_tiled_edge_grid", "ca_tiled_edge_grid_info", "ca_edge_grid_build")
 
 
 class Config(C.Structure):
@@ -64,6 +65,12 @@ class Trace(C.Structure):
                 ("every", C.c_int32), ("channels", C.c_uint32)]
 
 
+class EdgeGridDesc(C.Structure):
+    """struct ca_edge_grid_desc (include/ca_env.h): one table of the static edge grid."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("ics_x", C.c_float), ("ics_y", C.c_float),
+                ("gx", C.c_int32), ("gy", C.c_int32), ("n_entries", C.c_int32), ("margin", C.c_float)]
+
+
 _lib = None
 
 
@@ -87,6 +94,9 @@ def load():
     L.ca_create_ex.argtypes = [C.POINTER(Config), u32, C.c_int, vp, C.POINTER(vp)]
     L.ca_tiled_info.argtypes = [vp] + [C.POINTER(i32)] * 4
     L.ca_tiled_grid_info.argtypes = [vp] + [C.POINTER(i32)] * 3 + [C.POINTER(C.c_float), C.POINTER(i32)]
+    L.ca_tiled_edge_grid.argtypes = [vp, i32]
+    L.ca_tiled_edge_grid_info.argtypes = [vp, i32] + [C.POINTER(i32)] * 3 + [C.POINTER(C.c_float)] * 2 + [C.POINTER(i32)]
+    L.ca_edge_grid_build.argtypes = [vp, i32, C.c_float, C.POINTER(EdgeGridDesc), vp, i32, vp, i32]
     L.ca_destroy.argtypes = [vp]
     L.ca_last_error.argtypes = [vp]
     L.ca_last_error.restype = C.c_char_p
@@ -139,6 +149,22 @@ def load():
             getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+def edge_grid_build(edges_pq, rng):
+    """The static edge grid of one table, built on the host (ca_edge_grid_build; no device): edges_pq [n, 4] = (px, py, qx, qy),
+    rng the obstacle range.  Returns (EdgeGridDesc, cell_start [gx * gy + 1] uint32, entries [n_entries] uint32); a refusal raises
+    RuntimeError with the library's message."""
+    import numpy as np
+    L = load()
+    pq = np.ascontiguousarray(edges_pq, np.float32).reshape(-1, 4)
+    d = EdgeGridDesc()
+    ptr = pq.ctypes.data_as(C.c_void_p) if len(pq) else None
+    check(L, None, L.ca_edge_grid_build(ptr, len(pq), float(rng), C.byref(d), None, 0, None, 0), "ca_edge_grid_build")
+    cs, en = np.zeros(d.gx * d.gy + 1, np.uint32), np.zeros(max(1, d.n_entries), np.uint32)
+    check(L, None, L.ca_edge_grid_build(ptr, len(pq), float(rng), C.byref(d), cs.ctypes.data_as(C.c_void_p), len(cs),
+                                        en.ctypes.data_as(C.c_void_p), len(en)), "ca_edge_grid_build")
+    return d, cs, en[:d.n_entries]
 
 
 def check(L, handle, rc, what):

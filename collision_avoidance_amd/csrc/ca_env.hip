@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ca_kernels.h"
+#include "ca_edge_grid_host.h"
 
 using namespace ca;
 
@@ -124,6 +125,15 @@ struct ca_env {
     unsigned *tg_count = nullptr, *tg_start = nullptr, *tg_key = nullptr;   // [A][cells] | [A][cells + 1] | [A*N]
     float *tg_sx = nullptr, *tg_sy = nullptr; // [A*N] positions in cell order
     unsigned short* tg_sidx = nullptr;        // [A*N] agent ids in cell order
+    // ... and the static grid over the obstacle edges (ca_tiled_edge_grid; ca_tiled.h EdgeGridDev): configuration, like the tables it
+    // indexes; rebuilt by install_tables while on
+    struct EdgeGrids {
+        std::vector<EdgeGridDev> desc;            // one per table: [A] with tables per arena, else [1]
+        EdgeGridDev* d_desc = nullptr;
+        unsigned *d_cells = nullptr, *d_entries = nullptr;
+    };
+    bool egrid = false;
+    EdgeGrids eg;
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -402,8 +412,21 @@ static const void* tiled_grid_fn_for(int TILE) {
         default: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 128>);
     }
 }
+// ... and of a grid handle with the static edge grid on (ca_tiled_edge_grid)
+template <int KMAX>
+static const void* tiled_grid_edges_fn_for(int TILE) {
+    switch (TILE) {
+        case 64: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 64>);
+        case 256: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 256>);
+        default: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 128>);
+    }
+}
 enum { TILED_SORT_LAUNCHES = 3 };   // bin, scan, scatter
+static const void* tiled_edges_solve_fn(const ca_env* e) {
+    return e->KT == 5 ? tiled_grid_edges_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_edges_fn_for<16>(e->TILE) : tiled_grid_edges_fn_for<10>(e->TILE));
+}
 static const void* tiled_solve_fn(const ca_env* e) {
+    if (e->tgrid && e->egrid) return tiled_edges_solve_fn(e);
     if (e->tgrid) return e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE));
     return e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE));
 }
@@ -439,14 +462,18 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
         ga.sx = e->tg_sx; ga.sy = e->tg_sy; ga.sidx = e->tg_sidx;
         ga.gx = e->tgx; ga.gy = e->tgy; ga.ics = e->tics;
         TiledArgs ta = ga;   // (the advance and close launches take the plain arguments)
+        TiledEdgeArgs ea;    // (the static edge grid on: the solve and advance launches are the kernels that walk it)
+        static_cast<TiledGridArgs&>(ea) = ga;
+        ea.eg = e->eg.d_desc; ea.eg_cells = e->eg.d_cells; ea.eg_entries = e->eg.d_entries;
         void* gparams[] = {&ga};
         void* params[] = {&ta};
+        void* eparams[] = {&ea};
         struct { const void* fn; dim3 grid, block; size_t lds; void** args; } seq[TILED_SORT_LAUNCHES + 3] = {
             {fn_ptr(&tiled_bin_kernel), s.grid, s.block, 0, gparams},
             {fn_ptr(&tiled_scan_kernel), dim3(e->cfg.n_arenas), dim3(1024), 0, gparams},
             {fn_ptr(&tiled_scatter_kernel), s.grid, s.block, 0, gparams},
-            {s.fn, s.grid, s.block, s.lds, gparams},
-            {fn_ptr(&tiled_advance_kernel), s.grid, s.block, 0, params},
+            {s.fn, s.grid, s.block, s.lds, e->egrid ? eparams : gparams},
+            {e->egrid ? fn_ptr(&tiled_grid_edges_advance_kernel) : fn_ptr(&tiled_advance_kernel), s.grid, s.block, 0, e->egrid ? eparams : params},
             {fn_ptr(&tiled_close_kernel), s.grid, s.block, (size_t)e->TILE * 8, params}};
         for (const auto& k : seq) {   // (each launch timed on its own dispatch, kind 1)
             ProfScope ps(e, KIND_STEP);
@@ -715,7 +742,17 @@ static void pick_variant(ca_env* e) {
 static const size_t LDS_PER_CU = 160 * 1024;
 static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
     const SolveLaunch plain = solve_launch(e, false, false);
-    if (e->tiled) { *misfit = false; return allow_lds(plain); }   // (at most 256 lanes x (32 lines x 16 B + 8 B) = 130 KiB)
+    if (e->tiled) {   // (at most 256 lanes x (32 lines x 16 B + 8 B) = 130 KiB; a grid handle: its edge-grid twin too, whichever is on)
+        *misfit = false;
+        hipError_t r = allow_lds(plain);
+        if (r == hipSuccess && e->tgrid) {
+            SolveLaunch other = plain;
+            other.fn = e->egrid ? (e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE)))
+                                : tiled_edges_solve_fn(e);
+            r = allow_lds(other);
+        }
+        return r;
+    }
     *misfit = !e->pair && e->lds + lds_static_bytes(e) > LDS_PER_CU;
     hipError_t r = hipSuccess;
     if (e->pair) {
@@ -994,7 +1031,8 @@ int ca_destroy(ca_env* e) {
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
-                    e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx};
+                    e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx,
+                    e->eg.d_desc, e->eg.d_cells, e->eg.d_entries};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1060,6 +1098,62 @@ __global__ void clear_obst_counts_kernel(unsigned short* counts, size_t n) {
     if (q < n) counts[q] &= 0x00FFu;
 }
 
+// ---- the static edge grids (ca_tiled_edge_grid; ca_edge_grid_host.h builds one table's grid, ca_tiled.h walks it) ----------------------
+static void free_edge_grids(ca_env::EdgeGrids& g) {
+    if (g.d_desc) hipFree(g.d_desc);
+    if (g.d_cells) hipFree(g.d_cells);
+    if (g.d_entries) hipFree(g.d_entries);
+    g = ca_env::EdgeGrids();
+}
+// the grids of the tables `all` / `offs` (install_tables' arguments) into `out`, uploaded; a failure leaves `out` empty and the handle
+// as it was.  `who`: the call the message names.
+static int make_edge_grids(ca_env* e, const std::vector<ObstDev>& all, const std::vector<int>& offs, ca_env::EdgeGrids& out, const char* who) {
+    const float range = e->cfg.time_horizon_obst * e->cfg.max_speed + e->cfg.radius;   // (the kernels' expression)
+    const int tables = offs.empty() ? 1 : (int)offs.size() - 1;
+    std::vector<uint32_t> cells, entries, cs, en;
+    std::vector<float> pq;
+    out.desc.clear();
+    for (int k = 0; k < tables; ++k) {
+        const int t0 = offs.empty() ? 0 : offs[k], n = offs.empty() ? (int)all.size() : offs[k + 1] - offs[k];
+        pq.resize((size_t)4 * n);
+        for (int i = 0; i < n; ++i) {
+            const ObstDev& o = all[(size_t)t0 + i];
+            pq[4 * i] = o.px; pq[4 * i + 1] = o.py; pq[4 * i + 2] = o.qx; pq[4 * i + 3] = o.qy;
+        }
+        ca_edge_grid::Desc d;
+        const ca_edge_grid::Result r = ca_edge_grid::build(pq.data(), n, range, d, &cs, &en);
+        if (r == ca_edge_grid::TOO_MANY_EDGES)
+            return fail(e, CA_ERANGE, "%s: the edge grid holds at most %d edges per table, table %d has %d; the handle stays as "
+                        "it was", who, (int)ca_edge_grid::MAX_EDGES, k, n);
+        if (r == ca_edge_grid::TOO_MANY_ENTRIES)
+            return fail(e, CA_ERANGE, "%s: the edge grid of table %d would hold %d%s entries (at most %d): long walls cover many cells -- "
+                        "subdivide the walls; the handle stays as it was", who, k, (int)d.n_entries,
+                        d.n_entries == 0x7FFFFFFF ? "+" : "", (int)ca_edge_grid::MAX_ENTRIES);
+        if (r != ca_edge_grid::OK)
+            return fail(e, CA_ERANGE, "%s: obstacle range %g (time_horizon_obst * max_speed + radius) is not a positive number", who, (double)range);
+        if (cells.size() + cs.size() > 0x7FFFFFFFull || entries.size() + en.size() > 0x7FFFFFFFull)
+            return fail(e, CA_ERANGE, "%s: the edge grids of %d tables are too large; subdivide the walls", who, tables);
+        EdgeGridDev g;
+        g.x0 = d.x0; g.y0 = d.y0; g.ics_x = d.ics_x; g.ics_y = d.ics_y; g.gx = d.gx; g.gy = d.gy;
+        g.n_entries = (unsigned)d.n_entries; g.cells_off = (unsigned)cells.size(); g.entries_off = (unsigned)entries.size(); g.pad = 0u;
+        out.desc.push_back(g);
+        cells.insert(cells.end(), cs.begin(), cs.end());
+        entries.insert(entries.end(), en.begin(), en.end());
+    }
+    hipError_t r = hipMalloc((void**)&out.d_desc, out.desc.size() * sizeof(EdgeGridDev));
+    if (r == hipSuccess) r = upload(e, out.d_desc, out.desc.data(), out.desc.size() * sizeof(EdgeGridDev));
+    if (r == hipSuccess) r = hipMalloc((void**)&out.d_cells, cells.size() * sizeof(uint32_t));
+    if (r == hipSuccess) r = upload(e, out.d_cells, cells.data(), cells.size() * sizeof(uint32_t));
+    if (r == hipSuccess) r = hipMalloc((void**)&out.d_entries, (entries.size() + 1) * sizeof(uint32_t));
+    if (r == hipSuccess && !entries.empty()) r = upload(e, out.d_entries, entries.data(), entries.size() * sizeof(uint32_t));
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    if (r != hipSuccess) {
+        free_edge_grids(out);
+        return fail(e, CA_EHIP, "%s: %s (the edge grids; the handle is as it was)", who, hipGetErrorString(r));
+    }
+    return CA_OK;
+}
+
 // installs the table(s): `all` = every table concatenated, `offs` empty (one table for all arenas) or [A + 1].
 // The new tables are allocated and uploaded first and swapped in only when everything succeeded: a failure leaves the
 // handle as it was.  The obstacle-neighbour lists left by the last step refer to the old tables, so their counts are
@@ -1067,6 +1161,11 @@ __global__ void clear_obst_counts_kernel(unsigned short* counts, size_t n) {
 static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>& offs) {
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    ca_env::EdgeGrids n_eg;   // (the static edge grid is on: the new tables' grids first -- a world it refuses is not installed)
+    if (e->egrid) {
+        const int rc = make_edge_grids(e, all, offs, n_eg, "ca_set_obstacles");
+        if (rc) return rc;
+    }
     ObstDev* n_obst = nullptr;
     int* n_off = nullptr;
     hipError_t r = hipMalloc((void**)&n_obst, (all.size() + 1) * sizeof(ObstDev));
@@ -1084,6 +1183,7 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
     if (r != hipSuccess) {
         if (n_obst) hipFree(n_obst);
         if (n_off) hipFree(n_off);
+        free_edge_grids(n_eg);
         return fail(e, CA_EHIP, "ca_set_obstacles: %s (the previous tables stay installed)", hipGetErrorString(r));
     }
     // the solve-kernel variant depends on the size of the world (pick_variant): the variant the NEW world selects is chosen and
@@ -1104,6 +1204,7 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
         (void)apply_variant_attributes(e, &dummy);   // (the previous variant's limits again: the attribute calls are idempotent)
         hipFree(n_obst);
         if (n_off) hipFree(n_off);
+        free_edge_grids(n_eg);
         if (misfit)
             return fail(e, CA_ERANGE, "ca_set_obstacles: the solve kernel this world selects does not fit the 160 KiB of LDS of a CU "
                         "(n_agents=%d, max_neighbors=%d, max_obst_neighbors=%d); the previous tables stay installed", e->cfg.n_agents, e->K, e->S);
@@ -1115,6 +1216,10 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
     e->d_tab_off = n_off;
     e->h_obst.swap(all);
     e->h_tab_off.swap(offs);
+    if (e->egrid) {
+        free_edge_grids(e->eg);
+        e->eg = n_eg;
+    }
     return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
 }
 
@@ -2471,6 +2576,68 @@ int ca_tiled_grid_info(ca_env* e, int32_t* grid, int32_t* cells_x, int32_t* cell
     if (cells_y) *cells_y = e->tgrid ? e->tgy : 0;
     if (cell_size) *cell_size = e->tgrid ? e->tcs : 0.0f;
     if (sort_launches) *sort_launches = e->tgrid ? TILED_SORT_LAUNCHES : 0;
+    return CA_OK;
+}
+
+int ca_tiled_edge_grid(ca_env* e, int32_t on) {
+    if (!e) return CA_EINVAL;
+    if (!(e->tiled && e->tgrid))
+        return fail(e, CA_EINVAL, "ca_tiled_edge_grid: the static edge grid belongs to a grid handle (ca_create_ex with create_flags 0x5 = "
+                    "CA_CREATE_TILED | CA_CREATE_TILED_GRID); this handle was made with create_flags 0x%x", e->tiled ? 0x1 : 0x0);
+    if (on != 0 && on != 1) return fail(e, CA_EINVAL, "ca_tiled_edge_grid: on=%d (0 or 1)", (int)on);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (on) {
+        ca_env::EdgeGrids n_eg;
+        const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, n_eg, "ca_tiled_edge_grid");
+        if (rc) return rc;
+        free_edge_grids(e->eg);
+        e->eg = n_eg;
+        e->egrid = true;
+    } else {
+        e->egrid = false;
+        free_edge_grids(e->eg);
+    }
+    return CA_OK;
+}
+
+int ca_tiled_edge_grid_info(ca_env* e, int32_t arena, int32_t* on, int32_t* cells_x, int32_t* cells_y, float* cell_size_x, float* cell_size_y,
+                            int32_t* entries) {
+    if (!e) return CA_EINVAL;
+    if (arena < 0 || arena >= e->cfg.n_arenas) return fail(e, CA_ERANGE, "ca_tiled_edge_grid_info: arena %d of %d", (int)arena, e->cfg.n_arenas);
+    const EdgeGridDev* g = e->egrid ? &e->eg.desc[e->eg.desc.size() > 1 ? (size_t)arena : 0] : nullptr;
+    if (on) *on = g ? 1 : 0;
+    if (cells_x) *cells_x = g ? g->gx : 0;
+    if (cells_y) *cells_y = g ? g->gy : 0;
+    if (cell_size_x) *cell_size_x = g ? 1.0f / g->ics_x : 0.0f;
+    if (cell_size_y) *cell_size_y = g ? 1.0f / g->ics_y : 0.0f;
+    if (entries) *entries = g ? (int32_t)g->n_entries : 0;
+    return CA_OK;
+}
+
+int ca_edge_grid_build(const float* edges_pq, int32_t n_edges, float range, ca_edge_grid_desc* desc, uint32_t* cell_start, int32_t cell_cap,
+                       uint32_t* entries, int32_t entry_cap) {
+    if (!desc || n_edges < 0 || (n_edges > 0 && !edges_pq)) return fail(nullptr, CA_EINVAL, "ca_edge_grid_build: bad argument");
+    static_assert(sizeof(ca_edge_grid_desc) == sizeof(ca_edge_grid::Desc), "one layout");
+    static_assert(CA_EDGE_GRID_MAX_EDGES == ca_edge_grid::MAX_EDGES && CA_EDGE_GRID_MAX_ENTRIES == ca_edge_grid::MAX_ENTRIES, "one set of caps");
+    ca_edge_grid::Desc d;
+    std::vector<uint32_t> cs, en;
+    const bool fill = cell_start != nullptr && entries != nullptr;
+    const ca_edge_grid::Result r = ca_edge_grid::build(edges_pq, n_edges, range, d, fill ? &cs : nullptr, fill ? &en : nullptr);
+    memcpy(desc, &d, sizeof d);
+    if (r == ca_edge_grid::TOO_MANY_EDGES)
+        return fail(nullptr, CA_ERANGE, "ca_edge_grid_build: the edge grid holds at most %d edges per table, this one has %d", (int)ca_edge_grid::MAX_EDGES,
+                    (int)n_edges);
+    if (r == ca_edge_grid::TOO_MANY_ENTRIES)
+        return fail(nullptr, CA_ERANGE, "ca_edge_grid_build: the edge grid would hold %d%s entries (at most %d): long walls cover many cells -- "
+                    "subdivide the walls", (int)d.n_entries, d.n_entries == 0x7FFFFFFF ? "+" : "", (int)ca_edge_grid::MAX_ENTRIES);
+    if (r != ca_edge_grid::OK) return fail(nullptr, CA_ERANGE, "ca_edge_grid_build: range %g is not a positive number", (double)range);
+    if (!fill) return CA_OK;
+    if (cell_cap < 0 || entry_cap < 0 || (size_t)cell_cap < cs.size() || (size_t)entry_cap < en.size())
+        return fail(nullptr, CA_ESIZE, "ca_edge_grid_build: cell_start needs %zu words (cell_cap=%d), entries %zu (entry_cap=%d)", cs.size(), (int)cell_cap,
+                    en.size(), (int)entry_cap);
+    memcpy(cell_start, cs.data(), cs.size() * sizeof(uint32_t));
+    if (!en.empty()) memcpy(entries, en.data(), en.size() * sizeof(uint32_t));
     return CA_OK;
 }
 

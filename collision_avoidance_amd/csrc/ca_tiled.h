@@ -86,6 +86,30 @@ __device__ __forceinline__ int grid_cell(float v, float ics) {
     return (int)fminf(fmaxf(floorf(v * ics), -1073741824.0f), 1073741824.0f);
 }
 
+// ---- the static grid over the obstacle edges of a grid handle (ca_tiled_edge_grid; built by the host: ca_edge_grid_host.h) ----------
+// The solve launch above tests every edge of the arena's table for every agent, and so does the wall test of the advance launch.
+// Edges do not move: the host builds, once per installed table, a CSR table over the bounding box of the edges -- cell_start[cells + 1]
+// and entries (edge id | the lowest column of the edge's cell rectangle << 16 | its lowest row << 24) -- and the twins of the two
+// kernels walk the few cells an agent's range touches.  No launch, no sort, no barrier per step.  The table is unwrapped and clamped
+// (edge_cell): an agent outside the box, or a NaN, stands in an outermost cell.  Every index is clamped -- the run's end by the
+// table's entry count, the edge id by the arena's edge count -- so positions of any value stay inside the arrays.
+struct EdgeGridDev {   // one table's grid: a table per arena (indexed like tab_off), or one for all
+    float x0, y0, ics_x, ics_y;          // origin and reciprocal cell sizes
+    int gx, gy;                          // sides, 1 .. 256
+    unsigned n_entries;                  // entries of this table
+    unsigned cells_off, entries_off;     // where this table's cell_start / entries begin
+    unsigned pad;
+};
+struct TiledEdgeArgs : TiledGridArgs {
+    const EdgeGridDev* eg;
+    const unsigned* eg_cells;
+    const unsigned* eg_entries;
+};
+// ca_edge_grid_host.h's cell expression, operation for operation (fp32, no contraction): monotone in v
+__device__ __forceinline__ int edge_cell(float v, float x0, float ics, int g) {
+    return (int)fminf(fmaxf(floorf((v - x0) * ics), 0.0f), (float)(g - 1));
+}
+
 __global__ __launch_bounds__(256) void tiled_bin_kernel(const TiledGridArgs t) {
     const StepArgs& p = t.s;
     const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(256) void tiled_scatter_kernel(const TiledGridArgs 
 }
 
 // ---- launch 1: neighbour search, ORCA lines, LP2 / LP3 ------------------------------------------------------------------------
-// The solve launch has two kernels with one body (ca_tiled_solve.inl).
+// The solve launch has three kernels with one body (ca_tiled_solve.inl).
 // Grid (tiled_grid_solve_kernel, a handle made with CA_CREATE_TILED_GRID): lane tile * TILE + tid works for SORTED POSITION s of the
 // arena, its agent is i = sidx[s] -- the lanes of a wave then stand in the same few cells and walk the same runs -- and everything
 // else addresses by i as before.
@@ -164,85 +188,25 @@ __global__ __launch_bounds__(TILE) void tiled_grid_solve_kernel(const TiledGridA
 #include "ca_tiled_solve.inl"
 #undef CA_TILED_SOLVE_GRID
 }
+// ... and the grid kernel whose obstacle block walks the static edge grid (ca_tiled_edge_grid): everything else is the same text
+template <int KMAX, int TILE>
+__global__ __launch_bounds__(TILE) void tiled_grid_edges_solve_kernel(const TiledEdgeArgs t) {
+#define CA_TILED_SOLVE_GRID 2
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
+}
 
 // ---- launch 2: integrate, reward, wall / goal tests, the arena's partial results ---------------------------------------------------
-// (any workgroup size: a workgroup is one tile of one arena, blockDim.x = TILE)
+// (any workgroup size: a workgroup is one tile of one arena, blockDim.x = TILE; two kernels with one body, ca_tiled_advance.inl)
 __global__ __launch_bounds__(256) void tiled_advance_kernel(const TiledArgs t) {
-    const StepArgs& p = t.s;
-    const ColdK& c = *(ColdK*)p.cold;
-    __shared__ int s_red[4];   // [0] not-done agents, [1] wall hits, [2] goals, [3] largest squared speed (float bits)
-    const int tid = threadIdx.x, TILE = blockDim.x;
-    const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
-    if (arena_frozen(p, a)) return;   // (nobody writes arena_done in this launch)
-    const int N = p.N;
-    const int i = tile * TILE + tid;
-    const bool active = i < N;
-    const size_t q = (size_t)a * N + (active ? i : 0);
-    if (tid < 4) s_red[tid] = 0;
-    __syncthreads();
-    const bool nodone = (p.flags & 8u) != 0;  // CA_F_NODONE
-    const int steps0 = c.step_count[a];
-    float rew = 0.0f;
-    if (active) {
-        const V2 pos0 = mk(p.pos_x[q], p.pos_y[q]);
-        const V2 vel = mk(t.nv_x[q], t.nv_y[q]);
-        const V2 pos = pos0 + vel * p.time_step;   // (App. A.1)
-        double gx = c.goal_x[q], gy = c.goal_y[q];
-        V2 pref;
-        if (p.actions) {   // the directions of the prologue again, from the agent's own pre-step position: the same inputs, the same bits
-            V2 pf32;
-            action_pref(pos0, gx, gy, p.actions[q], pf32, pref);
-            rew = step_reward(c.reward_scale, vel, pf32, pref);
-            c.reward[q] = rew;
-        } else {
-            pref = goal_dir(pos, gx, gy);
-        }
-        if (p.flags & 2u) {  // CA_F_STATS
-            const ObstDev* tab = p.obst + (p.tab_off != nullptr ? p.tab_off[a] : 0);
-            const int ne = p.tab_off != nullptr ? p.tab_off[a + 1] - p.tab_off[a] : p.n_obst;
-            if (touches_wall(tab, ne, pos, p.radius)) atomicAdd(&s_red[1], 1);
-        }
-        bool goal_changed = false;
-        int done = c.agent_done[q];
-        if (!nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
-            if (c.done_mode == 2) {
-                const int rc = c.regoal_count[q];
-                regoal_draw(c, a, i, rc, &gx, &gy);
-                c.regoal_count[q] = rc + 1;
-            } else {
-                done = 1;
-                c.arrive_step[q] = tiled_steps_arrive(steps0, p.actions != nullptr, nodone);
-                arrival_goal(c, (int)q, &gx, &gy);
-                c.agent_done[q] = 1;
-            }
-            c.goal_x[q] = gx; c.goal_y[q] = gy;
-            goal_changed = true;
-            atomicAdd(&s_red[2], 1);
-        }
-        if (done == 0) atomicAdd(&s_red[0], 1);
-        atomicMax(reinterpret_cast<unsigned*>(&s_red[3]), __float_as_uint(absSq(vel)));
-        const V2 o = obs_frame(pref, p.actions != nullptr || goal_changed, pos, gx, gy);
-        c.orient_x[q] = o.x; c.orient_y[q] = o.y;
-        c.pos_x[q] = pos.x; c.pos_y[q] = pos.y;
-        c.vel_x[q] = vel.x; c.vel_y[q] = vel.y;
-        c.pref_x[q] = pref.x; c.pref_y[q] = pref.y;
-        t.nv_x[q] = pos.x; t.nv_y[q] = pos.y;   // the copy the pair count reads
-    }
-    if (p.actions && (p.flags & 2u)) {   // sum of rewards: a tree inside the wave, one f64 atomic per wave
-        double r = active ? (double)rew : 0.0;
-        for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
-        if ((tid & 63) == 0 && tile * TILE + tid < N)
-            atomicAdd(reinterpret_cast<double*>(&c.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), r);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned* sc = t.scr + (size_t)a * TS_STRIDE;
-        if (s_red[0]) atomicAdd(&sc[TS_NOTDONE], (unsigned)s_red[0]);
-        atomicMax(&sc[TS_VMAX2], (unsigned)s_red[3]);
-        unsigned long long* st = c.arena_stats + (size_t)a * ST_STRIDE;
-        if (s_red[1]) atomicAdd(&st[ST_OBST_COLL], (unsigned long long)s_red[1]);
-        if (s_red[2]) atomicAdd(&st[ST_GOALS], (unsigned long long)s_red[2]);
-    }
+#define CA_TILED_ADVANCE_EDGES 0
+#include "ca_tiled_advance.inl"
+#undef CA_TILED_ADVANCE_EDGES
+}
+__global__ __launch_bounds__(256) void tiled_grid_edges_advance_kernel(const TiledEdgeArgs t) {
+#define CA_TILED_ADVANCE_EDGES 1
+#include "ca_tiled_advance.inl"
+#undef CA_TILED_ADVANCE_EDGES
 }
 
 // ---- launch 3: pair count on the copy, end of the episode, the arena's words, the in-kernel reset ---------------------------------

@@ -1,6 +1,6 @@
-// ca_tiled_solve.inl -- the statements of the tiled path's solve launch, included by ca_tiled.h into each of its two kernels
-// (CA_TILED_SOLVE_GRID 0: tiled_solve_kernel, 1: tiled_grid_solve_kernel; `t` is the kernel's argument block, KMAX and TILE its
-// template parameters).  Textual inclusion and not a shared __device__ function: through a function -- by reference or by value --
+// ca_tiled_solve.inl -- the statements of the tiled path's solve launch, included by ca_tiled.h into each of its three kernels
+// (CA_TILED_SOLVE_GRID 0: tiled_solve_kernel, 1: tiled_grid_solve_kernel, 2: tiled_grid_edges_solve_kernel -- the grid kernel with the
+// obstacle edges found through the static edge grid; `t` is the kernel's argument block, KMAX and TILE its template parameters).  Textual inclusion and not a shared __device__ function: through a function -- by reference or by value --
 // the plain kernel's instruction text moved, and that kernel is to stay what it was before the grid existed.
     const StepArgs& p = t.s;
     extern __shared__ float4 smem4[];
@@ -53,6 +53,43 @@
 #pragma unroll
         for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
         const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
+#if CA_TILED_SOLVE_GRID == 2
+        // The static edge grid (ca_edge_grid_host.h): the cells of the columns cell(fl(x - range)) .. cell(fl(x + range)) and the rows
+        // likewise, 3 x 3 but for a rounding of ics; an edge registered in several of them is taken in the low corner of the intersection of its
+        // rectangle with this one, so no edge enters twice; an accepted edge passes the test of the scan below, on tab[e].  The list
+        // is the S smallest distinct keys of the accepted set: the order of the walk is immaterial.  Per-lane walks: the lanes of a
+        // wave stand in the same few cells (sorted positions), so their loads of a run and of its records fall into the same lines.
+        if (active) {
+            const EdgeGridDev g = t.eg[p.tab_off != nullptr ? a : 0];
+            const unsigned* cs = t.eg_cells + g.cells_off;
+            const unsigned* en = t.eg_entries + g.entries_off;
+            const float range = p.time_horizon_obst * p.max_speed + p.radius;
+            const int cxlo = edge_cell(pos.x - range, g.x0, g.ics_x, g.gx), cxhi = edge_cell(pos.x + range, g.x0, g.ics_x, g.gx);
+            const int cylo = edge_cell(pos.y - range, g.y0, g.ics_y, g.gy), cyhi = edge_cell(pos.y + range, g.y0, g.ics_y, g.gy);
+            for (int r = cylo; r <= cyhi; ++r) {
+                for (int c = cxlo; c <= cxhi; ++c) {
+                    const unsigned* run = cs + (r * g.gx + c);
+                    const unsigned hi = min(run[1], g.n_entries);   // (every index clamped: ca_tiled.h EdgeGridDev)
+                    for (unsigned u = run[0]; u < hi; ++u) {
+                        const unsigned w = en[u];
+                        const int e = (int)(w & 0xFFFFu);
+                        if (e >= n_edges || max((int)((w >> 16) & 0xFFu), cxlo) != c || max((int)(w >> 24), cylo) != r) continue;
+                        const ObstDev& o1 = tab[e];
+                        const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
+                        const float alol = leftOf(a1, a2, pos);
+                        const float dsl = div_ir(sqr(alol), absSq(a2 - a1));
+                        if (dsl < rangeSq && alol < 0.0f) {
+                            const float dsq = distSqPointSegment(a1, a2, pos);
+                            if (dsq < rangeSq) {
+                                ++oin;
+                                sorted_insert<SMAX>(okey, make_key(dsq, e));
+                            }
+                        }
+                    }
+                }
+            }
+        }
+#else
         for (int e = 0; e < n_edges; ++e) {   // (uniform: scalar loads of the edge records)
             const ObstDev& o1 = tab[e];
             const V2 a1 = mk(o1.px, o1.py), a2 = mk(o1.qx, o1.qy);
@@ -66,6 +103,7 @@
                 }
             }
         }
+#endif
         if (active) {
 #pragma unroll
             for (int k = 0; k < SMAX; ++k)

@@ -93,11 +93,14 @@ class VecCollisionAvoidanceEnv:
                workgroup per arena, n_agents <= 1024.  "grid": the tiled path with its uniform-grid neighbour search
                (CA_CREATE_TILED | CA_CREATE_TILED_GRID): the arena's agents are sorted by cell in three more launches per step and an
                agent tests the cells its range touches instead of the whole arena (tiled_grid_info()); the same results.
+    edge_grid: True (with tiled="grid" only; any other handle raises the library's error): set_edge_grid(True) once the obstacles are
+               installed -- the obstacle edges in range and the wall test come from a static grid over the edges instead of a scan
+               of the arena's whole table (edge_grid_info()); the same results.  False (default): the scan.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None, agent_counts=None, tiled=False):
+                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False):
         if tiled not in (False, True, "grid", None, 0, 1):
             raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
         if tiled and (agent_params or agent_counts is not None):
@@ -157,6 +160,8 @@ class VecCollisionAvoidanceEnv:
             self.set_obstacles_per_arena(worlds)
         else:
             self.set_obstacles(polys)
+        if edge_grid:
+            self.set_edge_grid(True)
         if agent_counts is not None:
             self.set_agent_counts(agent_counts)
         if scenario is not None:
@@ -416,6 +421,22 @@ class VecCollisionAvoidanceEnv:
         v = [C.c_int32() for _ in range(3)] + [C.c_float(), C.c_int32()]
         self._call("ca_tiled_grid_info", self.h, *[C.byref(x) for x in v])
         return dict(grid=bool(v[0].value), cells_x=v[1].value, cells_y=v[2].value, cell_size=v[3].value, sort_launches=v[4].value)
+
+    def set_edge_grid(self, on=True):
+        """The static edge grid of a tiled="grid" handle on or off (ca_tiled_edge_grid): a uniform grid over the obstacle edges of each
+        installed table, built once on the host and rebuilt by set_obstacles() / set_obstacles_per_arena() while on.  Configuration
+        like the obstacles: it survives reset() and init_scenario() and is no part of get_state().  Results do not change.  Raises
+        on any other handle, and for a world of more than 65535 edges or of walls so long that the table passes its cap (subdivide
+        them); the handle then keeps scanning."""
+        self._call("ca_tiled_edge_grid", self.h, 1 if on else 0)
+
+    def edge_grid_info(self, arena=0):
+        """dict(on, cells_x, cells_y, cell_size_x, cell_size_y, entries) of the static edge grid of `arena` (ca_tiled_edge_grid_info);
+        zeros while off and on every other handle."""
+        v = [C.c_int32() for _ in range(3)] + [C.c_float(), C.c_float(), C.c_int32()]
+        self._call("ca_tiled_edge_grid_info", self.h, int(arena), *[C.byref(x) for x in v])
+        return dict(on=v[0].value, cells_x=v[1].value, cells_y=v[2].value, cell_size_x=v[3].value, cell_size_y=v[4].value,
+                    entries=v[5].value)
 
     # ---- per-agent ORCA parameters (sim.addAgent's per-agent arguments, env.py:126-133) ---------------
     _AGENT_PARAMS = ("radius", "max_speed", "time_horizon", "time_horizon_obst")

@@ -484,6 +484,55 @@ int ca_tiled_info(ca_env* env, int32_t* tiled, int32_t* tile_agents, int32_t* ti
  * wrapped cell table (powers of two, at least 8), *cell_size = the width of a cell (half of neighbor_dist), *sort_launches = kernel
  * launches in front of the solve launch.  All zeros on every handle without the flag. */
 int ca_tiled_grid_info(ca_env* env, int32_t* grid, int32_t* cells_x, int32_t* cells_y, float* cell_size, int32_t* sort_launches);
+
+/* The static edge grid of a grid handle (CA_CREATE_TILED | CA_CREATE_TILED_GRID): opt-in, off by default.  Without it every agent tests
+ * every edge of its arena's table in every step, for its obstacle list and (CA_F_STATS) for the wall test: O(N * E).  Obstacle edges
+ * do not move, so an index over them is built once on the host when a table is installed: per table a uniform grid over the bounding
+ * box of its edges, UNWRAPPED and clamped, stored as CSR -- cell_start[cells_x * cells_y + 1] and entries[] --, and the solve and
+ * advance launches walk the few cells an agent's range touches.  No launch, sort or barrier per step: ca_tiled_info still reports
+ * launches_per_step = 6.  Everything a step leaves -- lists, order, counts, the overflow word and its status, statistics -- is the
+ * same bit for bit: an obstacle list is the max_obst_neighbors smallest (distance, edge id) keys of the in-range set, in whatever
+ * order the candidates arrive.
+ *   - The cell of a coordinate v along an axis with origin x0, reciprocal cell size ics and g cells, in fp32, each operation rounded once:
+ *         cell(v) = (int)fminf(fmaxf(floorf((v - x0) * ics), 0.0f), (float)(g - 1))
+ *     i.e. clamp((int)floor((v - x0) * ics), 0, g - 1), with a coordinate outside the box, an infinity or a NaN clamped into an outermost
+ *     cell.  The host builder and the kernels evaluate exactly this expression.  Cells are max(range, extent / 256) wide per axis,
+ *     range = time_horizon_obst * max_speed + radius, extent = the side of the edges' bounding box plus two margins: 1 .. 256 cells.
+ *   - An edge is registered in every cell of its bounding box inflated by `margin` = 16 * 2^-24 * (largest |coordinate| of the table +
+ *     range), which covers the fp32 rounding of the in-range test (DESIGN.md 7g derives it).  An entry is
+ *     edge id | lowest column of the edge's cell rectangle << 16 | its lowest row << 24.
+ *   - An agent at (x, y) walks the cells of columns cell(x - range) .. cell(x + range) and rows likewise (fp32 differences), 3 x 3
+ *     at most but for a rounding of ics (then 4 along an axis), and takes an edge only in cell (max(edge's lowest column, own lowest column), max(edge's lowest row, own lowest row)):
+ *     the low corner of the two rectangles' intersection, so no edge twice.
+ * ca_tiled_edge_grid(env, 1): builds the grids of the installed tables (one per arena with ca_set_obstacles_per_arena, else one for all
+ * arenas) and uses them from the next step; (env, 0): back to the scan.  Drains the stream.  Configuration, like the obstacle tables:
+ * it persists across ca_reset*, CA_F_AUTORESET and ca_init_scenario and is no part of the state a caller saves through ca_get.  While
+ * on, ca_set_obstacles and ca_set_obstacles_per_arena rebuild the grids for the new tables; if that fails the install fails as a
+ * whole and the previous tables and grids stay.
+ *   - not a grid handle (create_flags != 5) -> CA_EINVAL (ca_last_error names the flags); the handle keeps working;
+ *   - a table of more than CA_EDGE_GRID_MAX_EDGES edges, or whose grid would hold more than CA_EDGE_GRID_MAX_ENTRIES entries (very long
+ *     diagonal walls cover many cells) -> CA_ERANGE, "subdivide the walls"; the handle stays as it was (it keeps scanning). */
+#define CA_EDGE_GRID_MAX_EDGES 65535
+#define CA_EDGE_GRID_MAX_ENTRIES (1 << 22)
+int ca_tiled_edge_grid(ca_env* env, int32_t on);
+/* The static edge grid of `arena` (0 .. n_arenas - 1; a common table: the same for every arena): *on = 1, *cells_x / *cells_y = the
+ * table's sides, *cell_size_x / *cell_size_y = the cells' widths, *entries = entries of the table.  All zeros while off and on every
+ * other handle. */
+int ca_tiled_edge_grid_info(ca_env* env, int32_t arena, int32_t* on, int32_t* cells_x, int32_t* cells_y, float* cell_size_x, float* cell_size_y,
+                            int32_t* entries);
+/* The builder itself, handle-free and without a device (tests, tools): the grid of the n_edges edges edges_pq[n_edges][4] = (px, py,
+ * qx, qy) for obstacle range `range`.  cell_start == NULL or entries == NULL: fills *desc only, so that the caller can size its
+ * buffers (gx * gy + 1 words and n_entries words); else also cell_start[gx * gy + 1] and entries[n_entries] (too small a cap ->
+ * CA_ESIZE).  CA_ERANGE as for ca_tiled_edge_grid; messages through ca_last_error(NULL). */
+typedef struct ca_edge_grid_desc {
+    float x0, y0;        /* the table's origin */
+    float ics_x, ics_y;  /* reciprocal cell sizes */
+    int32_t gx, gy;      /* sides, 1 .. 256 */
+    int32_t n_entries;
+    float margin;        /* the inflation of an edge's bounding box (rounded up to fp32) */
+} ca_edge_grid_desc;
+int ca_edge_grid_build(const float* edges_pq, int32_t n_edges, float range, ca_edge_grid_desc* desc, uint32_t* cell_start, int32_t cell_cap,
+                       uint32_t* entries, int32_t entry_cap);
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
 const char* ca_source_sha(void);

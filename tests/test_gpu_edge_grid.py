@@ -1,0 +1,249 @@
+"""The static edge grid of a grid handle on the GPU (ca_tiled_edge_grid; csrc/ca_tiled.h tiled_grid_edges_solve_kernel and
+tiled_grid_edges_advance_kernel): the obstacle edges in range and the wall test found through a uniform grid over the edges instead of
+a scan of the arena's table.  Everything is compared bit for bit with the unchanged CPU oracle through tests/helpers.py, on the hall
+worlds of tests/edge_grid_scenes.py: the crowd's enclosing box full of pillars (N = 300: 488 edges, N = 1100: 1940; with the crowd's
+parameters -- range 2.0 -- the largest obstacle list over 12 steps of seed 3 is 8, so a capacity of 16 never truncates)."""
+import numpy as np
+import pytest
+
+from collision_avoidance_amd import _lib, alan, scenarios
+from oracle import oracle as o
+from tests import edge_grid_scenes as E
+from tests import helpers as H
+from tests import tiled_scenes as S
+
+pytestmark = pytest.mark.gpu
+OFF = dict(on=0, cells_x=0, cells_y=0, cell_size_x=0.0, cell_size_y=0.0, entries=0)
+
+
+def _pair(A, N, polys, seed=3, S_=16, p=None, **kw):
+    p = p or H.scenario_params("crowd", N)
+    g = H.make_gpu(A, N, "crowd", p, seed=seed, tiled="grid", edge_grid=True, polys=polys, max_obst_neighbors=S_, **kw)
+    orc = H.make_oracle(A, N, "crowd", p, seed=seed, polys=polys, max_obst_neighbors=S_)
+    info = g.edge_grid_info()
+    assert info["on"] == 1 and info["entries"] > 0 and info["cell_size_x"] >= 2.0 and info["cell_size_y"] >= 2.0, info
+    assert g.tiled_info()["launches_per_step"] == 6
+    return g, orc
+
+
+def _steps(g, orc, A, N, n, seed, what, obs=True):
+    rng = np.random.RandomState(seed)
+    for s in range(n):
+        act = rng.uniform(-1, 1, (A, N)).astype(np.float32)
+        g.step(act, with_obs=obs, stats=True)
+        orc.step(act, flags=S.FULL if obs else o.F_STATS)
+        H.assert_state_equal(g, orc, "%s step %d" % (what, s), obs=obs, reward=True)
+    H.assert_stats_equal(g, orc, what)
+
+
+def _place(env, fld, px, py):
+    env.set(fld.FLD_POS_X, np.ascontiguousarray(px, np.float32))
+    env.set(fld.FLD_POS_Y, np.ascontiguousarray(py, np.float32))
+
+
+# ---- 1. the hall ----------------------------------------------------------------------------------------------------------------------
+def test_hall_300():
+    N = 300
+    polys = E.hall(N)
+    assert len(polys) == 122 and sum(len(q) for q in polys) == 488
+    g, orc = _pair(1, N, polys)
+    assert g.tiled_info()["tiles_per_arena"] == 3 and g.edge_grid_info()["entries"] >= 488
+    _steps(g, orc, 1, N, 12, 3, "hall 300")
+    st = g.stats()
+    assert st["obst_collisions"] > 0 and st["obst_overflow"] == 0 and g.edge_grid_info()["on"] == 1, st
+    assert g.obstacle_neighbor_lists()[1].max() > 255                                      # edge ids beyond 8 bits are listed
+    g.close()
+
+
+# ---- 2. lists of four: the overflow -----------------------------------------------------------------------------------------------------
+def _quiet_positions(N, agent):
+    """every agent beside a pillar column, between two pillar rows (two or three edges in range), `agent` alone in the middle of four
+    pillars (eight edges in range)"""
+    spots = [(1.5 + 3.0 * i + dx, 3.0 + 3.0 * j) for j in range(10) for i in range(11) for dx in (-0.2, 0.0, 0.2)]
+    px, py = np.asarray(spots[:N], np.float32).T.copy()
+    px[agent], py[agent] = 15.0, 15.0
+    return px[None, :], py[None, :]
+
+
+def test_overflow_names_the_same_agent_and_truncates_alike():
+    N, agent = 300, 200
+    polys = E.hall(N)
+    p = H.scenario_params("crowd", N)
+    g, orc = _pair(1, N, polys, S_=4, arena_offset=0)
+    off = H.make_gpu(1, N, "crowd", p, seed=3, tiled="grid", polys=polys, max_obst_neighbors=4)
+    assert off.edge_grid_info() == OFF
+    px, py = _quiet_positions(N, agent)
+    msgs = []
+    for e in (g, off):
+        _place(e, _lib, px, py)
+        e.orca_step(stats=True)
+        with pytest.raises(RuntimeError) as ei:
+            e.sync()
+        msgs.append(str(ei.value))
+    assert "(-5)" in msgs[0] and "agent %d had 8 obstacle edges" % agent in msgs[0], msgs[0]
+    assert msgs[0] == msgs[1], msgs
+    _place(orc, o, px, py)
+    orc.orca_step(flags=o.F_STATS)
+    g._call("ca_allow_obstacle_overflow", g.h, 1)
+    H.assert_state_equal(g, orc, "overflow, the step that raised")
+    for s in range(3):
+        g.orca_step(stats=True)
+        orc.orca_step(flags=o.F_STATS)
+        H.assert_state_equal(g, orc, "overflow step %d" % s)
+    H.assert_stats_equal(g, orc, "overflow")
+    assert g.stats()["obst_overflow"] >= 1
+    g.close(); off.close()
+    # the random crowd in the same hall: many agents with more than four edges in range
+    g, orc = _pair(1, N, polys, S_=4, allow_obst_overflow=True)
+    _steps(g, orc, 1, N, 6, 3, "overflow crowd", obs=False)
+    assert g.stats()["obst_overflow"] > 0
+    g.close()
+
+
+# ---- 3. agents outside the table ------------------------------------------------------------------------------------------------------
+def test_agents_outside_the_table():
+    N = 300
+    g, orc = _pair(1, N, E.hall(N))
+    e = np.float32(scenarios.crowd_envsize(N))
+    rng = np.random.RandomState(5)
+    px, py = g.get(_lib.FLD_POS_X), g.get(_lib.FLD_POS_Y)
+    tenth = N // 10
+    for side in range(4):                                              # a tenth 50 units outside on each side
+        sl = slice(side * tenth, (side + 1) * tenth)
+        along = rng.uniform(-10, float(e) + 10, tenth)
+        out = (-50.0 - rng.uniform(0, 5, tenth)) if side % 2 == 0 else (float(e) + 50.0 + rng.uniform(0, 5, tenth))
+        (px if side < 2 else py)[0, sl], (py if side < 2 else px)[0, sl] = out, along
+    k = 4 * tenth                                                      # ... and some exactly `range` = 2.0 from the box's wall, outside
+    for j, (x, y) in enumerate([(-2.0, 7.0), (e + np.float32(2.0), 11.0), (9.0, -2.0), (13.0, e + np.float32(2.0)), (-2.0, -2.0),
+                                (np.nextafter(np.float32(-2.0), np.float32(0.0)), 20.0), (np.nextafter(np.float32(-2.0), np.float32(-3.0)), 23.0)]):
+        px[0, k + j], py[0, k + j] = x, y
+    _place(g, _lib, px, py)
+    _place(orc, o, px, py)
+    _steps(g, orc, 1, N, 3, 5, "outside")
+    g.close()
+
+
+# ---- 4. a world per arena ------------------------------------------------------------------------------------------------------------------
+def test_per_arena_worlds():
+    A, N = 2, 300
+    g, orc = _pair(A, N, dict(per_arena=[E.hall(N), E.lone_box(N)]), seed=6)
+    i0, i1 = g.edge_grid_info(0), g.edge_grid_info(1)
+    assert i0["on"] == i1["on"] == 1 and i0["entries"] >= 488 and 4 <= i1["entries"] < 100 and i0 != i1, (i0, i1)
+    _steps(g, orc, A, N, 5, 6, "two worlds")
+    assert g.stats()["obst_collisions"] > 0
+    g.close()
+
+
+# ---- 5. far from the origin ------------------------------------------------------------------------------------------------------------------
+def test_translated_world():
+    N, sx, sy = 300, 5e4, -5e4
+    e = scenarios.crowd_envsize(N)
+    p = H.scenario_params("crowd", N, spawn_x0=sx, spawn_x1=sx + e, spawn_y0=sy, spawn_y1=sy + e,
+                          goal_x0=sx, goal_x1=sx + e, goal_y0=sy, goal_y1=sy + e)
+    g, orc = _pair(1, N, E.hall(N, (sx, sy)), p=p)
+    rng = np.random.RandomState(9)
+    px, py = (sx + rng.uniform(0, e, (1, N))).astype(np.float32), (sy + rng.uniform(0, e, (1, N))).astype(np.float32)
+    gx, gy = sx + rng.uniform(0, e, (1, N)), sy + rng.uniform(0, e, (1, N))
+    for env, fld in ((g, _lib), (orc, o)):
+        _place(env, fld, px, py)
+        env.set(fld.FLD_GOAL_X, gx)
+        env.set(fld.FLD_GOAL_Y, gy)
+    _steps(g, orc, 1, N, 3, 9, "translated")
+    assert g.obstacle_neighbor_lists()[0].max() > 0
+    g.close()
+
+
+# ---- 6. switching ---------------------------------------------------------------------------------------------------------------------------
+def test_switching_and_new_tables():
+    N = 300
+    g, orc = _pair(1, N, E.hall(N))
+    first = g.edge_grid_info()
+    _steps(g, orc, 1, N, 2, 11, "on")
+    g.set_edge_grid(False)
+    assert g.edge_grid_info() == OFF and g.tiled_info()["launches_per_step"] == 6
+    _steps(g, orc, 1, N, 2, 12, "off")
+    g.set_edge_grid(True)
+    assert g.edge_grid_info() == first
+    _steps(g, orc, 1, N, 2, 13, "on again")
+    g.reset(with_obs=False)                                             # configuration: it survives a reset and a scenario
+    g.init_scenario("crowd")
+    orc.init_scenario(H.SCN["crowd"])
+    assert g.edge_grid_info() == first
+    world = E.hall(N)[:40] + E.lone_box(N)
+    g.set_obstacles(world)
+    orc.set_obstacles(world)
+    second = g.edge_grid_info()
+    assert second["on"] == 1 and second != first and second["entries"] < first["entries"], (first, second)
+    _steps(g, orc, 1, N, 3, 14, "another world")
+    g.set_obstacles([])                                                 # no edges at all: one empty cell
+    orc.set_obstacles([])
+    assert g.edge_grid_info()["entries"] == 0 and g.edge_grid_info()["cells_x"] == 1
+    _steps(g, orc, 1, N, 2, 15, "no world")
+    g.close()
+
+
+# ---- 7. refusals and neighbours --------------------------------------------------------------------------------------------------------------
+def test_refusals():
+    N = 300
+    p = H.scenario_params("crowd", N)
+    L = _lib.load()
+    for tiled, flags in ((True, b"0x1"), (False, b"0x0")):
+        h = H.make_gpu(1, N, "crowd", p, seed=1, tiled=tiled)
+        orc = H.make_oracle(1, N, "crowd", p, seed=1)
+        assert L.ca_tiled_edge_grid(h.h, 1) == -1
+        msg = L.ca_last_error(h.h)
+        assert b"create_flags 0x5" in msg and flags in msg, msg
+        assert h.edge_grid_info() == OFF
+        h.orca_step(stats=True)                                         # the handle keeps working
+        orc.orca_step(flags=o.F_STATS)
+        H.assert_state_equal(h, orc, "after the refusal")
+        h.close()
+        with pytest.raises(RuntimeError, match="ca_tiled_edge_grid"):
+            H.make_gpu(1, N, "crowd", p, seed=1, tiled=tiled, edge_grid=True)
+
+
+def test_alan_rollout_trace_and_freeze():
+    N = 300
+    g, orc = _pair(1, N, E.hall(N), seed=8)
+    g.alan_configure(alan.DEFAULT_ACTIONS)
+    orc.alan_configure(alan.DEFAULT_ACTIONS)
+    u = np.random.RandomState(8).uniform(0, 1, (1, N))
+    g.alan_step(u, stats=True)
+    orc.alan_step(u, flags=o.F_STATS)
+    H.assert_state_equal(g, orc, "alan step", reward=True)
+    tr = g.rollout(4, stats=True, freeze=True, trace=dict(every=1, channels=("pos",), arenas=False))
+    rec = tr["agents"].cpu().numpy()
+    for r in range(4):
+        orc.orca_step(flags=o.F_STATS | o.F_FREEZE)
+        H._eq(rec[r, 0], orc.get(o.FLD_POS_X), "trace record %d, pos_x" % r)
+        H._eq(rec[r, 1], orc.get(o.FLD_POS_Y), "trace record %d, pos_y" % r)
+    H.assert_state_equal(g, orc, "traced rollout")
+    done = np.ones((1, N), np.int32)                                    # everybody has arrived: the arena ends, and freezes
+    g.set(_lib.FLD_AGENT_DONE, done)
+    orc.set(o.FLD_AGENT_DONE, done)
+    for s in range(3):
+        g.orca_step(stats=True, freeze=True)
+        orc.orca_step(flags=o.F_STATS | o.F_FREEZE)
+        H.assert_state_equal(g, orc, "freeze step %d" % s)
+    H._eq(g.get(_lib.FLD_ARENA_STATS)[:, 6], orc.get(o.FLD_ARENA_STATS)[:, 6], "frozen steps")
+    assert g.get(_lib.FLD_ARENA_STATS)[0, 6] > 0 and g.tiled_info()["launches_per_step"] == 6
+    H.assert_stats_equal(g, orc, "alan, trace, freeze")
+    g.close()
+
+
+# ---- 8. the largest arena -----------------------------------------------------------------------------------------------------------------------
+def test_largest_arena_in_its_hall():
+    N = _lib.MAX_AGENTS_LARGE
+    polys = E.hall(N)
+    g, orc = _pair(1, N, polys, seed=5)
+    info = g.edge_grid_info()
+    assert sum(len(q) for q in polys) > 25000 and info["entries"] >= sum(len(q) for q in polys) and info["cells_x"] > 100, info
+    rng = np.random.RandomState(5)
+    for s in range(2):
+        act = rng.uniform(-1, 1, (1, N)).astype(np.float32)
+        g.step(act, with_obs=False, stats=True)
+        orc.step(act, flags=o.F_STATS)
+    H.assert_state_equal(g, orc, "16384 agents in their hall", reward=True)
+    H.assert_stats_equal(g, orc, "16384 agents in their hall")
+    assert g.stats()["obst_collisions"] > 0
+    g.close()
