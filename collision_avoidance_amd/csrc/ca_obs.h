@@ -2,6 +2,7 @@
 // Part of the HIP kernels of libcaenv.so (see ca_kernels.h for the overview and the numerics contract).
 #pragma once
 #include "ca_common.h"
+#include "ca_obs_chord.h"
 
 namespace ca {
 
@@ -22,7 +23,11 @@ namespace ca {
 //   agents form ONE list walked by all its lanes, and so do the wall items: a wave takes a trip only for
 //   what the waves before it do not hold (a settled crowd has three wall items per workgroup: one wave, once).
 //   The ray/segment test itself is the reference's arithmetic, so neither culling nor dealing ever
-//   changes a result.  A hit is merged into the ray's slot with one LDS ds_min_u64 on the key
+//   changes a result.  Of a neighbour's octagon a lane tests the chord its ray ENTERS by and nothing else, wherever that
+//   chord decides the pair: the agent outside the neighbour's circle and no vertex within the filter's tolerance of the
+//   ray's line (the rule and its argument: ca_obs_chord.h; CA_OBS_ENTRY_CHORD).  A wave whose lanes all qualify skips the
+//   exit chord's build and accept test and the ordering of the two behind one uniform branch; any other pair goes through
+//   both survivors as before.  A hit is merged into the ray's slot with one LDS ds_min_u64 on the key
 //   (distance bits << 32 | segment index): the minimum distance wins and equal distances resolve
 //   to the first segment, exactly like a serial first-minimum scan.
 // Phase B -- lane per RAY: re-derives the winning segment's hit point and velocity and writes its
@@ -78,6 +83,11 @@ struct ObsArgs {
 #endif
 #ifndef CA_OBS_DEAL_WALLS
 #define CA_OBS_DEAL_WALLS 1
+#endif
+// CA_OBS_ENTRY_CHORD -- phase A tests only the chord a ray ENTERS a neighbour's octagon by wherever that decides the pair
+// (ca_obs_chord.h; 0 = both surviving chords through the reference's arithmetic and an ordering of the two, the form it replaced).
+#ifndef CA_OBS_ENTRY_CHORD
+#define CA_OBS_ENTRY_CHORD 1
 #endif
 
 // LDS (bytes): arena px,py,vx,vy [N] | keys [16][16] u64 | neighbour positions relative to the agent [16][16] float2 | agent frames [16] float4 | nb idx [16][16] | obstacle idx [16][16]
@@ -494,6 +504,9 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
     // the waves took a second, nearly empty trip) still wastes a third of the issue slots of this loop; with one
     // list only the first wave ever takes a second trip, for the few pairs beyond the workgroup's lane count.
     const int ntot = s_cnt[0];
+#ifdef CA_STAMPS   // (diagnostic build) this wave's pair trips: all, those whose lanes all qualify, those that ran the two-chord block
+    unsigned long long n_trips = 0, n_fast = 0, n_two = 0;
+#endif
     for (int pi = tid; pi < ntot; pi += OBS_BS) {
         const int pr = s_pair[pi];
         const int ga = pr >> 8, k = (pr >> 4) & 15, ray = pr & 15;
@@ -513,55 +526,127 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
         // third one when the line grazes a vertex -- go through the reference's arithmetic below.
         // Vertex e of the octagon is R (cos e pi/4, -sin e pi/4) (env.py:335-350) and vertex e + 4 its mirror image,
         // so the eight cross products are four, each added to and subtracted from the ray x centre term.
-        const float wx = fr.x * s10x + fr.y * s10y, wy = fr.x * s10y - fr.y * s10x;
-        const float wb = wx * ry - wy * rx;
-        float Rp = p.radius, tol = tol_u;
-        if constexpr (AP) {   // the source's radius, in the filter and in its tolerance
-            Rp = s_noct[(pr >> 4) * 8].x;
-            tol = 2e-5f * p.rays[0] * (p.rays[0] + 2.0f * Rp + 1.0f);
-        }
-        const float R = Rp, Rh = 0.70710678f * R;
-        const float c0 = R * wy, c2 = R * wx, c1 = Rh * (wx + wy), c3 = Rh * (wy - wx);
-        const float cr[8] = {wb - c0, wb - c1, wb - c2, wb + c3, wb + c0, wb + c1, wb + c2, wb - c3};
-        unsigned acc = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float ca = cr[e], cb = cr[(e + 1) & 7];
-            const bool same_side = (ca > tol && cb > tol) || (ca < -tol && cb < -tol);
-            acc |= same_side ? 0u : (1u << e);
-        }
-        // ascending chord index, strict '<': the first minimum wins.  Two surviving chords (entry and exit)
-        // are taken together in straight-line code; the arithmetic of each is the reference's (utils.py:14-38).
-        while (acc) {
-            const int e1 = __ffs(acc) - 1;
-            acc &= acc - 1;
-            const bool two = acc != 0;
-            const int e2 = two ? __ffs(acc) - 1 : e1;
-            acc &= acc - 1;  // (0 & anything stays 0)
-            SegGeom g1, g2;
-            build_nb(fr, rx, ry, e1, g1, pr >> 4);
-            build_nb(fr, rx, ry, e2, g2, pr >> 4);
-            float dn1, dn2;
-            const bool ok1 = accept_nb(g1, s10x, s10y, dn1), ok2 = accept_nb(g2, s10x, s10y, dn2) && two;
-            // Both accepted (the ray enters through one chord and leaves through the other): the distance is monotone
-            // in t = t_numer / denom, so when the two quotients differ by more than 1e-5 relative -- 30x what the
-            // division, the products and the square root of utils.py:34-38 can round away -- the nearer chord is
-            // known from a cross-multiplication and only ITS distance is computed.  Anything closer than that (the
-            // ray through a shared vertex), or a crossing at the origin, takes both through the reference's
-            // arithmetic and compares the rounded distances as the reference does.
-            const float lhs = fabsf(g1.t_numer) * fabsf(dn2), rhs = fabsf(g2.t_numer) * fabsf(dn1);  // t1 < t2  <=>  lhs < rhs
-            const bool first = ok1 && (!ok2 || lhs < rhs);
-            const float tnw = first ? g1.t_numer : g2.t_numer, dnw = first ? dn1 : dn2;
-            const int ew = first ? e1 : e2;
-            const bool sure = fminf(lhs, rhs) < 0.99999f * fmaxf(lhs, rhs) && fmaxf(lhs, rhs) > 1e-30f &&
-                              fabsf(tnw) > 1e-12f * fabsf(dnw);
-            if (ok1 && ok2 && !sure) {
-                const float d1 = hit_dist(g1.t_numer, dn1, s10x, s10y), d2 = hit_dist(g2.t_numer, dn2, s10x, s10y);
-                if (d1 < best) { best = d1; best_m = 8 * k + e1; }
-                if (d2 < best) { best = d2; best_m = 8 * k + e2; }
-            } else {
-                const float dw = hit_dist(tnw, dnw, s10x, s10y);
-                if ((ok1 || ok2) && dw < best) { best = dw; best_m = 8 * k + ew; }
+        if constexpr (CA_OBS_ENTRY_CHORD != 0) {
+            // The selection rule is ca_obs_chord.h's (the argument is written there): a pair whose agent is outside the
+            // neighbour's circle and whose ray's line passes no vertex within `tol` is decided by its ENTRY chord alone -- accepted,
+            // it is the pair's first minimum; rejected, the pair has no hit -- so that chord is `first`, and nothing is left behind it.
+            // Every other pair (an agent inside or near the circle, a grazed vertex, three survivors) starts with its lowest
+            // survivor and keeps the arithmetic and the order of the form this replaced.  One chord is built for every lane; the
+            // second build and accept and the ordering of the two sit behind ONE wave-uniform branch, so a wave of qualifying
+            // lanes executes neither, and a wave with some slow lanes what it did before.
+            float Rp = p.radius, tol = tol_u;
+            if constexpr (AP) {   // the source's radius, in the filter and in its tolerance
+                Rp = s_noct[(pr >> 4) * 8].x;
+                tol = obs_chord_tol(p.rays[0], Rp);
+            }
+            float cr[8];
+            obs_chord_cross(fr.x, fr.y, rx, ry, s10x, s10y, Rp, cr);
+            const ChordSel sel = obs_chord_select(cr, tol, rx * rx + ry * ry, Rp);
+            unsigned acc = sel.rest;
+            int e1 = sel.first;
+            bool todo = sel.acc != 0u;
+#ifdef CA_STAMPS
+            bool ran_two = false;
+            n_trips += 1; n_fast += __ballot(!sel.fast) == 0ull ? 1 : 0;
+#endif
+            while (todo) {
+                SegGeom g1;
+                build_nb(fr, rx, ry, e1, g1, pr >> 4);
+                float dn1;
+                const bool ok1 = accept_nb(g1, s10x, s10y, dn1);
+                const bool two = acc != 0u;
+                if (__ballot(two) == 0ull) {   // every lane here has one chord left: its entry chord, or its last survivor
+                    const float dw = hit_dist(g1.t_numer, dn1, s10x, s10y);
+                    if (ok1 && dw < best) { best = dw; best_m = 8 * k + e1; }
+                    break;
+                }
+#ifdef CA_STAMPS
+                ran_two = true;
+#endif
+                // ascending chord index, strict '<': the first minimum wins.  (A lane with one chord takes it twice: ok2 is false.)
+                const int e2 = two ? __ffs(acc) - 1 : e1;
+                acc &= acc - 1;  // (0 & anything stays 0)
+                SegGeom g2;
+                build_nb(fr, rx, ry, e2, g2, pr >> 4);
+                float dn2;
+                const bool ok2 = accept_nb(g2, s10x, s10y, dn2) && two;
+                // Both accepted: the distance is monotone in t = t_numer / denom, so when the two quotients differ by more than
+                // 1e-5 relative -- 30x what the division, the products and the square root of utils.py:34-38 can round away --
+                // the nearer chord is known from a cross-multiplication and only ITS distance is computed.  Anything closer than
+                // that (the ray through a shared vertex), or a crossing at the origin, takes both through the reference's
+                // arithmetic and compares the rounded distances as the reference does.
+                const float lhs = fabsf(g1.t_numer) * fabsf(dn2), rhs = fabsf(g2.t_numer) * fabsf(dn1);  // t1 < t2  <=>  lhs < rhs
+                const bool first = ok1 && (!ok2 || lhs < rhs);
+                const float tnw = first ? g1.t_numer : g2.t_numer, dnw = first ? dn1 : dn2;
+                const int ew = first ? e1 : e2;
+                const bool sure = fminf(lhs, rhs) < 0.99999f * fmaxf(lhs, rhs) && fmaxf(lhs, rhs) > 1e-30f &&
+                                  fabsf(tnw) > 1e-12f * fabsf(dnw);
+                if (ok1 && ok2 && !sure) {
+                    const float d1 = hit_dist(g1.t_numer, dn1, s10x, s10y), d2 = hit_dist(g2.t_numer, dn2, s10x, s10y);
+                    if (d1 < best) { best = d1; best_m = 8 * k + e1; }
+                    if (d2 < best) { best = d2; best_m = 8 * k + e2; }
+                } else {
+                    const float dw = hit_dist(tnw, dnw, s10x, s10y);
+                    if ((ok1 || ok2) && dw < best) { best = dw; best_m = 8 * k + ew; }
+                }
+                todo = acc != 0u;
+                e1 = __ffs(acc) - 1;
+                acc &= acc - 1;
+            }
+#ifdef CA_STAMPS
+            n_two += __ballot(ran_two) != 0ull ? 1 : 0;
+#endif
+        } else {
+            const float wx = fr.x * s10x + fr.y * s10y, wy = fr.x * s10y - fr.y * s10x;
+            const float wb = wx * ry - wy * rx;
+            float Rp = p.radius, tol = tol_u;
+            if constexpr (AP) {   // the source's radius, in the filter and in its tolerance
+                Rp = s_noct[(pr >> 4) * 8].x;
+                tol = 2e-5f * p.rays[0] * (p.rays[0] + 2.0f * Rp + 1.0f);
+            }
+            const float R = Rp, Rh = 0.70710678f * R;
+            const float c0 = R * wy, c2 = R * wx, c1 = Rh * (wx + wy), c3 = Rh * (wy - wx);
+            const float cr[8] = {wb - c0, wb - c1, wb - c2, wb + c3, wb + c0, wb + c1, wb + c2, wb - c3};
+            unsigned acc = 0;
+    #pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float ca = cr[e], cb = cr[(e + 1) & 7];
+                const bool same_side = (ca > tol && cb > tol) || (ca < -tol && cb < -tol);
+                acc |= same_side ? 0u : (1u << e);
+            }
+            // ascending chord index, strict '<': the first minimum wins.  Two surviving chords (entry and exit)
+            // are taken together in straight-line code; the arithmetic of each is the reference's (utils.py:14-38).
+            while (acc) {
+                const int e1 = __ffs(acc) - 1;
+                acc &= acc - 1;
+                const bool two = acc != 0;
+                const int e2 = two ? __ffs(acc) - 1 : e1;
+                acc &= acc - 1;  // (0 & anything stays 0)
+                SegGeom g1, g2;
+                build_nb(fr, rx, ry, e1, g1, pr >> 4);
+                build_nb(fr, rx, ry, e2, g2, pr >> 4);
+                float dn1, dn2;
+                const bool ok1 = accept_nb(g1, s10x, s10y, dn1), ok2 = accept_nb(g2, s10x, s10y, dn2) && two;
+                // Both accepted (the ray enters through one chord and leaves through the other): the distance is monotone
+                // in t = t_numer / denom, so when the two quotients differ by more than 1e-5 relative -- 30x what the
+                // division, the products and the square root of utils.py:34-38 can round away -- the nearer chord is
+                // known from a cross-multiplication and only ITS distance is computed.  Anything closer than that (the
+                // ray through a shared vertex), or a crossing at the origin, takes both through the reference's
+                // arithmetic and compares the rounded distances as the reference does.
+                const float lhs = fabsf(g1.t_numer) * fabsf(dn2), rhs = fabsf(g2.t_numer) * fabsf(dn1);  // t1 < t2  <=>  lhs < rhs
+                const bool first = ok1 && (!ok2 || lhs < rhs);
+                const float tnw = first ? g1.t_numer : g2.t_numer, dnw = first ? dn1 : dn2;
+                const int ew = first ? e1 : e2;
+                const bool sure = fminf(lhs, rhs) < 0.99999f * fmaxf(lhs, rhs) && fmaxf(lhs, rhs) > 1e-30f &&
+                                  fabsf(tnw) > 1e-12f * fabsf(dnw);
+                if (ok1 && ok2 && !sure) {
+                    const float d1 = hit_dist(g1.t_numer, dn1, s10x, s10y), d2 = hit_dist(g2.t_numer, dn2, s10x, s10y);
+                    if (d1 < best) { best = d1; best_m = 8 * k + e1; }
+                    if (d2 < best) { best = d2; best_m = 8 * k + e2; }
+                } else {
+                    const float dw = hit_dist(tnw, dnw, s10x, s10y);
+                    if ((ok1 || ok2) && dw < best) { best = dw; best_m = 8 * k + ew; }
+                }
             }
         }
         merge(ga, ray, best, best_m);
@@ -601,6 +686,12 @@ __global__ __launch_bounds__(OBS_BS) void obs_kernel(const ObsArgs p) {
             if (hit(sg, s10x, s10y, d, hx, hy)) merge(g, ray, d, m);
         }
     }
+#if defined(CA_STAMPS) && CA_OBS_ENTRY_CHORD   // slots 9 .. 11 of the wave's row, behind the nine time stamps (tools/obs_chord_share.py)
+    if ((threadIdx.x & 63) == 0 && p.dbg) {
+        unsigned long long* row = p.dbg + ((size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 16;
+        row[9] = n_trips; row[10] = n_fast; row[11] = n_two;
+    }
+#endif
     CA_OSTAMP(5);
     __syncthreads();  // a ray's key takes hits from every wave of the workgroup
     CA_OSTAMP(6);
