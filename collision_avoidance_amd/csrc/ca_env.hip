@@ -134,6 +134,10 @@ struct ca_env {
     };
     bool egrid = false;
     EdgeGrids eg;
+    // ... and per-agent ORCA parameters on it (CA_CREATE_TILED_PARAMS; ca_tiled.h's tiled_params_* twins): tparams = the handle accepts
+    // ca_set_agent_params; while parameters are set, ap = ap_user = true as on an ordinary handle, and ap_rmax is their largest radius
+    bool tparams = false;
+    float ap_rmax = 0.0f;
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -421,15 +425,42 @@ static const void* tiled_grid_edges_fn_for(int TILE) {
         default: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 128>);
     }
 }
+// ... and their twins for per-agent parameters (CA_CREATE_TILED_PARAMS, while ca_set_agent_params is in force): edges 0 = the plain
+// tiled launch, 1 = the grid's, 2 = the grid's with the static edge grid
+template <int KMAX, int TILE>
+static const void* tiled_params_fn_for(int edges) {
+    return edges == 2 ? fn_ptr(&tiled_params_grid_edges_solve_kernel<KMAX, TILE>)
+                      : (edges == 1 ? fn_ptr(&tiled_params_grid_solve_kernel<KMAX, TILE>) : fn_ptr(&tiled_params_solve_kernel<KMAX, TILE>));
+}
+template <int KMAX>
+static const void* tiled_params_fn_for(int TILE, int edges) {
+    switch (TILE) {
+        case 64: return tiled_params_fn_for<KMAX, 64>(edges);
+        case 256: return tiled_params_fn_for<KMAX, 256>(edges);
+        default: return tiled_params_fn_for<KMAX, 128>(edges);
+    }
+}
 enum { TILED_SORT_LAUNCHES = 3 };   // bin, scan, scatter
 static const void* tiled_edges_solve_fn(const ca_env* e) {
     return e->KT == 5 ? tiled_grid_edges_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_edges_fn_for<16>(e->TILE) : tiled_grid_edges_fn_for<10>(e->TILE));
 }
-static const void* tiled_solve_fn(const ca_env* e) {
-    if (e->tgrid && e->egrid) return tiled_edges_solve_fn(e);
+// the solve launch of a tiled handle, with the static edge grid on or off (egrid: a grid handle only)
+static const void* tiled_solve_fn(const ca_env* e, bool egrid) {
+    if (e->ap) {
+        const int edges = e->tgrid ? (egrid ? 2 : 1) : 0;
+        return e->KT == 5 ? tiled_params_fn_for<5>(e->TILE, edges) : (e->KT == 16 ? tiled_params_fn_for<16>(e->TILE, edges) : tiled_params_fn_for<10>(e->TILE, edges));
+    }
+    if (e->tgrid && egrid) return tiled_edges_solve_fn(e);
     if (e->tgrid) return e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE));
     return e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE));
 }
+static const void* tiled_solve_fn(const ca_env* e) { return tiled_solve_fn(e, e->egrid); }
+// ... its advance and close launches (the close launch of the parameter twins takes TiledCloseParamsArgs)
+static const void* tiled_advance_fn(const ca_env* e) {
+    if (e->ap) return e->egrid ? fn_ptr(&tiled_params_grid_edges_advance_kernel) : fn_ptr(&tiled_params_advance_kernel);
+    return e->egrid ? fn_ptr(&tiled_grid_edges_advance_kernel) : fn_ptr(&tiled_advance_kernel);
+}
+static const void* tiled_close_fn(const ca_env* e) { return e->ap ? fn_ptr(&tiled_params_close_kernel) : fn_ptr(&tiled_close_kernel); }
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps;
 // trace: ... and records them (the Trace instantiations of the four-lanes kernel: the ORCA-only rollout and the fused ALAN rollout with
 // one action set; the callers ask for nothing else)
@@ -465,16 +496,19 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
         TiledEdgeArgs ea;    // (the static edge grid on: the solve and advance launches are the kernels that walk it)
         static_cast<TiledGridArgs&>(ea) = ga;
         ea.eg = e->eg.d_desc; ea.eg_cells = e->eg.d_cells; ea.eg_entries = e->eg.d_entries;
+        TiledCloseParamsArgs ca;   // (per-agent parameters: the close launch's twin takes the largest radius too)
+        static_cast<TiledArgs&>(ca) = ta; ca.r_max = e->ap_rmax;
         void* gparams[] = {&ga};
         void* params[] = {&ta};
         void* eparams[] = {&ea};
+        void* cparams[] = {&ca};
         struct { const void* fn; dim3 grid, block; size_t lds; void** args; } seq[TILED_SORT_LAUNCHES + 3] = {
             {fn_ptr(&tiled_bin_kernel), s.grid, s.block, 0, gparams},
             {fn_ptr(&tiled_scan_kernel), dim3(e->cfg.n_arenas), dim3(1024), 0, gparams},
             {fn_ptr(&tiled_scatter_kernel), s.grid, s.block, 0, gparams},
             {s.fn, s.grid, s.block, s.lds, e->egrid ? eparams : gparams},
-            {e->egrid ? fn_ptr(&tiled_grid_edges_advance_kernel) : fn_ptr(&tiled_advance_kernel), s.grid, s.block, 0, e->egrid ? eparams : params},
-            {fn_ptr(&tiled_close_kernel), s.grid, s.block, (size_t)e->TILE * 8, params}};
+            {tiled_advance_fn(e), s.grid, s.block, 0, e->egrid ? eparams : params},
+            {tiled_close_fn(e), s.grid, s.block, tiled_close_lds_bytes(e->TILE, e->ap), e->ap ? cparams : params}};
         for (const auto& k : seq) {   // (each launch timed on its own dispatch, kind 1)
             ProfScope ps(e, KIND_STEP);
             const hipError_t r = ps.t0 ? hipExtLaunchKernel(k.fn, k.grid, k.block, k.args, k.lds, e->stream, ps.t0, ps.t1, 0)
@@ -486,13 +520,17 @@ static hipError_t launch_step(ca_env* e, const StepArgs& a) {
     if (e->tiled) {   // solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
         TiledArgs ta;
         ta.s = a; ta.nv_x = e->nv_x; ta.nv_y = e->nv_y; ta.scr = e->tscr; ta.tiles = e->tiles;
+        TiledCloseParamsArgs ca;   // (per-agent parameters: the close launch's twin takes the largest radius too)
+        static_cast<TiledArgs&>(ca) = ta; ca.r_max = e->ap_rmax;
         void* params[] = {&ta};
-        const void* fns[3] = {s.fn, fn_ptr(&tiled_advance_kernel), fn_ptr(&tiled_close_kernel)};
-        const size_t lds[3] = {s.lds, 0, (size_t)e->TILE * 8};
+        void* cparams[] = {&ca};
+        const void* fns[3] = {s.fn, tiled_advance_fn(e), tiled_close_fn(e)};
+        const size_t lds[3] = {s.lds, 0, tiled_close_lds_bytes(e->TILE, e->ap)};
         for (int k = 0; k < 3; ++k) {   // (each launch timed on its own dispatch, kind 1)
             ProfScope ps(e, KIND_STEP);
-            const hipError_t r = ps.t0 ? hipExtLaunchKernel(fns[k], s.grid, s.block, params, lds[k], e->stream, ps.t0, ps.t1, 0)
-                                       : hipLaunchKernel(fns[k], s.grid, s.block, params, lds[k], e->stream);
+            void** args = (k == 2 && e->ap) ? cparams : params;
+            const hipError_t r = ps.t0 ? hipExtLaunchKernel(fns[k], s.grid, s.block, args, lds[k], e->stream, ps.t0, ps.t1, 0)
+                                       : hipLaunchKernel(fns[k], s.grid, s.block, args, lds[k], e->stream);
             if (r != hipSuccess) return r;
         }
         return hipSuccess;
@@ -747,8 +785,7 @@ static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
         hipError_t r = allow_lds(plain);
         if (r == hipSuccess && e->tgrid) {
             SolveLaunch other = plain;
-            other.fn = e->egrid ? (e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE)))
-                                : tiled_edges_solve_fn(e);
+            other.fn = tiled_solve_fn(e, !e->egrid);
             r = allow_lds(other);
         }
         return r;
@@ -794,10 +831,14 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) { re
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out) {
     if (!cfg || !out) return fail(nullptr, CA_EINVAL, "ca_create: null argument");
     *out = nullptr;
-    if (create_flags & ~(CA_CREATE_TILED | CA_CREATE_TILED_GRID))
+    if (create_flags & ~(CA_CREATE_TILED | CA_CREATE_TILED_GRID | CA_CREATE_TILED_PARAMS))
         return fail(nullptr, CA_EINVAL, "ca_create_ex: unknown create_flags 0x%x", create_flags);
     const bool tiled = (create_flags & CA_CREATE_TILED) != 0;
     const bool tgrid = (create_flags & CA_CREATE_TILED_GRID) != 0;
+    const bool tparams = (create_flags & CA_CREATE_TILED_PARAMS) != 0;
+    if (tparams && !tiled)
+        return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_PARAMS (create_flags 0x%x) without CA_CREATE_TILED: it selects the tiled "
+                    "path's per-agent-parameter kernels (an ordinary handle takes ca_set_agent_params as it is)", create_flags);
     if (tgrid && !tiled)
         return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_GRID (create_flags 0x%x) without CA_CREATE_TILED: the uniform grid "
                     "is the tiled path's neighbour search", create_flags);
@@ -855,6 +896,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         e->tiles = (cfg->n_agents + e->TILE - 1) / e->TILE;
     }
     e->tgrid = tgrid;
+    e->tparams = tparams;
     if (tgrid) {   // the cell table: g x g cells, g the power of two with n_agents / 2 <= g^2 (about one agent per cell where the arena
                    // is as wide as the table), 8 <= g <= 128: the scan launch sums 128 x 128 cells in one workgroup.
                    // CA_TILED_CELLS = 8 | 16 | 32 | 64 | 128 (diagnostic switch, tests): that side; anything else: the rule
@@ -1105,10 +1147,23 @@ static void free_edge_grids(ca_env::EdgeGrids& g) {
     if (g.d_entries) hipFree(g.d_entries);
     g = ca_env::EdgeGrids();
 }
-// the grids of the tables `all` / `offs` (install_tables' arguments) into `out`, uploaded; a failure leaves `out` empty and the handle
-// as it was.  `who`: the call the message names.
-static int make_edge_grids(ca_env* e, const std::vector<ObstDev>& all, const std::vector<int>& offs, ca_env::EdgeGrids& out, const char* who) {
-    const float range = e->cfg.time_horizon_obst * e->cfg.max_speed + e->cfg.radius;   // (the kernels' expression)
+// the obstacle range the grids are built for -- it sets the cell size and the margin of an edge's bounding box: the kernels' expression
+// on the handle's constants, or, with per-agent parameters `ap` (radius | max_speed | time_horizon | time_horizon_obst, as
+// ca_env::h_ap), the largest tho_i * ms_i + r_i over all agents, evaluated in fp32 as the kernels evaluate it.  The corner rule of
+// the walk does not depend on the cell size: an agent of a smaller range walks fewer cells of the same table.
+static float edge_grid_range(const ca_env* e, const std::vector<float>* ap) {
+    if (!ap) return e->cfg.time_horizon_obst * e->cfg.max_speed + e->cfg.radius;
+    float range = 0.0f;
+    for (size_t q = 0; q < ap[0].size(); ++q) {
+        const float v = ap[3][q] * ap[1][q] + ap[0][q];
+        range = v > range ? v : range;
+    }
+    return range;
+}
+static const std::vector<float>* agent_params_of(const ca_env* e) { return e->ap_user ? e->h_ap : nullptr; }
+// the grids of the tables `all` / `offs` (install_tables' arguments) for obstacle range `range` into `out`, uploaded; a failure leaves
+// `out` empty and the handle as it was.  `who`: the call the message names.
+static int make_edge_grids(ca_env* e, const std::vector<ObstDev>& all, const std::vector<int>& offs, float range, ca_env::EdgeGrids& out, const char* who) {
     const int tables = offs.empty() ? 1 : (int)offs.size() - 1;
     std::vector<uint32_t> cells, entries, cs, en;
     std::vector<float> pq;
@@ -1163,7 +1218,7 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
     HIPCHK(e, hipStreamSynchronize(e->stream));
     ca_env::EdgeGrids n_eg;   // (the static edge grid is on: the new tables' grids first -- a world it refuses is not installed)
     if (e->egrid) {
-        const int rc = make_edge_grids(e, all, offs, n_eg, "ca_set_obstacles");
+        const int rc = make_edge_grids(e, all, offs, edge_grid_range(e, agent_params_of(e)), n_eg, "ca_set_obstacles");
         if (rc) return rc;
     }
     ObstDev* n_obst = nullptr;
@@ -1458,9 +1513,11 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     static const char* const names[4] = {"radius", "max_speed", "time_horizon", "time_horizon_obst"};
     const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
     const bool any = radius || max_speed || time_horizon || time_horizon_obst;
-    if (e->tiled)
-        return fail(e, CA_EINVAL, "ca_set_agent_params: not on a tiled handle (CA_CREATE_TILED): the tiled kernels have no per-agent-parameter form");
+    if (e->tiled && !e->tparams)
+        return fail(e, CA_EINVAL, "ca_set_agent_params: not on a tiled handle made without CA_CREATE_TILED_PARAMS: the tiled kernels' per-agent-parameter "
+                    "form is chosen at ca_create_ex (create_flags 0x11 or 0x15)");
     HIPCHK(e, hipSetDevice(e->device));
+    ca_env::EdgeGrids n_eg;   // (a grid handle with the static edge grid on: the grids of the new obstacle range first, swapped in at the end)
     if (!any) {   // back to the handle's four constants and to the kernels it used with them
         if (!e->ap_user) return CA_OK;
         HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -1473,10 +1530,16 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
             for (auto& v : e->h_ap) v.clear();
             return alan_pick(e);
         }
+        if (e->egrid) {
+            const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, edge_grid_range(e, nullptr), n_eg, "ca_set_agent_params");
+            if (rc) return rc;
+        }
         bool misfit = false;
         const hipError_t r = switch_agent_params(e, false, false, &misfit);
+        if (r != hipSuccess || misfit) free_edge_grids(n_eg);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the per-agent parameters stay)", hipGetErrorString(r));
         if (misfit) return fail(e, CA_ERANGE, "ca_set_agent_params: the uniform solve kernel does not fit the 160 KiB of LDS of a CU (the per-agent parameters stay)");
+        if (e->egrid) { free_edge_grids(e->eg); e->eg = n_eg; }
         StepCold hc;
         fill_cold(e, hc);
         HIPCHK(e, upload(e, e->d_cold, &hc, sizeof hc));
@@ -1502,9 +1565,14 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     // the buffers exist before anything changes (the first call allocates them; they stay until ca_destroy)
     { const int rc = alloc_agent_params(e); if (rc) return rc; }
     HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous values
+    if (e->egrid) {   // (a refused rebuild fails the whole call: the handle keeps its parameters, kernels and grids)
+        const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, edge_grid_range(e, h), n_eg, "ca_set_agent_params");
+        if (rc) return rc;
+    }
     if (!e->ap) {   // the prospective variant is chosen and checked against the CU's LDS before anything is swapped
         bool misfit = false;
         const hipError_t r = switch_agent_params(e, true, false, &misfit);
+        if (r != hipSuccess || misfit) free_edge_grids(n_eg);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the handle keeps its uniform parameters)", hipGetErrorString(r));
         if (misfit)
             return fail(e, CA_ERANGE, "ca_set_agent_params: the per-agent solve kernel (LDS line table, max_neighbors + max_obst_neighbors lines per lane) "
@@ -1515,7 +1583,10 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     StepCold hc;
     fill_cold(e, hc);
     if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);
-    if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r));
+    if (r != hipSuccess) { free_edge_grids(n_eg); return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r)); }
+    if (e->egrid) { free_edge_grids(e->eg); e->eg = n_eg; }
+    e->ap_rmax = 0.0f;   // (the pair count's bound on a tiled handle: ca_tiled.h TiledCloseParamsArgs)
+    for (size_t q = 0; q < an; ++q) e->ap_rmax = h[0][q] > e->ap_rmax ? h[0][q] : e->ap_rmax;
     for (int k = 0; k < 4; ++k) e->h_ap[k].swap(h[k]);
     e->ap_user = true;   // (a handle with agent counts ran these kernels already, on the ca_config values)
     return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
@@ -2589,7 +2660,7 @@ int ca_tiled_edge_grid(ca_env* e, int32_t on) {
     HIPCHK(e, hipStreamSynchronize(e->stream));
     if (on) {
         ca_env::EdgeGrids n_eg;
-        const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, n_eg, "ca_tiled_edge_grid");
+        const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, edge_grid_range(e, agent_params_of(e)), n_eg, "ca_tiled_edge_grid");
         if (rc) return rc;
         free_edge_grids(e->eg);
         e->eg = n_eg;

@@ -172,10 +172,11 @@ __global__ __launch_bounds__(256) void tiled_scatter_kernel(const TiledGridArgs 
 }
 
 // ---- launch 1: neighbour search, ORCA lines, LP2 / LP3 ------------------------------------------------------------------------
-// The solve launch has three kernels with one body (ca_tiled_solve.inl).
+// The solve launch has three kernels with one body (ca_tiled_solve.inl; CA_TILED_PARAMS 0: the handle's four constants).
 // Grid (tiled_grid_solve_kernel, a handle made with CA_CREATE_TILED_GRID): lane tile * TILE + tid works for SORTED POSITION s of the
 // arena, its agent is i = sidx[s] -- the lanes of a wave then stand in the same few cells and walk the same runs -- and everything
 // else addresses by i as before.
+#define CA_TILED_PARAMS 0
 template <int KMAX, int TILE>
 __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const TiledArgs t) {
 #define CA_TILED_SOLVE_GRID 0
@@ -208,88 +209,63 @@ __global__ __launch_bounds__(256) void tiled_grid_edges_advance_kernel(const Til
 #include "ca_tiled_advance.inl"
 #undef CA_TILED_ADVANCE_EDGES
 }
+#undef CA_TILED_PARAMS
 
 // ---- launch 3: pair count on the copy, end of the episode, the arena's words, the in-kernel reset ---------------------------------
-// dynamic LDS: the staged candidate tile px py [TILE] (8 B per lane)
+// dynamic LDS: the staged candidate tile px py [TILE] (8 B per lane); the statements are ca_tiled_close.inl's
 __global__ __launch_bounds__(256) void tiled_close_kernel(const TiledArgs t) {
-    const StepArgs& p = t.s;
-    const ColdK& c = *(ColdK*)p.cold;
-    extern __shared__ float4 smem4[];
-    __shared__ int s_pairs;
-    const int tid = threadIdx.x, TILE = blockDim.x;
-    const int a = (int)blockIdx.x / t.tiles, tile = (int)blockIdx.x - a * t.tiles;
-    const unsigned* sc = t.scr + (size_t)a * TS_STRIDE;
-    if (sc[TS_LIVE] == 0u) return;   // frozen when the step began (arena_done itself is rewritten in this launch)
-    const int N = p.N, K = p.K;
-    const int i = tile * TILE + tid;
-    const bool active = i < N;
-    const size_t abase = (size_t)a * N;
-    const size_t q = abase + (active ? i : 0);
-    float* s_px = reinterpret_cast<float*>(smem4);
-    float* s_py = s_px + TILE;
-    if (tid == 0) s_pairs = 0;
-
-    if (p.flags & 2u) {  // CA_F_STATS: overlapping pairs (i < j) after the step -- step_kernel's shortcut through the neighbour lists
-        // with the arena-wide largest speed of this step, and for the lanes that cannot conclude from their list a scan of the copy
-        int pairs = 0;
-        const float R = p.radius;
-        const float crSq = sqr(R + R);
-        const float m2 = pair_reach(sc[TS_VMAX2], p.time_step);
-        V2 pos = mk(0.0f, 0.0f);
-        if (active) pos = mk(t.nv_x[q], t.nv_y[q]);
-        bool scan_all = active && !lists_bound_pairs(p.neighbor_dist, R, m2);
-        if (active && !scan_all) {
-            float far2 = 0.0f;
-            const int ncnt = (int)(p.counts[q] & 0xFFu);
-            for (int k = 0; k < ncnt; ++k) {
-                const int j = ld_idx_t<true>(p.nb_idx, ((size_t)a * K + k) * N + i);
-                const float d2 = absSq(pos - mk(t.nv_x[abase + j], t.nv_y[abase + j]));
-                far2 = d2 > far2 ? d2 : far2;
-                if (j > i && d2 < crSq) ++pairs;
-            }
-            scan_all = list_misses_pairs(ncnt, K, far2, R, m2);
-        }
-        if (__syncthreads_or(scan_all ? 1 : 0)) {   // (workgroup-uniform: the barriers below are met by every lane)
-            if (scan_all) pairs = 0;
-            for (int ct = tile; ct < t.tiles; ++ct) {   // candidates j > i: this tile and the ones behind it
-                const int j0 = ct * TILE;
-                const int nj = min(TILE, N - j0);
-                __syncthreads();
-                if (tid < nj) { s_px[tid] = t.nv_x[abase + j0 + tid]; s_py[tid] = t.nv_y[abase + j0 + tid]; }
-                __syncthreads();
-                if (scan_all) {
-                    for (int jj = (ct == tile ? tid + 1 : 0); jj < nj; ++jj)
-                        if (absSq(pos - mk(s_px[jj], s_py[jj])) < crSq) ++pairs;
-                }
-            }
-        }
-        if (pairs) atomicAdd(&s_pairs, pairs);
-        __syncthreads();
-        if (tid == 0 && s_pairs) atomicAdd(&c.arena_stats[(size_t)a * ST_STRIDE + ST_COLL], (unsigned long long)s_pairs);
-    }
-
-    const bool nodone = (p.flags & 8u) != 0;  // CA_F_NODONE
-    const int steps = tiled_steps_after((int)sc[TS_STEPS0], p.actions != nullptr, nodone);
-    const int not_done = (int)sc[TS_NOTDONE];
-    const bool all_done = episode_over(c, nodone, not_done, steps);
-    const bool do_reset = all_done && (p.flags & 4u);  // CA_F_AUTORESET
-    const int epi = (int)sc[TS_EPI];
-    if (active && do_reset) {  // env.py:461-488 for this arena
-        const V2 pos = spawn_draw(c, a, i, epi);
-        const V2 pref = goal_dir(pos, c.goal_x[q], c.goal_y[q]);
-        c.agent_done[q] = 0;
-        c.pos_x[q] = pos.x; c.pos_y[q] = pos.y;
-        c.pref_x[q] = pref.x; c.pref_y[q] = pref.y;
-        c.orient_x[q] = pref.x; c.orient_y[q] = pref.y;
-    }
-    if (tile == 0 && tid == 0) {   // the arena's words (the other workgroups add to ST_COLL only)
-        unsigned long long* st = c.arena_stats + (size_t)a * ST_STRIDE;
-        if (all_done) { atomicAdd(&st[ST_EPISODES], 1ull); st[ST_LASTEP] = lastep_word(steps, N, not_done); }
-        c.arena_done[a] = all_done ? 1 : 0;
-        c.step_count[a] = do_reset ? 0 : steps;
-        atomicAdd(&c.arena_steps[a], 1ull);
-        if (do_reset) c.episode[a] = epi + 1;
-    }
+#define CA_TILED_PARAMS 0
+#include "ca_tiled_close.inl"
+#undef CA_TILED_PARAMS
 }
+
+// ---- the twins for per-agent ORCA parameters (a handle made with CA_CREATE_TILED_PARAMS, while ca_set_agent_params is in force) ------
+// The same three texts with CA_TILED_PARAMS 1: radius, maximum speed and the two time horizons of agent i come from the per-agent arrays
+// (StepCold::ap_*), a neighbour's radius is gathered beside its position and velocity, and each enters where DESIGN.md 7b says --
+// the obstacle range sqr(tho_i * ms_i + r_i) and the edge-grid walk over cell(x +- (tho_i * ms_i + r_i)), the obstacle lines and their
+// covered test (r_i, 1 / tho_i), the agent lines (r_i, r_j, 1 / th_i), LP2 / LP3 (ms_i), the wall and goal tests (r_i), the pair count
+// (sqr(r_i + r_j)).  The sort launches are the uniform handle's: neighbor_dist and max_neighbors stay per handle.  The edge grid is
+// built for the LARGEST range of the handle (ca_env.hip edge_grid_range); the corner rule of the walk does not depend on the cell
+// size, so an agent of a smaller range simply walks fewer cells.
+struct TiledCloseParamsArgs : TiledArgs {
+    float r_max;   // the largest radius of the handle: R of lists_bound_pairs / list_misses_pairs (r_i + r_j <= 2 r_max)
+};
+// LDS of the close launch (bytes): the staged candidate tile px py [TILE], and with per-agent parameters its radii
+__host__ __device__ inline size_t tiled_close_lds_bytes(int TILE, bool params) { return (size_t)TILE * (params ? 12 : 8); }
+
+#define CA_TILED_PARAMS 1
+template <int KMAX, int TILE>
+__global__ __launch_bounds__(TILE) void tiled_params_solve_kernel(const TiledArgs t) {
+#define CA_TILED_SOLVE_GRID 0
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
+}
+template <int KMAX, int TILE>
+__global__ __launch_bounds__(TILE) void tiled_params_grid_solve_kernel(const TiledGridArgs t) {
+#define CA_TILED_SOLVE_GRID 1
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
+}
+template <int KMAX, int TILE>
+__global__ __launch_bounds__(TILE) void tiled_params_grid_edges_solve_kernel(const TiledEdgeArgs t) {
+#define CA_TILED_SOLVE_GRID 2
+#include "ca_tiled_solve.inl"
+#undef CA_TILED_SOLVE_GRID
+}
+__global__ __launch_bounds__(256) void tiled_params_advance_kernel(const TiledArgs t) {
+#define CA_TILED_ADVANCE_EDGES 0
+#include "ca_tiled_advance.inl"
+#undef CA_TILED_ADVANCE_EDGES
+}
+__global__ __launch_bounds__(256) void tiled_params_grid_edges_advance_kernel(const TiledEdgeArgs t) {
+#define CA_TILED_ADVANCE_EDGES 1
+#include "ca_tiled_advance.inl"
+#undef CA_TILED_ADVANCE_EDGES
+}
+// dynamic LDS: the staged candidate tile px py r [TILE] (12 B per lane)
+__global__ __launch_bounds__(256) void tiled_params_close_kernel(const TiledCloseParamsArgs t) {
+#include "ca_tiled_close.inl"
+}
+#undef CA_TILED_PARAMS
 
 }  // namespace ca

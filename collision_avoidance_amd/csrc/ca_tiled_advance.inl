@@ -1,6 +1,7 @@
 // ca_tiled_advance.inl -- the statements of the tiled path's advance launch, included by ca_tiled.h into each of its two kernels
 // (CA_TILED_ADVANCE_EDGES 0: tiled_advance_kernel, 1: tiled_grid_edges_advance_kernel, whose wall test walks the static edge grid; `t`
-// is the kernel's argument block).  Textual inclusion for the reason ca_tiled_solve.inl gives.
+// is the kernel's argument block; CA_TILED_PARAMS 1: the tiled_params_* twin of each, whose wall and goal tests take the agent's own radius).
+// Textual inclusion for the reason ca_tiled_solve.inl gives.
     const StepArgs& p = t.s;
     const ColdK& c = *(ColdK*)p.cold;
     __shared__ int s_red[4];   // [0] not-done agents, [1] wall hits, [2] goals, [3] largest squared speed (float bits)
@@ -18,6 +19,12 @@
     float rew = 0.0f;
     if (active) {
         const V2 pos0 = mk(p.pos_x[q], p.pos_y[q]);
+#if CA_TILED_PARAMS
+        const float ap_r = c.ap_radius[q];
+#define CA_T_RADIUS ap_r
+#else
+#define CA_T_RADIUS p.radius
+#endif
         const V2 vel = mk(t.nv_x[q], t.nv_y[q]);
         const V2 pos = pos0 + vel * p.time_step;   // (App. A.1)
         double gx = c.goal_x[q], gy = c.goal_y[q];
@@ -39,7 +46,7 @@
             const EdgeGridDev g = t.eg[p.tab_off != nullptr ? a : 0];
             const unsigned* cs = t.eg_cells + g.cells_off;
             const unsigned* en = t.eg_entries + g.entries_off;
-            const float R = p.radius;
+            const float R = CA_T_RADIUS;
             const int cxlo = edge_cell(pos.x - R, g.x0, g.ics_x, g.gx), cxhi = edge_cell(pos.x + R, g.x0, g.ics_x, g.gx);
             const int cylo = edge_cell(pos.y - R, g.y0, g.ics_y, g.gy), cyhi = edge_cell(pos.y + R, g.y0, g.ics_y, g.gy);
             bool wall = false;
@@ -57,12 +64,12 @@
             }
             if (wall) atomicAdd(&s_red[1], 1);
 #else
-            if (touches_wall(tab, ne, pos, p.radius)) atomicAdd(&s_red[1], 1);
+            if (touches_wall(tab, ne, pos, CA_T_RADIUS)) atomicAdd(&s_red[1], 1);
 #endif
         }
         bool goal_changed = false;
         int done = c.agent_done[q];
-        if (!nodone && goal_hit(c, pos, gx, gy, p.radius, done)) {
+        if (!nodone && goal_hit(c, pos, gx, gy, CA_T_RADIUS, done)) {
             if (c.done_mode == 2) {
                 const int rc = c.regoal_count[q];
                 regoal_draw(c, a, i, rc, &gx, &gy);
@@ -101,3 +108,4 @@
         if (s_red[1]) atomicAdd(&st[ST_OBST_COLL], (unsigned long long)s_red[1]);
         if (s_red[2]) atomicAdd(&st[ST_GOALS], (unsigned long long)s_red[2]);
     }
+#undef CA_T_RADIUS

@@ -1,6 +1,8 @@
 // ca_tiled_solve.inl -- the statements of the tiled path's solve launch, included by ca_tiled.h into each of its three kernels
 // (CA_TILED_SOLVE_GRID 0: tiled_solve_kernel, 1: tiled_grid_solve_kernel, 2: tiled_grid_edges_solve_kernel -- the grid kernel with the
-// obstacle edges found through the static edge grid; `t` is the kernel's argument block, KMAX and TILE its template parameters).  Textual inclusion and not a shared __device__ function: through a function -- by reference or by value --
+// obstacle edges found through the static edge grid; `t` is the kernel's argument block, KMAX and TILE its template parameters;
+// CA_TILED_PARAMS 1: the tiled_params_* twin of each, which takes radius, maximum speed and the two time horizons of agent i from the
+// per-agent arrays of ca_set_agent_params -- p.cold->ap_*, DESIGN.md 7h -- where the others take the handle's four constants).  Textual inclusion and not a shared __device__ function: through a function -- by reference or by value --
 // the plain kernel's instruction text moved, and that kernel is to stay what it was before the grid existed.
     const StepArgs& p = t.s;
     extern __shared__ float4 smem4[];
@@ -42,6 +44,22 @@
             pref = mk(p.pref_x[q], p.pref_y[q]);
         }
     }
+#if CA_TILED_PARAMS
+    // the agent's own four values (an inactive lane keeps the handle's: it computes nothing that is stored); a neighbour's radius is
+    // gathered next to its position and velocity, where its line is built
+    float ap_r = p.radius, ap_ms = p.max_speed, ap_th = p.time_horizon, ap_tho = p.time_horizon_obst;
+    const ColdK& ck = *(ColdK*)p.cold;
+    if (active) { ap_r = ck.ap_radius[q]; ap_ms = ck.ap_max_speed[q]; ap_th = ck.ap_time_horizon[q]; ap_tho = ck.ap_time_horizon_obst[q]; }
+#define CA_T_RADIUS ap_r
+#define CA_T_MAX_SPEED ap_ms
+#define CA_T_HORIZON ap_th
+#define CA_T_HORIZON_OBST ap_tho
+#else
+#define CA_T_RADIUS p.radius
+#define CA_T_MAX_SPEED p.max_speed
+#define CA_T_HORIZON p.time_horizon
+#define CA_T_HORIZON_OBST p.time_horizon_obst
+#endif
 
     // ---- obstacle neighbours (App. A.2; ca_nbr.h's keys; its edge_in_range and ca_common.h arena_edges written out: through them this kernel's text moved) ----
     const ObstDev* tab = p.obst + ((p.tab_off != nullptr) ? p.tab_off[a] : 0);          // this arena's edge table
@@ -52,7 +70,7 @@
         double okey[SMAX];
 #pragma unroll
         for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
-        const float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
+        const float rangeSq = sqr(CA_T_HORIZON_OBST * CA_T_MAX_SPEED + CA_T_RADIUS);
 #if CA_TILED_SOLVE_GRID == 2
         // The static edge grid (ca_edge_grid_host.h): the cells of the columns cell(fl(x - range)) .. cell(fl(x + range)) and the rows
         // likewise, 3 x 3 but for a rounding of ics; an edge registered in several of them is taken in the low corner of the intersection of its
@@ -63,7 +81,7 @@
             const EdgeGridDev g = t.eg[p.tab_off != nullptr ? a : 0];
             const unsigned* cs = t.eg_cells + g.cells_off;
             const unsigned* en = t.eg_entries + g.entries_off;
-            const float range = p.time_horizon_obst * p.max_speed + p.radius;
+            const float range = CA_T_HORIZON_OBST * CA_T_MAX_SPEED + CA_T_RADIUS;   // (per agent: a smaller range walks fewer cells)
             const int cxlo = edge_cell(pos.x - range, g.x0, g.ics_x, g.gx), cxhi = edge_cell(pos.x + range, g.x0, g.ics_x, g.gx);
             const int cylo = edge_cell(pos.y - range, g.y0, g.ics_y, g.gy), cyhi = edge_cell(pos.y + range, g.y0, g.ics_y, g.gy);
             for (int r = cylo; r <= cyhi; ++r) {
@@ -194,8 +212,8 @@
     // ---- ORCA lines into the LDS table (step_kernel's LDS-table path; the neighbours' state gathered from global memory) ----
     int nl = 0;
     {
-        const float invTO = 1.0f / p.time_horizon_obst;
-        const float R = p.radius;
+        const float invTO = 1.0f / CA_T_HORIZON_OBST;
+        const float R = CA_T_RADIUS;
         for (int s = 0; s < ocnt; ++s) {
             const int e = ld_idx_t<true>(p.obst_idx, ((size_t)a * S + s) * N + i);   // (this lane wrote it)
             Line line;
@@ -210,13 +228,17 @@
     }
     const int numObstLines = nl;
     {
-        const float invT = 1.0f / p.time_horizon;
+        const float invT = 1.0f / CA_T_HORIZON;
         const float invDt = 1.0f / p.time_step;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             if (k >= kofs && k - kofs < ncnt) {
                 const size_t j = abase + (size_t)key_index(nkey[k]);
+#if CA_TILED_PARAMS
+                ls.put(nl, agent_orca_line(pos, vel, mk(p.pos_x[j], p.pos_y[j]), mk(p.vel_x[j], p.vel_y[j]), ap_r, ck.ap_radius[j], invT, invDt));
+#else
                 ls.put(nl, agent_orca_line(pos, vel, mk(p.pos_x[j], p.pos_y[j]), mk(p.vel_x[j], p.vel_y[j]), p.radius, invT, invDt));
+#endif
                 ++nl;
             }
         }
@@ -224,6 +246,10 @@
     // ---- 2-D linear program (App. A.5), LP3 where it is infeasible ----
     V2 nv = mk(0.0f, 0.0f);
     int fail = nl;
-    if (active) fail = lp2(ls, nl, p.max_speed, pref, false, nv);
-    if (active && fail < nl) lp3<KMAX + SMAX>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, p.max_speed, nv);
+    if (active) fail = lp2(ls, nl, CA_T_MAX_SPEED, pref, false, nv);
+    if (active && fail < nl) lp3<KMAX + SMAX>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, CA_T_MAX_SPEED, nv);
     if (active) { t.nv_x[q] = nv.x; t.nv_y[q] = nv.y; }
+#undef CA_T_RADIUS
+#undef CA_T_MAX_SPEED
+#undef CA_T_HORIZON
+#undef CA_T_HORIZON_OBST

@@ -89,24 +89,33 @@ class VecCollisionAvoidanceEnv:
                n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
     tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
                arena spread over several workgroups, a step in three launches (tiled_info()); max_obst_neighbors <= 16, no
-               agent_params / agent_counts (ValueError).  Results are the ordinary handle's bit for bit.  False (default): one
+               agent_counts, and agent_params only with tiled_params=True (ValueError).  Results are the ordinary handle's bit for bit.  False (default): one
                workgroup per arena, n_agents <= 1024.  "grid": the tiled path with its uniform-grid neighbour search
                (CA_CREATE_TILED | CA_CREATE_TILED_GRID): the arena's agents are sorted by cell in three more launches per step and an
                agent tests the cells its range touches instead of the whole arena (tiled_grid_info()); the same results.
     edge_grid: True (with tiled="grid" only; any other handle raises the library's error): set_edge_grid(True) once the obstacles are
                installed -- the obstacle edges in range and the wall test come from a static grid over the edges instead of a scan
                of the arena's whole table (edge_grid_info()); the same results.  False (default): the scan.
+    tiled_params: True (with tiled=True or "grid" only; ValueError otherwise): the tiled handle is made with CA_CREATE_TILED_PARAMS
+               and takes agent_params= / set_agent_params() -- a heterogeneous crowd of up to 16384 agents in one world.  Until
+               parameters are set it runs the uniform tiled kernels.  agent_counts stays refused.  False (default): a tiled
+               handle refuses per-agent parameters.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False):
+                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False):
         if tiled not in (False, True, "grid", None, 0, 1):
             raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
-        if tiled and (agent_params or agent_counts is not None):
-            raise ValueError("tiled=%r: the tiled kernels have no per-agent-parameter and no per-arena-count form "
-                             "(agent_params= / agent_counts= go with tiled=False)" % (tiled,))
+        if tiled_params and not tiled:
+            raise ValueError("tiled_params=True without tiled=True or tiled='grid': it selects the tiled path's per-agent-parameter "
+                             "kernels (an ordinary handle takes agent_params= as it is)")
+        if tiled and ((agent_params and not tiled_params) or agent_counts is not None):
+            raise ValueError("tiled=%r: the tiled kernels have no per-arena-count form, and their per-agent-parameter form is chosen "
+                             "at construction (agent_params= goes with tiled_params=True or with tiled=False, agent_counts= with "
+                             "tiled=False)" % (tiled,))
         self.tiled = "grid" if tiled == "grid" else bool(tiled)
+        self.tiled_params = bool(tiled_params)
         if agent_counts is not None and scenario not in (None, "doorway"):
             raise ValueError("agent_counts: scenario %r lays its agents out as a function of n_agents; only 'doorway' or None "
                              "go with per-arena agent counts" % (scenario,))
@@ -134,7 +143,8 @@ class VecCollisionAvoidanceEnv:
         self.use_torch = (torch is not None and torch.cuda.is_available()) if use_torch is None else bool(use_torch)
         h = C.c_void_p()
         if self.tiled:
-            flags = _lib.CREATE_TILED | (_lib.CREATE_TILED_GRID if self.tiled == "grid" else 0)
+            flags = _lib.CREATE_TILED | (_lib.CREATE_TILED_GRID if self.tiled == "grid" else 0) | \
+                (_lib.CREATE_TILED_PARAMS if self.tiled_params else 0)
             rc = self.L.ca_create_ex(C.byref(self.cfg), flags, self.device, None, C.byref(h))
         else:
             rc = self.L.ca_create(C.byref(self.cfg), self.device, None, C.byref(h))

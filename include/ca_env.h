@@ -47,7 +47,9 @@ extern "C" {
 #define CA_CREATE_TILED 1u /* the tiled solve path: n_agents 1..CA_MAX_AGENTS_LARGE, see ca_create_ex */
 #define CA_CREATE_TILED_GRID 4u /* with CA_CREATE_TILED only (flags == 5): the tiled path finds the agent neighbours through a uniform
                                    grid sorted across workgroups, see ca_create_ex.  Bit 2u is NOT a flag: it stays unknown
-                                   (CA_EINVAL), as does every other bit */
+                                   (CA_EINVAL), as does bit 8u and every bit above 16u */
+#define CA_CREATE_TILED_PARAMS 16u /* with CA_CREATE_TILED only (flags == 17 or 21): the tiled handle takes ca_set_agent_params, see
+                                      ca_create_ex */
 
 /* error codes */
 #define CA_OK 0
@@ -185,7 +187,7 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
  *   - Every step, reset, scenario, field, obstacle-table and ALAN call works as on an ordinary handle, with all step flags and the
  *     sticky overflow error; ca_rollout is T times the three launches, ca_alan_step / ca_alan_rollout take the three-launch form
  *     around them (select, solve, update); neighbour ids are 16 bits on the device.
- *   - ca_set_agent_params and ca_set_agent_counts -> CA_EINVAL (no tiled form); the handle keeps working.
+ *   - ca_set_agent_params (without CA_CREATE_TILED_PARAMS, below) and ca_set_agent_counts -> CA_EINVAL; the handle keeps working.
  *   - ca_solver_info reports lanes_per_agent = 1, rollout_one_launch = 0; ca_launch_info the first of the three launches;
  *     ca_profile counts each of the three launches on its own under kind 1.
  * CA_CREATE_TILED | CA_CREATE_TILED_GRID (flags == 5; CA_CREATE_TILED_GRID alone -> CA_EINVAL: the grid is the tiled path's): a tiled
@@ -199,7 +201,23 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
  *     launches_per_step = sort_launches + 3, and ca_profile counts each under kind 1;
  *   - ca_launch_info reports the first launch of the sequence (the bin launch: no dynamic LDS).
  *   The sort's buffers belong to the handle and are no part of its state (no field reads them).  CA_TILED_CELLS=<g> (a power of
- *   two, 8 .. 128; diagnostic switch latched here, like CA_TILE) forces a g x g table. */
+ *   two, 8 .. 128; diagnostic switch latched here, like CA_TILE) forces a g x g table.
+ * CA_CREATE_TILED_PARAMS, together with CA_CREATE_TILED (flags == 17: the plain tiled handle, 21: the grid handle; without
+ * CA_CREATE_TILED, or with bit 2u or 8u -> CA_EINVAL): the tiled handle of those flags that also takes ca_set_agent_params --
+ * a heterogeneous crowd of up to CA_MAX_AGENTS_LARGE agents in one world.  Opt-in at create, like the grid: the tiled path fixes
+ * its kernel family when the handle is made, and a handle made without the flag keeps refusing the call.
+ *   - Until parameters are set the handle runs the uniform tiled kernels: the launches and the bits of flags 1 / 5.
+ *   - ca_set_agent_params behaves as on an ordinary handle (value checks, CA_ESIZE, drains the stream, configuration that survives
+ *     resets and scenarios, a failure leaves the handle as it was, four NULLs return to the uniform kernels; ca_get_agent_params,
+ *     ca_agent_params_info).  No LDS misfit exists: the tile's line table is sized at create.
+ *   - While parameters are set the solve, advance and close launches are their per-agent twins (the same number of launches;
+ *     results are the ordinary per-agent handle's and the oracle's bit for bit), every call of a tiled handle works, and the
+ *     observation takes every neighbour's own octagon.  The pair count (CA_F_STATS) counts a pair within r_i + r_j.
+ *   - The static edge grid (ca_tiled_edge_grid) is built for the LARGEST obstacle range tho_i * ms_i + r_i of the handle, in fp32:
+ *     that range is the cell size and the margin of an edge's bounding box.  Setting and clearing the parameters rebuild the grids
+ *     while the edge grid is on (a refused rebuild fails the call and changes nothing); switching it on afterwards uses the same
+ *     range.  The walk's corner rule does not depend on the cell size, so an agent of a smaller range walks fewer cells.
+ *   - ca_set_agent_counts stays CA_EINVAL; neighbor_dist and max_neighbors stay per handle. */
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out);
 int ca_destroy(ca_env* env);
 const char* ca_last_error(const ca_env* env);
