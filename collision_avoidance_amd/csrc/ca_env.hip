@@ -134,7 +134,7 @@ struct ca_env {
     };
     bool egrid = false;
     EdgeGrids eg;
-    // ... and per-agent ORCA parameters on it (CA_CREATE_TILED_PARAMS; ca_tiled.h's tiled_params_* twins): tparams = the handle accepts
+    // ... and per-agent ORCA parameters on it (CA_CREATE_TILED_PARAMS; ca_tiled.h's AgentParams instantiations): tparams = the handle accepts
     // ca_set_agent_params; while parameters are set, ap = ap_user = true as on an ordinary handle, and ap_rmax is their largest radius
     bool tparams = false;
     float ap_rmax = 0.0f;
@@ -398,75 +398,40 @@ static const void* quad_fn_for(const ca_env* e) {   // (K <= 10)
     if (e->SQ > 4) return e->KT == 5 ? quad_fn_for<5, 16, ALAN, PER...>(e->BSq) : quad_fn_for<10, 16, ALAN, PER...>(e->BSq);
     return e->KT == 5 ? quad_fn_for<5, 4, ALAN, PER...>(e->BSq) : quad_fn_for<10, 4, ALAN, PER...>(e->BSq);
 }
-// the tiled path's first launch (ca_tiled.h): KMAX class x TILE
-template <int KMAX>
-static const void* tiled_fn_for(int TILE) {
+// the tiled path's solve launch (ca_tiled.h): KMAX class x TILE, written once for every search and parameter form
+template <int KMAX, int SEARCH, class... PER>
+static const void* tiled_solve_fn_for(int TILE) {
     switch (TILE) {
-        case 64: return fn_ptr(&tiled_solve_kernel<KMAX, 64>);
-        case 256: return fn_ptr(&tiled_solve_kernel<KMAX, 256>);
-        default: return fn_ptr(&tiled_solve_kernel<KMAX, 128>);
+        case 64: return fn_ptr(&tiled_solve_kernel<KMAX, 64, SEARCH, PER...>);
+        case 256: return fn_ptr(&tiled_solve_kernel<KMAX, 256, SEARCH, PER...>);
+        default: return fn_ptr(&tiled_solve_kernel<KMAX, 128, SEARCH, PER...>);
     }
 }
-// ... and the solve launch of a grid handle (CA_CREATE_TILED_GRID)
-template <int KMAX>
-static const void* tiled_grid_fn_for(int TILE) {
-    switch (TILE) {
-        case 64: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 64>);
-        case 256: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 256>);
-        default: return fn_ptr(&tiled_grid_solve_kernel<KMAX, 128>);
-    }
-}
-// ... and of a grid handle with the static edge grid on (ca_tiled_edge_grid)
-template <int KMAX>
-static const void* tiled_grid_edges_fn_for(int TILE) {
-    switch (TILE) {
-        case 64: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 64>);
-        case 256: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 256>);
-        default: return fn_ptr(&tiled_grid_edges_solve_kernel<KMAX, 128>);
-    }
-}
-// ... and their twins for per-agent parameters (CA_CREATE_TILED_PARAMS, while ca_set_agent_params is in force): edges 0 = the plain
-// tiled launch, 1 = the grid's, 2 = the grid's with the static edge grid
-template <int KMAX, int TILE>
-static const void* tiled_params_fn_for(int edges) {
-    return edges == 2 ? fn_ptr(&tiled_params_grid_edges_solve_kernel<KMAX, TILE>)
-                      : (edges == 1 ? fn_ptr(&tiled_params_grid_solve_kernel<KMAX, TILE>) : fn_ptr(&tiled_params_solve_kernel<KMAX, TILE>));
-}
-template <int KMAX>
-static const void* tiled_params_fn_for(int TILE, int edges) {
-    switch (TILE) {
-        case 64: return tiled_params_fn_for<KMAX, 64>(edges);
-        case 256: return tiled_params_fn_for<KMAX, 256>(edges);
-        default: return tiled_params_fn_for<KMAX, 128>(edges);
-    }
+template <int SEARCH, class... PER>
+static const void* tiled_solve_fn_for(const ca_env* e) {
+    return e->KT == 5 ? tiled_solve_fn_for<5, SEARCH, PER...>(e->TILE)
+                      : (e->KT == 16 ? tiled_solve_fn_for<16, SEARCH, PER...>(e->TILE) : tiled_solve_fn_for<10, SEARCH, PER...>(e->TILE));
 }
 enum { TILED_SORT_LAUNCHES = 3 };   // bin, scan, scatter
-static const void* tiled_edges_solve_fn(const ca_env* e) {
-    return e->KT == 5 ? tiled_grid_edges_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_edges_fn_for<16>(e->TILE) : tiled_grid_edges_fn_for<10>(e->TILE));
-}
-// the solve launch of a tiled handle, with the static edge grid on or off (egrid: a grid handle only)
+// the solve launch of a tiled handle, with the static edge grid on or off (egrid: a grid handle only); AgentParams while
+// ca_set_agent_params is in force (CA_CREATE_TILED_PARAMS)
 static const void* tiled_solve_fn(const ca_env* e, bool egrid) {
-    if (e->ap) {
-        const int edges = e->tgrid ? (egrid ? 2 : 1) : 0;
-        return e->KT == 5 ? tiled_params_fn_for<5>(e->TILE, edges) : (e->KT == 16 ? tiled_params_fn_for<16>(e->TILE, edges) : tiled_params_fn_for<10>(e->TILE, edges));
-    }
-    if (e->tgrid && egrid) return tiled_edges_solve_fn(e);
-    if (e->tgrid) return e->KT == 5 ? tiled_grid_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_grid_fn_for<16>(e->TILE) : tiled_grid_fn_for<10>(e->TILE));
-    return e->KT == 5 ? tiled_fn_for<5>(e->TILE) : (e->KT == 16 ? tiled_fn_for<16>(e->TILE) : tiled_fn_for<10>(e->TILE));
+    if (e->tgrid && egrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID_EDGES, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID_EDGES>(e);
+    if (e->tgrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID>(e);
+    return e->ap ? tiled_solve_fn_for<SEARCH_ALL, AgentParams>(e) : tiled_solve_fn_for<SEARCH_ALL>(e);
 }
-static const void* tiled_solve_fn(const ca_env* e) { return tiled_solve_fn(e, e->egrid); }
-// ... its advance and close launches (the close launch of the parameter twins takes TiledCloseParamsArgs)
+// ... its advance and close launches (with AgentParams the close launch takes TiledCloseParamsArgs)
 static const void* tiled_advance_fn(const ca_env* e) {
-    if (e->ap) return e->egrid ? fn_ptr(&tiled_params_grid_edges_advance_kernel) : fn_ptr(&tiled_params_advance_kernel);
-    return e->egrid ? fn_ptr(&tiled_grid_edges_advance_kernel) : fn_ptr(&tiled_advance_kernel);
+    if (e->ap) return e->egrid ? fn_ptr(&tiled_advance_kernel<true, AgentParams>) : fn_ptr(&tiled_advance_kernel<false, AgentParams>);
+    return e->egrid ? fn_ptr(&tiled_advance_kernel<true>) : fn_ptr(&tiled_advance_kernel<false>);
 }
-static const void* tiled_close_fn(const ca_env* e) { return e->ap ? fn_ptr(&tiled_params_close_kernel) : fn_ptr(&tiled_close_kernel); }
+static const void* tiled_close_fn(const ca_env* e) { return e->ap ? fn_ptr(&tiled_close_kernel<AgentParams>) : fn_ptr(&tiled_close_kernel<>); }
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps;
 // trace: ... and records them (the Trace instantiations of the four-lanes kernel: the ORCA-only rollout and the fused ALAN rollout with
 // one action set; the callers ask for nothing else)
 static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout, bool trace = false) {
     if (e->tiled)   // (the solve launch of a step's sequence; no ALAN and no rollout form)
-        return {tiled_solve_fn(e), dim3(e->grid), dim3(e->TILE), e->lds};
+        return {tiled_solve_fn(e, e->egrid), dim3(e->grid), dim3(e->TILE), e->lds};
     const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
     if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
         const void* f = trace ? (alan ? quad_fn_for<true, Trace>(e) : quad_fn_for<false, Trace>(e))
@@ -486,51 +451,29 @@ static hipError_t allow_lds(const SolveLaunch& s) {
 static hipError_t launch_step(ca_env* e, const StepArgs& a) {
     const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1, e->trace_on && a.T > 1);
     if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
-    if (e->tiled && e->tgrid) {   // bin -> scan -> scatter -> solve -> advance -> close (ca_tiled.h)
-        TiledGridArgs ga;
-        ga.s = a; ga.nv_x = e->nv_x; ga.nv_y = e->nv_y; ga.scr = e->tscr; ga.tiles = e->tiles;
-        ga.cell_count = e->tg_count; ga.cell_start = e->tg_start; ga.key = e->tg_key;
-        ga.sx = e->tg_sx; ga.sy = e->tg_sy; ga.sidx = e->tg_sidx;
-        ga.gx = e->tgx; ga.gy = e->tgy; ga.ics = e->tics;
-        TiledArgs ta = ga;   // (the advance and close launches take the plain arguments)
-        TiledEdgeArgs ea;    // (the static edge grid on: the solve and advance launches are the kernels that walk it)
-        static_cast<TiledGridArgs&>(ea) = ga;
-        ea.eg = e->eg.d_desc; ea.eg_cells = e->eg.d_cells; ea.eg_entries = e->eg.d_entries;
-        TiledCloseParamsArgs ca;   // (per-agent parameters: the close launch's twin takes the largest radius too)
-        static_cast<TiledArgs&>(ca) = ta; ca.r_max = e->ap_rmax;
-        void* gparams[] = {&ga};
-        void* params[] = {&ta};
-        void* eparams[] = {&ea};
-        void* cparams[] = {&ca};
-        struct { const void* fn; dim3 grid, block; size_t lds; void** args; } seq[TILED_SORT_LAUNCHES + 3] = {
-            {fn_ptr(&tiled_bin_kernel), s.grid, s.block, 0, gparams},
-            {fn_ptr(&tiled_scan_kernel), dim3(e->cfg.n_arenas), dim3(1024), 0, gparams},
-            {fn_ptr(&tiled_scatter_kernel), s.grid, s.block, 0, gparams},
-            {s.fn, s.grid, s.block, s.lds, e->egrid ? eparams : gparams},
-            {tiled_advance_fn(e), s.grid, s.block, 0, e->egrid ? eparams : params},
-            {tiled_close_fn(e), s.grid, s.block, tiled_close_lds_bytes(e->TILE, e->ap), e->ap ? cparams : params}};
-        for (const auto& k : seq) {   // (each launch timed on its own dispatch, kind 1)
-            ProfScope ps(e, KIND_STEP);
-            const hipError_t r = ps.t0 ? hipExtLaunchKernel(k.fn, k.grid, k.block, k.args, k.lds, e->stream, ps.t0, ps.t1, 0)
-                                       : hipLaunchKernel(k.fn, k.grid, k.block, k.args, k.lds, e->stream);
-            if (r != hipSuccess) return r;
-        }
-        return hipSuccess;
-    }
-    if (e->tiled) {   // solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
-        TiledArgs ta;
+    if (e->tiled) {   // [bin -> scan -> scatter ->] solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
+        // one block for every launch but one: a kernel reads the base of TiledEdgeArgs that it declares (fields a handle does not have stay null / zero)
+        TiledEdgeArgs ta;
         ta.s = a; ta.nv_x = e->nv_x; ta.nv_y = e->nv_y; ta.scr = e->tscr; ta.tiles = e->tiles;
-        TiledCloseParamsArgs ca;   // (per-agent parameters: the close launch's twin takes the largest radius too)
+        ta.cell_count = e->tg_count; ta.cell_start = e->tg_start; ta.key = e->tg_key;
+        ta.sx = e->tg_sx; ta.sy = e->tg_sy; ta.sidx = e->tg_sidx;
+        ta.gx = e->tgx; ta.gy = e->tgy; ta.ics = e->tics;
+        ta.eg = e->eg.d_desc; ta.eg_cells = e->eg.d_cells; ta.eg_entries = e->eg.d_entries;
+        TiledCloseParamsArgs ca;   // (per-agent parameters: the close launch takes the largest radius behind TiledArgs)
         static_cast<TiledArgs&>(ca) = ta; ca.r_max = e->ap_rmax;
         void* params[] = {&ta};
         void* cparams[] = {&ca};
-        const void* fns[3] = {s.fn, tiled_advance_fn(e), tiled_close_fn(e)};
-        const size_t lds[3] = {s.lds, 0, tiled_close_lds_bytes(e->TILE, e->ap)};
-        for (int k = 0; k < 3; ++k) {   // (each launch timed on its own dispatch, kind 1)
+        const struct { const void* fn; dim3 grid, block; size_t lds; void** args; } seq[TILED_SORT_LAUNCHES + 3] = {
+            {fn_ptr(&tiled_bin_kernel), s.grid, s.block, 0, params},
+            {fn_ptr(&tiled_scan_kernel), dim3(e->cfg.n_arenas), dim3(1024), 0, params},
+            {fn_ptr(&tiled_scatter_kernel), s.grid, s.block, 0, params},
+            {s.fn, s.grid, s.block, s.lds, params},
+            {tiled_advance_fn(e), s.grid, s.block, 0, params},
+            {tiled_close_fn(e), s.grid, s.block, tiled_close_lds_bytes(e->TILE, e->ap), e->ap ? cparams : params}};
+        for (int k = e->tgrid ? 0 : TILED_SORT_LAUNCHES; k < TILED_SORT_LAUNCHES + 3; ++k) {   // (each launch timed on its own dispatch, kind 1)
             ProfScope ps(e, KIND_STEP);
-            void** args = (k == 2 && e->ap) ? cparams : params;
-            const hipError_t r = ps.t0 ? hipExtLaunchKernel(fns[k], s.grid, s.block, args, lds[k], e->stream, ps.t0, ps.t1, 0)
-                                       : hipLaunchKernel(fns[k], s.grid, s.block, args, lds[k], e->stream);
+            const hipError_t r = ps.t0 ? hipExtLaunchKernel(seq[k].fn, seq[k].grid, seq[k].block, seq[k].args, seq[k].lds, e->stream, ps.t0, ps.t1, 0)
+                                       : hipLaunchKernel(seq[k].fn, seq[k].grid, seq[k].block, seq[k].args, seq[k].lds, e->stream);
             if (r != hipSuccess) return r;
         }
         return hipSuccess;

@@ -96,7 +96,8 @@ def test_vec_env_has_the_interface():
 def test_per_agent_kernels_are_compiled_as_instantiations_of_their_own():
     """The compiler's metadata (tools/kernel_resources.py): the one-lane LDS-line-table kernel with the AgentParams tag for every
     K class and workgroup size, three observation kernels; no spilled register, no scratch in the observation ones (the table
-    kernels keep LP3's projected lines in a private array by design); nothing else carries the tag."""
+    kernels keep LP3's projected lines in a private array by design); beside them the tag names the per-agent instantiations of the
+    tiled path's three kernel templates (csrc/ca_tiled.h), and nothing else carries it."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources as kr
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
@@ -110,4 +111,6 @@ def test_per_agent_kernels_are_compiled_as_instantiations_of_their_own():
         assert rows[name]["vgpr_spill"] == 0, (name, rows[name])
     for name in obs:
         assert rows[name]["scratch"] == 0 and rows[name]["sgpr_spill"] == 0, (name, rows[name])
-    assert sorted(n for n in rows if "AgentParams" in n) == sorted(want + obs)
+    tiled = ["tiled_solve_kernel<%d, %d, %d, AgentParams>" % (k, tile, search) for k in (5, 10, 16) for tile in (64, 128, 256) for search in (0, 1, 2)] + \
+            ["tiled_advance_kernel<false, AgentParams>", "tiled_advance_kernel<true, AgentParams>", "tiled_close_kernel<AgentParams>"]
+    assert sorted(n for n in rows if "AgentParams" in n) == sorted(want + obs + tiled)

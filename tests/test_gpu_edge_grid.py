@@ -1,5 +1,5 @@
-"""The static edge grid of a grid handle on the GPU (ca_tiled_edge_grid; csrc/ca_tiled.h tiled_grid_edges_solve_kernel and
-tiled_grid_edges_advance_kernel): the obstacle edges in range and the wall test found through a uniform grid over the edges instead of
+"""The static edge grid of a grid handle on the GPU (ca_tiled_edge_grid; csrc/ca_tiled.h tiled_solve_kernel<KMAX, TILE,
+SEARCH_GRID_EDGES> and tiled_advance_kernel<true>): the obstacle edges in range and the wall test found through a uniform grid over the edges instead of
 a scan of the arena's table.  Everything is compared bit for bit with the unchanged CPU oracle through tests/helpers.py, on the hall
 worlds of tests/edge_grid_scenes.py: the crowd's enclosing box full of pillars (N = 300: 488 edges, N = 1100: 1940; with the crowd's
 parameters -- range 2.0 -- the largest obstacle list over 12 steps of seed 3 is 8, so a capacity of 16 never truncates)."""

@@ -1,5 +1,5 @@
 """ORCA parameters per agent on the tiled handles (ca_create_ex with CA_CREATE_TILED_PARAMS: flags 17 and 21; csrc/ca_tiled.h's
-tiled_params_* kernels).  Held bit for bit against what the suite already holds to the oracle: the ordinary per-agent handle up to
+AgentParams instantiations of the tiled kernels).  Held bit for bit against what the suite already holds to the oracle: the ordinary per-agent handle up to
 its 1024 agents (tests/test_gpu_agent_params.py), the oracle's PyRVOSimulator above them (tests/tiled_param_scenes.py), and the
 uniform tiled handles where the arrays equal the configuration.  Every test asserts launch_info() / tiled_info(), so that it cannot
 pass on another kernel family."""

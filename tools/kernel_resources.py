@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Registers, scratch and code size of every kernel of libcaenv.so, read from the compiler's own metadata.
 
-  python tools/kernel_resources.py [--check] [--filter SUBSTR] [--against OTHER.s] [extra hipcc flags ...]
+  python tools/kernel_resources.py [--check] [--filter SUBSTR] [--against OTHER.s [--rename OLD=NEW ...]] [extra hipcc flags ...]
 
 Compiles collision_avoidance_amd/csrc/ca_env.hip for gfx950 with the product flags plus -save-temps into build/isa/
 (hipcc cross-compiles without a GPU), parses the `amdhsa.kernels` metadata of the device assembly and prints one row
@@ -12,10 +12,14 @@ spill at the 128-VGPR limit turns into HBM traffic (round 1: 19 MB per launch) a
 
 --against OTHER.s: the before / after table of a change that must not move the code.  OTHER.s is the device assembly of another
 tree (this tool's build/isa/*.s there, copied aside).  One row per function with both sets of figures (OTHER's first), and
-`identical` where the instruction text is the same after normalisation: comments and blank lines dropped, local labels numbered
-in order of appearance.  It counts and compares; --check then fails when a name is on one side only, when a kernel's VGPRs, SGPRs,
-scratch, spilled VGPRs or static LDS differ, when a function whose text differs has more vector instructions or code bytes than
-OTHER's, or when a hot kernel uses scratch (as without --against).
+`identical` where the instruction text is the same after normalisation: comments, blank lines and section directives dropped, local
+labels numbered in order of appearance.  It counts and compares; --check then fails when a name is on one side only, when a
+kernel's VGPRs, SGPRs, scratch, spilled VGPRs or static LDS differ, when a function whose text differs has more vector instructions
+or code bytes than OTHER's, or when a hot kernel uses scratch (as without --against).
+
+--rename OLD=NEW (with --against, repeatable): a function of OTHER.s whose name -- as the table prints it, with its parameter list --
+matches the regular expression OLD as a whole is paired with this tree's function of the name NEW (groups of OLD as \\1, \\2, ...),
+and the pair is compared like any other.  A function's own symbol inside its text is written as one placeholder on both sides.
 """
 import os
 import re
@@ -28,6 +32,7 @@ from collision_avoidance_amd import build as b  # noqa: E402
 
 OUT = os.path.join(ROOT, "build", "isa")
 ASM = os.path.join(OUT, "ca_env-hip-amdgcn-amd-amdhsa-gfx950.s")
+TILED_ARGS = re.compile(r"\(ca::Tiled\w+<[^()]*>::type\)")   # the tiled kernels' argument block, named by their template arguments already
 HOT = ("step_kernel", "quad_kernel", "pair_kernel", "obs_kernel")   # kernels that must not spill
 
 
@@ -67,44 +72,55 @@ def parse(asm_path=ASM):
                          sgpr_spill=int(g("sgpr_spill_count")), lds=int(g("group_segment_fixed_size")),
                          code_bytes=size.get(sym, 0), valu=valu.get(sym, 0)))
     for r, n in zip(rows, demangle([r["sym"] for r in rows])):
-        r["name"] = n.replace("void ca::", "").replace("(ca::StepArgs)", "").replace("(ca::ObsArgs)", "")
+        r["name"] = TILED_ARGS.sub("", n.replace("void ca::", "").replace("(ca::StepArgs)", "").replace("(ca::ObsArgs)", ""))
     return rows
 
 
 def functions(asm_path):
-    """{symbol: normalised instruction text} of every function of the assembly file: comments and blank lines dropped, white space
-    collapsed, local labels (.LBB<function>_<block>, .Ltmp<n>, ...) renamed in order of appearance."""
+    """{symbol: normalised instruction text} of every function of the assembly file: comments, blank lines and section directives
+    dropped, white space collapsed, the function's own symbol replaced, local labels (.LBB<function>_<block>, .Ltmp<n>, ...) renamed
+    in order of appearance."""
     text = open(asm_path).read()
     out = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
         lines, labels = [], {}
         for ln in m.group(2).splitlines():
             ln = " ".join(ln.split(";", 1)[0].split())
-            if ln:
+            if ln and not re.match(r"\.(text|section)\b", ln):   # (where the function lies -- a template's own section -- is not its text)
                 lines.append(ln)
         body = "\n".join(lines)
         for lab in re.findall(r"\.L\w+", body):
             labels.setdefault(lab, ".L%d" % len(labels))
+        body = body.replace(m.group(1), "<self>")   # (a renamed function differs in its own symbol and nothing else)
         out[m.group(1)] = re.sub(r"\.L\w+", lambda mm: labels[mm.group(0)], body)
     return out
 
 
 def short(name):
-    return name.replace("void ca::", "").replace("ca::", "").replace("(ca::StepArgs)", "").replace("(ca::ObsArgs)", "")
+    return TILED_ARGS.sub("", name.replace("void ca::", "").replace("(ca::StepArgs)", "").replace("(ca::ObsArgs)", "")).replace("ca::", "")
 
 
 FIGS = ("vgpr", "sgpr", "scratch", "vgpr_spill", "lds")   # what decides occupancy and scratch traffic: must not move
 
 
-def against(other, flt=None):
+def against(other, flt=None, renames=()):
     """Prints the before / after table; returns the number of rows that break the bars: a name on one side only, a figure of FIGS
-    moved, or differing text with more vector instructions or code bytes than the other side's."""
+    moved, or differing text with more vector instructions or code bytes than the other side's.  renames: [(OLD, NEW)] of --rename."""
     new_f, old_f = functions(ASM), functions(other)
     new_k = {r["sym"]: r for r in parse(ASM)}
     old_k = {r["sym"]: r for r in parse(other)}
     syms = sorted(set(new_f) | set(old_f))
     names = dict(zip(syms, (short(n) for n in demangle(syms))))
+    by_name = {names[s]: s for s in new_f}
+    for s in [s for s in old_f if s not in new_f]:   # the other side's functions under this tree's symbols
+        to = next((by_name.get(re.fullmatch(pat, names[s]).expand(new)) for pat, new in renames if re.fullmatch(pat, names[s])), None)
+        if to is not None and to not in old_f:
+            old_f[to] = old_f.pop(s)
+            if s in old_k: old_k[to] = old_k.pop(s)
+            names[to] = "%s <- %s" % (names[to].split("(")[0], names[s].split("(")[0])   # (printed whole: label())
+            syms.remove(s)
     size = lambda body: len(re.findall(r"^v_", body, re.M))
+    label = lambda s: names[s] if " <- " in names[s] else names[s][:52]
     bad = same = 0
     print("%-52s %11s %11s %11s %9s %11s %15s %13s  %s" % ("function (other -> this)", "VGPR", "SGPR", "scratch", "v-spill", "LDS", "code B", "VALU", "text"))
     for s in sorted(syms, key=lambda s: names[s]):
@@ -122,7 +138,7 @@ def against(other, flt=None):
         grew = not ident and (size(new_f[s]) > size(old_f[s]) or bool(o and n) and n["code_bytes"] > o["code_bytes"])
         bad += moved or grew
         valu = ("%d -> %d" % (size(old_f[s]), size(new_f[s]))).rjust(13)
-        print("%-52s %s %s %s %s %s %s %s  %s" % (names[s][:52], pair("vgpr", 11), pair("sgpr", 11), pair("scratch", 11), pair("vgpr_spill", 9),
+        print("%-52s %s %s %s %s %s %s %s  %s" % (label(s), pair("vgpr", 11), pair("sgpr", 11), pair("scratch", 11), pair("vgpr_spill", 9),
                                                  pair("lds", 11), pair("code_bytes", 15), valu,
                                                  "identical" if ident else ("differs, FIGURES MOVED" if moved else ("differs, GREW" if grew else "differs"))))
     print("\n%d functions, %d with identical instruction text, %d differ; %d break a bar (a name on one side only; VGPRs / SGPRs / scratch / "
@@ -158,10 +174,11 @@ def main():
     if "--filter" in args:
         flt = args[args.index("--filter") + 1]
     other = args[args.index("--against") + 1] if "--against" in args else None
-    extra = [a for a in args if a.startswith("-") and a not in ("--check", "--filter", "--against")]
+    renames = [tuple(args[k + 1].split("=", 1)) for k, a in enumerate(args) if a == "--rename"]
+    extra = [a for a in args if a.startswith("-") and a not in ("--check", "--filter", "--against", "--rename")]
     ensure_asm(extra)
     if other:
-        bad = against(other, flt)
+        bad = against(other, flt, renames)
         spills = spilling(parse())
         for r in spills:
             print("hot-path kernel with scratch memory: %s: %d B per lane, %d VGPRs spilled" % (r["name"], r["scratch"], r["vgpr_spill"]))

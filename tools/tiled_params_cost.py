@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What per-agent parameters cost on a tiled grid handle (CA_CREATE_TILED_PARAMS; csrc/ca_tiled.h's tiled_params_* kernels): a
+"""What per-agent parameters cost on a tiled grid handle (CA_CREATE_TILED_PARAMS; csrc/ca_tiled.h's AgentParams instantiations): a
 report, no threshold.
 
   python tools/tiled_params_cost.py [--steps 100] [--warmup 30] [--repeats 5] [--out profiles/tiled_params_cost.txt]
