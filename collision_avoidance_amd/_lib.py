@@ -14,6 +14,7 @@ MAX_AGENTS_LARGE = 16384   # on a tiled handle (ca_create_ex with CREATE_TILED)
 CREATE_TILED = 1
 CREATE_TILED_GRID = 4   # only together with CREATE_TILED: the uniform-grid neighbour search of the tiled path
 CREATE_TILED_PARAMS = 16   # only together with CREATE_TILED: the tiled handle takes ca_set_agent_params
+CREATE_TILED_WIDE = 32   # only together with CREATE_TILED, never with CREATE_TILED_PARAMS: max_obst_neighbors up to 64 on the tiled handle
 EDGE_GRID_MAX_EDGES, EDGE_GRID_MAX_ENTRIES = 65535, 1 << 22   # per table of the static edge grid (ca_tiled_edge_grid)
 DONE_XLESS, DONE_GOAL, DONE_REGOAL = 0, 1, 2
 F_OBS, F_STATS, F_AUTORESET, F_NODONE, F_FREEZE = 1, 2, 4, 8, 16

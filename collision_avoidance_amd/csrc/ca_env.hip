@@ -138,6 +138,8 @@ struct ca_env {
     // ca_set_agent_params; while parameters are set, ap = ap_user = true as on an ordinary handle, and ap_rmax is their largest radius
     bool tparams = false;
     float ap_rmax = 0.0f;
+    // ... or obstacle lists of up to 64 on it (CA_CREATE_TILED_WIDE; ca_tiled.h's WideObstLists instantiations, run when S > 16)
+    bool twide = false;
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -414,8 +416,12 @@ static const void* tiled_solve_fn_for(const ca_env* e) {
 }
 enum { TILED_SORT_LAUNCHES = 3 };   // bin, scan, scatter
 // the solve launch of a tiled handle, with the static edge grid on or off (egrid: a grid handle only); AgentParams while
-// ca_set_agent_params is in force (CA_CREATE_TILED_PARAMS)
+// ca_set_agent_params is in force (CA_CREATE_TILED_PARAMS); WideObstLists for obstacle lists above 16 (CA_CREATE_TILED_WIDE)
 static const void* tiled_solve_fn(const ca_env* e, bool egrid) {
+    if (e->S > SMAX) {   // (CA_CREATE_TILED_WIDE: never with per-agent parameters)
+        if (e->tgrid && egrid) return tiled_solve_fn_for<SEARCH_GRID_EDGES, WideObstLists>(e);
+        return e->tgrid ? tiled_solve_fn_for<SEARCH_GRID, WideObstLists>(e) : tiled_solve_fn_for<SEARCH_ALL, WideObstLists>(e);
+    }
     if (e->tgrid && egrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID_EDGES, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID_EDGES>(e);
     if (e->tgrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID>(e);
     return e->ap ? tiled_solve_fn_for<SEARCH_ALL, AgentParams>(e) : tiled_solve_fn_for<SEARCH_ALL>(e);
@@ -491,8 +497,9 @@ static obs_fn_t obs_fn(int obs_bs, bool w16, bool dense = false, bool wide = fal
     if (ac) return dense ? obs_kernel<256, false, true, ArenaCounts> : (w16 ? obs_kernel<256, true, false, ArenaCounts> : obs_kernel<256, false, false, ArenaCounts>);
     // (per-agent parameters: 256 lanes, what obs_block_threads gives every arena size; never with obstacle lists above 16)
     if (ap) return dense ? obs_kernel<256, false, true, AgentParams> : (w16 ? obs_kernel<256, true, false, AgentParams> : obs_kernel<256, false, false, AgentParams>);
-    // (obstacle lists above 16: arenas of at most 128 agents -- 256 lanes, 8-bit ids; ca_create checks that)
-    if (wide) return dense ? obs_kernel<256, false, true, WideObstLists> : obs_kernel<256, false, false, WideObstLists>;
+    // (obstacle lists above 16: arenas of at most 128 agents -- 256 lanes, 8-bit ids; ca_create checks that -- or a tiled handle made
+    // with CA_CREATE_TILED_WIDE: 16-bit ids, the neighbours gathered from global memory)
+    if (wide) return dense ? obs_kernel<256, false, true, WideObstLists> : (w16 ? obs_kernel<256, true, false, WideObstLists> : obs_kernel<256, false, false, WideObstLists>);
     if (dense) return obs_kernel<256, false, true>;   // (arenas of fewer than 16 agents: 256 lanes, 8-bit ids)
     switch (obs_bs) {
         case 1024: return w16 ? obs_kernel<1024, true> : obs_kernel<1024, false>;
@@ -688,8 +695,8 @@ static void pick_variant(ca_env* e) {
     // (CA_REG_LINES, latched by ca_create: 0 forces the LDS line table, 1 the register lines wherever they exist)
     const bool allow = e->sw.reg_lines != 0, force = e->sw.reg_lines == 1;
     e->KT = e->K <= 5 ? 5 : (e->K <= 10 ? 10 : 16);
-    if (e->tiled) {   // one kernel family whatever the world: the LDS line table of a tile, lists of up to 16
-        e->ST = 0; e->SMX = SMAX; e->pair = false;
+    if (e->tiled) {   // one kernel family whatever the world: the LDS line table of a tile, lists of up to 16 (CA_CREATE_TILED_WIDE: 64)
+        e->ST = 0; e->SMX = e->S > SMAX ? SWIDE : SMAX; e->pair = false;
         e->lds = tiled_lds_bytes(e->TILE, e->K, e->S);
         return;
     }
@@ -723,8 +730,9 @@ static void pick_variant(ca_env* e) {
 static const size_t LDS_PER_CU = 160 * 1024;
 static hipError_t apply_variant_attributes(ca_env* e, bool* misfit) {
     const SolveLaunch plain = solve_launch(e, false, false);
-    if (e->tiled) {   // (at most 256 lanes x (32 lines x 16 B + 8 B) = 130 KiB; a grid handle: its edge-grid twin too, whichever is on)
-        *misfit = false;
+    if (e->tiled) {   // (at most 256 lanes x (32 lines x 16 B + 8 B) = 130 KiB, wide lists: ca_create_ex has checked the tile; a grid handle: its edge-grid twin too, whichever is on)
+        *misfit = e->lds > LDS_PER_CU;
+        if (*misfit) return hipSuccess;
         hipError_t r = allow_lds(plain);
         if (r == hipSuccess && e->tgrid) {
             SolveLaunch other = plain;
@@ -774,11 +782,18 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out) { re
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out) {
     if (!cfg || !out) return fail(nullptr, CA_EINVAL, "ca_create: null argument");
     *out = nullptr;
-    if (create_flags & ~(CA_CREATE_TILED | CA_CREATE_TILED_GRID | CA_CREATE_TILED_PARAMS))
+    if (create_flags & ~(CA_CREATE_TILED | CA_CREATE_TILED_GRID | CA_CREATE_TILED_PARAMS | CA_CREATE_TILED_WIDE))
         return fail(nullptr, CA_EINVAL, "ca_create_ex: unknown create_flags 0x%x", create_flags);
     const bool tiled = (create_flags & CA_CREATE_TILED) != 0;
     const bool tgrid = (create_flags & CA_CREATE_TILED_GRID) != 0;
     const bool tparams = (create_flags & CA_CREATE_TILED_PARAMS) != 0;
+    const bool twide = (create_flags & CA_CREATE_TILED_WIDE) != 0;
+    if (twide && !tiled)
+        return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_WIDE (create_flags 0x%x) without CA_CREATE_TILED: it selects the tiled "
+                    "path's wide-obstacle-list kernels (an ordinary handle takes max_obst_neighbors up to %d as it is)", create_flags, CA_MAX_OBST_NEIGHBORS);
+    if (twide && tparams)
+        return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_WIDE together with CA_CREATE_TILED_PARAMS (create_flags 0x%x): per-agent "
+                    "parameters go with obstacle lists of up to %d, as on ordinary handles", create_flags, SMAX);
     if (tparams && !tiled)
         return fail(nullptr, CA_EINVAL, "ca_create_ex: CA_CREATE_TILED_PARAMS (create_flags 0x%x) without CA_CREATE_TILED: it selects the tiled "
                     "path's per-agent-parameter kernels (an ordinary handle takes ca_set_agent_params as it is)", create_flags);
@@ -789,7 +804,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
     if (cfg->n_arenas <= 0 || cfg->n_agents <= 0 || cfg->n_agents > max_agents)
         return fail(nullptr, CA_ERANGE, "ca_create: n_arenas=%d n_agents=%d out of range (agents 1..%d)",
                     cfg->n_arenas, cfg->n_agents, max_agents);
-    if (tiled && cfg->max_obst_neighbors > SMAX)
+    if (tiled && !twide && cfg->max_obst_neighbors > SMAX)
         return fail(nullptr, CA_ERANGE, "ca_create_ex: max_obst_neighbors=%d: wide obstacle lists (above %d) have no tiled form",
                     cfg->max_obst_neighbors, SMAX);
     if (cfg->max_neighbors < 0 || cfg->max_neighbors > CA_MAX_NEIGHBORS)
@@ -832,10 +847,26 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.pair = digit("CA_PAIR"); e->sw.alan_fused = digit("CA_ALAN_FUSED");
     }
     e->tiled = tiled;
+    e->twide = twide;
     if (tiled) {   // CA_TILE = 64 | 128 | 256 (diagnostic switch, tools/tiled_cost.py): the tile of the tiled path; anything else: 128
         const char* v = getenv("CA_TILE");
         const int want = v ? atoi(v) : 0;
         e->TILE = (want == 64 || want == 256) ? want : 128;
+        // obstacle lists above 16 (CA_CREATE_TILED_WIDE): 64 unless CA_TILE names one of the three.  The line table bounds the
+        // residency by LDS per lane whatever the tile, and the smaller tile wastes less of a CU to rounding; a tile
+        // whose table does not fit a CU is refused here -- nothing is launched above the limit
+        if (cfg->max_obst_neighbors > SMAX) {
+            e->TILE = (want == 64 || want == 128 || want == 256) ? want : 64;
+            const size_t need = tiled_lds_bytes(e->TILE, cfg->max_neighbors, cfg->max_obst_neighbors);
+            if (need > LDS_PER_CU) {
+                fail(nullptr, CA_ERANGE, "ca_create_ex: the tiled solve kernel for a tile of %d agents (CA_TILE), max_neighbors=%d, max_obst_neighbors=%d "
+                     "does not fit the 160 KiB of LDS of a CU (%zu B: max_neighbors + max_obst_neighbors lines per lane)", e->TILE,
+                     cfg->max_neighbors, cfg->max_obst_neighbors, need);
+                if (e->own_stream && e->stream) hipStreamDestroy(e->stream);
+                delete e;
+                return CA_ERANGE;
+            }
+        }
         e->tiles = (cfg->n_agents + e->TILE - 1) / e->TILE;
     }
     e->tgrid = tgrid;
@@ -913,7 +944,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         e->lds_q = quad_lds_bytes(e->BSq, e->KT, e->SQ);
         e->quad_cfg = e->quad; e->quad_roll_cfg = e->quad_roll;
     }
-    if (e->S > SMAX && (e->lds + lds_static_bytes(e) > LDS_PER_CU || e->BS > 128 || obs_block_threads(cfg->n_agents) != 256)) {
+    if (!tiled && e->S > SMAX && (e->lds + lds_static_bytes(e) > LDS_PER_CU || e->BS > 128 || obs_block_threads(cfg->n_agents) != 256)) {
         // obstacle lists above 16 live in the LDS line table, K + S lines per lane: 64 lanes with K <= 16, 128 lanes with K <= 10 at S = 64
         if (e->lds + lds_static_bytes(e) > LDS_PER_CU)
             fail(nullptr, CA_ERANGE, "ca_create: the solve kernel for n_agents=%d, max_neighbors=%d, max_obst_neighbors=%d does not fit the "
@@ -2597,7 +2628,8 @@ int ca_tiled_edge_grid(ca_env* e, int32_t on) {
     if (!e) return CA_EINVAL;
     if (!(e->tiled && e->tgrid))
         return fail(e, CA_EINVAL, "ca_tiled_edge_grid: the static edge grid belongs to a grid handle (ca_create_ex with create_flags 0x5 = "
-                    "CA_CREATE_TILED | CA_CREATE_TILED_GRID); this handle was made with create_flags 0x%x", e->tiled ? 0x1 : 0x0);
+                    "CA_CREATE_TILED | CA_CREATE_TILED_GRID, with CA_CREATE_TILED_PARAMS or CA_CREATE_TILED_WIDE or not); this handle was made "
+                    "without CA_CREATE_TILED_GRID (create_flags 0x%x)", e->tiled ? (e->twide ? 0x21 : (e->tparams ? 0x11 : 0x1)) : 0x0);
     if (on != 0 && on != 1) return fail(e, CA_EINVAL, "ca_tiled_edge_grid: on=%d (0 or 1)", (int)on);
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));

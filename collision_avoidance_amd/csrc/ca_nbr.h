@@ -45,6 +45,41 @@ __device__ __forceinline__ void sorted_insert(double (&key)[MAXN], double x) {
     key[0] = key_min(key[0], x);
 }
 
+// A sorted list too long for registers (the wide obstacle lists, up to SWIDE keys): the lane's column of 64-bit words in LDS, slot k
+// at col[k * STRIDE], ascending in slots [0, cnt).  The key is `distance bits << 32 | index`, sorted_insert's order as an integer.  A
+// newcomer shifts the larger keys up by one slot; on a full list (cnt == cap) the largest key falls off -- the newcomer itself, if it
+// is that -- so the list is the cap smallest keys whatever order they arrive in.  Stated once for the one-workgroup kernel (nbr_body)
+// and the tiled solve launch (ca_tiled.h).  (A closure written out -- references to the caller's three variables -- and not a function
+// with parameters: through one the instruction text of the wide step_kernel instantiations moved.)
+template <int STRIDE>
+struct WideInsert {
+    unsigned long long*& col;   // the lane's column, its fill and its capacity
+    int& cnt;
+    const int& cap;
+    __device__ __forceinline__ void operator()(unsigned long long x) const {
+        int k = cnt;
+        if (cnt == cap) {
+            if (col[(cap - 1) * STRIDE] < x) return;
+            k = cap - 1;
+        } else {
+            ++cnt;
+        }
+        while (k > 0) {
+            const unsigned long long y = col[(k - 1) * STRIDE];
+            if (y < x) break;
+            col[k * STRIDE] = y;
+            --k;
+        }
+        col[k * STRIDE] = x;
+    }
+};
+// the index of slot k as the lists store it: an empty slot reads -1, as in the register form
+template <int STRIDE>
+__device__ __forceinline__ unsigned short wide_id(const unsigned long long* col, int cnt, int k) {
+    return k < cnt ? (unsigned short)(unsigned)col[k * STRIDE] : (unsigned short)0xFFFFu;
+}
+__device__ __forceinline__ unsigned long long wide_key(float d, int idx) { return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx; }
+
 // App. A.2, the range test of the obstacle-neighbour list: the agent at pos is on the outer side of edge o1, within range of its line and -- only then
 // computed, into dsq -- of the segment.  `mine`: this lane really has such an edge (inside, and the statements in this order: the kernels' text depends on it).
 __device__ __forceinline__ bool edge_in_range(const ObstDev& o1, V2 pos, float rangeSq, bool mine, float& dsq) {
@@ -114,30 +149,14 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #pragma unroll
     for (int k = 0; k < SR; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
     int oin = 0;
-    // (wide) the lane's column of the LDS list, ascending in slots [0, wcnt): a newcomer shifts the larger keys up by one slot;
-    // on a full list the largest key falls off -- the newcomer itself, if it is that
+    // (wide) the lane's column of the LDS list (WideList above)
     unsigned long long* wkey = nullptr;
     int wcnt = 0;
     if constexpr (WIDE) {
         extern __shared__ float4 smem4[];
         wkey = reinterpret_cast<unsigned long long*>(smem4) + tid;
     }
-    auto wide_insert = [&](unsigned long long x) __attribute__((always_inline)) {
-        int k = wcnt;
-        if (wcnt == S) {
-            if (wkey[(S - 1) * BS] < x) return;
-            k = S - 1;
-        } else {
-            ++wcnt;
-        }
-        while (k > 0) {
-            const unsigned long long y = wkey[(k - 1) * BS];
-            if (y < x) break;
-            wkey[k * BS] = y;
-            --k;
-        }
-        wkey[k * BS] = x;
-    };
+    const WideInsert<BS> wide_insert{wkey, wcnt, S};
     {
         float rangeSq = sqr(p.time_horizon_obst * p.max_speed + p.radius);
         if constexpr (AP) {
@@ -148,7 +167,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             float dsq;
             if (edge_in_range(o1, pos, rangeSq, mine, dsq)) {
                 ++oin;
-                if constexpr (WIDE) wide_insert(((unsigned long long)__float_as_uint(dsq) << 32) | (unsigned)e);
+                if constexpr (WIDE) wide_insert(wide_key(dsq, e));
                 else sorted_insert<SR>(okey, make_key(dsq, e));
             }
         };
@@ -165,8 +184,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     const int ocnt = oin < S ? oin : S;
     if constexpr (WIDE) {     // the LDS list goes to memory before the agent scan (an empty slot reads -1, as in the register form)
         if (active) {
-            for (int k = 0; k < S; ++k)
-                p.obst_idx[((size_t)a * S + k) * N + i] = k < wcnt ? (unsigned short)(unsigned)wkey[k * BS] : (unsigned short)0xFFFFu;
+            for (int k = 0; k < S; ++k) p.obst_idx[((size_t)a * S + k) * N + i] = wide_id<BS>(wkey, wcnt, k);
         }
     } else if constexpr (SM > 4) {   // a list of 16 keys is 32 registers: it goes to memory now, not after the agent scan
         if (active) {

@@ -186,6 +186,11 @@ enum TiledSearch { SEARCH_ALL = 0,          // every agent of the arena, a tile 
 // neighbor_dist and max_neighbors stay per handle.  The edge grid is built for the LARGEST range of the handle (ca_env.hip
 // edge_grid_range); the corner rule of the walk does not depend on the cell size, so an agent of a smaller range simply walks fewer
 // cells.
+// WideObstLists in PER (a handle made with CA_CREATE_TILED_WIDE whose max_obst_neighbors exceeds SMAX; never beside AgentParams): the
+// solve launch keeps up to SWIDE obstacle neighbours.  The sorted list is built in LDS, in the lane's column at the head of the line
+// table (ca_nbr.h WideInsert), goes to obst_idx before the agent scan, and a barrier stands between the columns' last use and the first
+// line; up to K + S lines per lane go into the table, LP3 projects KMAX + SWIDE.  The advance and close launches do not depend on S.
+// The host sizes the tile so that tiled_lds_bytes fits a CU (ca_env.hip ca_create_ex: 64 unless CA_TILE says otherwise).
 struct TiledCloseParamsArgs : TiledArgs {
     float r_max;   // the largest radius of the handle: R of lists_bound_pairs / list_misses_pairs (r_i + r_j <= 2 r_max)
 };
@@ -203,6 +208,8 @@ template <class... PER> struct TiledCloseArgs { using type = std::conditional_t<
 template <int KMAX, int TILE, int SEARCH, class... PER>
 __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledSolveArgs<SEARCH>::type t) {
     constexpr bool AP = has_tag<AgentParams, PER...>;
+    constexpr bool WIDE = has_tag<WideObstLists, PER...>;
+    static_assert(!(WIDE && AP), "per-agent parameters go with obstacle lists of up to 16");
     const StepArgs& p = t.s;
     extern __shared__ float4 smem4[];
     const int tid = threadIdx.x;
@@ -254,10 +261,19 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
     const int n_edges = p.tab_off != nullptr ? p.tab_off[a + 1] - p.tab_off[a] : p.n_obst;
     int oin = 0;
     {
-        const int sofs = SMAX - S;   // the S-entry list is right-aligned in the register array
-        double okey[SMAX];
+        // WideObstLists in PER (lists of 17 .. SWIDE edges, a handle made with CA_CREATE_TILED_WIDE): 2 S registers for the keys do not
+        // exist, so the sorted list is built in the lane's column at the head of the line table, which is idle until the lines are built
+        // (ca_nbr.h WideInsert: key slot k of lane t is the 64-bit word [k][t], consecutive lanes' words consecutive in LDS).  All
+        // three searches feed it; it keeps the S smallest keys in whatever order they arrive.
+        constexpr int SR = WIDE ? 1 : SMAX;   // register slots of the list (wide: none)
+        const int sofs = SR - S;   // the S-entry list is right-aligned in the register array
+        double okey[SR];
 #pragma unroll
-        for (int k = 0; k < SMAX; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
+        for (int k = 0; k < SR; ++k) okey[k] = (k < sofs) ? key_dummy() : key_empty();
+        unsigned long long* wkey = nullptr;
+        int wcnt = 0;
+        if constexpr (WIDE) wkey = reinterpret_cast<unsigned long long*>(smem4) + tid;
+        const WideInsert<TILE> wide_insert{wkey, wcnt, S};
         const float rangeSq = sqr(horizon_obst * max_speed + radius);
         if constexpr (SEARCH == SEARCH_GRID_EDGES) {
             // The static edge grid (ca_edge_grid_host.h): the cells of the columns cell(fl(x - range)) .. cell(fl(x + range)) and the rows
@@ -288,7 +304,8 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
                                 const float dsq = distSqPointSegment(a1, a2, pos);
                                 if (dsq < rangeSq) {
                                     ++oin;
-                                    sorted_insert<SMAX>(okey, make_key(dsq, e));
+                                    if constexpr (WIDE) wide_insert(wide_key(dsq, e));
+                                    else sorted_insert<SR>(okey, make_key(dsq, e));
                                 }
                             }
                         }
@@ -305,14 +322,22 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
                     const float dsq = distSqPointSegment(a1, a2, pos);
                     if (dsq < rangeSq) {
                         ++oin;
-                        sorted_insert<SMAX>(okey, make_key(dsq, e));
+                        if constexpr (WIDE) wide_insert(wide_key(dsq, e));
+                        else sorted_insert<SR>(okey, make_key(dsq, e));
                     }
                 }
             }
         }
-        if (active) {
+        if constexpr (WIDE) {   // the LDS list goes to memory before the agent scan (an empty slot reads -1, as in the register form)
+            if (active) {
+                for (int k = 0; k < S; ++k) p.obst_idx[((size_t)a * S + k) * N + i] = wide_id<TILE>(wkey, wcnt, k);
+            }
+            // a lane's line slot overlaps OTHER lanes' key words (16 B lines over 8 B keys): every column has been read before the
+            // first line is written, whatever the search -- the grid forms have no other barrier, the scan below none at K = 0
+            __syncthreads();
+        } else if (active) {
 #pragma unroll
-            for (int k = 0; k < SMAX; ++k)
+            for (int k = 0; k < SR; ++k)
                 if (k >= sofs) p.obst_idx[((size_t)a * S + (k - sofs)) * N + i] = (unsigned short)key_index(okey[k]);
         }
     }
@@ -432,7 +457,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
     V2 nv = mk(0.0f, 0.0f);
     int fail = nl;
     if (active) fail = lp2(ls, nl, max_speed, pref, false, nv);
-    if (active && fail < nl) lp3<KMAX + SMAX>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, max_speed, nv);
+    if (active && fail < nl) lp3<KMAX + (WIDE ? SWIDE : SMAX)>((__attribute__((address_space(3))) char*)ls.base, ls.stride, nl, numObstLines, fail, max_speed, nv);
     if (active) { t.nv_x[q] = nv.x; t.nv_y[q] = nv.y; }
 }
 

@@ -74,7 +74,8 @@ class Collision_Avoidance_Env(*_bases):
         self.vec = VecCollisionAvoidanceEnv(1, self.numAgents, scenario="doorway", device=self._device,
                                             seed=self._seed, use_torch=False, max_obst_neighbors=self._max_obst_neighbors,
                                             allow_obst_overflow=self._allow_obst_overflow,
-                                            tiled=self.numAgents > _lib.MAX_AGENTS)   # (any numAgents, like the reference's)
+                                            tiled=self.numAgents > _lib.MAX_AGENTS,   # (any numAgents, like the reference's)
+                                            tiled_wide=self.numAgents > _lib.MAX_AGENTS and (self._max_obst_neighbors or 0) > 16)
 
     @property
     def step_count(self):

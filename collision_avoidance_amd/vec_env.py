@@ -88,7 +88,7 @@ class VecCollisionAvoidanceEnv:
     agent_counts: [A] ints handed to set_agent_counts() before the scenario is initialised: arena a holds agent_counts[a] of its
                n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
     tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
-               arena spread over several workgroups, a step in three launches (tiled_info()); max_obst_neighbors <= 16, no
+               arena spread over several workgroups, a step in three launches (tiled_info()); max_obst_neighbors <= 16 (tiled_wide=True: 64), no
                agent_counts, and agent_params only with tiled_params=True (ValueError).  Results are the ordinary handle's bit for bit.  False (default): one
                workgroup per arena, n_agents <= 1024.  "grid": the tiled path with its uniform-grid neighbour search
                (CA_CREATE_TILED | CA_CREATE_TILED_GRID): the arena's agents are sorted by cell in three more launches per step and an
@@ -100,22 +100,35 @@ class VecCollisionAvoidanceEnv:
                and takes agent_params= / set_agent_params() -- a heterogeneous crowd of up to 16384 agents in one world.  Until
                parameters are set it runs the uniform tiled kernels.  agent_counts stays refused.  False (default): a tiled
                handle refuses per-agent parameters.
+    tiled_wide: True (with tiled=True or "grid" only, never with tiled_params=True; ValueError otherwise): the tiled handle is made
+               with CA_CREATE_TILED_WIDE and takes max_obst_neighbors up to 64 -- a large crowd in a polyline world (a pillar hall)
+               without truncated obstacle lists.  With max_obst_neighbors <= 16 it is the handle of tiled= alone; above, the solve
+               launch builds the sorted list in the tile's LDS line table, the tile is 64 agents (tiled_info()), and the results
+               are the ordinary wide handle's and the oracle's bit for bit.  False (default): a tiled handle refuses
+               max_obst_neighbors > 16.
     """
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False):
+                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False, tiled_wide=False):
         if tiled not in (False, True, "grid", None, 0, 1):
             raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
         if tiled_params and not tiled:
             raise ValueError("tiled_params=True without tiled=True or tiled='grid': it selects the tiled path's per-agent-parameter "
                              "kernels (an ordinary handle takes agent_params= as it is)")
+        if tiled_wide and not tiled:
+            raise ValueError("tiled_wide=True without tiled=True or tiled='grid': it selects the tiled path's wide-obstacle-list "
+                             "kernels (an ordinary handle takes max_obst_neighbors up to 64 as it is)")
+        if tiled_wide and tiled_params:
+            raise ValueError("tiled_wide=True together with tiled_params=True: per-agent parameters go with obstacle lists of up to "
+                             "16, as on ordinary handles")
         if tiled and ((agent_params and not tiled_params) or agent_counts is not None):
             raise ValueError("tiled=%r: the tiled kernels have no per-arena-count form, and their per-agent-parameter form is chosen "
                              "at construction (agent_params= goes with tiled_params=True or with tiled=False, agent_counts= with "
                              "tiled=False)" % (tiled,))
         self.tiled = "grid" if tiled == "grid" else bool(tiled)
         self.tiled_params = bool(tiled_params)
+        self.tiled_wide = bool(tiled_wide)
         if agent_counts is not None and scenario not in (None, "doorway"):
             raise ValueError("agent_counts: scenario %r lays its agents out as a function of n_agents; only 'doorway' or None "
                              "go with per-arena agent counts" % (scenario,))
@@ -144,7 +157,7 @@ class VecCollisionAvoidanceEnv:
         h = C.c_void_p()
         if self.tiled:
             flags = _lib.CREATE_TILED | (_lib.CREATE_TILED_GRID if self.tiled == "grid" else 0) | \
-                (_lib.CREATE_TILED_PARAMS if self.tiled_params else 0)
+                (_lib.CREATE_TILED_PARAMS if self.tiled_params else 0) | (_lib.CREATE_TILED_WIDE if self.tiled_wide else 0)
             rc = self.L.ca_create_ex(C.byref(self.cfg), flags, self.device, None, C.byref(h))
         else:
             rc = self.L.ca_create(C.byref(self.cfg), self.device, None, C.byref(h))

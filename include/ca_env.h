@@ -35,6 +35,8 @@ extern "C" {
                                     pillar halls).  Lists above 16 take a kernel of their own (ca_solver_info) and need
                                     n_agents <= 128 and max_neighbors + max_obst_neighbors lines per lane in a CU's LDS:
                                     at 64, n_agents <= 64 with any max_neighbors, n_agents <= 128 with max_neighbors <= 10.
+                                    Larger crowds: a tiled handle made with CA_CREATE_TILED_WIDE (ca_create_ex), up to
+                                    CA_MAX_AGENTS_LARGE agents with lists of up to 64 and any max_neighbors.
                                     A list that meets more edges in range
                                     than it holds drops the farthest, counts it (ca_stats.obst_overflow) AND makes every
                                     later step call fail with CA_ERANGE: see ca_allow_obstacle_overflow */
@@ -47,9 +49,11 @@ extern "C" {
 #define CA_CREATE_TILED 1u /* the tiled solve path: n_agents 1..CA_MAX_AGENTS_LARGE, see ca_create_ex */
 #define CA_CREATE_TILED_GRID 4u /* with CA_CREATE_TILED only (flags == 5): the tiled path finds the agent neighbours through a uniform
                                    grid sorted across workgroups, see ca_create_ex.  Bit 2u is NOT a flag: it stays unknown
-                                   (CA_EINVAL), as does bit 8u and every bit above 16u */
+                                   (CA_EINVAL), as does bit 8u and every bit above 32u */
 #define CA_CREATE_TILED_PARAMS 16u /* with CA_CREATE_TILED only (flags == 17 or 21): the tiled handle takes ca_set_agent_params, see
                                       ca_create_ex */
+#define CA_CREATE_TILED_WIDE 32u /* with CA_CREATE_TILED only (flags == 33 or 37), never with CA_CREATE_TILED_PARAMS: the tiled handle
+                                    takes max_obst_neighbors up to CA_MAX_OBST_NEIGHBORS, see ca_create_ex */
 
 /* error codes */
 #define CA_OK 0
@@ -177,8 +181,8 @@ typedef struct ca_env ca_env;
 int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
 /* ca_create with create flags; ca_create(cfg, ...) is ca_create_ex(cfg, 0, ...).  Unknown flag bits -> CA_EINVAL.
  * CA_CREATE_TILED: one large crowd in one world (the reference's Collision_Avoidance_Env(numAgents) / Collision_Avoidance_Sim(numAgents)
- * take any number).  n_agents may be 1..CA_MAX_AGENTS_LARGE (above -> CA_ERANGE, "out of range"); max_obst_neighbors <= 16 (above ->
- * CA_ERANGE: wide lists have no tiled form); max_neighbors 0..16 at any size.
+ * take any number).  n_agents may be 1..CA_MAX_AGENTS_LARGE (above -> CA_ERANGE, "out of range"); max_obst_neighbors <= 16 (above,
+ * without CA_CREATE_TILED_WIDE -> CA_ERANGE: wide lists have no tiled form; with it, below: up to 64); max_neighbors 0..16 at any size.
  *   - The handle runs the tiled kernels whatever its size (below 1025 agents: for comparison and tests): one lane per agent, an
  *     arena spread over ceil(n_agents / tile) workgroups, a step in three launches on the handle's stream -- solve (neighbour
  *     search over the whole arena, N^2 per arena; lines; LP), advance (integration, reward, goal / wall tests), close (pair count,
@@ -217,7 +221,22 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
  *     that range is the cell size and the margin of an edge's bounding box.  Setting and clearing the parameters rebuild the grids
  *     while the edge grid is on (a refused rebuild fails the call and changes nothing); switching it on afterwards uses the same
  *     range.  The walk's corner rule does not depend on the cell size, so an agent of a smaller range walks fewer cells.
- *   - ca_set_agent_counts stays CA_EINVAL; neighbor_dist and max_neighbors stay per handle. */
+ *   - ca_set_agent_counts stays CA_EINVAL; neighbor_dist and max_neighbors stay per handle.
+ * CA_CREATE_TILED_WIDE, together with CA_CREATE_TILED (flags == 33: the plain tiled handle, 37: the grid handle; without
+ * CA_CREATE_TILED, with CA_CREATE_TILED_PARAMS -- per-agent parameters go with lists of up to 16, as on ordinary handles --, or with
+ * bit 2u or 8u -> CA_EINVAL): the tiled handle of those flags with max_obst_neighbors 1..CA_MAX_OBST_NEIGHBORS -- a large crowd in a
+ * polyline world (a pillar hall puts 30 to 60 edges in range of an agent) without truncated obstacle lists.  Opt-in at create, like
+ * the grid: the tiled path fixes its kernel family when the handle is made.
+ *   - With max_obst_neighbors <= 16 the handle IS the handle of flags 1 / 5: the same kernels, launches and bits.
+ *   - With max_obst_neighbors > 16 the solve launch and the observation are their wide twins: the sorted obstacle list is built in
+ *     the tile's LDS line table (max_neighbors + max_obst_neighbors lines per lane), the results are the oracle's and the ordinary
+ *     wide handle's bit for bit, the lists (CA_FLD_OBST_*) the same, order included.  The number of launches does not change, nor
+ *     does anything else of a tiled handle: limits, 16-bit ids, step flags, the sticky overflow error, ca_rollout, ALAN in the
+ *     three-launch form, per-arena obstacle tables, ca_tiled_edge_grid on the grid handle, the two refusals above.  Installing small
+ *     or large worlds does not change its kernels.
+ *   - The tile of such a handle is 64 agents (ca_tiled_info; the table is bounded by LDS per lane: DESIGN.md 7i).  CA_TILE=128 or 256
+ *     is honoured where tile x ((max_neighbors + max_obst_neighbors) x 16 + 8) bytes fit the 160 KiB of LDS of a CU; where they do
+ *     not, ca_create_ex -> CA_ERANGE.  Nothing is launched above the limit. */
 int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* stream, ca_env** out);
 int ca_destroy(ca_env* env);
 const char* ca_last_error(const ca_env* env);
