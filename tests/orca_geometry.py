@@ -35,14 +35,28 @@ def _left(v):
 # ---------------------------------------------------------------------------------------------------------------------
 # obstacles
 # ---------------------------------------------------------------------------------------------------------------------
-def obstacle_table(verts, nxt, n_original=None):
+def obstacle_table(verts, nxt, poly_sizes=None):
     """From the processed vertex table (positions + successor, as sim.getObstacleVertex / getNextObstacleVertexNo expose it):
     predecessor, unit edge directions and the convexity flag of every vertex -- derived here from the coordinates alone
     (a vertex is convex when the boundary turns left at it or goes straight on).  Vertices beyond the caller's own
-    (n_original: the points where processObstacles cut an edge, appended behind them) lie ON an edge: straight on, convex by
-    construction -- their rounded coordinates must not decide it."""
+    (the points where processObstacles cut an edge, appended behind them) lie ON an edge: straight on, convex by
+    construction -- their rounded coordinates must not decide it.  poly_sizes: the vertex count of every polygon as the caller
+    added it (its vertices come first in the table, polygon after polygon).  Both ends of a TWO-vertex polygon -- a free-standing
+    wall -- are convex whatever processObstacles did to it: once the wall is cut its cycle has four vertices, all collinear, and
+    the turn at its own ends is a cross product of two parallel vectors, i.e. rounding (upstream sets the flag when the
+    obstacle is added, before any cut).  An int is taken as the number of original vertices alone (no wall is then known)."""
     verts = np.asarray(verts, np.float64)
     n = len(verts)
+    wall_end = np.zeros(n, bool)
+    if poly_sizes is None or isinstance(poly_sizes, (int, np.integer)):
+        n_original = poly_sizes
+    else:
+        n_original = int(sum(poly_sizes))
+        base = 0
+        for m in poly_sizes:
+            if m == 2:
+                wall_end[base:base + 2] = True
+            base += m
     prv = np.zeros(n, int)
     for i in range(n):
         prv[nxt[i]] = i
@@ -52,7 +66,7 @@ def obstacle_table(verts, nxt, n_original=None):
         unit[i] = d / np.linalg.norm(d)
     convex = np.zeros(n, bool)
     for i in range(n):
-        if nxt[nxt[i]] == i or (n_original is not None and i >= n_original):   # a free-standing wall: both ends convex; a cut point
+        if wall_end[i] or nxt[nxt[i]] == i or (n_original is not None and i >= n_original):   # a free-standing wall's end; a cut point
             convex[i] = True
         else:
             a, b = verts[i] - verts[prv[i]], verts[nxt[i]] - verts[i]

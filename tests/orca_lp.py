@@ -31,12 +31,15 @@ def _det(a, b):
     return a[0] * b[1] - a[1] * b[0]
 
 
-def lp1_f64(lines, k, radius, opt, dir_opt):
-    """App. A.5 LP1 on lines[k] = (point, dir) against lines[:k]; the new point, or None."""
+def lp1_f64(lines, k, radius, opt, dir_opt, slack=None):
+    """App. A.5 LP1 on lines[k] = (point, dir) against lines[:k]; the new point, or None.  slack: a list that receives how far the
+    outcome was from the other one -- the length of the interval left on the line, or by how much it came out empty."""
+    note = (lambda x: slack.append(abs(float(x)))) if slack is not None else (lambda x: None)
     p, d = lines[k]
     dp = p @ d
     disc = dp * dp + radius * radius - p @ p
     if disc < 0.0:
+        note(disc)
         return None
     sq = np.sqrt(disc)
     t_left, t_right = -dp - sq, -dp + sq
@@ -44,6 +47,7 @@ def lp1_f64(lines, k, radius, opt, dir_opt):
         den, num = _det(d, dj), _det(dj, p - pj)
         if abs(den) <= EPS:
             if num < 0.0:
+                note(num)
                 return None
             continue
         t = num / den
@@ -52,14 +56,17 @@ def lp1_f64(lines, k, radius, opt, dir_opt):
         else:
             t_left = max(t_left, t)
         if t_left > t_right:
+            note(t_left - t_right)
             return None
+    note(t_right - t_left)
     if dir_opt:
         return p + (t_right if opt @ d > 0.0 else t_left) * d
     return p + min(max((opt - p) @ d, t_left), t_right) * d
 
 
-def lp2_f64(lines, radius, opt, dir_opt):
-    """App. A.5 LP2: (index of the line it failed at, or len(lines); the point)."""
+def lp2_f64(lines, radius, opt, dir_opt, slack=None):
+    """App. A.5 LP2: (index of the line it failed at, or len(lines); the point).  slack: a list that receives, for every line
+    visited, the distance of its decision from the other outcome: how far the point lay inside the half-plane, or LP1's slack."""
     if dir_opt:
         res = opt * radius
     elif opt @ opt > radius * radius:
@@ -68,18 +75,23 @@ def lp2_f64(lines, radius, opt, dir_opt):
         res = opt.copy()
     for i, (p, d) in enumerate(lines):
         if _det(d, p - res) > 0.0:
-            new = lp1_f64(lines, i, radius, opt, dir_opt)
+            new = lp1_f64(lines, i, radius, opt, dir_opt, slack)
             if new is None:
                 return i, res
             res = new
+        elif slack is not None:
+            slack.append(abs(float(_det(d, p - res))))
     return len(lines), res
 
 
-def lp3_f64(lines, n_obst, begin, radius, res):
-    """App. A.5 LP3: (the point, the largest |point| among the projected lines it built)."""
+def lp3_f64(lines, n_obst, begin, radius, res, slack=None):
+    """App. A.5 LP3: (the point, the largest |point| among the projected lines it built).  slack: as in lp2_f64, for every decision
+    of this call and of the LP2 calls it makes."""
     distance, far = 0.0, 0.0
     for i in range(begin, len(lines)):
         pi, di = lines[i]
+        if slack is not None:
+            slack.append(abs(float(_det(di, pi - res) - distance)))
         if _det(di, pi - res) > distance:
             proj = list(lines[:n_obst])
             for pj, dj in lines[n_obst:i]:
@@ -93,7 +105,7 @@ def lp3_f64(lines, n_obst, begin, radius, res):
                 nd = dj - di
                 proj.append((pt, nd / np.sqrt(nd @ nd)))
                 far = max(far, float(np.sqrt(pt @ pt)))
-            fail, new = lp2_f64(proj, radius, np.array([-di[1], di[0]]), True)
+            fail, new = lp2_f64(proj, radius, np.array([-di[1], di[0]]), True, slack)
             if fail == len(proj):
                 res = new
             distance = _det(di, pi - res)

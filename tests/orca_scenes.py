@@ -20,6 +20,10 @@ Families (what each is built to provoke):
   dense     (dense_scenes, apart from all_scenes: eleven agents) the bench's regime -- a full list of ten neighbours, three to
             seven of them overlapping the focus agent, a wall in range; in every other scene two of those on opposite sides of it:
             LP3 on nearly parallel far-away lines, whose fp32 answer leaves the speed disc (tests/orca_lp.py)
+  slats     (slats_scenes, apart from all_scenes) 17 .. 40 short walls in two rings, or in one ring of rising distance: obstacle
+            lists of more than 16 edges, many covered edges or many uncovered lines, walls cut by processObstacles
+  crossing  (crossing_scenes, apart as well) short walls of any direction that cross each other: cut walls, lists towards 64
+with_agent_params(scenes) attaches radius, max_speed and the two horizons per agent to copies of any of these.
 """
 import math
 
@@ -303,7 +307,65 @@ def dense_overlap(rng, n):
     return out
 
 
+def _neighbours_round(rng, p0):
+    """zero to three neighbours 1.0 .. 2.5 from p0 -> positions, velocities, preferred velocities with the focus agent first"""
+    k = rng.randint(0, 4)
+    pos = [p0] + [p0 + rng.uniform(1.0, 2.5) * _unit(rng.uniform(0, 2 * math.pi)) for _ in range(k)]
+    vel = [_vel(rng) for _ in range(k + 1)]
+    pref = [_unit(rng.uniform(0, 2 * math.pi)) for _ in range(k + 1)]
+    return pos, vel, pref
+
+
+def slats(rng, n, m=None):
+    """m = 17 .. 40 short free-standing walls round the focus agent, roughly tangential and every one of them in range (tau_obst
+    vmax + r = 2): the obstacle list holds more than 16 edges, and processObstacles cuts the walls whose line another one crosses.
+    Even scenes: two rings (0.8 .. 1.1 and 1.45 .. 1.85 away) -- the inner ring's lines cover most of the outer ring (the
+    already-covered scan over a long list), and their legs meet at the origin of velocity space (the degenerate apex of
+    tests/test_oracle_orca_definition.py).  Odd scenes: ONE ring of shorter walls whose distance grows with the angle, from 1.45
+    to 1.85 once round -- a wall d2 away is covered by a nearer one d1 away and an angle D off once d2 cos D >= d1, so neighbours
+    whose distances differ by less than their pitch squared cover nothing, and the programme gets more than 16 obstacle lines."""
+    out = []
+    for k in range(n):
+        p0 = rng.uniform(3, 7, 2)
+        mk = rng.randint(17, 41) if m is None else m
+        rings = ((mk // 2, 0.8, 1.1), (mk - mk // 2, 1.45, 1.85)) if k % 2 == 0 else ((mk, 1.45, 1.85),)
+        polys = []
+        for c, lo, hi in rings:
+            a0 = rng.uniform(0, 2 * math.pi)
+            for i in range(c):
+                t = (i + rng.uniform(-0.15, 0.15)) / c
+                rad = rng.uniform(lo, hi) if k % 2 == 0 else lo + (hi - lo) * t
+                ang = a0 + 2 * math.pi * t
+                half = (rng.uniform(0.3, 0.8) if k % 2 == 0 else rng.uniform(0.1, 0.3)) * 0.3 * 2 * math.pi * rad / c
+                u = _unit(ang + math.pi / 2 + rng.uniform(-0.5, 0.5))
+                ctr = p0 + rad * _unit(ang)
+                polys.append([ctr - half * u, ctr + half * u])
+        pos, vel, pref = _neighbours_round(rng, p0)
+        out.append(_scene("slats", polys, pos, vel, pref))
+    return out
+
+
+def crossing(rng, n):
+    """Short free-standing walls of any direction strewn round the focus agent, many of them crossing each other: processObstacles
+    cuts them into pieces (a cut wall is a cycle of four or more collinear vertices), and the list grows towards its 64."""
+    out = []
+    for k in range(n):
+        p0 = rng.uniform(3, 7, 2)
+        polys = []
+        for i in range(rng.randint(22, 37)):
+            ctr = p0 + rng.uniform(0.7, 1.9) * _unit(rng.uniform(0, 2 * math.pi))
+            u = _unit(rng.uniform(0, 2 * math.pi))
+            half = rng.uniform(0.05, 0.3)
+            polys.append([ctr - half * u, ctr + half * u])
+        pos, vel, pref = _neighbours_round(rng, p0)
+        out.append(_scene("crossing", polys, pos, vel, pref))
+    return out
+
+
 DENSE = ("dense", dense_overlap, 300, 18)
+SLATS = ("slats", slats, 300, 19)
+CROSSING = ("crossing", crossing, 120, 20)
+WIDE_CAP = 64               # the obstacle-list capacity the two families above are run with
 FAMILIES = (("walls", walls, 1500, 11), ("convex", convex, 1200, 12), ("notch", notch, 900, 13), ("room", room, 3000, 14),
             ("crowd", crowd, 1600, 15), ("mirror", mirror, 800, 16), ("hemmed", hemmed, 1200, 17))
 
@@ -322,16 +384,49 @@ def dense_scenes(scale=1.0):
     return fn(np.random.RandomState(seed), max(6, int(n * scale)))
 
 
+def slats_scenes(scale=1.0):
+    """The two families of many short walls (lists of 17 .. 64 edges: their own batches, with lists of WIDE_CAP), seeded."""
+    return SLATS[1](np.random.RandomState(SLATS[3]), max(6, int(SLATS[2] * scale)))
+
+
+def crossing_scenes(scale=1.0):
+    return CROSSING[1](np.random.RandomState(CROSSING[3]), max(6, int(CROSSING[2] * scale)))
+
+
+PARAM_NAMES = ("radius", "max_speed", "time_horizon", "time_horizon_obst")
+PARAM_RANGES = dict(radius=(0.3, 0.7), max_speed=(0.6, 1.4), time_horizon=(0.75, 3.0), time_horizon_obst=(0.75, 3.0))
+PARAM_DEFAULTS = dict(radius=R, max_speed=VMAX, time_horizon=TAU, time_horizon_obst=TAU_OBST)
+PARAM_SEED = 77
+
+
+def with_agent_params(scenes, seed=PARAM_SEED):
+    """Copies of the scenes (which stay as they are) with ORCA parameters of its own for every agent: four fp32 arrays a scene, drawn
+    from PARAM_RANGES by ONE generator running through the list -- the configuration's values lie inside every range."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for sc in scenes:
+        sc = dict(sc)
+        for name in PARAM_NAMES:
+            sc[name] = rng.uniform(PARAM_RANGES[name][0], PARAM_RANGES[name][1], len(sc["pos"])).astype(np.float32)
+        out.append(sc)
+    return out
+
+
 def run_oracle_sim(scene, capture=True):
     """One doStep of the scene through the oracle's simulator (oracle/rvo2_shim.py); returns (new velocity of the focus agent,
-    its captured lines) -- CPU test infrastructure."""
+    its captured lines) -- CPU test infrastructure.  A scene of with_agent_params adds every agent with its own parameters."""
     from oracle import oracle as o
     from oracle.rvo2_shim import PyRVOSimulator
     n = len(scene["pos"])
-    s = PyRVOSimulator(timeStep=DT, neighborDist=NEIGHBOR_DIST, maxNeighbors=max(1, n - 1), timeHorizon=TAU,
+    K = max(1, n - 1)
+    s = PyRVOSimulator(timeStep=DT, neighborDist=NEIGHBOR_DIST, maxNeighbors=K, timeHorizon=TAU,
                        timeHorizonObst=TAU_OBST, radius=R, maxSpeed=VMAX)
     for i in range(n):
-        s.addAgent((float(scene["pos"][i, 0]), float(scene["pos"][i, 1])))
+        if "radius" in scene:
+            s.addAgent((float(scene["pos"][i, 0]), float(scene["pos"][i, 1])), NEIGHBOR_DIST, K, float(scene["time_horizon"][i]),
+                       float(scene["time_horizon_obst"][i]), float(scene["radius"][i]), float(scene["max_speed"][i]))
+        else:
+            s.addAgent((float(scene["pos"][i, 0]), float(scene["pos"][i, 1])))
         s.setAgentVelocity(i, (float(scene["vel"][i, 0]), float(scene["vel"][i, 1])))
         s.setAgentPrefVelocity(i, (float(scene["pref"][i, 0]), float(scene["pref"][i, 1])))
     for q in scene["polys"]:
@@ -341,7 +436,7 @@ def run_oracle_sim(scene, capture=True):
     if capture:
         o.capture_next(0, scene["focus"])
     s.doStep()
-    cap = o.captured() if capture else None
+    cap = o.captured(128) if capture else None          # (up to WIDE_CAP obstacle lines and the agents')
     if capture:
         o.capture_next(-1, -1)
     return np.array(s.getAgentVelocity(scene["focus"]), np.float64), cap, s
