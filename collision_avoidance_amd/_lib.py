@@ -18,6 +18,7 @@ CREATE_TILED_WIDE = 32   # only together with CREATE_TILED, never with CREATE_TI
 EDGE_GRID_MAX_EDGES, EDGE_GRID_MAX_ENTRIES = 65535, 1 << 22   # per table of the static edge grid (ca_tiled_edge_grid)
 DONE_XLESS, DONE_GOAL, DONE_REGOAL = 0, 1, 2
 F_OBS, F_STATS, F_AUTORESET, F_NODONE, F_FREEZE = 1, 2, 4, 8, 16
+F_CONTACT = 32   # leave the per-agent contact report of the state the call leaves (ca_get_contacts)
 TRACE_POS, TRACE_VEL = 1, 2   # channels of a recording rollout (struct ca_trace)
 SCN_CROWD, SCN_CIRCLE, SCN_DOORWAY, SCN_CONGESTED, SCN_INCOMING, SCN_BLOCKS, SCN_DEADLOCK, SCN_CROWD_SEPARATED = range(8)
 
@@ -34,7 +35,8 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_step_packed", "ca_allow_obstacle_overflow", "ca_alan_configure_per_arena", "ca_alan_actions_arena",
            "ca_set_agent_params", "ca_get_agent_params", "ca_agent_params_info",
            "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info",
-           "ca_rollout_trace", "ca_alan_rollout_trace", "ca_tiled_edge_grid", "ca_tiled_edge_grid_info", "ca_edge_grid_build")
+           "ca_rollout_trace", "ca_alan_rollout_trace", "ca_tiled_edge_grid", "ca_tiled_edge_grid_info", "ca_edge_grid_build",
+           "ca_contacts", "ca_get_contacts", "ca_contacts_ptr")
 
 
 class Config(C.Structure):
@@ -121,6 +123,9 @@ def load():
     L.ca_host_free.argtypes = [vp, vp]
     L.ca_orca_step.argtypes = [vp, u32]
     L.ca_observe.argtypes = [vp]
+    L.ca_contacts.argtypes = [vp]
+    L.ca_get_contacts.argtypes = [vp, vp, vp, vp, vp, vp, sz, i32]
+    L.ca_contacts_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.ca_rollout.argtypes = [vp, i32, u32]
     L.ca_alan_configure.argtypes = [vp, vp, i32, C.c_double, C.c_double, C.c_double]
     L.ca_alan_configure_per_arena.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double]

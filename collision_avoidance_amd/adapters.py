@@ -84,10 +84,16 @@ class AgentVectorEnv(object):
                              A * N, such a slot carries a zero observation and reward and its arena's done, and its action is ignored
       "collisions", "obst_collisions", "goals_reached"  counted during this step, per arena
       "episode"  dict(arena, length, arrived, truncated) for the arenas that finished in this step
+    contacts=True adds, from the contact report of the state the step leaves (vec.step(..., contacts=True); an arena that was
+    reset inside the call reports its respawned state, like its observation; absent slots read False / 0 / inf):
+      "agent_contact" [A*N]     bool: the agent overlaps another agent of its arena or a wall
+      "agent_touching" [A*N]    int: how many other agents it overlaps
+      "agent_nearest_d2" [A*N]  float: squared distance to the nearest other agent of its arena (inf alone)
     """
 
-    def __init__(self, vec, new_step_api=False, collect_stats=True):
+    def __init__(self, vec, new_step_api=False, collect_stats=True, contacts=False):
         self.vec, self.A, self.N = vec, vec.A, vec.N
+        self.contacts = bool(contacts)
         self.num_envs = self.A * self.N
         self.new_step_api, self.collect_stats = bool(new_step_api), bool(collect_stats)
         (self.single_observation_space, self.single_action_space,
@@ -105,7 +111,8 @@ class AgentVectorEnv(object):
 
     def step(self, actions):
         a = actions.reshape(self.A, self.N) if hasattr(actions, "reshape") else np.asarray(actions, np.float32).reshape(self.A, self.N)
-        obs, rew, done, _ = self.vec.step(a, with_obs=True, stats=self.collect_stats, autoreset=True)
+        kw = dict(contacts=True) if self.contacts else {}
+        obs, rew, done, vinfo = self.vec.step(a, with_obs=True, stats=self.collect_stats, autoreset=True, **kw)
         if torch is not None and isinstance(done, torch.Tensor):
             done_agents = done.reshape(self.A, 1).expand(self.A, self.N).reshape(self.num_envs) != 0
             ended = done.cpu().numpy() != 0 if self.collect_stats else None
@@ -125,6 +132,11 @@ class AgentVectorEnv(object):
             trunc[infos["episode"]["arena"]] = infos["episode"]["truncated"]
             trunc_agents = np.repeat(trunc, self.N)
         infos["agent_active"] = (np.arange(self.N)[None, :] < _agent_counts(self.vec)[:, None]).reshape(self.num_envs)
+        if self.contacts:
+            c = vinfo["contacts"]
+            infos["agent_contact"] = self._flat((c["agents"] > 0) | (c["wall"] != 0))
+            infos["agent_touching"] = self._flat(c["agents"])
+            infos["agent_nearest_d2"] = self._flat(c["nearest_d2"])
         obs, rew = self._flat(obs, (_lib.OBS_DIM,)), self._flat(rew)
         if not self.new_step_api:
             return obs, rew, done_agents, infos
@@ -151,10 +163,13 @@ class MultiAgentVectorEnv(object):
     infos[env]['__common__'] carries the arena's collision counters of the step (common_info=True).
     On an env with per-arena agent counts (set_agent_counts) the dictionaries of sub-environment e hold agent_0 .. agent_{n_e-1}
     only, and an action dictionary need not contain the absent ids.
+    contacts=True: infos[env]['agent_<i>'] carries `contact` (the agent overlaps another agent of its arena or a wall) and
+    `nearest_d2` (squared distance to the nearest other agent, inf alone) from the contact report of the state the step leaves.
     """
 
-    def __init__(self, vec, per_agent_dones=True, common_info=True):
+    def __init__(self, vec, per_agent_dones=True, common_info=True, contacts=False):
         self.vec, self.num_envs, self.N = vec, vec.A, vec.N
+        self.contacts = bool(contacts)
         self.per_agent_dones, self.common_info = bool(per_agent_dones), bool(common_info)
         self.agent_ids = ['agent_%d' % i for i in range(self.N)]
         self.single_observation_space, self.single_action_space, _, _ = _spaces(vec, 1)
@@ -201,8 +216,13 @@ class MultiAgentVectorEnv(object):
 
     def vector_step(self, actions):
         act = self._actions(actions)
-        obs, rew, done, _ = self.vec.step(act, with_obs=True, stats=True, autoreset=False)
+        kw = dict(contacts=True) if self.contacts else {}
+        obs, rew, done, vinfo = self.vec.step(act, with_obs=True, stats=True, autoreset=False, **kw)
         obs, rew, done = self._host(obs), self._host(rew), self._host(done) != 0
+        if self.contacts:
+            c = vinfo["contacts"]
+            hit = (self._host(c["agents"]) > 0) | (self._host(c["wall"]) != 0)
+            near = self._host(c["nearest_d2"])
         arrived = self.vec.get(_lib.FLD_AGENT_DONE) != 0
         st = self.vec.arena_stats()
         counts = _agent_counts(self.vec)
@@ -217,6 +237,8 @@ class MultiAgentVectorEnv(object):
                 if was[i]:
                     continue
                 od[aid], rd[aid], idd[aid] = obs[e, i], float(rew[e, i]), {}
+                if self.contacts:
+                    idd[aid] = dict(contact=bool(hit[e, i]), nearest_d2=float(near[e, i]))
                 dd[aid] = bool(newly[i]) or (self.per_agent_dones and bool(done[e]))
             newly[counts[e]:] = False
             if self.per_agent_dones:

@@ -43,6 +43,10 @@ struct ca_env {
     unsigned long long* arena_steps = nullptr;  // [A] steps each arena was advanced, counted by the solve kernels
     float* obs = nullptr;
     bool obs_external = false;
+    // the per-agent contact report (ca_contacts, CA_F_CONTACT; ca_contact.h): [5][A*N] words, allocated on first use; no field and no
+    // part of the state.  contact_valid: a report has been computed on this handle (ca_get_contacts refuses before)
+    int* contact = nullptr;
+    bool contact_valid = false;
     // what a step hands back -- observation | reward | arena_done | step_count -- lies in ONE device allocation in this order, so
     // that the host-array form of a step (ca_step_packed) fetches all of it with one copy (obs points elsewhere after ca_bind_obs)
     float* slab = nullptr;
@@ -564,6 +568,41 @@ static hipError_t launch_obs(ca_env* e) {
     return hipGetLastError();
 }
 
+// The contact report of the current state (ca_contact.h): one launch on the handle's stream, behind whatever left that state, timed
+// under kind 3 like the other small kernels.  The buffer is the handle's, allocated on first use.
+static hipError_t contact_buffer(ca_env* e) {
+    if (e->contact) return hipSuccess;
+    return hipMalloc((void**)&e->contact, 5 * AN(e) * 4);
+}
+static hipError_t launch_contacts(ca_env* e) {
+    hipError_t r = contact_buffer(e);
+    if (r != hipSuccess) return r;
+    ContactArgs c;
+    c.pos_x = e->pos_x; c.pos_y = e->pos_y;
+    c.ap_radius = e->ap ? e->d_ap[0] : nullptr;      // (what fill_cold puts into StepCold::ap_radius / agent_counts)
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.obst = e->d_obst; c.tab_off = e->d_tab_off;
+    c.out = e->contact;
+    c.an = (unsigned)AN(e);
+    c.n_obst = e->h_tab_off.empty() ? (int)e->h_obst.size() : 0; c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents;
+    c.apb = c.N <= CONTACT_BS ? CONTACT_BS / c.N : 0;
+    c.tiles = c.N <= CONTACT_BS ? 0 : (c.N + CONTACT_BS - 1) / CONTACT_BS;
+    c.radius = e->cfg.radius;
+    const unsigned grid = c.apb ? (unsigned)((c.A + c.apb - 1) / c.apb) : (unsigned)((size_t)c.A * c.tiles);
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, contact_kernel, dim3(grid), dim3(CONTACT_BS), 0, e->stream, c);
+    r = hipGetLastError();
+    if (r == hipSuccess) e->contact_valid = true;
+    return r;
+}
+// CA_F_CONTACT is consumed on the host: the entry points strip it, make their call, and leave the report of the state that call
+// left -- one launch behind the last launch of the call (a rollout: behind its last step).  No kernel's `flags` word sees the bit.
+static int contacts_behind(ca_env* e, int rc) {
+    if (rc) return rc;
+    HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
 // reset_kernel + reset_arena_kernel, each timed on its own dispatch (kind 3) when the step is sampled
 static hipError_t launch_reset(ca_env* e, const StepArgs& a) {
     const unsigned an = (unsigned)AN(e);
@@ -1048,7 +1087,7 @@ int ca_destroy(ca_env* e) {
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
                     e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx,
-                    e->eg.d_desc, e->eg.d_cells, e->eg.d_entries};
+                    e->eg.d_desc, e->eg.d_cells, e->eg.d_entries, e->contact};
     for (void* b : bufs) if (b) hipFree(b);
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
@@ -1906,6 +1945,7 @@ int ca_bind_obs(ca_env* e, void* dev_ptr, size_t bytes) {
 }
 
 int ca_reset(ca_env* e, const float* pos_x, const float* pos_y, int32_t pos_is_device, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_reset(e, pos_x, pos_y, pos_is_device, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
     if ((pos_x == nullptr) != (pos_y == nullptr)) return fail(e, CA_EINVAL, "ca_reset: pos_x and pos_y go together");
     HIPCHK(e, hipSetDevice(e->device));
@@ -1928,6 +1968,7 @@ int ca_reset(ca_env* e, const float* pos_x, const float* pos_y, int32_t pos_is_d
 }
 
 int ca_reset_masked(ca_env* e, const int32_t* mask, int32_t mask_is_device, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_reset_masked(e, mask, mask_is_device, flags & ~CA_F_CONTACT));
     if (!e || !mask) return fail(e, CA_EINVAL, "ca_reset_masked: null argument");
     HIPCHK(e, hipSetDevice(e->device));
     const int A = e->cfg.n_arenas;
@@ -1958,6 +1999,7 @@ static int do_step(ca_env* e, const float* actions, uint32_t flags) {
 }
 
 int ca_step(ca_env* e, const float* actions, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_step(e, actions, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
     if (!actions) return fail(e, CA_EINVAL, "ca_step: actions is null (use ca_orca_step for the ORCA-only step)");
     if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "ca_step: CA_F_NODONE applies to ca_orca_step only");
@@ -1966,6 +2008,7 @@ int ca_step(ca_env* e, const float* actions, uint32_t flags) {
 }
 
 int ca_step_host(ca_env* e, const float* actions_host, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_step_host(e, actions_host, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
     if (!actions_host) return fail(e, CA_EINVAL, "ca_step_host: actions is null");
     if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "ca_step_host: CA_F_NODONE applies to ca_orca_step only");
@@ -1981,6 +2024,7 @@ int ca_step_host(ca_env* e, const float* actions_host, uint32_t flags) {
  * ca_step_host + three ca_get cost four synchronisations.  Buffers from ca_host_alloc are page-locked AND device-visible: such
  * an action buffer is read by the kernel where it lies (no staging copy). */
 int ca_step_packed(ca_env* e, const float* actions_host, uint32_t flags, void* out_host, size_t out_bytes) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_step_packed(e, actions_host, flags & ~CA_F_CONTACT, out_host, out_bytes));
     if (!e || !out_host) return fail(e, CA_EINVAL, "ca_step_packed: null argument");
     const size_t an = AN(e), A = (size_t)e->cfg.n_arenas;
     const size_t obs_b = an * CA_OBS_DIM * 4, rest_b = an * 4 + 2 * A * 4;
@@ -2012,6 +2056,7 @@ int ca_step_packed(ca_env* e, const float* actions_host, uint32_t flags, void* o
 }
 
 int ca_orca_step(ca_env* e, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_orca_step(e, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
     HIPCHK(e, hipSetDevice(e->device));
     return do_step(e, nullptr, flags);
@@ -2125,6 +2170,7 @@ int ca_alan_actions_arena(ca_env* e, int32_t arena, double* cs_xy, int32_t cap, 
 }
 
 int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_step(e, u, u_is_device, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
     if (e->ac) return fail(e, CA_EINVAL, "ca_alan_step: ALAN is not supported while per-arena agent counts are set");
     if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_step: call ca_alan_configure first");
@@ -2183,6 +2229,7 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
 }
 
 int ca_alan_rollout(ca_env* e, int32_t steps, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_rollout(e, steps, flags & ~CA_F_CONTACT));
     if (!e || steps < 0) return fail(e, CA_EINVAL, "ca_alan_rollout: bad argument");
     if (e->ac) return fail(e, CA_EINVAL, "ca_alan_rollout: ALAN is not supported while per-arena agent counts are set");
     { const int rs = overflow_status(e, "ca_alan_rollout"); if (rs) return rs; }
@@ -2221,7 +2268,42 @@ int ca_observe(ca_env* e) {
     return CA_OK;
 }
 
+int ca_contacts(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+int ca_get_contacts(ca_env* e, int32_t* agents, int32_t* wall, int32_t* nearest, float* nearest_d2, float* wall_d2, size_t bytes_each,
+                    int32_t dst_is_device) {
+    if (!e) return CA_EINVAL;
+    const size_t an = AN(e);
+    if (bytes_each != an * 4) return fail(e, CA_ESIZE, "ca_get_contacts: a plane holds %zu bytes, got %zu", an * 4, bytes_each);
+    if (!e->contact_valid)
+        return fail(e, CA_EINVAL, "ca_get_contacts: no contact report has been computed on this handle (ca_contacts, or a step with "
+                                  "CA_F_CONTACT)");
+    HIPCHK(e, hipSetDevice(e->device));
+    void* dst[5] = {agents, wall, nearest, nearest_d2, wall_d2};
+    for (int k = 0; k < 5; ++k)
+        if (dst[k])
+            HIPCHK(e, hipMemcpyAsync(dst[k], e->contact + (size_t)k * an, bytes_each,
+                                     dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, e->stream));
+    if (!dst_is_device) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return CA_OK;
+}
+
+int ca_contacts_ptr(ca_env* e, void** dev_ptr, size_t* bytes) {
+    if (!e || !dev_ptr) return fail(e, CA_EINVAL, "ca_contacts_ptr: null argument");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, contact_buffer(e));
+    *dev_ptr = e->contact;
+    if (bytes) *bytes = 5 * AN(e) * 4;
+    return CA_OK;
+}
+
 int ca_rollout(ca_env* e, int32_t steps, uint32_t flags) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_rollout(e, steps, flags & ~CA_F_CONTACT));
     if (!e || steps < 0) return fail(e, CA_EINVAL, "ca_rollout: bad argument");
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout"); if (rs) return rs; }
@@ -2304,6 +2386,7 @@ static hipError_t launch_step_traced(ca_env* e, const StepArgs& a, const ca_trac
 }
 
 int ca_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_rollout_trace(e, steps, flags & ~CA_F_CONTACT, tr));
     TracePlan pl;
     { const int rc = trace_check(e, "ca_rollout_trace", steps, tr, &pl); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
@@ -2334,6 +2417,7 @@ int ca_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* t
 }
 
 int ca_alan_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr) {
+    if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_rollout_trace(e, steps, flags & ~CA_F_CONTACT, tr));
     TracePlan pl;
     { const int rc = trace_check(e, "ca_alan_rollout_trace", steps, tr, &pl); if (rc) return rc; }
     if (e->ac) return fail(e, CA_EINVAL, "ca_alan_rollout_trace: ALAN is not supported while per-arena agent counts are set");

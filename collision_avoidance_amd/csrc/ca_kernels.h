@@ -31,7 +31,8 @@
 // ca_nbr.h (neighbour search; key_empty / key_dummy, edge_in_range), ca_rules.h (the environment's per-agent rules: actions,
 // reward, done test, goals, resets, the wall test and the pair count's shortcut, ALAN's draw and update), ca_step.h (lane solve +
 // reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
-// ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout).
+// ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout),
+// ca_contact.h (the per-agent contact report).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -41,6 +42,7 @@
 #include "ca_alan.h"
 #include "ca_obs.h"
 #include "ca_trace.h"
+#include "ca_contact.h"
 
 namespace ca {
 

@@ -45,9 +45,12 @@ _bases = (_EnvBase,) if _MultiAgentEnv is object or _EnvBase is _MultiAgentEnv e
 class Collision_Avoidance_Env(*_bases):
     metadata = {'render.modes': ['human']}
 
-    def __init__(self, numAgents=10, device=0, seed=0, max_obst_neighbors=None, allow_obst_overflow=False):
+    def __init__(self, numAgents=10, device=0, seed=0, max_obst_neighbors=None, allow_obst_overflow=False, contacts=False):
         # (max_obst_neighbors / allow_obst_overflow: VecCollisionAvoidanceEnv's keywords, no reference counterpart -- the
         # reference's simulator keeps every obstacle edge in range; the defaults are the vector env's)
+        # contacts=True (no reference counterpart either: its gym_infos stay empty, env.py:474): after step(),
+        # gym_infos['agent_i'] = {'contact': the agent overlaps another agent or a wall, 'nearest_d2': squared distance to the
+        # nearest other agent (inf alone)} from the contact report of the state the step leaves
         # constants of env.py:27-44
         self.timeStep = 1 / 60.
         self.neighborDist = 1.5
@@ -65,6 +68,7 @@ class Collision_Avoidance_Env(*_bases):
         self.observation_space = box(low=-self.neighborDist, high=self.neighborDist,
                                      shape=(self.laser_num * 4,))                               # env.py:53
         self._device, self._seed = device, seed
+        self._contacts = bool(contacts)
         self._max_obst_neighbors, self._allow_obst_overflow = max_obst_neighbors, allow_obst_overflow
         self._keys = ['agent_' + str(i) for i in range(numAgents)]                              # env.py:275, 373, 400
         self._make()
@@ -103,7 +107,14 @@ class Collision_Avoidance_Env(*_bases):
     def step(self, action):
         # env.py:367-416.  A missing agent key raises KeyError like the reference (env.py:373).
         act = [float(np.asarray(action[k]).reshape(-1)[0]) for k in self._keys]
-        obs, rew, done, _ = self.vec.step_packed(act)      # one round trip: actions in, obs | reward | done out (ca_step_packed)
+        if self._contacts:
+            obs, rew, done, _ = self.vec.step_packed(act, contacts=True)
+            c = self.vec.last_contacts()
+            hit = ((c["agents"][0] > 0) | (c["wall"][0] != 0)).tolist()
+            for k, h, d2 in zip(self._keys, hit, c["nearest_d2"][0].tolist()):
+                self.gym_infos[k] = {'contact': bool(h), 'nearest_d2': d2}
+        else:
+            obs, rew, done, _ = self.vec.step_packed(act)  # one round trip: actions in, obs | reward | done out (ca_step_packed)
         for k, r in zip(self._keys, rew[0].tolist()):
             self.gym_rewards[k] = r
         self.gym_dones['__all__'] = bool(done[0])

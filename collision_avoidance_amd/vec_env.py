@@ -270,11 +270,12 @@ class VecCollisionAvoidanceEnv:
             bufs[field] = self.host_array(shape, dt)
         return bufs[field]
 
-    def step_packed(self, actions=None, with_obs=True, stats=False, autoreset=False, no_done=False):
+    def step_packed(self, actions=None, with_obs=True, stats=False, autoreset=False, no_done=False, contacts=False):
         """One host-side step in one round trip (ca_step_packed): actions [A,N] (None: the ORCA-only step) in, (obs, rewards, dones,
         step_counts) out as views of ONE page-locked buffer owned by the environment, valid until the next call and never after
         close() (host_array: the buffer is freed with the handle).  The form for one
-        environment per worker with results on the host every step (run_rllib.py:77, 108)."""
+        environment per worker with results on the host every step (run_rllib.py:77, 108).  contacts=True: also leave the contact
+        report of the state the step leaves (last_contacts()); the four views and their layout do not change."""
         an, A = self.A * self.N, self.A
         if "_packed" not in self.__dict__:
             words = an * _lib.OBS_DIM + an + 2 * A
@@ -284,7 +285,7 @@ class VecCollisionAvoidanceEnv:
             self._packed_act = self.host_array((A, self.N), np.float32)
         raw, obs, rew, done, steps = self._packed
         flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
-                (_lib.F_NODONE if no_done else 0)
+                (_lib.F_NODONE if no_done else 0) | (_lib.F_CONTACT if contacts else 0)
         act_ptr = None
         if actions is not None:
             if torch is not None and isinstance(actions, torch.Tensor):
@@ -545,10 +546,11 @@ class VecCollisionAvoidanceEnv:
     def _obs_out(self):
         return self._obs_t if self.use_torch else self.get(_lib.FLD_OBS)
 
-    def reset(self, pos_x=None, pos_y=None, with_obs=True):
+    def reset(self, pos_x=None, pos_y=None, with_obs=True, contacts=False):
         """reference reset() (env.py:461-488) for every arena.  pos_x/pos_y [A,N]: explicit new
-        positions (numpy or device tensor); default: drawn from the spawn box."""
-        flags = _lib.F_OBS if with_obs else 0
+        positions (numpy or device tensor); default: drawn from the spawn box.  contacts=True: also leave the contact report of
+        the new state (last_contacts())."""
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_CONTACT if contacts else 0)
         if pos_x is None:
             self._call("ca_reset", self.h, None, None, 0, flags)
         elif torch is not None and isinstance(pos_x, torch.Tensor) and pos_x.is_cuda and \
@@ -569,9 +571,9 @@ class VecCollisionAvoidanceEnv:
             self._call("ca_reset", self.h, _ptr(px), _ptr(py), 0, flags)
         return self._obs_out() if with_obs else None
 
-    def reset_masked(self, mask, with_obs=True):
-        """reset() for the arenas with mask[a] != 0 only (numpy or device int32 tensor [A])."""
-        flags = _lib.F_OBS if with_obs else 0
+    def reset_masked(self, mask, with_obs=True, contacts=False):
+        """reset() for the arenas with mask[a] != 0 only (numpy or device int32 tensor [A]).  contacts: as for reset()."""
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_CONTACT if contacts else 0)
         on_dev = False
         if torch is not None and isinstance(mask, torch.Tensor):
             mask, on_dev = self._on_device(mask, torch.int32)
@@ -593,13 +595,16 @@ class VecCollisionAvoidanceEnv:
                     last_episode_steps=(r[:, 7] >> np.uint64(32)).astype(np.int64),
                     last_episode_arrived=(r[:, 7] & np.uint64(0xFFFFFFFF)).astype(np.int64))
 
-    def step(self, actions, with_obs=True, stats=False, autoreset=False, copy=True):
+    def step(self, actions, with_obs=True, stats=False, autoreset=False, copy=True, contacts=False):
         """reference step(action) (env.py:367-416) for every arena.
         actions [A,N] heading offsets (rad).  Returns (obs [A,N,64], rewards [A,N], dones [A], {}).
+        contacts=True: the infos are {"contacts": <the report of the state this step leaves, as last_contacts() returns it>}
+        instead of {} -- who touches whom, the nearest neighbour, the walls, per agent (CA_F_CONTACT: one small launch behind
+        the step; with autoreset an arena that was reset reports its respawned state, like the observation).
         copy=False (numpy mode): the results land in the environment's own page-locked host buffers (host_buffer) and are
         valid until the next step / reset -- no allocation per step and the device -> host copy at the link's rate."""
         flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | \
-                (_lib.F_AUTORESET if autoreset else 0)
+                (_lib.F_AUTORESET if autoreset else 0) | (_lib.F_CONTACT if contacts else 0)
         if self.use_torch:
             if not isinstance(actions, torch.Tensor):
                 actions = torch.as_tensor(np.asarray(actions, np.float32).reshape(self.A, self.N))
@@ -610,22 +615,25 @@ class VecCollisionAvoidanceEnv:
                 self._act_t.copy_(actions.reshape(self.A, self.N), non_blocking=True)
                 src = self._act_t
             self._call("ca_step", self.h, C.c_void_p(src.data_ptr()), flags)
-            return (self._obs_t if with_obs else None), self._rew_t, self._done_t, {}
+            return (self._obs_t if with_obs else None), self._rew_t, self._done_t, \
+                ({"contacts": self.last_contacts()} if contacts else {})
         a = np.ascontiguousarray(np.asarray(actions, np.float32).reshape(self.A, self.N))
         self._call("ca_step_host", self.h, _ptr(a), flags)
+        infos = {"contacts": self.last_contacts()} if contacts else {}
         if not copy:
             return (self.get(_lib.FLD_OBS, self.host_buffer(_lib.FLD_OBS)) if with_obs else None), \
                 self.get(_lib.FLD_REWARD, self.host_buffer(_lib.FLD_REWARD)), \
-                self.get(_lib.FLD_ARENA_DONE, self.host_buffer(_lib.FLD_ARENA_DONE)), {}
+                self.get(_lib.FLD_ARENA_DONE, self.host_buffer(_lib.FLD_ARENA_DONE)), infos
         return (self.get(_lib.FLD_OBS) if with_obs else None), self.get(_lib.FLD_REWARD), \
-            self.get(_lib.FLD_ARENA_DONE), {}
+            self.get(_lib.FLD_ARENA_DONE), infos
 
-    def orca_step(self, with_obs=False, stats=False, no_done=False, autoreset=False, freeze=False):
+    def orca_step(self, with_obs=False, stats=False, no_done=False, autoreset=False, freeze=False, contacts=False):
         """reference orca_step (env.py:447-458 with no_done=True; ALAN_true.py:631-636 + done test).
-        freeze: arenas whose episode is over are no longer advanced."""
+        freeze: arenas whose episode is over are no longer advanced.  contacts=True: also leave the contact report of the state
+        the step leaves (last_contacts())."""
         flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | \
                 (_lib.F_NODONE if no_done else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
-                (_lib.F_FREEZE if freeze else 0)
+                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
         self._call("ca_orca_step", self.h, flags)
         return self._obs_out() if with_obs else None
 
@@ -633,6 +641,49 @@ class VecCollisionAvoidanceEnv:
         """reference _get_obs() (env.py:231-277) on the current state."""
         self._call("ca_observe", self.h)
         return self._obs_out()
+
+    # ---- the per-agent contact report (ca_contacts / CA_F_CONTACT) ------------------------------------
+    _CONTACT_PLANES = (("agents", np.int32), ("wall", np.int32), ("nearest", np.int32), ("nearest_d2", np.float32),
+                       ("wall_d2", np.float32))
+
+    def contacts(self):
+        """The contact report of the current state (ca_contacts), a dict of five [A,N] arrays:
+          agents      int32    other agents of the arena this agent overlaps: |p_i - p_j|^2 < (r_i + r_j)^2
+          wall        int32    1 if the agent lies within its radius of an obstacle edge of its arena
+          nearest     int32    index of the nearest other agent of the arena (ties: the smaller index), -1 in an arena of one
+          nearest_d2  float32  the squared distance to it, inf when there is none
+          wall_d2     float32  the squared distance to the nearest obstacle edge, inf in a world without obstacles
+        Radii are the agents' own under set_agent_params(); absent rows (set_agent_counts) read 0, 0, -1, inf, inf.  Over an
+        arena `agents` sums to twice the pairs and `wall` to the wall hits that stats=True counts for the same state.
+        With use_torch the arrays are tensor views of the handle's one device buffer (valid until close(), rewritten by the next
+        report); else host copies."""
+        self._call("ca_contacts", self.h)
+        return self.last_contacts()
+
+    def last_contacts(self):
+        """The last contact report computed -- by contacts() or by a call with contacts=True -- without recomputing it.  Raises
+        if the handle has computed none yet."""
+        if self.use_torch:
+            planes = self.__dict__.get("_contact_t")
+            if planes is None:
+                ptr, nbytes = C.c_void_p(), C.c_size_t()
+                self._call("ca_contacts_ptr", self.h, C.byref(ptr), C.byref(nbytes))
+
+                class _View(object):   # the CUDA array interface, as in field_tensor
+                    pass
+                v = _View()
+                v.__cuda_array_interface__ = {"shape": (5, self.A, self.N), "typestr": np.dtype(np.float32).str,
+                                              "data": (int(ptr.value), False), "version": 2, "strides": None}
+                t = torch.as_tensor(v, device=torch.device("cuda", self.device))
+                assert t.numel() * 4 == nbytes.value
+                planes = self._contact_t = {name: (t[k].view(torch.int32) if dt is np.int32 else t[k])
+                                            for k, (name, dt) in enumerate(self._CONTACT_PLANES)}
+            # (the library refuses a read before the first report: asked for here, without a copy)
+            self._call("ca_get_contacts", self.h, None, None, None, None, None, self.A * self.N * 4, 1)
+            return dict(planes)
+        out = {name: np.empty((self.A, self.N), dt) for name, dt in self._CONTACT_PLANES}
+        self._call("ca_get_contacts", self.h, *[_ptr(out[name]) for name, _ in self._CONTACT_PLANES], self.A * self.N * 4, 0)
+        return out
 
     def _traced(self, name, steps, flags, trace):
         """ca_rollout_trace / ca_alan_rollout_trace into torch tensors on the handle's device; returns dict(agents, arenas)."""
@@ -658,14 +709,15 @@ class VecCollisionAvoidanceEnv:
             self.sync()
         return dict(agents=agents, arenas=arenas)
 
-    def rollout(self, steps, with_obs=False, stats=False, autoreset=False, freeze=False, trace=None):
+    def rollout(self, steps, with_obs=False, stats=False, autoreset=False, freeze=False, trace=None, contacts=False):
         """`steps` ORCA-only steps without returning to the host (ca_rollout).  trace=dict(every=1, channels=("pos", "vel"),
         arenas=True): also record the state after every `every`-th step (ca_rollout_trace) and return
         dict(agents=[R, C, A, N] float32, arenas=[R, 3, A] int32 or None) of torch tensors on the handle's device (shapes:
         trace_shape); record r is the state after (r + 1) * every steps.  The tensors are filled on the handle's stream (torch's
-        current stream of construction with use_torch=True; else the call waits for them)."""
+        current stream of construction with use_torch=True; else the call waits for them).  contacts=True: also leave the contact
+        report of the final state (last_contacts()): one launch behind the last step, not one per step."""
         flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | \
-                (_lib.F_AUTORESET if autoreset else 0) | (_lib.F_FREEZE if freeze else 0)
+                (_lib.F_AUTORESET if autoreset else 0) | (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
         if trace is not None:
             return self._traced("ca_rollout_trace", steps, flags, trace)
         self._call("ca_rollout", self.h, int(steps), flags)
@@ -698,11 +750,13 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_alan_actions_arena", self.h, int(arena), _ptr(out), cnt.value, C.byref(cnt))
         return out[:cnt.value]
 
-    def alan_step(self, u=None, with_obs=False, stats=False, freeze=False):
+    def alan_step(self, u=None, with_obs=False, stats=False, freeze=False, contacts=False):
         """reference online_step (ALAN_true.py:569-628) + step counter + goal test (ALAN:118-121).
         u [A,N] float64: the uniforms behind np.random.choice, one per agent (numpy or device tensor);
-        None: the handle's counter-based RNG."""
-        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_FREEZE if freeze else 0)
+        None: the handle's counter-based RNG.  contacts=True: also leave the contact report of the state the step leaves
+        (last_contacts())."""
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_FREEZE if freeze else 0) | \
+                (_lib.F_CONTACT if contacts else 0)
         if u is None:
             self._call("ca_alan_step", self.h, None, 0, flags)
         elif torch is not None and isinstance(u, torch.Tensor) and u.is_cuda:
@@ -718,10 +772,10 @@ class VecCollisionAvoidanceEnv:
             self._call("ca_alan_step", self.h, _ptr(uh), 0, flags)
         return self._obs_out() if with_obs else None
 
-    def alan_rollout(self, steps, stats=False, freeze=True, trace=None):
+    def alan_rollout(self, steps, stats=False, freeze=True, trace=None, contacts=False):
         """run_sim(mode=1) (ALAN_true.py:106-123) for every arena at once: each arena stops at the end of
-        its own episode (freeze) or after `steps` steps.  trace: as for rollout() (ca_alan_rollout_trace)."""
-        flags = (_lib.F_STATS if stats else 0) | (_lib.F_FREEZE if freeze else 0)
+        its own episode (freeze) or after `steps` steps.  trace, contacts: as for rollout() (ca_alan_rollout_trace)."""
+        flags = (_lib.F_STATS if stats else 0) | (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
         if trace is not None:
             return self._traced("ca_alan_rollout_trace", steps, flags, trace)
         self._call("ca_alan_rollout", self.h, int(steps), flags)

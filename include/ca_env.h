@@ -76,6 +76,8 @@ extern "C" {
 #define CA_F_FREEZE 16u   /* an arena whose arena_done flag is set is not advanced any more: the
                              `break` of the reference's episode loops (ALAN:121-123), per arena,
                              without a host round trip.  ca_reset clears the flag.                */
+#define CA_F_CONTACT 32u  /* leave the per-agent contact report of the state this call leaves (ca_get_contacts): one small
+                             launch behind the call's own, consumed on the host -- no kernel sees the bit            */
 #define CA_ALAN_MAX_ACTIONS 32
 
 /* scenarios for ca_init_scenario */
@@ -369,6 +371,39 @@ int ca_step_packed(ca_env* env, const float* actions_host, uint32_t flags, void*
 int ca_orca_step(ca_env* env, uint32_t flags);
 /* Replaces _get_obs() alone (env.py:231-277): recompute the observation of the current state. */
 int ca_observe(ca_env* env);
+/* The per-agent contact report: who touches whom, the nearest neighbour, the walls -- what a per-agent `infos` entry, a collision
+ * or discomfort-distance penalty or a termination rule needs, without copying the positions back for an O(N^2) scan on the host.
+ * (CA_F_STATS counts the same events, per arena.)  For every agent i of every arena, of the state a call leaves, in fp32, one
+ * operation per source operation, in the order of the statistics' own pair and wall tests:
+ *   agents      i32  number of other present agents j of the same arena with absSq(p_i - p_j) < sqr(r_i + r_j)
+ *   wall        i32  1 if distSqPointSegment(edge, p_i) < sqr(r_i) for any edge of the arena's processed table, else 0
+ *   nearest     i32  the j != i with the smallest key (absSq(p_i - p_j), j) -- ties go to the smaller index --, or -1 when the arena
+ *                    holds one agent
+ *   nearest_d2  f32  that squared distance, or +inf when nearest is -1
+ *   wall_d2     f32  the smallest distSqPointSegment over the arena's edges, or +inf when the table is empty
+ *   - r_i is the agent's own radius while ca_set_agent_params is in force, else ca_config.radius.
+ *   - On a handle with per-arena counts an absent row is never a j, and reports 0, 0, -1, +inf, +inf whatever the caller left in its
+ *     position.
+ *   - Contacts have no range limit: neighbor_dist plays no part, and on a grid handle with the static edge grid on the walls are
+ *     still a scan of the whole table (wall_d2 may lie beyond any obstacle range).
+ *   - Over an arena, `agents` sums to twice the pairs and `wall` to the wall hits that CA_F_STATS counts for the same state.
+ * The report lives in ONE device buffer [5, A, N] of 4-byte words, the planes in the order above, agent index fastest, allocated on
+ * first use.  It is no ca_field and no part of the state (nothing a later step depends on).
+ * ca_contacts: recompute the report of the current state (like ca_observe: one launch on the handle's stream).
+ * CA_F_CONTACT on ca_step / ca_step_host / ca_step_packed / ca_orca_step / ca_alan_step / ca_reset / ca_reset_masked: the same launch
+ * behind the call's own, so the report is of the state the call leaves -- a frozen arena (CA_F_FREEZE) reports its unchanged state;
+ * under CA_F_AUTORESET an arena that was reset inside the call reports its RESPAWNED state, as the observation does, while the
+ * statistics of that step were counted before the reset.  The packed layout of ca_step_packed does not change.  On ca_rollout /
+ * ca_alan_rollout / ca_rollout_trace / ca_alan_rollout_trace: ONE launch behind the last step, not one per step (a one-launch rollout
+ * stays one launch, plus this one); no report per trace record.  ca_profile counts the launch under kind 3.  Every kind of handle
+ * takes the flag and the calls; nothing else a call computes depends on it.
+ * ca_get_contacts: copies the planes out ([A,N] each; any pointer may be NULL): bytes_each != A*N*4 -> CA_ESIZE; no report computed
+ * yet on this handle -> CA_EINVAL (zeros would read as "no contact"); otherwise the last report computed, like CA_FLD_OBS.
+ * ca_contacts_ptr: zero-copy view of the [5, A, N] buffer (allocates it if needed; valid until ca_destroy). */
+int ca_contacts(ca_env* env);
+int ca_get_contacts(ca_env* env, int32_t* agents, int32_t* wall, int32_t* nearest, float* nearest_d2, float* wall_d2, size_t bytes_each,
+                    int32_t dst_is_device);
+int ca_contacts_ptr(ca_env* env, void** dev_ptr, size_t* bytes);
 /* `steps` consecutive ca_orca_step calls without returning to the host (with CA_F_FREEZE: every
  * arena runs to the end of its own episode, at most `steps` steps): the reference's ORCA-only loops, env.py:570-573
  * (`while True: orca_step()`) and ALAN:106-123 (run_sim).  One kernel launch per 256 steps where the handle uses
@@ -490,8 +525,8 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * (kinds: 0 nbr_kernel -- always 0: the neighbour search is the head of step_kernel, with no launch of its own; the
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
- * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, each
- * launch on its own), then clears them.  ca_profile(env, 0) switches
+ * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
