@@ -20,6 +20,13 @@ struct AgentParams;
 // without parameters of the caller's has the arrays filled with its constants) -- and stands alone in the pack, so that
 // "AgentParams" keeps naming exactly the instantiations it named before.
 struct ArenaCounts;
+// Tag of the per-agent-sensing instantiations (step_kernel<KMAX, BS, 0, SMAX, false, AgentSensing>, ... ArenaCounts, AgentSensing>,
+// tiled_solve_kernel<..., AgentSensing>, tiled_close_kernel<AgentSensing>): neighbor_dist and max_neighbors of every agent come from
+// [A,N] arrays (ca_set_agent_sensing) instead of the handle's two constants, which stay the capacities that size the K class, the
+// list layout, the grids and the composite-key image.  Like ArenaCounts the tag INCLUDES AgentParams -- these are the
+// per-agent-parameter kernels with a range and a list length per agent -- and stands in the pack without it, so that "AgentParams"
+// keeps naming exactly the instantiations it named before; with counts per arena it stands behind ArenaCounts.
+struct AgentSensing;
 // Tag of the four-lanes kernel's recording instantiations (quad_kernel<KMAX, BS, SQ, ALAN, Trace>: ca_rollout_trace /
 // ca_alan_rollout_trace): inside the T-step loop the selected planes of the state and the arena's three words go to the caller's
 // trace buffer whenever the rollout's step count reaches a multiple of `every` (TraceDev below).
@@ -85,6 +92,10 @@ struct StepCold {
     // the trace block of the handle (ca_rollout_trace): read by the Trace instantiations of the four-lanes kernel only.  Last
     // member again.
     const TraceDev* trace;
+    // per-agent sensing [A*N] (ca_set_agent_sensing; null on a handle without it): neighbor_dist_i f32 and max_neighbors_i u8, read by
+    // the AgentSensing instantiations only.  Last members again.
+    const float* as_neighbor_dist;
+    const unsigned char* as_max_neighbors;
 };
 
 // The trace of a recording rollout (include/ca_env.h ca_trace), as the Trace instantiations of the four-lanes kernel read it: a

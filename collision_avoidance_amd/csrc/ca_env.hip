@@ -116,6 +116,14 @@ struct ca_env {
     bool ac = false, ap_user = false;
     int* d_counts = nullptr;                                 // [A]
     std::vector<int> h_counts;                               // host copy (ca_get_agent_counts, ca_get_stats); empty while !ac
+    // per-agent sensing (ca_set_agent_sensing): configuration too.  sens = the handle runs the AgentSensing instantiations, which
+    // exist beside AgentParams / ArenaCounts only: ap = ap_user || ac || sens, the per-agent arrays holding the ca_config values
+    // unless the caller set them, as under counts.  cfg.neighbor_dist and cfg.max_neighbors stay the capacities everything is sized by.
+    bool sens = false;
+    float* d_as_nd = nullptr;                                // [A*N] neighbor_dist_i
+    unsigned char* d_as_k = nullptr;                         // [A*N] max_neighbors_i (0 .. CA_MAX_NEIGHBORS fits a byte)
+    std::vector<float> h_as_nd;                              // host copies (ca_get_agent_sensing); empty while !sens
+    std::vector<int> h_as_k;
     // the tiled solve path (ca_create_ex, CA_CREATE_TILED; ca_tiled.h): an arena spans `tiles` workgroups of TILE lanes, a step is
     // three launches (solve, advance, close)
     bool tiled = false;
@@ -305,6 +313,7 @@ static void fill_cold(const ca_env* e, StepCold& c) {
     c.ap_time_horizon = e->ap ? e->d_ap[2] : nullptr; c.ap_time_horizon_obst = e->ap ? e->d_ap[3] : nullptr;
     c.agent_counts = e->ac ? e->d_counts : nullptr;
     c.trace = e->d_trace;
+    c.as_neighbor_dist = e->sens ? e->d_as_nd : nullptr; c.as_max_neighbors = e->sens ? e->d_as_k : nullptr;
 }
 
 static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t flags) {
@@ -386,10 +395,27 @@ static const void* ac_fn_for(int BS) {
         default: return fn_ptr(&step_kernel<KMAX, 1024, 0, SMAX, false, ArenaCounts>);
     }
 }
+// ... and either of the two with neighbor_dist and max_neighbors per agent (ca_set_agent_sensing): the AgentSensing tag
+// (the tag includes AgentParams and stands without it; with counts per arena, behind ArenaCounts)
+template <int KMAX, class... TAGS>
+static const void* sens_fn_for(int BS) {
+    switch (BS) {
+        case 64: return fn_ptr(&step_kernel<KMAX, 64, 0, SMAX, false, TAGS...>);
+        case 128: return fn_ptr(&step_kernel<KMAX, 128, 0, SMAX, false, TAGS...>);
+        case 256: return fn_ptr(&step_kernel<KMAX, 256, 0, SMAX, false, TAGS...>);
+        case 512: return fn_ptr(&step_kernel<KMAX, 512, 0, SMAX, false, TAGS...>);
+        default: return fn_ptr(&step_kernel<KMAX, 1024, 0, SMAX, false, TAGS...>);
+    }
+}
+template <class... TAGS>
+static const void* sens_fn_of(const ca_env* e) {
+    return e->KT == 5 ? sens_fn_for<5, TAGS...>(e->BS) : (e->KT == 16 ? sens_fn_for<16, TAGS...>(e->BS) : sens_fn_for<10, TAGS...>(e->BS));
+}
 // the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
 // more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
 template <bool ALAN, class... PER>
 static const void* lane_fn_for(const ca_env* e) {
+    if (e->sens) return e->ac ? sens_fn_of<ArenaCounts, AgentSensing>(e) : sens_fn_of<AgentSensing>(e);   // (ap is on with it; no ALAN form either)
     if (e->ac) return e->KT == 5 ? ac_fn_for<5>(e->BS) : (e->KT == 16 ? ac_fn_for<16>(e->BS) : ac_fn_for<10>(e->BS));   // (refused by the ALAN calls)
     if (e->ap) return e->KT == 5 ? ap_fn_for<5>(e->BS) : (e->KT == 16 ? ap_fn_for<16>(e->BS) : ap_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->SMX > SMAX) return e->KT == 5 ? wide_fn_for<5>(e->BS) : (e->KT == 16 ? wide_fn_for<16>(e->BS) : wide_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
@@ -426,6 +452,10 @@ static const void* tiled_solve_fn(const ca_env* e, bool egrid) {
         if (e->tgrid && egrid) return tiled_solve_fn_for<SEARCH_GRID_EDGES, WideObstLists>(e);
         return e->tgrid ? tiled_solve_fn_for<SEARCH_GRID, WideObstLists>(e) : tiled_solve_fn_for<SEARCH_ALL, WideObstLists>(e);
     }
+    if (e->sens) {   // (ca_set_agent_sensing on a handle made with CA_CREATE_TILED_PARAMS: ap is on with it)
+        if (e->tgrid && egrid) return tiled_solve_fn_for<SEARCH_GRID_EDGES, AgentSensing>(e);
+        return e->tgrid ? tiled_solve_fn_for<SEARCH_GRID, AgentSensing>(e) : tiled_solve_fn_for<SEARCH_ALL, AgentSensing>(e);
+    }
     if (e->tgrid && egrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID_EDGES, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID_EDGES>(e);
     if (e->tgrid) return e->ap ? tiled_solve_fn_for<SEARCH_GRID, AgentParams>(e) : tiled_solve_fn_for<SEARCH_GRID>(e);
     return e->ap ? tiled_solve_fn_for<SEARCH_ALL, AgentParams>(e) : tiled_solve_fn_for<SEARCH_ALL>(e);
@@ -435,7 +465,10 @@ static const void* tiled_advance_fn(const ca_env* e) {
     if (e->ap) return e->egrid ? fn_ptr(&tiled_advance_kernel<true, AgentParams>) : fn_ptr(&tiled_advance_kernel<false, AgentParams>);
     return e->egrid ? fn_ptr(&tiled_advance_kernel<true>) : fn_ptr(&tiled_advance_kernel<false>);
 }
-static const void* tiled_close_fn(const ca_env* e) { return e->ap ? fn_ptr(&tiled_close_kernel<AgentParams>) : fn_ptr(&tiled_close_kernel<>); }
+static const void* tiled_close_fn(const ca_env* e) {
+    if (e->sens) return fn_ptr(&tiled_close_kernel<AgentSensing>);   // (the list shortcut of the pair count takes the lane's own range and K)
+    return e->ap ? fn_ptr(&tiled_close_kernel<AgentParams>) : fn_ptr(&tiled_close_kernel<>);
+}
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps;
 // trace: ... and records them (the Trace instantiations of the four-lanes kernel: the ORCA-only rollout and the fused ALAN rollout with
 // one action set; the callers ask for nothing else)
@@ -1085,7 +1118,7 @@ int ca_destroy(ca_env* e) {
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
-                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts,
+                    e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
                     e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx,
                     e->eg.d_desc, e->eg.d_cells, e->eg.d_entries, e->contact};
     for (void* b : bufs) if (b) hipFree(b);
@@ -1367,19 +1400,20 @@ static void agent_octagons(const std::vector<float>& radius, std::vector<float>&
 }
 
 // the handle's variant state that per-agent parameters change (saved before a prospective pick_variant, restored on failure)
-struct VariantState { bool ap, ap_user, ac, quad, quad_roll, pair; int ST, SMX, KT; size_t lds, lds_p; };
-static VariantState save_variant(const ca_env* e) { return {e->ap, e->ap_user, e->ac, e->quad, e->quad_roll, e->pair, e->ST, e->SMX, e->KT, e->lds, e->lds_p}; }
+struct VariantState { bool ap, ap_user, ac, sens, quad, quad_roll, pair; int ST, SMX, KT; size_t lds, lds_p; };
+static VariantState save_variant(const ca_env* e) { return {e->ap, e->ap_user, e->ac, e->sens, e->quad, e->quad_roll, e->pair, e->ST, e->SMX, e->KT, e->lds, e->lds_p}; }
 static void restore_variant(ca_env* e, const VariantState& v) {
-    e->ap = v.ap; e->ap_user = v.ap_user; e->ac = v.ac; e->quad = v.quad; e->quad_roll = v.quad_roll; e->pair = v.pair; e->ST = v.ST; e->SMX = v.SMX; e->KT = v.KT;
+    e->ap = v.ap; e->ap_user = v.ap_user; e->ac = v.ac; e->sens = v.sens; e->quad = v.quad; e->quad_roll = v.quad_roll; e->pair = v.pair; e->ST = v.ST; e->SMX = v.SMX; e->KT = v.KT;
     e->lds = v.lds; e->lds_p = v.lds_p;
 }
 // switch the handle to the kernels of (parameters of the caller's: ap_user, agent counts per arena: ac) -- the AgentParams kernels
 // if either is set, with the ArenaCounts tag if ac, else the uniform ones: variant and dynamic-LDS limits, checked against the CU's
 // LDS before anything is swapped (as install_tables does).  *misfit: the kernel does not fit; the handle is then left as it was.
-static hipError_t switch_agent_params(ca_env* e, bool ap_user, bool ac, bool* misfit) {
+// sens (per-agent sensing, ca_set_agent_sensing) selects the AgentSensing twin of whichever of the two it is, and switches them on by itself.
+static hipError_t switch_agent_params(ca_env* e, bool ap_user, bool ac, bool sens, bool* misfit) {
     const VariantState old_v = save_variant(e);
-    const bool on = ap_user || ac;
-    e->ap = on; e->ap_user = ap_user; e->ac = ac;
+    const bool on = ap_user || ac || sens;
+    e->ap = on; e->ap_user = ap_user; e->ac = ac; e->sens = sens;
     e->quad = on ? false : e->quad_cfg;
     e->quad_roll = on ? false : e->quad_roll_cfg;
     pick_variant(e);
@@ -1432,6 +1466,12 @@ __global__ void clear_absent_kernel(const int* counts, int A, int N, float* rewa
     reinterpret_cast<float4*>(obs)[q * 16 + r] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (r == 0) reward[q] = 0.0f;
 }
+// ca_set_agent_sensing: the agent-neighbour half (low byte) of every packed count reads 0 -- a list of the previous lengths may be
+// longer than its agent's new K_i; the obstacle half stays
+__global__ void clear_agent_nbr_counts_kernel(unsigned short* counts, size_t n) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) counts[q] &= (unsigned short)0xFF00u;
+}
 
 extern "C" {
 
@@ -1461,7 +1501,7 @@ int ca_set_agent_counts(ca_env* e, const int32_t* counts, size_t bytes, int32_t 
     HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous counts
     if (e->ac != (counts != nullptr)) {   // the prospective kernels are chosen and checked against the CU's LDS before anything is swapped
         bool misfit = false;
-        const hipError_t r = switch_agent_params(e, e->ap_user, counts != nullptr, &misfit);
+        const hipError_t r = switch_agent_params(e, e->ap_user, counts != nullptr, e->sens, &misfit);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_counts: %s (the handle keeps its previous counts)", hipGetErrorString(r));
         if (misfit)
             return fail(e, CA_ERANGE, "ca_set_agent_counts: the %s solve kernel does not fit the 160 KiB of LDS of a CU for n_agents=%d, max_neighbors=%d, "
@@ -1534,11 +1574,17 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     if (!any) {   // back to the handle's four constants and to the kernels it used with them
         if (!e->ap_user) return CA_OK;
         HIPCHK(e, hipStreamSynchronize(e->stream));
-        if (e->ac) {   // agent counts stay set: their kernels stay, the per-agent arrays return to the ca_config values
+        if (e->ac || e->sens) {   // agent counts or per-agent sensing stay set: their kernels stay, the per-agent arrays return to the ca_config values
+            if (e->egrid) {   // (a tiled grid handle with sensing: the edge grid returns to the handle's own obstacle range)
+                const int rc = make_edge_grids(e, e->h_obst, e->h_tab_off, edge_grid_range(e, nullptr), n_eg, "ca_set_agent_params");
+                if (rc) return rc;
+            }
             std::vector<float> h[4];
             for (int k = 0; k < 4; ++k) h[k].assign(AN(e), defaults[k]);
             const hipError_t r = push_agent_params(e, h);
-            if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r));
+            if (r != hipSuccess) { free_edge_grids(n_eg); return fail(e, CA_EHIP, "ca_set_agent_params: %s", hipGetErrorString(r)); }
+            if (e->egrid) { free_edge_grids(e->eg); e->eg = n_eg; }
+            e->ap_rmax = e->cfg.radius;
             e->ap_user = false;
             for (auto& v : e->h_ap) v.clear();
             return alan_pick(e);
@@ -1548,7 +1594,7 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
             if (rc) return rc;
         }
         bool misfit = false;
-        const hipError_t r = switch_agent_params(e, false, false, &misfit);
+        const hipError_t r = switch_agent_params(e, false, false, false, &misfit);
         if (r != hipSuccess || misfit) free_edge_grids(n_eg);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the per-agent parameters stay)", hipGetErrorString(r));
         if (misfit) return fail(e, CA_ERANGE, "ca_set_agent_params: the uniform solve kernel does not fit the 160 KiB of LDS of a CU (the per-agent parameters stay)");
@@ -1584,7 +1630,7 @@ int ca_set_agent_params(ca_env* e, const float* radius, const float* max_speed, 
     }
     if (!e->ap) {   // the prospective variant is chosen and checked against the CU's LDS before anything is swapped
         bool misfit = false;
-        const hipError_t r = switch_agent_params(e, true, false, &misfit);
+        const hipError_t r = switch_agent_params(e, true, false, false, &misfit);
         if (r != hipSuccess || misfit) free_edge_grids(n_eg);
         if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_params: %s (the handle keeps its uniform parameters)", hipGetErrorString(r));
         if (misfit)
@@ -1627,6 +1673,116 @@ int ca_get_agent_params(ca_env* e, float* radius, float* max_speed, float* time_
 int ca_agent_params_info(ca_env* e, int32_t* per_agent) {
     if (!e) return CA_EINVAL;
     if (per_agent) *per_agent = e->ap_user ? 1 : 0;
+    return CA_OK;
+}
+
+// ---- per-agent sensing: the two remaining per-agent arguments of sim.addAgent (neighborDist, maxNeighbors; env.py:126-133, ALAN:81-87) ----
+int ca_set_agent_sensing(ca_env* e, const float* neighbor_dist, const int32_t* max_neighbors, size_t bytes_each, int32_t src_is_device) {
+    if (!e) return CA_EINVAL;
+    if (e->tiled && !e->tparams)
+        return fail(e, CA_EINVAL, "ca_set_agent_sensing: not on a tiled handle made without CA_CREATE_TILED_PARAMS: the tiled kernels' per-agent "
+                    "form is chosen at ca_create_ex (create_flags 0x11 or 0x15)");
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t an = AN(e), N = (size_t)e->cfg.n_agents;
+    const bool any = neighbor_dist || max_neighbors;
+    std::vector<float> hn;
+    std::vector<int> hk;
+    std::vector<unsigned char> hk8;
+    if (any) {
+        if (e->S > SMAX)
+            return fail(e, CA_EINVAL, "ca_set_agent_sensing: not together with wide obstacle lists (max_obst_neighbors=%d > %d)", e->S, SMAX);
+        if (bytes_each != an * 4) return fail(e, CA_ESIZE, "ca_set_agent_sensing: each array holds %zu bytes, got %zu", an * 4, bytes_each);
+        // a configuration call: every value is checked (a device array is copied back for it), absent rows' too.  The ca_config values
+        // are the capacities: they size the K class, the list layout, the grids and the composite-key image
+        hn.assign(an, e->cfg.neighbor_dist);
+        hk.assign(an, e->cfg.max_neighbors);
+        if (neighbor_dist) {
+            if (src_is_device) HIPCHK(e, download(e, hn.data(), neighbor_dist, an * 4));
+            else memcpy(hn.data(), neighbor_dist, an * 4);
+            for (size_t q = 0; q < an; ++q)
+                if (!(hn[q] >= CA_MIN_LENGTH && hn[q] <= e->cfg.neighbor_dist))   // (also false for NaN)
+                    return fail(e, CA_ERANGE, "ca_set_agent_sensing: neighbor_dist=%g of arena %zu, agent %zu is outside [%g, the handle's neighbor_dist=%g] "
+                                "or not a number", (double)hn[q], q / N, q % N, (double)CA_MIN_LENGTH, (double)e->cfg.neighbor_dist);
+        }
+        if (max_neighbors) {
+            if (src_is_device) HIPCHK(e, download(e, hk.data(), max_neighbors, an * 4));
+            else memcpy(hk.data(), max_neighbors, an * 4);
+            for (size_t q = 0; q < an; ++q)
+                if (hk[q] < 0 || hk[q] > e->cfg.max_neighbors)
+                    return fail(e, CA_ERANGE, "ca_set_agent_sensing: max_neighbors=%d of arena %zu, agent %zu is outside [0, the handle's max_neighbors=%d]",
+                                hk[q], q / N, q % N, e->cfg.max_neighbors);
+        }
+        hk8.resize(an);
+        for (size_t q = 0; q < an; ++q) hk8[q] = (unsigned char)hk[q];
+        // the buffers exist before anything changes (the first call allocates them; they stay until ca_destroy)
+        if (!e->d_as_nd) HIPCHK(e, hipMalloc((void**)&e->d_as_nd, an * 4));
+        if (!e->d_as_k) HIPCHK(e, hipMalloc((void**)&e->d_as_k, an));
+        { const int rc = alloc_agent_params(e); if (rc) return rc; }
+    } else if (!e->sens) {
+        return CA_OK;
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // steps in flight read the previous values
+    if (e->sens != any) {   // the prospective kernels are chosen and checked against the CU's LDS before anything is swapped
+        bool misfit = false;
+        const hipError_t r = switch_agent_params(e, e->ap_user, e->ac, any, &misfit);
+        if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_sensing: %s (the handle keeps what it had)", hipGetErrorString(r));
+        if (misfit)
+            return fail(e, CA_ERANGE, "ca_set_agent_sensing: the %s solve kernel does not fit the 160 KiB of LDS of a CU for n_agents=%d, max_neighbors=%d, "
+                        "max_obst_neighbors=%d (with per-agent sensing: the LDS line table, max_neighbors + max_obst_neighbors lines per lane); the handle "
+                        "keeps what it had", any ? "per-agent" : "uniform", e->cfg.n_agents, e->K, e->S);
+    }
+    hipError_t r = hipSuccess;
+    if (any) {
+        if (!e->ap_user) {   // no parameters of the caller's: the per-agent arrays hold the ca_config values
+            const float defaults[4] = {e->cfg.radius, e->cfg.max_speed, e->cfg.time_horizon, e->cfg.time_horizon_obst};
+            std::vector<float> hp[4];
+            for (int k = 0; k < 4; ++k) hp[k].assign(an, defaults[k]);
+            r = push_agent_params(e, hp);
+            e->ap_rmax = e->cfg.radius;
+        }
+        if (r == hipSuccess) r = hipMemcpyAsync(e->d_as_nd, hn.data(), an * 4, hipMemcpyHostToDevice, e->stream);
+        if (r == hipSuccess) r = hipMemcpyAsync(e->d_as_k, hk8.data(), an, hipMemcpyHostToDevice, e->stream);
+    }
+    // a list of the previous lengths may be longer than its agent's K_i: the agent-neighbour count of every row reads 0
+    if (r == hipSuccess) {
+        hipLaunchKernelGGL(clear_agent_nbr_counts_kernel, dim3((unsigned)((an + 255) / 256)), dim3(256), 0, e->stream, e->counts, an);
+        r = hipGetLastError();
+    }
+    e->h_as_nd.swap(hn);   // (both empty when the call clears)
+    e->h_as_k.swap(hk);
+    e->lists_trusted = false;
+    StepCold hc;
+    fill_cold(e, hc);
+    if (r == hipSuccess) r = upload(e, e->d_cold, &hc, sizeof hc);   // (synchronises: the host vectors may go)
+    if (r != hipSuccess) return fail(e, CA_EHIP, "ca_set_agent_sensing: %s", hipGetErrorString(r));
+    return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
+}
+
+int ca_get_agent_sensing(ca_env* e, float* neighbor_dist, int32_t* max_neighbors, size_t bytes_each, int32_t dst_is_device) {
+    if (!e) return CA_EINVAL;
+    const size_t an = AN(e);
+    if (bytes_each != an * 4) return fail(e, CA_ESIZE, "ca_get_agent_sensing: each array holds %zu bytes, got %zu", an * 4, bytes_each);
+    HIPCHK(e, hipSetDevice(e->device));
+    if (neighbor_dist) {
+        std::vector<float> uni;
+        if (!e->sens) uni.assign(an, e->cfg.neighbor_dist);   // without per-agent sensing: the handle's constant for every agent
+        const float* s = e->sens ? e->h_as_nd.data() : uni.data();
+        if (dst_is_device) { HIPCHK(e, upload(e, neighbor_dist, s, an * 4)); }
+        else memcpy(neighbor_dist, s, an * 4);
+    }
+    if (max_neighbors) {
+        std::vector<int> uni;
+        if (!e->sens) uni.assign(an, e->cfg.max_neighbors);
+        const int* s = e->sens ? e->h_as_k.data() : uni.data();
+        if (dst_is_device) { HIPCHK(e, upload(e, max_neighbors, s, an * 4)); }
+        else memcpy(max_neighbors, s, an * 4);
+    }
+    return CA_OK;
+}
+
+int ca_agent_sensing_info(ca_env* e, int32_t* per_agent) {
+    if (!e) return CA_EINVAL;
+    if (per_agent) *per_agent = e->sens ? 1 : 0;
     return CA_OK;
 }
 

@@ -112,7 +112,15 @@ __device__ __forceinline__ bool edge_in_range(const ObstDev& o1, V2 pos, float r
 // counts for j < n_a: the loops over candidates keep their wave-uniform trip count N (several arenas of different counts may share
 // a wave) and the count joins the accept test, so the staged position of an absent lane is never taken, whatever it holds.  The
 // grid scan sorts the present agents only.
-template <int KMAX, int BS, int SM, bool AP = false, bool AC = false>
+// AS (the AgentSensing instantiations): agent i's list is the K_i = as_max_neighbors[i] smallest (dsq, j) keys with dsq < fl(nd_i * nd_i),
+// nd_i = as_neighbor_dist[i] -- the oracle's compute_neighbors with the agent's own two values.  K_i <= K and nd_i <= neighbor_dist
+// (checked by the host), so that list is the head of the K-list taken with range nd_i: the three searches below test against the
+// lane's fl(nd_i^2) and keep K slots as before, and the cut to K_i entries is made once, where the list is stored (slots at or beyond
+// the count read -1).  What is wave-uniform stays the handle's: K and its right-aligned register list, the composite-key image
+// (top / u0 from neighbor_dist^2: a passing dsq lies below fl(nd_i^2) <= fl(neighbor_dist^2), so the image is exact over the same
+// binades), the grid's cell size and the block of cells walked (B from neighbor_dist covers every smaller range).  Lists are
+// asymmetric -- i may hold j while j does not hold i -- and nothing below relies on symmetry: a lane reads positions, never lists.
+template <int KMAX, int BS, int SM, bool AP = false, bool AC = false, bool AS = false>
 __device__ __forceinline__ void nbr_body(const StepArgs& p) {
 #ifndef CA_NBR_NO_VGPR_PAD
     // Claim 128 VGPRs (the kernel needs 56): at most 4 waves then fit on a SIMD, so a launch that brings one
@@ -202,6 +210,12 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? key_dummy() : key_empty();
     int ncnt = 0;
     bool scanned = false;
+    [[maybe_unused]] float ndSq_own = 0.0f;   // (AS) the lane's fl(nd_i^2): one fp32 product, as the oracle forms it
+    [[maybe_unused]] int K_own = 0;           // (AS) the lane's K_i; an idle lane keeps nothing
+    if constexpr (AS) {
+        const StepCold* cp = p.cold;
+        if (active) { ndSq_own = sqr(cp->as_neighbor_dist[q]); K_own = (int)cp->as_max_neighbors[q]; }
+    }
     if constexpr (BS >= 256) {
         // Large arenas (one arena per workgroup, >= 192 agents): a uniform grid with cells at least neighbor_dist
         // wide, rebuilt in LDS every step (counting sort of the agent indices by cell), so that an agent scans
@@ -272,7 +286,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
                 if constexpr (SXY) s_sxy[dst] = make_float2(pos.x, pos.y);
             }
             __syncthreads();
-            const float rangeSq0 = sqr(p.neighbor_dist);
+            const float rangeSq0 = AS ? ndSq_own : sqr(p.neighbor_dist);
             float rangeK = rangeSq0;  // distance of the current K-th entry once the list is full
             // WHICH CELLS.  Not a fixed block cx +- RC: pos - x0 and its product with ics are rounded, so a candidate a few
             // ulps inside the range can land one cell beyond such a block (a pair at |dx| = nd - 1 ulp, 3 cells apart at
@@ -353,7 +367,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
         for (int k = 0; k <= KMAX; ++k) ck[k] = (k < kofs) ? 0u : 0xFFFFFFFFu;
         auto visit = [&](int j, V2 o) __attribute__((always_inline)) {
             const float dsq = absSq(pos - o);
-            const bool pass = active && j != i && (!AC || j < n_a) && dsq < rangeSq0;
+            const bool pass = active && j != i && (!AC || j < n_a) && dsq < (AS ? ndSq_own : rangeSq0);
             const unsigned u = __float_as_uint(dsq);
             unsigned key = (((u > u0 ? u : u0) - u0) << p.logP) | (unsigned)j;
             asm volatile("" : "+v"(key));   // (computed for every lane: left to itself the compiler branches around these three
@@ -388,7 +402,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
         }
     }
     if (K > 0 && !scanned) {
-        float rangeSq = sqr(p.neighbor_dist);
+        float rangeSq = AS ? ndSq_own : sqr(p.neighbor_dist);
         V2 o_next = mk(s_px[lbase], s_py[lbase]);
         for (int j = 0; j < N; ++j) {
             const V2 o = o_next;  // the next candidate's position is in flight while this one is inserted
@@ -408,10 +422,11 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             atomicAdd(reinterpret_cast<int*>(&p.arena_stats[(size_t)a * ST_STRIDE + ST_OVERFLOW]), 1);
             note_overflow(p.cold, a, i, oin);
         }
+        if constexpr (AS) ncnt = ncnt < K_own ? ncnt : K_own;   // the head of the K-list: its K_i nearest
         p.counts[q] = (unsigned short)(ncnt | (ocnt << 8));
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
-            if (k >= kofs) st_idx_t<CA_NBW16(BS)>(p.nb_idx, ((size_t)a * K + (k - kofs)) * N + i, key_index(nkey[k]));  // ids of <= 256 agents fit a byte
+            if (k >= kofs) st_idx_t<CA_NBW16(BS)>(p.nb_idx, ((size_t)a * K + (k - kofs)) * N + i, (AS && k - kofs >= K_own) ? -1 : key_index(nkey[k]));  // ids of <= 256 agents fit a byte
         if constexpr (SM <= 4) {
 #pragma unroll
             for (int k = 0; k < SM; ++k)

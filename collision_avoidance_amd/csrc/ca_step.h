@@ -93,11 +93,16 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 //   ArenaCounts (includes AgentParams) = arena a holds agent_counts[a] of its N rows (ca_set_agent_counts): lanes i >= n_a are
 //   idle like the lanes beyond N, the neighbour search and the pair count take candidates j < n_a (ca_nbr.h), and the done test,
 //   the last-episode word and the in-kernel reset see the arena's n_a agents.  Nothing of an absent row is loaded or stored.
+//   AgentSensing (includes AgentParams, as ArenaCounts does; alone in the pack, or behind ArenaCounts) = neighbor_dist and
+//   max_neighbors per agent (ca_set_agent_sensing): the neighbour search at the head of the kernel takes the lane's own range and list length (ca_nbr.h).
+//   Nothing behind the search changes: lines, LP and epilogue read the lists and counts it stored, and the pair count of these
+//   instantiations scans the arena (below), so it never reasons from a list.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
     constexpr bool AC = has_tag<ArenaCounts, PER...>;
-    constexpr bool AP = has_tag<AgentParams, PER...> || AC;   // (ArenaCounts includes AgentParams: one tag names the instantiation)
+    constexpr bool AS = has_tag<AgentSensing, PER...>;        // neighbor_dist and max_neighbors per agent: the neighbour search's alone (ca_nbr.h)
+    constexpr bool AP = has_tag<AgentParams, PER...> || AC || AS;   // (ArenaCounts and AgentSensing include AgentParams: the tag names the instantiation)
     static_assert(!AP || (ST == 0 && !ALAN && SMX <= SMAX), "per-agent parameters: the LDS line table with lists of up to 16, no ALAN form");
     extern __shared__ float4 smem4[];
     constexpr bool LISTP = BS > 64 && !AP;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // The neighbour search runs at the head of this kernel (one drain/fill less per step than a launch of its own, and its
     // dispatch skew overlaps useful work).  A lane later reads back only the lists of its own agent, which it wrote itself;
     // the search's LDS arrays are not used again.
-    nbr_body<KMAX, BS, SMX, AP, AC>(p);
+    nbr_body<KMAX, BS, SMX, AP, AC, AS>(p);
     constexpr int ML = ST + KMAX;  // register slots (ST > 0)
     const int tid = threadIdx.x;
     const int P = p.P;

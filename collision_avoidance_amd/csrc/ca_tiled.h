@@ -183,7 +183,9 @@ enum TiledSearch { SEARCH_ALL = 0,          // every agent of the arena, a tile 
 // and velocity, and each enters where DESIGN.md 7b says -- the obstacle range sqr(tho_i * ms_i + r_i) and the edge-grid walk over
 // cell(x +- (tho_i * ms_i + r_i)), the obstacle lines and their covered test (r_i, 1 / tho_i), the agent lines (r_i, r_j, 1 / th_i),
 // LP2 / LP3 (ms_i), the wall and goal tests (r_i), the pair count (sqr(r_i + r_j)).  The sort launches are the uniform handle's:
-// neighbor_dist and max_neighbors stay per handle.  The edge grid is built for the LARGEST range of the handle (ca_env.hip
+// the cells stay half the handle's neighbor_dist wide.  AgentSensing in PER (ca_set_agent_sensing; the tag includes AgentParams): neighbor_dist and
+// max_neighbors per agent -- the solve launch's three searches take the lane's own range and list length, the close launch's list
+// shortcut likewise; the advance launch does not see them.  The edge grid is built for the LARGEST range of the handle (ca_env.hip
 // edge_grid_range); the corner rule of the walk does not depend on the cell size, so an agent of a smaller range simply walks fewer
 // cells.
 // WideObstLists in PER (a handle made with CA_CREATE_TILED_WIDE whose max_obst_neighbors exceeds SMAX; never beside AgentParams): the
@@ -200,14 +202,15 @@ __host__ __device__ inline size_t tiled_close_lds_bytes(int TILE, bool params) {
 // the argument block of each launch follows from its variant (traits of our own, so that an instantiation's name stays short)
 template <int SEARCH> struct TiledSolveArgs { using type = std::conditional_t<SEARCH == SEARCH_GRID_EDGES, TiledEdgeArgs, std::conditional_t<SEARCH == SEARCH_GRID, TiledGridArgs, TiledArgs>>; };
 template <bool EDGES> struct TiledAdvanceArgs { using type = std::conditional_t<EDGES, TiledEdgeArgs, TiledArgs>; };
-template <class... PER> struct TiledCloseArgs { using type = std::conditional_t<has_tag<AgentParams, PER...>, TiledCloseParamsArgs, TiledArgs>; };
+template <class... PER> struct TiledCloseArgs { using type = std::conditional_t<has_tag<AgentParams, PER...> || has_tag<AgentSensing, PER...>, TiledCloseParamsArgs, TiledArgs>; };
 
 // ---- launch 1: neighbour search, ORCA lines, LP2 / LP3 ------------------------------------------------------------------------
 // On a grid handle lane tile * TILE + tid works for SORTED POSITION s of the arena, its agent is i = sidx[s] -- the lanes of a wave then
 // stand in the same few cells and walk the same runs -- and everything else addresses by i as before.
 template <int KMAX, int TILE, int SEARCH, class... PER>
 __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledSolveArgs<SEARCH>::type t) {
-    constexpr bool AP = has_tag<AgentParams, PER...>;
+    constexpr bool AS = has_tag<AgentSensing, PER...>;
+    constexpr bool AP = has_tag<AgentParams, PER...> || AS;   // (AgentSensing includes AgentParams: ca_common.h)
     constexpr bool WIDE = has_tag<WideObstLists, PER...>;
     static_assert(!(WIDE && AP), "per-agent parameters go with obstacle lists of up to 16");
     const StepArgs& p = t.s;
@@ -349,6 +352,13 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) nkey[k] = (k < kofs) ? key_dummy() : key_empty();
     int ncnt = 0;
+    // AgentSensing in PER: the lane's own range nd_i and list length K_i (ca_nbr.h states the rule: the list is the head of the K-list
+    // taken with range nd_i, so the searches keep K slots and the cut to K_i is made once, at the store).  An idle lane keeps nothing.
+    [[maybe_unused]] float nd_own = p.neighbor_dist;
+    [[maybe_unused]] int K_own = 0;
+    if constexpr (AS) {
+        if (active) { nd_own = ck.as_neighbor_dist[q]; K_own = (int)ck.as_max_neighbors[q]; }
+    }
     if constexpr (SEARCH != SEARCH_ALL) {
         // The cells of the columns c(fl(x - B)) .. c(fl(x + B)) and the rows likewise, B = nd * 1.0001 + 1e-4 (ca_nbr.h: a candidate
         // that passes the distance test has |xi - xj| < B, so xj lies between the two floats, and c is monotone) -- not a fixed
@@ -357,9 +367,11 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
         // K-th distance` and the 64-bit keys settle ties, which also makes the order inside a cell immaterial.
         if (K > 0 && active) {
             const size_t cbase = (size_t)a * (t.gx * t.gy + 1);
-            const float rangeSq0 = sqr(p.neighbor_dist);
+            // (AS: the lane's fl(nd_i^2), and the block of its own B_i -- the derivation above holds for any range, the cell size stays the
+            // handle's, so a short-sighted agent walks fewer cells)
+            const float rangeSq0 = AS ? sqr(nd_own) : sqr(p.neighbor_dist);
             float rangeK = rangeSq0;
-            const float B = p.neighbor_dist * 1.0001f + 1e-4f;
+            const float B = (AS ? nd_own : p.neighbor_dist) * 1.0001f + 1e-4f;
             const int cxlo = grid_cell(pos.x - B, t.ics), cxhi = grid_cell(pos.x + B, t.ics);
             const int cylo = grid_cell(pos.y - B, t.ics), cyhi = grid_cell(pos.y + B, t.ics);
             const int ncol = (int)min((unsigned)cxhi - (unsigned)cxlo, (unsigned)(t.gx - 1)) + 1;   // (lo <= hi: c is monotone; NaN gives 1)
@@ -387,7 +399,7 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
     } else {
         // candidates in index order, a tile at a time through LDS -- the oracle's scan, so the shrinking range is its strict one
         if (K > 0) {
-            float rangeSq = sqr(p.neighbor_dist);
+            float rangeSq = AS ? sqr(nd_own) : sqr(p.neighbor_dist);
             for (int ct = 0; ct < t.tiles; ++ct) {
                 const int j0 = ct * TILE;
                 const int nj = min(TILE, N - j0);
@@ -414,10 +426,11 @@ __global__ __launch_bounds__(TILE) void tiled_solve_kernel(const typename TiledS
             atomicAdd(reinterpret_cast<int*>(&p.arena_stats[(size_t)a * ST_STRIDE + ST_OVERFLOW]), 1);
             note_overflow_tiled(p.cold, a, i, oin);
         }
+        if constexpr (AS) ncnt = ncnt < K_own ? ncnt : K_own;   // the head of the K-list: its K_i nearest (the lines below take ncnt entries)
         p.counts[q] = (unsigned short)(ncnt | (ocnt << 8));
 #pragma unroll
         for (int k = 0; k < KMAX; ++k)
-            if (k >= kofs) st_idx_t<true>(p.nb_idx, ((size_t)a * K + (k - kofs)) * N + i, key_index(nkey[k]));
+            if (k >= kofs) st_idx_t<true>(p.nb_idx, ((size_t)a * K + (k - kofs)) * N + i, (AS && k - kofs >= K_own) ? -1 : key_index(nkey[k]));
     }
 
     // ---- ORCA lines into the LDS table (step_kernel's LDS-table path; the neighbours' state gathered from global memory) ----
@@ -577,7 +590,8 @@ __global__ __launch_bounds__(256) void tiled_advance_kernel(const typename Tiled
 // through the neighbour lists is bounded by t.r_max, the handle-wide largest radius.
 template <class... PER>
 __global__ __launch_bounds__(256) void tiled_close_kernel(const typename TiledCloseArgs<PER...>::type t) {
-    constexpr bool AP = has_tag<AgentParams, PER...>;
+    constexpr bool AS = has_tag<AgentSensing, PER...>;
+    constexpr bool AP = has_tag<AgentParams, PER...> || AS;   // (AgentSensing includes AgentParams: ca_common.h)
     const StepArgs& p = t.s;
     const ColdK& c = *(ColdK*)p.cold;
     extern __shared__ float4 smem4[];
@@ -608,7 +622,15 @@ __global__ __launch_bounds__(256) void tiled_close_kernel(const typename TiledCl
         const float m2 = pair_reach(sc[TS_VMAX2], p.time_step);
         V2 pos = mk(0.0f, 0.0f);
         if (active) pos = mk(t.nv_x[q], t.nv_y[q]);
-        bool scan_all = active && !lists_bound_pairs(p.neighbor_dist, R, m2);
+        // (AS: the shortcut reasons "my list holds every agent that can overlap me" -- from the lane's OWN range and list length: its list
+        // reaches nd_i, and is full at K_i entries.  K_i = 0 is a list both full and empty (far2 = 0): such a lane scans.  Lane i counts
+        // the pairs (i, j > i) from its own list alone, so the asymmetry of the lists does not enter.)
+        [[maybe_unused]] float nd_own = p.neighbor_dist;
+        [[maybe_unused]] int K_own = K;
+        if constexpr (AS) {
+            if (active) { nd_own = c.as_neighbor_dist[q]; K_own = (int)c.as_max_neighbors[q]; }
+        }
+        bool scan_all = active && !lists_bound_pairs(AS ? nd_own : p.neighbor_dist, R, m2);
         if (active && !scan_all) {
             float far2 = 0.0f;
             const int ncnt = (int)(p.counts[q] & 0xFFu);
@@ -618,7 +640,7 @@ __global__ __launch_bounds__(256) void tiled_close_kernel(const typename TiledCl
                 far2 = d2 > far2 ? d2 : far2;
                 if (j > i && (AP ? d2 < sqr(ri + c.ap_radius[abase + j]) : d2 < crSq)) ++pairs;
             }
-            scan_all = list_misses_pairs(ncnt, K, far2, R, m2);
+            scan_all = list_misses_pairs(ncnt, AS ? K_own : K, far2, R, m2);
         }
         if (__syncthreads_or(scan_all ? 1 : 0)) {   // (workgroup-uniform: the barriers below are met by every lane)
             if (scan_all) pairs = 0;

@@ -85,6 +85,9 @@ class VecCollisionAvoidanceEnv:
                error wants this raised, not allow_obst_overflow.
     agent_params: dict(radius=, max_speed=, time_horizon=, time_horizon_obst=) handed to set_agent_params() once the handle
                exists: ORCA parameters per agent instead of the four constants of `params`.
+    agent_sensing: dict(neighbor_dist=, max_neighbors=) handed to set_agent_sensing() once the handle exists: how far every agent
+               looks and how many others it attends to, with the two values of `params` as capacities.  On a tiled handle it
+               follows the rule of agent_params=: only with tiled_params=True (ValueError).
     agent_counts: [A] ints handed to set_agent_counts() before the scenario is initialised: arena a holds agent_counts[a] of its
                n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
     tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
@@ -110,7 +113,8 @@ class VecCollisionAvoidanceEnv:
 
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
-                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False, tiled_wide=False):
+                 agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False, tiled_wide=False,
+                 agent_sensing=None):
         if tiled not in (False, True, "grid", None, 0, 1):
             raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
         if tiled_params and not tiled:
@@ -122,6 +126,11 @@ class VecCollisionAvoidanceEnv:
         if tiled_wide and tiled_params:
             raise ValueError("tiled_wide=True together with tiled_params=True: per-agent parameters go with obstacle lists of up to "
                              "16, as on ordinary handles")
+        if agent_sensing is not None and (not isinstance(agent_sensing, dict) or set(agent_sensing) - {"neighbor_dist", "max_neighbors"}):
+            raise ValueError("agent_sensing=%r: a dict with the keys neighbor_dist and / or max_neighbors" % (agent_sensing,))
+        if tiled and agent_sensing and not tiled_params:
+            raise ValueError("tiled=%r: the tiled kernels' per-agent form is chosen at construction (agent_sensing= goes with "
+                             "tiled_params=True or with tiled=False)" % (tiled,))
         if tiled and ((agent_params and not tiled_params) or agent_counts is not None):
             raise ValueError("tiled=%r: the tiled kernels have no per-arena-count form, and their per-agent-parameter form is chosen "
                              "at construction (agent_params= goes with tiled_params=True or with tiled=False, agent_counts= with "
@@ -191,6 +200,8 @@ class VecCollisionAvoidanceEnv:
             self.init_scenario(scenario)
         if agent_params:
             self.set_agent_params(**agent_params)
+        if agent_sensing:
+            self.set_agent_sensing(**agent_sensing)
 
     # ---- plumbing -------------------------------------------------------------------------------
     def _call(self, name, *args):
@@ -425,12 +436,13 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_launch_info", self.h, *[C.byref(x) for x in v])
         lanes, roll = C.c_int32(), C.c_int32()
         self._call("ca_solver_info", self.h, C.byref(lanes), C.byref(roll))
-        per, cnt = C.c_int32(), C.c_int32()
+        per, cnt, sen = C.c_int32(), C.c_int32(), C.c_int32()
         self._call("ca_agent_params_info", self.h, C.byref(per))
         self._call("ca_agent_counts_info", self.h, C.byref(cnt))
+        self._call("ca_agent_sensing_info", self.h, C.byref(sen))
         return dict(block=v[0].value, grid=v[1].value, lds_bytes=v[2].value, obs_grid=v[3].value,
                     lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value),
-                    agent_counts=bool(cnt.value))
+                    agent_counts=bool(cnt.value), agent_sensing=bool(sen.value))
 
     def tiled_info(self):
         """dict(tiled, tile_agents, tiles_per_arena, launches_per_step) of the tiled solve path (ca_tiled_info); zeros on an
@@ -470,7 +482,7 @@ class VecCollisionAvoidanceEnv:
         tensor of shape [A,N] -- a scalar or an [A] array (one value per arena) is broadcast --, or None: every agent keeps the
         value of `params`.  Configuration like the obstacles: it survives reset() and init_scenario() and is not part of
         get_state().  The handle then runs the per-agent kernels (launch_info()["agent_params"]); all four None returns it to
-        uniform parameters, like clear_agent_params().  neighbor_dist and max_neighbors stay per handle."""
+        uniform parameters, like clear_agent_params().  neighbor_dist and max_neighbors per agent: set_agent_sensing()."""
         keep, ptrs = [], []
         for name, v in zip(self._AGENT_PARAMS, (radius, max_speed, time_horizon, time_horizon_obst)):
             if v is None:
@@ -499,6 +511,51 @@ class VecCollisionAvoidanceEnv:
         `params` everywhere on a handle with uniform parameters)."""
         out = {k: np.empty((self.A, self.N), np.float32) for k in self._AGENT_PARAMS}
         self._call("ca_get_agent_params", self.h, *[_ptr(out[k]) for k in self._AGENT_PARAMS], self.A * self.N * 4, 0)
+        return out
+
+    # ---- per-agent sensing (sim.addAgent's neighborDist and maxNeighbors, env.py:126-133) ---------------
+    def _broadcast_an(self, who, name, v, dtype):
+        """v as a contiguous [A,N] array of dtype: a scalar, an [A] array (one value per arena) or an [A,N] array."""
+        if torch is not None and isinstance(v, torch.Tensor):   # a configuration call: the library checks every value on the host anyway
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v)
+        if dtype == np.int32:
+            if a.dtype.kind not in "iu":
+                if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+                    raise ValueError("%s: %s must hold whole numbers, got dtype %s" % (who, name, a.dtype))
+            if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError("%s: %s does not fit 32 bits" % (who, name))
+        a = a.astype(dtype)
+        if a.ndim == 1 and a.shape[0] == self.A:   # one value per arena (also where A == N)
+            a = a[:, None]
+        try:
+            return np.ascontiguousarray(np.broadcast_to(a, (self.A, self.N)), dtype)
+        except ValueError:
+            raise ValueError("%s: %s must be a scalar, an [A] array or an [A,N] array (A=%d, N=%d), got shape %s"
+                             % (who, name, self.A, self.N, a.shape))
+
+    def set_agent_sensing(self, neighbor_dist=None, max_neighbors=None):
+        """neighbor_dist (float) and max_neighbors (int) per agent (ca_set_agent_sensing): each a numpy array or torch tensor of
+        shape [A,N] -- a scalar or an [A] array (one value per arena) is broadcast --, or None: every agent keeps the value of
+        `params`.  The values of `params` are capacities: neighbor_dist_i in [1e-3, params neighbor_dist], max_neighbors_i in
+        [0, params max_neighbors]; the library raises otherwise.  Agent i's list is its max_neighbors_i nearest within
+        neighbor_dist_i; the observation's laser range stays the handle's.  Configuration like the obstacles: it survives reset()
+        and init_scenario() and is not part of get_state().  The handle then runs the per-agent kernels
+        (launch_info()["agent_sensing"]); both None returns it to what it ran before, like clear_agent_sensing()."""
+        nd = None if neighbor_dist is None else self._broadcast_an("set_agent_sensing", "neighbor_dist", neighbor_dist, np.float32)
+        mk = None if max_neighbors is None else self._broadcast_an("set_agent_sensing", "max_neighbors", max_neighbors, np.int32)
+        self._call("ca_set_agent_sensing", self.h, None if nd is None else _ptr(nd), None if mk is None else _ptr(mk),
+                   self.A * self.N * 4, 0)
+
+    def clear_agent_sensing(self):
+        """Back to the handle's neighbor_dist and max_neighbors for every agent and to the kernels it used with them."""
+        self._call("ca_set_agent_sensing", self.h, None, None, 0, 0)
+
+    def agent_sensing(self):
+        """dict(neighbor_dist [A,N] float32, max_neighbors [A,N] int32): what the kernels use (the values of `params` everywhere
+        on a handle without per-agent sensing)."""
+        out = dict(neighbor_dist=np.empty((self.A, self.N), np.float32), max_neighbors=np.empty((self.A, self.N), np.int32))
+        self._call("ca_get_agent_sensing", self.h, _ptr(out["neighbor_dist"]), _ptr(out["max_neighbors"]), self.A * self.N * 4, 0)
         return out
 
     # ---- agents per arena (the reference's constructor argument numAgents, env.py:23-60, per arena) ---

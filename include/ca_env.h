@@ -223,7 +223,8 @@ int ca_create(const ca_config* cfg, int device, void* stream, ca_env** out);
  *     that range is the cell size and the margin of an edge's bounding box.  Setting and clearing the parameters rebuild the grids
  *     while the edge grid is on (a refused rebuild fails the call and changes nothing); switching it on afterwards uses the same
  *     range.  The walk's corner rule does not depend on the cell size, so an agent of a smaller range walks fewer cells.
- *   - ca_set_agent_counts stays CA_EINVAL; neighbor_dist and max_neighbors stay per handle.
+ *   - ca_set_agent_counts stays CA_EINVAL; neighbor_dist and max_neighbors per agent come through ca_set_agent_sensing, which these
+ *     handles (and no other tiled handle) accept.
  * CA_CREATE_TILED_WIDE, together with CA_CREATE_TILED (flags == 33: the plain tiled handle, 37: the grid handle; without
  * CA_CREATE_TILED, with CA_CREATE_TILED_PARAMS -- per-agent parameters go with lists of up to 16, as on ordinary handles --, or with
  * bit 2u or 8u -> CA_EINVAL): the tiled handle of those flags with max_obst_neighbors 1..CA_MAX_OBST_NEIGHBORS -- a large crowd in a
@@ -271,8 +272,9 @@ int ca_get_obstacles_arena(ca_env* env, int32_t arena, float* verts_xy, int32_t*
  * for that parameter.  All four NULL: the handle returns to uniform parameters and to the kernels it used before.
  *   - Configuration, like the obstacle tables, not state: the values persist across ca_reset, ca_reset_masked, CA_F_AUTORESET and
  *     ca_init_scenario, and are not a ca_field.  The scenario generators and the spawn boxes keep using ca_config.radius.
- *   - neighbor_dist and max_neighbors stay per handle: they size the neighbour-key image, the search grid, the ray table of the
- *     observation and the kernels' K classes.
+ *   - neighbor_dist and max_neighbors stay per handle in this call: they size the neighbour-key image, the search grid, the ray
+ *     table of the observation and the kernels' K classes.  ca_set_agent_sensing (below) takes them per agent, with the handle's
+ *     values as capacities.
  *   - Every value is checked (a device array is copied back for the check): a value that is not finite or lies outside
  *     [CA_MIN_LENGTH, CA_MAX_LENGTH] -> CA_ERANGE (ca_last_error names the parameter, the arena and the agent);
  *     bytes_each != A*N*4 -> CA_ESIZE; a handle with max_obst_neighbors > 16 -> CA_EINVAL (not together with wide obstacle lists);
@@ -328,6 +330,41 @@ int ca_set_agent_counts(ca_env* env, const int32_t* counts, size_t bytes, int32_
 int ca_get_agent_counts(ca_env* env, int32_t* counts, size_t bytes, int32_t dst_is_device);
 /* *per_arena = 1 while counts are set (the ArenaCounts kernels run), else 0. */
 int ca_agent_counts_info(ca_env* env, int32_t* per_arena);
+
+/* The two remaining per-agent arguments of sim.addAgent (env.py:126-133; ALAN:81-87), neighborDist and maxNeighbors: how far an agent
+ * looks and how many others it attends to -- attentive and distracted pedestrians in one crowd, or a perception range per arena.
+ * neighbor_dist: f32 [A,N], max_neighbors: i32 [A,N] (host or device); NULL = every agent keeps the handle's ca_config value for
+ * that parameter.  Both NULL: the handle returns to the kernels it ran before.
+ *   - The ca_config values become CAPACITIES, as n_agents does under ca_set_agent_counts: neighbor_dist_i must be finite and lie in
+ *     [CA_MIN_LENGTH, ca_config.neighbor_dist], max_neighbors_i in [0, ca_config.max_neighbors]; anything else -> CA_ERANGE
+ *     (ca_last_error names the parameter, the arena and the agent).  The capacities keep sizing the kernels' K class, the [A,K,N]
+ *     list layout, the LDS line table, the search grids and the neighbour-key image.
+ *   - Semantics, exactly RVO2's computeAgentNeighbors: agent i's list holds the max_neighbors_i smallest (squared distance, index)
+ *     keys among the other agents j with fl(dx^2) + fl(dy^2) < fl(neighbor_dist_i * neighbor_dist_i) (fp32), nearest first, ties to the
+ *     lower index; slots at or beyond the count read -1.  Lists are asymmetric: i may see j while j does not see i.
+ *   - The observation's laser range stays ca_config.neighbor_dist: the ray table belongs to the environment (env.py:321-332), not
+ *     to the agent.  The observation enumerates the lists (env.py:283-285) and so follows them with no rule of its own.
+ *   - Configuration, not state: it persists across ca_reset, ca_reset_masked, CA_F_AUTORESET and ca_init_scenario and is not a ca_field.
+ *   - The call drains the stream and clears the agent-neighbour count of every row of every arena (a list left by the last step may
+ *     be longer than its agent's new max_neighbors; the next step rebuilds them).  It touches nothing else.
+ *   - bytes_each != A*N*4 -> CA_ESIZE; a handle with max_obst_neighbors > 16 -> CA_EINVAL; a shape whose LDS line table does not fit
+ *     a CU -> CA_ERANGE (as for ca_set_agent_params); a NULL handle -> CA_EINVAL.  On any failure the handle keeps what it had.
+ *   - While set, an ordinary handle runs the one-lane LDS-line-table kernels of ca_set_agent_params, in an instantiation of their
+ *     own (ca_solver_info: lanes_per_agent = 1, rollout_one_launch = 0; ALAN in the three-launch form); the four per-agent
+ *     parameter arrays hold the ca_config values unless the caller set them, as under counts.
+ *   - Composes with ca_set_agent_params and ca_set_agent_counts in any order; clearing one keeps the others.  An absent row's values
+ *     are checked but never read.
+ *   - Tiled handles: only those made with CA_CREATE_TILED_PARAMS (flags 17 and 21) accept it, every other tiled handle -> CA_EINVAL
+ *     and keeps working.  The number of launches does not change and the sort launches are the uniform handle's (the cells stay
+ *     half the handle's neighbor_dist wide; an agent walks the cells of its own range).  The pair count's shortcut through the
+ *     lists takes the agent's own range and list length.
+ * Results are the CPU oracle's with these values per agent, bit for bit; arrays equal to the ca_config values give the bits of the
+ * same handle without them. */
+int ca_set_agent_sensing(ca_env* env, const float* neighbor_dist, const int32_t* max_neighbors, size_t bytes_each, int32_t src_is_device);
+/* The two arrays as the kernels use them (the ca_config value for every agent on a handle without per-agent sensing); either may be NULL. */
+int ca_get_agent_sensing(ca_env* env, float* neighbor_dist, int32_t* max_neighbors, size_t bytes_each, int32_t dst_is_device);
+/* *per_agent = 1 while per-agent sensing is set (the AgentSensing kernels run), else 0. */
+int ca_agent_sensing_info(ca_env* env, int32_t* per_agent);
 
 /* Replaces _init_world's agent loop (env.py:86-97) / ALAN's scenario generators (ALAN:175-457).  Runs on the device: every
  * agent's heading, start and targets come from the handle's counter-based streams (keyed by the global arena id) or, for
