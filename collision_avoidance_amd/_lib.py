@@ -37,7 +37,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info",
            "ca_rollout_trace", "ca_alan_rollout_trace", "ca_tiled_edge_grid", "ca_tiled_edge_grid_info", "ca_edge_grid_build",
            "ca_contacts", "ca_get_contacts", "ca_contacts_ptr",
-           "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info")
+           "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info")
 
 
 class Config(C.Structure):
@@ -153,6 +153,7 @@ def load():
     L.ca_set_agent_sensing.argtypes = [vp, vp, vp, sz, i32]
     L.ca_get_agent_sensing.argtypes = [vp, vp, vp, sz, i32]
     L.ca_agent_sensing_info.argtypes = [vp, C.POINTER(i32)]
+    L.ca_nbr_seed_info.argtypes = [vp, C.POINTER(i32)]
     L.ca_source_sha.argtypes = []
     L.ca_source_sha.restype = C.c_char_p
     for name in EXPORTS:

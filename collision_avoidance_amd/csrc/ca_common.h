@@ -31,6 +31,12 @@ struct AgentSensing;
 // ca_alan_rollout_trace): inside the T-step loop the selected planes of the state and the arena's three words go to the caller's
 // trace buffer whenever the rollout's step count reaches a multiple of `every` (TraceDev below).
 struct Trace;
+// Tag of the one-wave solve kernels whose agent scan starts from last step's neighbour list and skips, wave-wide, the candidates no
+// lane can take (step_kernel<KMAX, 64, ST, SMX, ALAN, [AlanArenaSets | ArenaCounts,] SeededScan>; ca_nbr.h, CA_NBR_SEED).  It stands
+// last in the pack: the plain register-line and line-table kernels, their ALAN forms (with one action set or one per arena) and the
+// ArenaCounts kernels have a seeded twin; the AgentParams, AgentSensing and wide-list kernels do not, and every instantiation
+// without the tag keeps its name, its text and its resources (they serve CA_NBR_SEED=0 in the environment).
+struct SeededScan;
 
 namespace ca {
 

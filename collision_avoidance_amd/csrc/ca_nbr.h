@@ -120,8 +120,21 @@ __device__ __forceinline__ bool edge_in_range(const ObstDev& o1, V2 pos, float r
 // (top / u0 from neighbor_dist^2: a passing dsq lies below fl(nd_i^2) <= fl(neighbor_dist^2), so the image is exact over the same
 // binades), the grid's cell size and the block of cells walked (B from neighbor_dist covers every smaller range).  Lists are
 // asymmetric -- i may hold j while j does not hold i -- and nothing below relies on symmetry: a lane reads positions, never lists.
-template <int KMAX, int BS, int SM, bool AP = false, bool AC = false, bool AS = false>
+#ifndef CA_CK_MAXN
+#define CA_CK_MAXN 64    // the largest arena that first tries the composite keys (see below: larger arenas measured slower)
+#endif
+// SD (the SeededScan instantiations of the solve kernel; CA_NBR_SEED, build switch: 0 = there are none): the composite-key scan of
+// arenas of at most 64 agents starts from the lane's list of the LAST step and skips, wave-wide, every candidate that no lane can
+// take (see the scan itself, below).  One-wave workgroups only -- an arena of at most 64 agents has no other (ca_create: BS =
+// max(64, P)) -- and never with AgentSensing: those kernels store K_i < K entries, so their seed never fills the K slots and most
+// candidates in range would run the network anyway.  Without the tag the scan starts every list empty and runs the insertion
+// network for every candidate, as it always did: those instantiations keep their instruction text.
+#ifndef CA_NBR_SEED
+#define CA_NBR_SEED 1
+#endif
+template <int KMAX, int BS, int SM, bool AP = false, bool AC = false, bool AS = false, bool SD = false>
 __device__ __forceinline__ void nbr_body(const StepArgs& p) {
+    static_assert(!SD || (CA_NBR_SEED && !AS && BS == 64), "the seeded scan: one wave, not with AgentSensing");
 #ifndef CA_NBR_NO_VGPR_PAD
     // Claim 128 VGPRs (the kernel needs 56): at most 4 waves then fit on a SIMD, so a launch that brings one
     // wave per SIMD slot (4096 x 64 lanes on 256 CUs) is spread evenly.  Without it the dispatcher puts
@@ -146,6 +159,28 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
     V2 pos = mk(0.0f, 0.0f);
     if (active) pos = mk(p.pos_x[q], p.pos_y[q]);
     s_px[tid] = pos.x; s_py[tid] = pos.y;
+#if CA_NBR_SEED
+    // (seeded scan) the lane's list of the last step -- count and K ids, whatever they hold: the scan below takes nothing from
+    // them unchecked -- loaded here, so that the obstacle-edge loop hides the latency
+    constexpr bool SEED = SD;
+    [[maybe_unused]] int seed_n = 0;
+    [[maybe_unused]] int seed_id[KMAX];
+    if constexpr (SEED) {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) seed_id[k] = 0;
+        if (active && K > 0 && N <= CA_CK_MAXN) {
+            seed_n = (int)p.counts[q] & 0xFF;
+            // (one 64-bit index per lane and a scalar stride, not a 64-bit product per slot; slots at or beyond K read slot K - 1
+            // again and are not looked at: no branch between the loads)
+            size_t at = (size_t)a * K * N + i;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                seed_id[k] = ld_idx_t<CA_NBW16(BS)>(p.nb_idx, at);
+                if (k + 1 < K) at += (unsigned)N;
+            }
+        }
+    }
+#endif
     __syncthreads();
 
     const float INF = __int_as_float(0x7f800000);
@@ -339,14 +374,12 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             scanned = true;
         }
     }
-#ifndef CA_CK_MAXN
-#define CA_CK_MAXN 64    // the largest arena that first tries the composite keys (see below: larger arenas measured slower)
-#endif
     if (K > 0 && !scanned && N <= CA_CK_MAXN) {
         // Arenas of at most 64 agents: 32-bit composite keys = (distance image << logP) | candidate index and
         // one v_med3_u32 per list slot and candidate -- new[k] = med3(old[k-1], old[k], x) IS the sorted insert,
         // at half the instructions of the 64-bit network (in so small an arena some lane accepts nearly every
-        // candidate, so the shrinking range of the contract never lets a wave skip the network anyway).
+        // candidate, so the shrinking range of the contract never lets a wave skip the network anyway -- as long as
+        // every list starts empty: the seeded scan below, CA_NBR_SEED, starts from last step's list and does skip).
         // The image is the fp32 BIT PATTERN of the squared distance, counted down from that of neighbor_dist^2
         // (round 5): 32 - logP bits hold every float of the top 2^(9 - logP) binades below the range -- for 64 agents and a range
         // of 5 every d2 in [0.125, 25) -- at full resolution, so there the composite order IS the contract's exact (distance, index)
@@ -376,6 +409,117 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             for (int k = KMAX; k >= 1; --k) ck[k] = umed3(ck[k - 1], ck[k], c);
             ck[0] = ck[0] < c ? ck[0] : c;
         };
+#if CA_NBR_SEED
+        if constexpr (SEED) {
+            // THE SEEDED SCAN.  An agent moves at most max_speed * time_step per step, a sixtieth of its radius or so: the K nearest
+            // of this step are, but for one or two, those of the last.  So the list starts from them -- the lane's K ids of the last
+            // step, inserted first with their CURRENT distances through the same pass test, key and network -- and the scan in
+            // index order then runs the network only for a candidate that some lane of the wave can still take: one whose squared
+            // distance is at most the lane's threshold, the distance of its current K-th key (the range, while the list is short),
+            // and that the lane has not inserted already.  Everything else is five instructions of distance and three of test.
+            // WHY THE LISTS ARE THE SAME BITS.  A key c >= ck[KMAX - 1], the lane's K-th smallest so far, leaves slots 0 .. KMAX - 1
+            // as they are: slot k becomes med3(ck[k - 1], ck[k], c) = ck[k].  It can only enter slot KMAX, which is read once, by
+            // clamped_pair when K = 1 (the second smallest key): there the threshold is that of ck[KMAX].  The K-th smallest only
+            // shrinks, so a skipped candidate is none of the final K smallest, and the K smallest of a set of distinct keys (the index
+            // sits in the low bits) do not depend on the order of insertion.  Each candidate is inserted at most once: `vis` holds,
+            // per lane, a bit for itself, for every absent row (AC: j >= n_a; an idle lane: all 64) and for every seed member taken.
+            // Two clamped candidates carry the smallest keys there are, never above a threshold: clamped_pair sees what it saw.
+            // The threshold is the K-th key's image taken back to fp32 bits, u0 + (key >> logP), capped at the bits of the range
+            // (top): key_c < key_K implies image_c <= image_K, that is max(u_c, u0) <= u0 + image_K, and a passing u_c lies below top.
+            // Squared distances are non-negative, so their order as floats is their order as unsigned bit patterns (a NaN lies
+            // above top either way and never passes, here as in the exact test).
+            // THE SEED IS NOT TRUSTED: the lists are settable (ca_set), stale after a reset or set_state, zero in a fresh handle.
+            // The count is clamped to K; a member is taken only if it is a present row other than the lane's own and not yet
+            // taken (the vis bit), and only then is its position read from the staged arena.
+            unsigned long long vis = ~0ull;
+            if (active) vis = (n_a < 64 ? ~0ull << n_a : 0ull) | (1ull << i);
+            auto insert = [&](unsigned jj, float dsq, bool take) __attribute__((always_inline)) {
+                const bool pass = take && dsq < rangeSq0;
+                const unsigned u = __float_as_uint(dsq);
+                unsigned key = (((u > u0 ? u : u0) - u0) << p.logP) | jj;
+                asm volatile("" : "+v"(key));   // (as in visit above)
+                const unsigned c = pass ? key : 0xFFFFFFFFu;
+#pragma unroll
+                for (int k = KMAX; k >= 1; --k) ck[k] = umed3(ck[k - 1], ck[k], c);
+                ck[0] = ck[0] < c ? ck[0] : c;
+            };
+            unsigned thr = 0u;
+            auto refresh = [&]() __attribute__((always_inline)) {
+                const unsigned kth = (K >= 2) ? ck[KMAX - 1] : ck[KMAX];
+                const unsigned t = u0 + (kth >> p.logP);   // (no overflow: at most top + 1, or u0 = 0)
+                thr = t < top ? t : top;
+            };
+            const int sn = seed_n < K ? seed_n : K;
+#pragma unroll
+            for (int k = 0; k < KMAX; ++k) {
+                if (k < K) {   // wave-uniform
+                    // (a slot that holds no member stands for the lane itself: its bit is set, so it is never taken, and its
+                    // staged position is the lane's own slot -- no test of its own, no index that was not checked)
+                    const unsigned m = (unsigned)seed_id[k];
+                    const unsigned mm = (k < sn && m < (unsigned)n_a) ? m : (unsigned)i;
+                    const unsigned long long bit = 1ull << mm;
+                    const bool ok = (vis & bit) == 0ull;
+                    if (__builtin_amdgcn_ballot_w64(ok) != 0ull) {   // wave-uniform
+                        vis |= bit;
+                        const int src = lbase + (int)mm;
+                        insert(mm, absSq(pos - mk(s_px[src], s_py[src])), ok);
+                    }
+                }
+            }
+            refresh();
+#ifdef CA_STAMPS
+            unsigned long long dbg_trips = 0ull, dbg_ran = 0ull;
+#endif
+            // a candidate this lane can still take: not taken yet, at or below the threshold (ties pass: the exact test follows)
+            auto want = [&](unsigned visw, unsigned bit, float dsq) __attribute__((always_inline)) {
+                return __float_as_uint(dsq) <= thr && (visw & bit) == 0u;
+            };
+            auto take = [&](int jj, unsigned visw, unsigned bit, float dsq, bool w) __attribute__((always_inline)) {
+                if (__builtin_amdgcn_ballot_w64(w) != 0ull) {   // wave-uniform: some lane can take candidate jj
+                    insert((unsigned)jj, dsq, (visw & bit) == 0u);
+                    refresh();
+#ifdef CA_STAMPS
+                    ++dbg_ran;
+#endif
+                }
+            };
+            int j = 0;
+            for (; j + 4 <= N; j += 4) {   // (four per trip, positions read at the head of the trip: as in the unseeded scan below)
+                const V2 o0 = mk(s_px[lbase + j], s_py[lbase + j]), o1 = mk(s_px[lbase + j + 1], s_py[lbase + j + 1]);
+                const V2 o2 = mk(s_px[lbase + j + 2], s_py[lbase + j + 2]), o3 = mk(s_px[lbase + j + 3], s_py[lbase + j + 3]);
+                const unsigned visw = (j & 32) ? (unsigned)(vis >> 32) : (unsigned)vis;   // (j is a multiple of four: one word for the trip)
+                const unsigned b0 = 1u << (j & 31);
+                const float d0 = absSq(pos - o0), d1 = absSq(pos - o1), d2 = absSq(pos - o2), d3 = absSq(pos - o3);
+                const bool w0 = want(visw, b0, d0), w1 = want(visw, b0 << 1, d1), w2 = want(visw, b0 << 2, d2), w3 = want(visw, b0 << 3, d3);
+#ifdef CA_STAMPS
+                dbg_trips += 4;
+#endif
+                if (__builtin_amdgcn_ballot_w64(w0 || w1 || w2 || w3) != 0ull) {   // wave-uniform
+                    take(j, visw, b0, d0, w0); take(j + 1, visw, b0 << 1, d1, w1);
+                    take(j + 2, visw, b0 << 2, d2, w2); take(j + 3, visw, b0 << 3, d3, w3);
+                }
+            }
+            for (; j < N; ++j) {
+                const unsigned visw = (j & 32) ? (unsigned)(vis >> 32) : (unsigned)vis;
+                const unsigned b = 1u << (j & 31);
+                const float d = absSq(pos - mk(s_px[lbase + j], s_py[lbase + j]));
+#ifdef CA_STAMPS
+                ++dbg_trips;
+#endif
+                take(j, visw, b, d, want(visw, b, d));
+            }
+#ifdef CA_STAMPS   // (diagnostic build) this wave's candidate trips and how many of them ran the network: the row behind the launch's time stamps
+            // (rows [0, ceil(A / apb)) are the time stamps of a launch over all arenas, one per wave, indexed by blockIdx.x as CA_STAMP
+            // does; the counts go behind them whatever this launch's own grid is -- a chunked launch (a0 > 0) overwrites rows from 0,
+            // like its stamps, and a block order (work_block) changes which arenas a row stands for, not the row)
+            if (CA_STAMPS < 3 && (tid & 63) == 0 && p.dbg) {
+                unsigned long long* r = p.dbg + ((size_t)((p.A + apb - 1) / apb + blockIdx.x) * (BS / 64) + (tid >> 6)) * 16;
+                r[0] = dbg_trips; r[1] = dbg_ran;
+            }
+#endif
+        } else
+#endif
+        {
         // four candidates per trip, their positions read at the head of the trip (immediate LDS offsets, no register rotation
         // between trips: the rolled loop with a one-ahead prefetch spent 5 of its 28 vector instructions per candidate on moves
         // and address increments)
@@ -386,6 +530,7 @@ __device__ __forceinline__ void nbr_body(const StepArgs& p) {
             visit(j, o0); visit(j + 1, o1); visit(j + 2, o2); visit(j + 3, o3);
         }
         for (; j < N; ++j) visit(j, mk(s_px[lbase + j], s_py[lbase + j]));
+        }
         int cnt = 0;
         bool clamped_pair = false;   // (the list is ascending: two clamped candidates, if there are any, are its first two entries)
 #pragma unroll

@@ -97,6 +97,8 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 //   max_neighbors per agent (ca_set_agent_sensing): the neighbour search at the head of the kernel takes the lane's own range and list length (ca_nbr.h).
 //   Nothing behind the search changes: lines, LP and epilogue read the lists and counts it stored, and the pair count of these
 //   instantiations scans the arena (below), so it never reasons from a list.
+//   SeededScan (one wave, alone in the pack, ALAN or not) = the agent scan of the neighbour search starts from last step's list
+//   (ca_nbr.h); nothing else of the kernel reads the tag.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     // The neighbour search runs at the head of this kernel (one drain/fill less per step than a launch of its own, and its
     // dispatch skew overlaps useful work).  A lane later reads back only the lists of its own agent, which it wrote itself;
     // the search's LDS arrays are not used again.
-    nbr_body<KMAX, BS, SMX, AP, AC, AS>(p);
+    nbr_body<KMAX, BS, SMX, AP, AC, AS, has_tag<SeededScan, PER...>>(p);
     constexpr int ML = ST + KMAX;  // register slots (ST > 0)
     const int tid = threadIdx.x;
     const int P = p.P;

@@ -444,6 +444,13 @@ class VecCollisionAvoidanceEnv:
                     lanes_per_agent=lanes.value, rollout_one_launch=roll.value, agent_params=bool(per.value),
                     agent_counts=bool(cnt.value), agent_sensing=bool(sen.value))
 
+    def nbr_seed_info(self):
+        """True if a plain step of this handle launches a SeededScan solve kernel: the agent-neighbour scan of arenas of at most 64
+        agents seeded with last step's lists (ca_nbr_seed_info; CA_NBR_SEED=0 in the environment at construction switches it off)."""
+        v = C.c_int32()
+        self._call("ca_nbr_seed_info", self.h, C.byref(v))
+        return bool(v.value)
+
     def tiled_info(self):
         """dict(tiled, tile_agents, tiles_per_arena, launches_per_step) of the tiled solve path (ca_tiled_info); zeros on an
         ordinary handle."""

@@ -366,6 +366,14 @@ int ca_get_agent_sensing(ca_env* env, float* neighbor_dist, int32_t* max_neighbo
 /* *per_agent = 1 while per-agent sensing is set (the AgentSensing kernels run), else 0. */
 int ca_agent_sensing_info(ca_env* env, int32_t* per_agent);
 
+/* The agent-neighbour scan of arenas of at most 64 agents starts each agent's list from the one the last step left in memory and runs
+ * the sorted insertion only for candidates that some agent of the wave can still take (the SeededScan kernels).  Results are the
+ * same bits; lists written through ca_set, or left by a reset or another state, are sanitised, never trusted.  *seeded = 1 if a plain
+ * ca_step of this handle launches such a kernel, else 0: arenas above 64 agents, tiled handles, handles on the four-lanes kernel,
+ * per-agent parameters or sensing and obstacle lists above 16 have none.  CA_NBR_SEED=0 in the environment when the handle is made
+ * (a diagnostic switch, like CA_QUAD) keeps the handle on the unseeded kernels. */
+int ca_nbr_seed_info(ca_env* env, int32_t* seeded);
+
 /* Replaces _init_world's agent loop (env.py:86-97) / ALAN's scenario generators (ALAN:175-457).  Runs on the device: every
  * agent's heading, start and targets come from the handle's counter-based streams (keyed by the global arena id) or, for
  * the layouts that do not depend on the arena, from a per-agent table made once on the host (its cos / sin / sqrt are
