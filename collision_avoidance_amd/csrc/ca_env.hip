@@ -20,6 +20,22 @@
 
 using namespace ca;
 
+// a second set of the state buffers (state_planes below): one allocation for the planes every handle has, one for the bandit's,
+// which exist after ca_alan_configure* only and change shape with n_actions
+struct StateSet {
+    unsigned char* base = nullptr;
+    unsigned char* alan = nullptr;
+    int alan_nA = 0;   // n_actions the bandit's allocation was made for
+};
+struct ca_env;
+struct ca_snapshot {
+    ca_env* owner = nullptr;
+    StateSet set;
+    bool saved = false;
+    int n_actions = 0;         // the ALAN shape at the save
+    std::vector<int> counts;   // the per-arena agent counts at the save (empty: none were set)
+};
+
 struct ca_env {
     ca_config cfg;
     int device = 0;
@@ -152,6 +168,12 @@ struct ca_env {
     float ap_rmax = 0.0f;
     // ... or obstacle lists of up to 64 on it (CA_CREATE_TILED_WIDE; ca_tiled.h's WideObstLists instantiations, run when S > 16)
     bool twide = false;
+    // forking and rewinding arenas (ca_arena_gather, ca_snapshot_*; ca_fork.h): fork_scratch is the second set of the state buffers the
+    // in-place gather copies through, allocated on first use; fork_idx the [A] index array on the device; snapshots the sets handed out
+    // and still alive (ca_destroy frees them)
+    StateSet fork_scratch;
+    int* fork_idx = nullptr;
+    std::vector<ca_snapshot*> snapshots;
     uint64_t agent_steps_base = 0;   // agent-steps of the arena steps counted before the counts last changed (ca_get_stats)
     uint64_t steps_done = 0;  // env steps enqueued (profiling cadence only: ca_stats.agent_steps is counted in the kernels)
     float rays[32], oct[32];
@@ -1131,8 +1153,13 @@ int ca_destroy(ca_env* e) {
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
                     e->nv_x, e->nv_y, e->tscr, e->tg_count, e->tg_start, e->tg_key, e->tg_sx, e->tg_sy, e->tg_sidx,
-                    e->eg.d_desc, e->eg.d_cells, e->eg.d_entries, e->contact};
+                    e->eg.d_desc, e->eg.d_cells, e->eg.d_entries, e->contact, e->fork_scratch.base, e->fork_scratch.alan, e->fork_idx};
     for (void* b : bufs) if (b) hipFree(b);
+    for (ca_snapshot* sn : e->snapshots) {   // (a snapshot the caller still holds dangles from here on, like the handle itself)
+        if (sn->set.base) hipFree(sn->set.base);
+        if (sn->set.alan) hipFree(sn->set.alan);
+        delete sn;
+    }
     for (const auto& h : e->host_allocs) hipHostFree(h.first);
     if (e->ovf_host) hipHostFree(e->ovf_host);
     for (const ca_env::Span& sp : e->spans) { hipEventDestroy(sp.t0); hipEventDestroy(sp.t1); }
@@ -2944,6 +2971,263 @@ int ca_edge_grid_build(const float* edges_pq, int32_t n_edges, float range, ca_e
                     en.size(), (int)entry_cap);
     memcpy(cell_start, cs.data(), cs.size() * sizeof(uint32_t));
     if (!en.empty()) memcpy(entries, en.data(), en.size() * sizeof(uint32_t));
+    return CA_OK;
+}
+
+}  // extern "C"
+
+// ---- forking and rewinding arenas: ca_arena_gather, ca_snapshot_* (ca_fork.h) ---------------------------------------
+// THE list of what an arena's state is: every plane that moves, as [A][rows][n] elements of esize bytes.  The scratch set, the
+// snapshots and the kernel's descriptor table are all laid out from it, and the header's list of moved fields (include/ca_env.h,
+// "State that moves") and VecCollisionAvoidanceEnv._STATE_FIELDS name the same fields (tests/test_fork_cpu.py holds the three
+// together).  What is not here stays with the slot: configuration (obstacle tables, per-agent parameters, counts and sensing, ALAN
+// action sets, the edge grid), statistics, the contact report, the observation, and seed / arena_offset + a, which key the draws.
+// The sort buffers, nv_x / nv_y and tscr of a tiled handle, alan_dirs / alan_u and orient_x / orient_y are scratch or derived.
+struct StatePlane { const char* fields; void* ptr; unsigned esize, n, rows; bool per_agent, alan; };
+static int state_planes(const ca_env* e, StatePlane* out) {
+    const unsigned N = (unsigned)e->cfg.n_agents, K = (unsigned)(e->K > 0 ? e->K : 1), S = (unsigned)e->S, nA = (unsigned)e->n_actions;
+    const StatePlane all[] = {
+        {"POS_X", e->pos_x, 4, N, 1, true, false},
+        {"POS_Y", e->pos_y, 4, N, 1, true, false},
+        {"VEL_X", e->vel_x, 4, N, 1, true, false},
+        {"VEL_Y", e->vel_y, 4, N, 1, true, false},
+        {"PREF_X", e->pref_x, 4, N, 1, true, false},
+        {"PREF_Y", e->pref_y, 4, N, 1, true, false},
+        {"GOAL_X", e->goal_x, 8, N, 1, true, false},
+        {"GOAL_Y", e->goal_y, 8, N, 1, true, false},
+        {"GOAL2_X", e->goal2_x, 8, N, 1, true, false},
+        {"GOAL2_Y", e->goal2_y, 8, N, 1, true, false},
+        {"REWARD", e->reward, 4, N, 1, true, false},
+        {"AGENT_DONE", e->agent_done, 4, N, 1, true, false},
+        {"ARRIVE_STEP", e->arrive_step, 4, N, 1, true, false},
+        {"REGOAL_COUNT", e->regoal_count, 4, N, 1, true, false},
+        {"NB_COUNT OBST_COUNT", e->counts, 2, N, 1, true, false},   // one packed u16: agent-neighbour count | obstacle-neighbour count << 8
+        {"NB_IDX", e->nb_idx, e->nidx16 ? 2u : 1u, N, K, true, false},
+        {"OBST_IDX", e->obst_idx, 2, N, S, true, false},
+        {"STEP_COUNT", e->step_count, 4, 1, 1, false, false},
+        {"ARENA_DONE", e->arena_done, 4, 1, 1, false, false},
+        {"EPISODE", e->episode, 4, 1, 1, false, false},
+        {"ALAN_WEIGHTS", e->alan_w, 8, N, nA, true, true},
+        {"ALAN_TIMES", e->alan_t, 8, N, nA, true, true},
+        {"ALAN_ACTION", e->alan_action, 4, N, 1, true, true},
+    };
+    static_assert(sizeof all / sizeof all[0] <= FORK_MAX_PLANES, "ca_fork.h ForkArgs holds every plane");
+    int n = 0;
+    for (const StatePlane& p : all)
+        if (!p.alan || e->n_actions > 0) out[n++] = p;
+    return n;
+}
+static size_t state_plane_bytes(const ca_env* e, const StatePlane& p) {
+    return (size_t)e->cfg.n_arenas * p.esize * p.n * p.rows;
+}
+static size_t fork_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// the buffers of a set for the handle's present shape; the bandit's part follows n_actions (a change drains the stream first)
+static int state_set_reserve(ca_env* e, StateSet& s, const char* who) {
+    StatePlane pl[FORK_MAX_PLANES];
+    const int n = state_planes(e, pl);
+    size_t base = 0, alan = 0;
+    for (int k = 0; k < n; ++k) (pl[k].alan ? alan : base) += fork_align(state_plane_bytes(e, pl[k]));
+    if (!s.base) {
+        const hipError_t r = hipMalloc((void**)&s.base, base);
+        if (r != hipSuccess) { s.base = nullptr; return fail(e, CA_EHIP, "%s: %zu bytes for a second set of the state buffers: %s", who, base, hipGetErrorString(r)); }
+    }
+    if (s.alan_nA != e->n_actions) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (s.alan) HIPCHK(e, hipFree(s.alan));
+        s.alan = nullptr; s.alan_nA = 0;
+        if (e->n_actions > 0) {
+            const hipError_t r = hipMalloc((void**)&s.alan, alan);
+            if (r != hipSuccess) { s.alan = nullptr; return fail(e, CA_EHIP, "%s: %zu bytes for the bandit's state: %s", who, alan, hipGetErrorString(r)); }
+            s.alan_nA = e->n_actions;
+        }
+    }
+    return CA_OK;
+}
+
+// One launch of fork_kernel over every plane.  save: handle -> set, every arena, no index.  Else set -> handle: arena a takes arena
+// idx[a] of the set (idx == nullptr: arena a), negative entries -- and with keep_self idx[a] == a -- are not written; the two clearing
+// rules and the per-arena counts apply to what is written.
+static hipError_t launch_fork(ca_env* e, const StateSet& s, bool save, const int* idx, bool keep_self) {
+    StatePlane pl[FORK_MAX_PLANES];
+    const int n = state_planes(e, pl);
+    ForkArgs f;
+    memset(&f, 0, sizeof f);
+    size_t off[2] = {0, 0}, most = 0;
+    unsigned keep_counts = 0xFFFFu;
+    if (!save && !e->h_tab_off.empty()) keep_counts &= 0x00FFu;   // a world per arena: obstacle ids are local to a table, the moved list is void
+    if (!save && e->sens) keep_counts &= 0xFF00u;                 // per-agent sensing: a copied list may be longer than its new owner's max_neighbors
+    const bool counts = !save && e->ac;
+    for (int k = 0; k < n; ++k) {
+        unsigned char* in_set = (pl[k].alan ? s.alan : s.base) + off[pl[k].alan];
+        off[pl[k].alan] += fork_align(state_plane_bytes(e, pl[k]));
+        ForkPlane& p = f.p[k];
+        p.src = save ? (const unsigned char*)pl[k].ptr : in_set;
+        p.dst = save ? in_set : (unsigned char*)pl[k].ptr;
+        p.esize = pl[k].esize; p.n = pl[k].n; p.rows = pl[k].rows;
+        p.per_agent = pl[k].per_agent ? 1u : 0u;
+        p.keep = pl[k].ptr == (void*)e->counts ? (keep_counts | keep_counts << 16) : 0xFFFFFFFFu;
+        const size_t arena_bytes = (size_t)p.esize * p.n * p.rows;
+        p.vec = (arena_bytes % 16 == 0 && (uintptr_t)p.src % 16 == 0 && (uintptr_t)p.dst % 16 == 0 && !(counts && pl[k].per_agent)) ? 1u : 0u;
+        p.items = (unsigned)(p.vec ? arena_bytes / 16 : (size_t)p.n * p.rows);
+        most = std::max(most, (size_t)e->cfg.n_arenas * p.items);
+    }
+    f.idx = idx; f.counts = counts ? e->d_counts : nullptr; f.A = e->cfg.n_arenas; f.keep_self = keep_self ? 1 : 0;
+    // a grid-stride loop: enough workgroups to fill the chip, no more than the largest plane has items for
+    const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((most + FORK_BS - 1) / FORK_BS, (size_t)e->n_cus * 8));
+    const dim3 grid(gx, (unsigned)n), block(FORK_BS);
+    ProfScope ps(e, KIND_RESET);
+    if (idx) {
+        if (counts) launch_k(ps, fork_kernel<true, true>, grid, block, 0, e->stream, f);
+        else launch_k(ps, fork_kernel<true, false>, grid, block, 0, e->stream, f);
+    } else {
+        if (counts) launch_k(ps, fork_kernel<false, true>, grid, block, 0, e->stream, f);
+        else launch_k(ps, fork_kernel<false, false>, grid, block, 0, e->stream, f);
+    }
+    return hipGetLastError();
+}
+
+// the index array of a gather / load on the host, checked: lo = 0 (gather) or -1 (load: -1 keeps the arena)
+static int fork_index(ca_env* e, const char* who, const int32_t* src, size_t bytes, int32_t src_is_device, int lo, std::vector<int>& h) {
+    const int A = e->cfg.n_arenas;
+    if (bytes != (size_t)A * 4) return fail(e, CA_ESIZE, "%s: the index array holds %zu bytes, got %zu", who, (size_t)A * 4, bytes);
+    h.resize(A);
+    if (src_is_device) HIPCHK(e, download(e, h.data(), src, (size_t)A * 4));   // (drains the stream)
+    else memcpy(h.data(), src, (size_t)A * 4);
+    for (int a = 0; a < A; ++a)
+        if (h[a] < lo || h[a] >= A)
+            return fail(e, CA_ERANGE, "%s: arena %d takes arena %d, outside [%d, n_arenas=%d)", who, a, h[a], lo, A);
+    return CA_OK;
+}
+// per-arena counts: an arena takes the state of an arena of the same size only (from: the counts the source set was saved under)
+static int fork_counts_match(ca_env* e, const char* who, const std::vector<int>& h, const std::vector<int>& from, bool keep_self) {
+    if (!e->ac && from.empty()) return CA_OK;
+    if (e->ac != !from.empty())
+        return fail(e, CA_EINVAL, "%s: the snapshot was saved %s per-arena agent counts and the handle now runs %s them", who,
+                    from.empty() ? "without" : "with", e->ac ? "with" : "without");
+    for (int a = 0; a < (int)h.size(); ++a) {
+        if (h[a] < 0 || (keep_self && h[a] == a)) continue;
+        if (from[h[a]] != e->h_counts[a])
+            return fail(e, CA_EINVAL, "%s: arena %d holds %d agents and would take arena %d, which holds %d (ca_set_agent_counts: an arena "
+                        "takes the state of an arena of its own size)", who, a, e->h_counts[a], h[a], from[h[a]]);
+    }
+    return CA_OK;
+}
+static int fork_flags(ca_env* e, const char* who, uint32_t flags) {
+    if (flags & ~(CA_F_OBS | CA_F_CONTACT)) return fail(e, CA_EINVAL, "%s: flags=0x%x: CA_F_OBS and CA_F_CONTACT only", who, flags);
+    return CA_OK;
+}
+// the state has been written from outside the step kernels: the observation's frame is re-derived, the seeded scan sanitises the lists
+static int fork_after(ca_env* e, uint32_t flags) {
+    e->orient_valid = false;
+    e->lists_trusted = false;
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+static int fork_upload_index(ca_env* e, const std::vector<int>& h) {
+    if (!e->fork_idx) HIPCHK(e, hipMalloc((void**)&e->fork_idx, h.size() * 4));
+    HIPCHK(e, upload(e, e->fork_idx, h.data(), h.size() * 4));
+    return CA_OK;
+}
+
+extern "C" {
+
+int ca_arena_gather(ca_env* e, const int32_t* src, size_t bytes, int32_t src_is_device, uint32_t flags) {
+    if (!e) return CA_EINVAL;
+    if (!src) return fail(e, CA_EINVAL, "ca_arena_gather: null argument");
+    { const int rc = fork_flags(e, "ca_arena_gather", flags); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<int> h;
+    { const int rc = fork_index(e, "ca_arena_gather", src, bytes, src_is_device, 0, h); if (rc) return rc; }
+    { const int rc = fork_counts_match(e, "ca_arena_gather", h, e->h_counts, true); if (rc) return rc; }
+    { const int rc = state_set_reserve(e, e->fork_scratch, "ca_arena_gather"); if (rc) return rc; }
+    { const int rc = fork_upload_index(e, h); if (rc) return rc; }
+    HIPCHK(e, launch_fork(e, e->fork_scratch, true, nullptr, false));
+    HIPCHK(e, launch_fork(e, e->fork_scratch, false, e->fork_idx, true));
+    return fork_after(e, flags);
+}
+
+int ca_snapshot_create(ca_env* e, ca_snapshot** out) {
+    if (!e) return CA_EINVAL;
+    if (!out) return fail(e, CA_EINVAL, "ca_snapshot_create: null argument");
+    HIPCHK(e, hipSetDevice(e->device));
+    ca_snapshot* sn = new ca_snapshot();
+    sn->owner = e;
+    const int rc = state_set_reserve(e, sn->set, "ca_snapshot_create");
+    if (rc) {
+        if (sn->set.base) hipFree(sn->set.base);
+        if (sn->set.alan) hipFree(sn->set.alan);
+        delete sn;
+        return rc;
+    }
+    e->snapshots.push_back(sn);
+    *out = sn;
+    return CA_OK;
+}
+
+static int snapshot_of(ca_env* e, const char* who, const ca_snapshot* sn) {
+    if (!sn) return fail(e, CA_EINVAL, "%s: null argument", who);
+    if (std::find(e->snapshots.begin(), e->snapshots.end(), sn) == e->snapshots.end())
+        return fail(e, CA_EINVAL, "%s: the snapshot is not one of this handle's (a snapshot belongs to the handle it was created on)", who);
+    return CA_OK;
+}
+
+int ca_snapshot_save(ca_env* e, ca_snapshot* sn) {
+    if (!e) return CA_EINVAL;
+    { const int rc = snapshot_of(e, "ca_snapshot_save", sn); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rc = state_set_reserve(e, sn->set, "ca_snapshot_save"); if (rc) return rc; }
+    HIPCHK(e, launch_fork(e, sn->set, true, nullptr, false));
+    sn->saved = true;
+    sn->n_actions = e->n_actions;
+    sn->counts = e->ac ? e->h_counts : std::vector<int>();
+    return CA_OK;
+}
+
+int ca_snapshot_load(ca_env* e, const ca_snapshot* sn, const int32_t* src, size_t bytes, int32_t src_is_device, uint32_t flags) {
+    if (!e) return CA_EINVAL;
+    { const int rc = snapshot_of(e, "ca_snapshot_load", sn); if (rc) return rc; }
+    { const int rc = fork_flags(e, "ca_snapshot_load", flags); if (rc) return rc; }
+    if (!sn->saved) return fail(e, CA_EINVAL, "ca_snapshot_load: nothing has been saved into the snapshot (ca_snapshot_save)");
+    if (sn->n_actions != e->n_actions)
+        return fail(e, CA_EINVAL, "ca_snapshot_load: the snapshot was saved with n_actions=%d and the handle now has n_actions=%d (ca_alan_configure* "
+                    "changed the shape of the bandit's state)", sn->n_actions, e->n_actions);
+    HIPCHK(e, hipSetDevice(e->device));
+    std::vector<int> h;
+    if (src) {
+        const int rc = fork_index(e, "ca_snapshot_load", src, bytes, src_is_device, -1, h);
+        if (rc) return rc;
+    } else {
+        h.resize(e->cfg.n_arenas);
+        for (int a = 0; a < e->cfg.n_arenas; ++a) h[a] = a;
+    }
+    { const int rc = fork_counts_match(e, "ca_snapshot_load", h, sn->counts, false); if (rc) return rc; }
+    if (src) { const int rc = fork_upload_index(e, h); if (rc) return rc; }
+    HIPCHK(e, launch_fork(e, sn->set, false, src ? e->fork_idx : nullptr, false));
+    return fork_after(e, flags);
+}
+
+int ca_snapshot_destroy(ca_env* e, ca_snapshot* sn) {
+    if (!e) return CA_EINVAL;
+    { const int rc = snapshot_of(e, "ca_snapshot_destroy", sn); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // a save or a load may still be in flight
+    if (sn->set.base) hipFree(sn->set.base);
+    if (sn->set.alan) hipFree(sn->set.alan);
+    e->snapshots.erase(std::find(e->snapshots.begin(), e->snapshots.end(), sn));
+    delete sn;
+    return CA_OK;
+}
+
+// (diagnostic for tools/fork_cost.py: the bytes of ONE arena that the plane descriptors move, i.e. what a save reads and writes once each)
+int ca_fork_bytes_per_arena(ca_env* e, size_t* out) {
+    if (!e || !out) return fail(e, CA_EINVAL, "ca_fork_bytes_per_arena: null argument");
+    StatePlane pl[FORK_MAX_PLANES];
+    const int n = state_planes(e, pl);
+    size_t b = 0;
+    for (int k = 0; k < n; ++k) b += (size_t)pl[k].esize * pl[k].n * pl[k].rows;
+    *out = b;
     return CA_OK;
 }
 

@@ -32,7 +32,7 @@
 // reward, done test, goals, resets, the wall test and the pair count's shortcut, ALAN's draw and update), ca_step.h (lane solve +
 // reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
 // ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout),
-// ca_contact.h (the per-agent contact report).
+// ca_contact.h (the per-agent contact report), ca_fork.h (the arena copy behind ca_arena_gather / ca_snapshot_*).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -43,6 +43,7 @@
 #include "ca_obs.h"
 #include "ca_trace.h"
 #include "ca_contact.h"
+#include "ca_fork.h"
 
 namespace ca {
 

@@ -67,6 +67,47 @@ def trace_shape(steps, every, channels, A, N):
     return (R, Cn, int(A), int(N)), (R, 3, int(A))
 
 
+def fork_index(src, A, allow_keep=False):
+    """The index array of fork() / restore() as the library takes it, without a device: contiguous int32 [A], entry a = the arena
+    that arena a takes.  Raises ValueError for what the library would refuse: a length other than A, a dtype that is not an
+    integer one (bools included), an entry outside 0 .. A-1 -- with allow_keep (restore): outside -1 .. A-1, where -1 keeps the
+    arena.  A torch tensor is judged by its own dtype and shape and comes back as a host array."""
+    A = int(A)
+    if torch is not None and isinstance(src, torch.Tensor):
+        if src.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError("fork_index: src must hold integers, got dtype %s" % (src.dtype,))
+        src = src.detach().cpu().numpy()
+    a = np.asarray(src)
+    if a.dtype.kind not in "iu":
+        raise ValueError("fork_index: src must hold integers, got dtype %s" % (a.dtype,))
+    if a.shape != (A,):
+        raise ValueError("fork_index: src must be an [A] array (A=%d), got shape %s" % (A, a.shape))
+    lo = -1 if allow_keep else 0
+    bad = np.flatnonzero((a.astype(np.int64) < lo) | (a.astype(np.int64) >= A)) if a.dtype != np.uint64 else np.flatnonzero(a >= np.uint64(A))
+    if len(bad):
+        raise ValueError("fork_index: arena %d takes arena %d, outside [%d, %d)" % (bad[0], int(a[bad[0]]), lo, A))
+    return np.ascontiguousarray(a, np.int32)
+
+
+class Snapshot:
+    """A second set of the state buffers on the environment's device (ca_snapshot_*): made and filled by
+    VecCollisionAvoidanceEnv.snapshot(), read by restore().  close() destroys it; the environment's close() invalidates every
+    snapshot it still has."""
+
+    def __init__(self, env, handle):
+        self._env, self._h = env, handle
+
+    @property
+    def closed(self):
+        return self._h is None or self._env.h is None or self not in self._env.__dict__.get("_snapshots", ())
+
+    def close(self):
+        if not self.closed:
+            self._env._snapshots.remove(self)
+            self._env._call("ca_snapshot_destroy", self._env.h, self._h)
+        self._h = None
+
+
 class VecCollisionAvoidanceEnv:
     """A arenas x N agents advanced per call.
 
@@ -215,6 +256,8 @@ class VecCollisionAvoidanceEnv:
                 arr.flags.writeable = False
             except Exception:
                 pass
+        for snap in self.__dict__.pop("_snapshots", []):     # ca_destroy frees them
+            snap._h = None
         if getattr(self, "h", None):
             self.L.ca_destroy(self.h)
             self.h = None
@@ -322,7 +365,9 @@ class VecCollisionAvoidanceEnv:
         """Everything the next step depends on, as a dict of host arrays: simulator state, targets, the neighbour lists of
         the last doStep (the observation of a reset reads them, env.py:461-488), the counters that key the random draws
         (episode, re-goal count, step count), the last rewards (an arena frozen by CA_F_FREEZE keeps them) and, after alan_configure,
-        the bandit's weights, times and last actions.  The reference never
+        the bandit's weights, times and last actions.  This is the HOST checkpoint (portable, a dict of numpy arrays);
+        fork() / snapshot() / restore() move the same fields between arenas or into a second set of buffers on the device,
+        without the round trip.  The reference never
         serialises its environment (checkpoints exist at the trainer's level only); with counter-based
         draws a restored environment continues bit for bit.  Statistics counters are not part of the state."""
         st = {name: self.get(getattr(_lib, "FLD_" + name)) for name in self._STATE_FIELDS}
@@ -335,7 +380,8 @@ class VecCollisionAvoidanceEnv:
 
     def set_state(self, st):
         """Restore a get_state() dict into an environment of the same shape and configuration (seed included: it keys the
-        draws); the obstacle tables and the ALAN action set are configuration, not state."""
+        draws); the obstacle tables and the ALAN action set are configuration, not state.  The device counterpart, between
+        arenas of one environment: fork() / snapshot() / restore()."""
         shape = [int(v) for v in np.asarray(st["_shape"]).reshape(-1)]
         if shape != [self.A, self.N, self.K, self.S, self.n_actions]:
             raise ValueError("set_state: the state is of an environment of shape %s, this one is %s"
@@ -353,6 +399,66 @@ class VecCollisionAvoidanceEnv:
             self.set(_lib.FLD_ALAN_TIMES, st["ALAN_TIMES"])
             if "ALAN_ACTION" in st:
                 self.set(_lib.FLD_ALAN_ACTION, st["ALAN_ACTION"])
+
+    # ---- fork / rewind on the device (ca_arena_gather, ca_snapshot_*) --------------------------------
+    def _fork_src(self, src, allow_keep):
+        """(pointer, is_device, keep-alive) of an index array: a device integer tensor goes by pointer, as int32 on this GPU (the
+        library copies it back for its checks), everything else through fork_index on the host."""
+        if torch is not None and isinstance(src, torch.Tensor) and src.is_cuda:
+            if src.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or tuple(src.shape) != (self.A,):
+                raise ValueError("fork: a device src must be an integer tensor of shape [A] (A=%d), got %s %s"
+                                 % (self.A, src.dtype, tuple(src.shape)))
+            if src.dtype == torch.int64:      # (narrowed on the device: out of range stays out of range for the library's check)
+                src = src.clamp(-2 ** 31, 2 ** 31 - 1)
+            t, _ = self._on_device(src, torch.int32)
+            return C.c_void_p(t.data_ptr()), 1, t
+        a = fork_index(src, self.A, allow_keep)
+        return _ptr(a), 0, a
+
+    def fork(self, src, obs=False, contacts=False):
+        """Arena a becomes a copy of arena src[a] as it was before the call, on the device (ca_arena_gather): src is a list, an
+        array or a torch int tensor of A entries in 0 .. A-1 (a device tensor is passed by pointer); src[a] == a leaves
+        arena a alone.  What moves is exactly what get_state() lists (get_state / set_state remain the host checkpoint);
+        obstacles, per-agent parameters, counts and sensing, ALAN action sets, statistics and the random streams' identity stay with
+        the slot, so copies of one arena share a past and draw futures of their own.  With a world per arena the written arenas'
+        obstacle lists are emptied, with per-agent sensing their agent lists (the next step rebuilds them).  obs=True: returns the
+        observation of the new state as observe() does; contacts=True: also leaves the contact report (last_contacts())."""
+        ptr, on_dev, keep = self._fork_src(src, False)
+        flags = (_lib.F_OBS if obs else 0) | (_lib.F_CONTACT if contacts else 0)
+        self._call("ca_arena_gather", self.h, ptr, self.A * 4, on_dev, flags)
+        return self._obs_out() if obs else None
+
+    def snapshot(self, into=None):
+        """Save the state of every arena into a Snapshot on the device (ca_snapshot_save: one launch, asynchronous) and return it.
+        into: a Snapshot of this environment to overwrite instead of making a new one."""
+        if into is None:
+            h = C.c_void_p()
+            self._call("ca_snapshot_create", self.h, C.byref(h))
+            into = Snapshot(self, h)
+            self.__dict__.setdefault("_snapshots", []).append(into)
+        elif not isinstance(into, Snapshot) or into._env is not self or into.closed:
+            raise ValueError("snapshot: into= must be an open Snapshot of this environment")
+        self._call("ca_snapshot_save", self.h, into._h)
+        return into
+
+    def restore(self, snap, src=None, obs=False, contacts=False):
+        """Arena a becomes arena src[a] of the snapshot (ca_snapshot_load); an entry of -1 keeps arena a as it is; src=None: every
+        arena returns to its own saved state.  The rules, obs= and contacts= are fork()'s.  The host counterpart is set_state()."""
+        if not isinstance(snap, Snapshot) or snap.closed:
+            raise ValueError("restore: snap must be an open Snapshot (closed by its close() or by the environment's)")
+        flags = (_lib.F_OBS if obs else 0) | (_lib.F_CONTACT if contacts else 0)
+        if src is None:
+            self._call("ca_snapshot_load", self.h, snap._h, None, 0, 0, flags)
+        else:
+            ptr, on_dev, keep = self._fork_src(src, True)
+            self._call("ca_snapshot_load", self.h, snap._h, ptr, self.A * 4, on_dev, flags)
+        return self._obs_out() if obs else None
+
+    def fork_bytes_per_arena(self):
+        """Bytes of one arena in the planes that fork() / snapshot() / restore() move (ca_fork_bytes_per_arena)."""
+        n = C.c_size_t()
+        self._call("ca_fork_bytes_per_arena", self.h, C.byref(n))
+        return int(n.value)
 
     def field_tensor(self, field):
         """Zero-copy torch view of a state field's device buffer (valid until close(); kernels of this handle run on

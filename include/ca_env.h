@@ -449,6 +449,59 @@ int ca_contacts(ca_env* env);
 int ca_get_contacts(ca_env* env, int32_t* agents, int32_t* wall, int32_t* nearest, float* nearest_d2, float* wall_d2, size_t bytes_each,
                     int32_t dst_is_device);
 int ca_contacts_ptr(ca_env* env, void** dev_ptr, size_t* bytes);
+/* Forking and rewinding arenas on the device: what planning by sampling (copy the real arena into every other slot, roll each copy
+ * out under its own actions with ca_rollout / ca_step, pick, rewind), population-based training (overwrite the worst arenas with
+ * the best) and curricula (return to a stored situation) need, without the host round trip of ca_get / ca_set per field.  The
+ * reference never copies a simulator; its counterpart is rebuilding one from stored positions (env.py:461-488).
+ * State that moves (CA_FLD_*): POS_X POS_Y VEL_X VEL_Y PREF_X PREF_Y GOAL_X GOAL_Y GOAL2_X GOAL2_Y REWARD AGENT_DONE ARRIVE_STEP
+ *   REGOAL_COUNT NB_COUNT OBST_COUNT NB_IDX OBST_IDX STEP_COUNT ARENA_DONE EPISODE; after ca_alan_configure*: ALAN_WEIGHTS ALAN_TIMES
+ *   ALAN_ACTION.
+ * What stays with the slot: configuration (obstacle tables, ca_set_agent_params / _counts / _sensing values, ALAN action sets, the
+ * edge grid), statistics (CA_FLD_ARENA_STATS, the per-arena step counts, ca_stats), the contact report, the observation buffer
+ * (unless CA_F_OBS is given), and the identity that keys the random streams: seed and arena_offset + a.  The last is the intended
+ * meaning: copies of one arena share a past and draw futures of their own -- spawn positions, re-goals and ALAN draws after the
+ * call are those of the destination's arena id.
+ * ca_arena_gather: arena a := arena src[a] as it was BEFORE the call, for every a, however src overlaps (a permutation, a broadcast).
+ *   src: i32 [A], host or device, each in 0 .. n_arenas-1; src[a] == a leaves arena a alone: it is not written at all.
+ * ca_snapshot_create: a second set of the state buffers on the handle's device, owned by the handle; it holds no state yet.
+ * ca_snapshot_save: snap := the state of every arena, asynchronously on the handle's stream (one launch); may be repeated, the
+ *   last save counts.  ca_snapshot_load: arena a := arena src[a] OF THE SNAPSHOT; src[a] == -1 leaves arena a as it is (not
+ *   written); src == NULL (bytes ignored): every arena a := snapshot arena a.  ca_snapshot_destroy frees one (drains the stream);
+ *   ca_destroy frees those still alive.
+ * Rules
+ *   - In place, and pointers stay: ca_field_ptr's buffers do not move.  The gather copies through a scratch set of the state buffers
+ *     that the handle owns (allocated on first use, freed by ca_destroy): one launch saves into it, one loads from it with src.  A
+ *     save or a load is one launch of the same kernel.  ca_profile counts these launches under kind 3.
+ *   - The observation's frame is re-derived from the moved positions and goals at the next observation, and the moved neighbour
+ *     lists are treated like lists written through ca_set: the seeded scan sanitises them on the next step.  Results are the bits a
+ *     handle brought to the same state through ca_set computes.
+ *   - flags: CA_F_OBS -- one observation launch behind the move, for the state the call leaves, as ca_reset(..., CA_F_OBS) does;
+ *     CA_F_CONTACT -- the contact launch likewise.  Any other bit -> CA_EINVAL.
+ *   - A world per arena (ca_set_obstacles_per_arena): obstacle-neighbour ids are local to a table, so the obstacle-neighbour count of
+ *     every row of every arena that was WRITTEN reads 0 afterwards (a fresh simulator has empty lists; the next solve rebuilds
+ *     them).  With one common table the lists move intact.
+ *   - Per-agent sensing (ca_set_agent_sensing): the agent-neighbour count of every row of a written arena reads 0, as after that call
+ *     itself (a copied list may be longer than its new owner's max_neighbors).
+ *   - Per-arena counts (ca_set_agent_counts): only rows i < counts[a] are written, an absent row keeps what the caller put there.
+ *     An arena takes the state of an arena of its own size only: counts[src[a]] != counts[a] -- for a load: the counts saved with
+ *     the snapshot -- -> CA_EINVAL (ca_last_error names the arena and both counts).
+ *   - Checks, all before anything is launched (a failure leaves the handle as it was): bytes != A*4 -> CA_ESIZE; an index outside
+ *     0 .. n_arenas-1 (load: -1 .. n_arenas-1) -> CA_ERANGE (the message names the arena and the value); a snapshot of another
+ *     handle, one with nothing saved, or one saved under another ALAN shape (n_actions changed since) -> CA_EINVAL; a NULL handle ->
+ *     CA_EINVAL.  The index array is read before the call returns: a device src is copied back for the check, as
+ *     ca_set_agent_params does with its arrays, which drains the stream (so does the upload of a host src).
+ *   - These calls advance nothing, so like ca_get they do not report the sticky obstacle-overflow status.
+ *   - Every kind of handle takes them: one-, two- and four-lanes kernels, wide lists, per-agent parameters, counts and sensing, tiled
+ *     handles of every create flag (16-bit ids; the sort buffers and the launches' scratch are no state and do not move). */
+typedef struct ca_snapshot ca_snapshot;
+int ca_arena_gather(ca_env* env, const int32_t* src, size_t bytes, int32_t src_is_device, uint32_t flags);
+int ca_snapshot_create(ca_env* env, ca_snapshot** out);
+int ca_snapshot_save(ca_env* env, ca_snapshot* snap);
+int ca_snapshot_load(ca_env* env, const ca_snapshot* snap, const int32_t* src, size_t bytes, int32_t src_is_device, uint32_t flags);
+int ca_snapshot_destroy(ca_env* env, ca_snapshot* snap);
+/* Diagnostic (tools/fork_cost.py): *bytes = the bytes of ONE arena in the planes listed above, as the copy kernel's descriptors
+ * state them; a save reads and writes each of them once. */
+int ca_fork_bytes_per_arena(ca_env* env, size_t* bytes);
 /* `steps` consecutive ca_orca_step calls without returning to the host (with CA_F_FREEZE: every
  * arena runs to the end of its own episode, at most `steps` steps): the reference's ORCA-only loops, env.py:570-573
  * (`while True: orca_step()`) and ALAN:106-123 (run_sim).  One kernel launch per 256 steps where the handle uses
@@ -571,7 +624,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
