@@ -39,7 +39,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_contacts", "ca_get_contacts", "ca_contacts_ptr",
            "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info",
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
-           "ca_fork_bytes_per_arena")
+           "ca_fork_bytes_per_arena", "ca_rollout_actions")
 
 
 class Config(C.Structure):
@@ -70,6 +70,13 @@ class Trace(C.Structure):
     """struct ca_trace (include/ca_env.h): the caller's buffers of a recording rollout."""
     _fields_ = [("agents", C.c_void_p), ("agents_bytes", C.c_size_t), ("arenas", C.c_void_p), ("arenas_bytes", C.c_size_t),
                 ("every", C.c_int32), ("channels", C.c_uint32)]
+
+
+class ActionSeq(C.Structure):
+    """struct ca_action_seq (include/ca_env.h): the caller's buffers of an action-sequence rollout."""
+    _fields_ = [("actions", C.c_void_p), ("actions_bytes", C.c_size_t), ("hold", C.c_int32),
+                ("weights", C.c_void_p), ("weights_bytes", C.c_size_t), ("returns", C.c_void_p), ("returns_bytes", C.c_size_t),
+                ("first_done", C.c_void_p), ("first_done_bytes", C.c_size_t)]
 
 
 class EdgeGridDesc(C.Structure):
@@ -137,6 +144,7 @@ def load():
     L.ca_alan_rollout.argtypes = [vp, i32, u32]
     L.ca_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
     L.ca_alan_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
+    L.ca_rollout_actions.argtypes = [vp, i32, u32, C.POINTER(ActionSeq)]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]

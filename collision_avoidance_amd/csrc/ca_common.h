@@ -31,6 +31,10 @@ struct AgentSensing;
 // ca_alan_rollout_trace): inside the T-step loop the selected planes of the state and the arena's three words go to the caller's
 // trace buffer whenever the rollout's step count reaches a multiple of `every` (TraceDev below).
 struct Trace;
+// Tag of the four-lanes kernel's action-sequence instantiations (quad_kernel<KMAX, BS, SQ, false, ActionSeq>: ca_rollout_actions): the
+// T-step loop runs WITH actions -- each step reads its own element of the caller's [R, A, N] tensor, the agent's weighted return
+// stays in a register and goes to the caller's buffers once per launch (ActSeqDev below).
+struct ActionSeq;
 // Tag of the one-wave solve kernels whose agent scan starts from last step's neighbour list and skips, wave-wide, the candidates no
 // lane can take (step_kernel<KMAX, 64, ST, SMX, ALAN, [AlanArenaSets | ArenaCounts,] SeededScan>; ca_nbr.h, CA_NBR_SEED).  It stands
 // last in the pack: the plain register-line and line-table kernels, their ALAN forms (with one action set or one per arena) and the
@@ -70,6 +74,7 @@ struct Line {
 // constants -- sits in a per-handle block in device memory (StepCold, written once by ca_create) and is loaded, as
 // scalar loads, where the epilogue begins.
 struct TraceDev;   // (below)
+struct ActSeqDev;  // (below)
 struct StepCold {
     float *pos_x, *pos_y, *vel_x, *vel_y, *pref_x, *pref_y;
     double *goal_x, *goal_y;        // targets stay fp64 like the reference's Python floats
@@ -102,6 +107,9 @@ struct StepCold {
     // the AgentSensing instantiations only.  Last members again.
     const float* as_neighbor_dist;
     const unsigned char* as_max_neighbors;
+    // the action-sequence block of the handle (ca_rollout_actions): read by the ActionSeq instantiations of the four-lanes kernel
+    // only.  Last member again.
+    const ActSeqDev* actseq;
 };
 
 // The trace of a recording rollout (include/ca_env.h ca_trace), as the Trace instantiations of the four-lanes kernel read it: a
@@ -119,6 +127,23 @@ struct TraceDev {
     int every;
     int next;           // the record the next store of this launch fills: (steps the rollout did before the launch) / every
     int countdown;      // steps of this launch until that store: every - (steps before the launch) % every
+};
+
+// The action sequence of ca_rollout_actions (include/ca_env.h ca_action_seq), as the ActionSeq instantiations of the four-lanes
+// kernel read it (the per-step form takes its arguments by value: ca_actseq.h): a block of the handle's in device memory behind
+// StepCold::actseq, rewritten on the stream in front of every such launch (actseq_setup_kernel).  Step t of the call is driven by
+// row t / hold; a launch that follows t0 steps starts at row t0 / hold with hold - t0 % hold steps of it left, so a launch
+// boundary may fall in the middle of a hold.  returns and first_done carry the running values from launch to launch.
+struct ActSeqDev {
+    const float* actions;   // [R][A*N]
+    const float* weights;   // [steps], or null: 1 for every step
+    float* returns;         // [A*N] running weighted return, or null: not wanted
+    int* first_done;        // [A] the first step of the call that left arena_done set, -1 so far (the handle's own array if the caller gave none)
+    unsigned an;            // A * N: the stride of a row
+    int hold;
+    int t0;                 // steps of the call in front of this launch
+    int row;                // t0 / hold
+    int countdown;          // hold - t0 % hold: steps until the next row
 };
 
 // ALAN online learning inside the four-lanes kernel (ca_quad.h): the bandit's arguments, in device memory like StepCold

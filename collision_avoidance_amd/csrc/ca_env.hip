@@ -95,6 +95,9 @@ struct ca_env {
     StepCold* d_cold = nullptr;      // the epilogue's arguments (ca_common.h)
     TraceDev* d_trace = nullptr;     // the trace block behind StepCold::trace, rewritten in front of every Trace launch of the four-lanes kernel
     bool trace_on = false;           // ca_rollout_trace / ca_alan_rollout_trace: the T-step launch in flight is a Trace instantiation
+    ActSeqDev* d_actseq = nullptr;   // the action-sequence block behind StepCold::actseq, rewritten in front of every ActionSeq launch of the four-lanes kernel
+    bool actseq_on = false;          // ca_rollout_actions: the launch in flight is an ActionSeq instantiation
+    int* actseq_words = nullptr;     // [2][A] first_done of a caller that gave none | frozen at entry (the per-step form); allocated on first use
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -335,6 +338,7 @@ static void fill_cold(const ca_env* e, StepCold& c) {
     c.ap_time_horizon = e->ap ? e->d_ap[2] : nullptr; c.ap_time_horizon_obst = e->ap ? e->d_ap[3] : nullptr;
     c.agent_counts = e->ac ? e->d_counts : nullptr;
     c.trace = e->d_trace;
+    c.actseq = e->d_actseq;
     c.as_neighbor_dist = e->sens ? e->d_as_nd : nullptr; c.as_max_neighbors = e->sens ? e->d_as_k : nullptr;
 }
 
@@ -502,13 +506,15 @@ static const void* tiled_close_fn(const ca_env* e) {
 }
 // alan: the ALAN bandit runs inside the launch (ca_alan_step, ca_alan_rollout); rollout: the launch advances a.T > 1 steps;
 // trace: ... and records them (the Trace instantiations of the four-lanes kernel: the ORCA-only rollout and the fused ALAN rollout with
-// one action set; the callers ask for nothing else)
-static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout, bool trace = false) {
+// one action set; the callers ask for nothing else); actseq: ... under the caller's action tensor (the ActionSeq instantiations, without
+// ALAN: ca_rollout_actions asks for them on the handles whose rollout is this kernel, with rollout = true whatever a.T is)
+static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout, bool trace = false, bool actseq = false) {
     if (e->tiled)   // (the solve launch of a step's sequence; no ALAN and no rollout form)
         return {tiled_solve_fn(e, e->egrid), dim3(e->grid), dim3(e->TILE), e->lds};
     const bool per = alan && e->alan_per;   // (an action set per arena: the AlanArenaSets instantiations)
     if (e->quad || (rollout && e->quad_roll) || (alan && !e->alan_lane)) {   // four lanes per agent (ca_quad.h)
-        const void* f = trace ? (alan ? quad_fn_for<true, Trace>(e) : quad_fn_for<false, Trace>(e))
+        const void* f = actseq ? quad_fn_for<false, ActionSeq>(e)
+                      : trace ? (alan ? quad_fn_for<true, Trace>(e) : quad_fn_for<false, Trace>(e))
                               : (per ? quad_fn_for<true, AlanArenaSets>(e) : (alan ? quad_fn_for<true>(e) : quad_fn_for<false>(e)));
         return {f, dim3(e->grid_q), dim3(e->BSq), alan ? quad_lds_bytes(e->BSq, e->KT, e->SQ, e->n_actions) : e->lds_q};
     }
@@ -524,7 +530,7 @@ static hipError_t allow_lds(const SolveLaunch& s) {
 }
 // neighbour search + lines + LP + integration + reward/done (+ the ALAN bandit), a.T steps
 static hipError_t launch_step(ca_env* e, const StepArgs& a) {
-    const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1, e->trace_on && a.T > 1);
+    const SolveLaunch s = solve_launch(e, a.alan != nullptr, a.T > 1 || e->actseq_on, e->trace_on && a.T > 1, e->actseq_on);
     if (!(a.flags & CA_F_FREEZE)) e->lists_trusted = true;   // every arena's lists are this launch's now (frozen arenas keep theirs)
     if (e->tiled) {   // [bin -> scan -> scatter ->] solve -> advance -> close: the kernel boundaries on the stream are the arena-wide barriers (ca_tiled.h)
         // one block for every launch but one: a kernel reads the base of TiledEdgeArgs that it declares (fields a handle does not have stay null / zero)
@@ -1119,6 +1125,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         if (r == hipSuccess) *e->ovf_host = 0ull;
     }
     if (r == hipSuccess) r = dalloc(e, &e->d_trace, (size_t)1);
+    if (r == hipSuccess) r = dalloc(e, &e->d_actseq, (size_t)1);
     if (r == hipSuccess) r = hipMalloc((void**)&e->d_cold, sizeof(StepCold));
     if (r == hipSuccess) {
         StepCold hc;
@@ -1148,7 +1155,7 @@ int ca_destroy(ca_env* e) {
     void* bufs[] = {e->pos_x, e->pos_y, e->vel_x, e->vel_y, e->pref_x, e->pref_y, e->goal_x, e->goal_y,
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
-                    e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_order,
+                    e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -2651,6 +2658,109 @@ int ca_alan_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_tra
         if (rc) return rc;
         if ((s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
     }
+    return CA_OK;
+}
+
+// ---- action-sequence rollouts (include/ca_env.h ca_action_seq) --------------------------------------------------------------
+struct ActSeqPlan { int* first_done; int* entry_frozen; };
+// every refusal of the call, before anything is launched
+static int actseq_check(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
+    const char* who = "ca_rollout_actions";
+    if (!seq || !seq->actions) return fail(e, CA_EINVAL, "%s: the sequence or its actions buffer is null", who);
+    if (steps < 0) return fail(e, CA_EINVAL, "%s: steps=%d", who, steps);
+    if (seq->hold < 1) return fail(e, CA_EINVAL, "%s: hold=%d, must be at least 1", who, seq->hold);
+    if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "%s: CA_F_NODONE applies to ca_orca_step only", who);
+    if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE | CA_F_CONTACT))
+        return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
+    const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold, A = (size_t)e->cfg.n_arenas;
+    if (seq->actions_bytes < R * AN(e) * 4)
+        return fail(e, CA_ESIZE, "%s: the actions buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d], R = ceil(steps / hold)), got %zu", who,
+                    R * AN(e) * 4, R, e->cfg.n_arenas, e->cfg.n_agents, seq->actions_bytes);
+    if (seq->weights && seq->weights_bytes < (size_t)steps * 4)
+        return fail(e, CA_ESIZE, "%s: the weights buffer needs %zu bytes (f32 [steps=%d]), got %zu", who, (size_t)steps * 4, steps, seq->weights_bytes);
+    if (seq->returns && seq->returns_bytes < AN(e) * 4)
+        return fail(e, CA_ESIZE, "%s: the returns buffer needs %zu bytes (f32 [A=%d, N=%d]), got %zu", who, AN(e) * 4, e->cfg.n_arenas,
+                    e->cfg.n_agents, seq->returns_bytes);
+    if (seq->first_done && seq->first_done_bytes < A * 4)
+        return fail(e, CA_ESIZE, "%s: the first_done buffer needs %zu bytes (i32 [A=%d]), got %zu", who, A * 4, e->cfg.n_arenas, seq->first_done_bytes);
+    return CA_OK;
+}
+// in front of the first step: zeros, -1, the arenas frozen at entry (kind 3 for ca_profile, like the record kernel)
+static hipError_t launch_actseq_begin(ca_env* e, const ca_action_seq* seq, const ActSeqPlan& pl, uint32_t flags) {
+    ActSeqBeginArgs b;
+    b.arena_done = e->arena_done; b.returns = seq->returns; b.first_done = pl.first_done; b.entry_frozen = pl.entry_frozen;
+    b.an = (unsigned)AN(e); b.A = e->cfg.n_arenas; b.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    const unsigned n = b.an > (unsigned)b.A ? b.an : (unsigned)b.A;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, actseq_begin_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, b);
+    return hipGetLastError();
+}
+// behind the launches of step t of the per-step form
+static hipError_t launch_actseq_accumulate(ca_env* e, const ca_action_seq* seq, const ActSeqPlan& pl, uint32_t flags, int t) {
+    ActSeqAccArgs c;
+    c.reward = e->reward; c.arena_done = e->arena_done; c.entry_frozen = pl.entry_frozen;
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.weight = seq->weights ? seq->weights + t : nullptr;
+    c.returns = seq->returns; c.first_done = pl.first_done;
+    c.an = (unsigned)AN(e); c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents; c.t = t; c.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, actseq_accumulate_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
+    return hipGetLastError();
+}
+// an ActionSeq launch of the four-lanes kernel that follows `done` steps of the call (a.T steps of it)
+static hipError_t launch_step_actseq(ca_env* e, const StepArgs& a, const ca_action_seq* seq, const ActSeqPlan& pl, int done) {
+    hipError_t r = allow_lds(solve_launch(e, false, true, false, true));
+    if (r != hipSuccess) return r;
+    ActSeqDev v;
+    v.actions = seq->actions; v.weights = seq->weights; v.returns = seq->returns; v.first_done = pl.first_done;
+    v.an = (unsigned)AN(e); v.hold = seq->hold; v.t0 = done; v.row = done / seq->hold; v.countdown = seq->hold - done % seq->hold;
+    {
+        ProfScope ps(e, KIND_RESET);
+        launch_k(ps, actseq_setup_kernel, dim3(1), dim3(64), 0, e->stream, e->d_actseq, v);
+    }
+    r = hipGetLastError();
+    if (r != hipSuccess) return r;
+    e->actseq_on = true;
+    r = launch_step(e, a);
+    e->actseq_on = false;
+    return r;
+}
+
+int ca_rollout_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
+    if (!e) return CA_EINVAL;
+    { const int rc = actseq_check(e, steps, flags, seq); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, "ca_rollout_actions"); if (rs) return rs; }
+    const size_t A = (size_t)e->cfg.n_arenas;
+    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
+    const bool one_launch = e->quad_roll;   // (ca_solver_info: rollout_one_launch; an ALAN-configured handle steps without the bandit here)
+    ActSeqPlan pl;
+    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
+    pl.entry_frozen = one_launch ? nullptr : e->actseq_words + A;
+    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, below)
+    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    HIPCHK(e, launch_actseq_begin(e, seq, pl, flags));
+    if (one_launch) {
+        // one launch per CA_ROLLOUT_MAX_T steps, as ca_rollout: the arena stays in registers / LDS, each step reads its own action
+        StepArgs a;
+        fill_args(e, a, seq->actions, sf);
+        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
+            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
+            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
+            HIPCHK(e, launch_step_actseq(e, a, seq, pl, done));
+            e->steps_done += (uint64_t)a.T;
+        }
+    } else {
+        const size_t an = AN(e);
+        for (int t = 0; t < steps; ++t) {   // the launches of ca_step with this step's row, the accumulate kernel behind them
+            const int rc = do_step(e, seq->actions + (size_t)(t / seq->hold) * an, sf);
+            if (rc) return rc;
+            HIPCHK(e, launch_actseq_accumulate(e, seq, pl, flags, t));
+        }
+    }
+    if (steps > 0) e->orient_valid = true;
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
     return CA_OK;
 }
 

@@ -32,7 +32,8 @@
 // reward, done test, goals, resets, the wall test and the pair count's shortcut, ALAN's draw and update), ca_step.h (lane solve +
 // reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
 // ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout),
-// ca_contact.h (the per-agent contact report), ca_fork.h (the arena copy behind ca_arena_gather / ca_snapshot_*).
+// ca_contact.h (the per-agent contact report), ca_fork.h (the arena copy behind ca_arena_gather / ca_snapshot_*),
+// ca_actseq.h (the small kernels of ca_rollout_actions and the rule of its return).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -44,6 +45,7 @@
 #include "ca_trace.h"
 #include "ca_contact.h"
 #include "ca_fork.h"
+#include "ca_actseq.h"
 
 namespace ca {
 

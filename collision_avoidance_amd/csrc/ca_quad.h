@@ -29,6 +29,7 @@
 // wave (CA_QUAD=0/1 forces it).
 #pragma once
 #include "ca_step.h"
+#include "ca_actseq.h"
 
 namespace ca {
 
@@ -176,6 +177,12 @@ __host__ __device__ inline size_t quad_lds_bytes(int BS, int KMAX, int SQ, int n
 // trace (ca_common.h TraceDev).  It stands at the very end of the step -- behind the in-kernel reset's update of pos, vel, steps,
 // adone and epi --, so a record is what ca_get would read had the launch ended there; a frozen arena's registers hold the state it
 // was loaded with, and are stored like any other.
+// ActionSeq in the pack (ca_rollout_actions; without ALAN): the T-step loop runs WITH actions.  Step t of the launch reads its own
+// element of the caller's tensor -- the row pointer is wave-uniform and moves on every `hold` steps, a countdown like the trace's --,
+// the reward stays in a register instead of going to memory every step, and the agent's weighted return (ca_actseq.h actseq_add) is
+// carried in another.  Once per launch the quad stores the return, the reward of the last step that advanced it, and the arena's owner
+// the first step that left arena_done set.  The running return, that first step and the cursor come from the handle's block
+// (ca_common.h ActSeqDev), so a rollout of more than 256 steps carries on across its launches.
 #ifndef CA_TRACE_STORE   // 0: lane q of a quad stores plane q (one store per wave and record, every lane busy); 1: lane 0 stores
 #define CA_TRACE_STORE 0 // the four planes; 2: as 0 with non-temporal stores.  tools/trace_cost.py measures them: DESIGN.md 7f
 #endif
@@ -183,6 +190,8 @@ template <int KMAX, int BS, int SQ, bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
     constexpr bool TR = has_tag<Trace, PER...>;
+    constexpr bool AS = has_tag<ActionSeq, PER...>;
+    static_assert(!AS || (!ALAN && !TR), "ca_step on an ALAN handle is the kernel without the bandit; a trace takes no actions");
     static_assert(POOL_SLOTS == 16, "a wave holds 16 quads: one line-table slot each");
     static_assert(SQ == 4 || SQ == 16, "obstacle lists of 4 or 16");
     static_assert(!CA_NBW16(BS / 4), "the quad kernel stores 8-bit agent-neighbour ids: at most 256 agent slots per workgroup "
@@ -266,7 +275,24 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
     int tr_next = 0, tr_cd = 0;
     if constexpr (TR) { const TraceK& td = *(TraceK*)c.trace; tr_next = td.next; tr_cd = td.countdown; }
 
-    const int T = p.actions ? 1 : (p.T > 0 ? p.T : 1);
+    // the action sequence's cursor: wave-uniform; the return so far, the first step that ended an episode, the last reward
+    const float* as_row = nullptr;
+    const float* as_w = nullptr;
+    int as_cd = 0, as_t0 = 0, as_fd = -1;
+    unsigned as_an = 0;
+    float as_ret = 0.0f, as_rew = 0.0f;
+    if constexpr (AS) {
+        const ActSeqK& ad = *(ActSeqK*)c.actseq;
+        as_an = ad.an; as_t0 = ad.t0; as_cd = ad.countdown;
+        as_row = ad.actions + (size_t)ad.row * as_an;
+        as_w = ad.weights != nullptr ? ad.weights + as_t0 : nullptr;
+        if (in_arena) {
+            as_fd = ad.first_done[a];
+            if (ad.returns != nullptr) as_ret = ad.returns[gq];
+        }
+    }
+
+    const int T = (!AS && p.actions) ? 1 : (p.T > 0 ? p.T : 1);
     for (int t = 0; t < T; ++t) {
         const bool frozen = (p.flags & 16u) != 0 && in_arena && adone != 0;  // CA_F_FREEZE: the episode of this arena is over
         const bool active = in_arena && !frozen;
@@ -281,7 +307,8 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
 #endif
         // ---- preferred velocity of this step (env.py:371-383) and the arena image ----
         V2 pf32 = mk(1.0f, 0.0f);
-        if (active && p.actions) action_pref(pos, gx, gy, p.actions[gq], pf32, pref);
+        if constexpr (AS) { if (active) action_pref(pos, gx, gy, as_row[gq], pf32, pref); }
+        else if (active && p.actions) action_pref(pos, gx, gy, p.actions[gq], pf32, pref);
         int act_id = 0;
         double dgx = 1.0, dgy = 0.0, dlx = 1.0, dly = 0.0;   // goal direction and rotated direction of this step (ALAN:588-595)
         if constexpr (ALAN) {
@@ -486,7 +513,8 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
         if (active) {
             if (p.actions) {
                 rew = step_reward(c.reward_scale, vel, pf32, pref);
-                if (q == 0) c.reward[gq] = rew;
+                if constexpr (AS) as_rew = rew;   // (stored once, behind the loop)
+                else if (q == 0) c.reward[gq] = rew;
             } else {
                 pref = goal_dir(pos, gx, gy);
             }
@@ -571,6 +599,13 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
             adone = all_done ? 1 : 0;
             if (do_reset) { steps = 0; epi += 1; }
         }
+        if constexpr (AS) {   // ---- the return of this step, the first episode end, the next step's row ----
+            if (active) {
+                as_ret = actseq_add(as_ret, as_w != nullptr ? as_w[t] : 1.0f, rew);
+                if (all_done && as_fd < 0) as_fd = as_t0 + t;
+            }
+            if (--as_cd == 0) { as_row += as_an; as_cd = ((ActSeqK*)c.actseq)->hold; }
+        }
         if constexpr (TR) {   // ---- record (ca_common.h TraceDev): the state as the launch would write it back here ----
             if (--tr_cd == 0) {
                 const TraceK& td = *(TraceK*)c.trace;   // (scalar loads, like the cold block)
@@ -619,6 +654,14 @@ __global__ __launch_bounds__(BS) void quad_kernel(const StepArgs p) {
                 al.reward[gq] = last_rew;
                 if (p.flags & 2u) atomicAdd(reinterpret_cast<double*>(&c.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), acc_rew);
             }
+        }
+    }
+    if constexpr (AS) {
+        const ActSeqK& ad = *(ActSeqK*)c.actseq;
+        if (in_arena && q == 0 && touched) {
+            c.reward[gq] = as_rew;
+            if (ad.returns != nullptr) ad.returns[gq] = as_ret;
+            if (i == 0) ad.first_done[a] = as_fd;
         }
     }
     if (in_arena && q == 0 && acc_frozen && i == 0) c.arena_stats[(size_t)a * ST_STRIDE + ST_FROZEN] += acc_frozen;

@@ -14,6 +14,7 @@ namespace ca {
 typedef const __attribute__((address_space(4))) StepCold ColdK;  // the cold block through the constant address space
 typedef const __attribute__((address_space(4))) AlanCold AlanK;
 typedef const __attribute__((address_space(4))) TraceDev TraceK;
+typedef const __attribute__((address_space(4))) ActSeqDev ActSeqK;
 
 // the unit vector pos -> goal of env.py:236 / 449 (pref_dir64), rounded to fp32
 __device__ __forceinline__ V2 goal_dir(V2 pos, double gx, double gy) {

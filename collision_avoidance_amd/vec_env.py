@@ -89,6 +89,26 @@ def fork_index(src, A, allow_keep=False):
     return np.ascontiguousarray(a, np.int32)
 
 
+def action_seq_shape(actions_shape, A, N, hold=1, steps=None, weights_shape=None):
+    """(R, steps) of rollout_actions() for an action tensor of shape `actions_shape`, without a device.  Raises ValueError for what
+    the library would refuse or misread: hold < 1, a shape other than [R, A, N], steps < 0 or a row count other than
+    ceil(steps / hold), weights of a shape other than [steps].  steps=None: R * hold."""
+    hold = int(hold)
+    if hold < 1:
+        raise ValueError("rollout_actions: hold=%d, must be at least 1" % hold)
+    shape = tuple(int(d) for d in actions_shape)
+    if len(shape) != 3 or shape[1:] != (int(A), int(N)):
+        raise ValueError("rollout_actions: actions must be [R, A=%d, N=%d], got shape %s" % (A, N, shape))
+    R = shape[0]
+    steps = R * hold if steps is None else int(steps)
+    if steps < 0 or (steps + hold - 1) // hold != R:
+        raise ValueError("rollout_actions: steps=%d with hold=%d needs %d rows of actions, got %d" %
+                         (steps, hold, (max(steps, 0) + hold - 1) // hold, R))
+    if weights_shape is not None and tuple(weights_shape) != (steps,):
+        raise ValueError("rollout_actions: weights must be [steps=%d], got shape %s" % (steps, tuple(weights_shape)))
+    return R, steps
+
+
 class Snapshot:
     """A second set of the state buffers on the environment's device (ca_snapshot_*): made and filled by
     VecCollisionAvoidanceEnv.snapshot(), read by restore().  close() destroys it; the environment's close() invalidates every
@@ -891,6 +911,94 @@ class VecCollisionAvoidanceEnv:
         if trace is not None:
             return self._traced("ca_rollout_trace", steps, flags, trace)
         self._call("ca_rollout", self.h, int(steps), flags)
+
+    # ---- action-sequence rollouts (ca_rollout_actions) ------------------------------------------------
+    def _actseq_host(self, name, shape, dtype):
+        """A page-locked, device-visible array of the handle's for the numpy form of rollout_actions(), kept per name and shape."""
+        bufs = self.__dict__.setdefault("_actseq_bufs", {})
+        key = (name, tuple(shape))
+        if key not in bufs:
+            bufs[key] = self.host_array(shape, dtype)
+        return bufs[key]
+
+    def rollout_actions(self, actions, hold=1, weights=None, returns=True, first_done=False, with_obs=False, stats=False,
+                        autoreset=False, freeze=False, contacts=False, steps=None):
+        """`steps` step() calls under the action tensor `actions` [R, A, N] without returning to the host (ca_rollout_actions): row
+        t // hold drives step t, so every row is held for `hold` steps (frame skip) and steps = R * hold; steps= gives a shorter
+        last row (R == ceil(steps / hold)).  The state, fields and statistics left are those of the step() calls, bit for bit.
+        weights [steps] float32 (a planner's gamma ** t) or None: 1.  Returns dict(returns=, first_done=, obs=):
+          returns     [A, N] float32: ret = ret + weights[t] * reward_t over the steps that advanced the agent's arena, in step
+                      order, each operation rounded to float32 (returns_reference in tests/actseq_scenes.py restates the rule); a
+                      frozen arena (freeze=True) adds nothing, an absent row (set_agent_counts) stays 0, and with autoreset the
+                      sum runs across the respawn.  None with returns=False.
+          first_done  [A] int32: the first step of the call that left the arena's done flag set, -1 if none (and for an arena
+                      already frozen at entry).  None with first_done=False.
+          obs         the observation of the state the call leaves (with_obs=True), else None.
+        With use_torch a contiguous float32 tensor on the handle's device is read where it lies and the outputs are device
+        tensors, filled on the handle's stream; otherwise numpy goes in and out and the call synchronises.  contacts=True: also
+        leave the contact report of the final state (last_contacts())."""
+        on_torch = self.use_torch
+        if not (torch is not None and isinstance(actions, torch.Tensor)):
+            actions = np.asarray(actions, np.float32)
+        if weights is not None and not (torch is not None and isinstance(weights, torch.Tensor)):
+            weights = np.asarray(weights, np.float32)
+        hold = int(hold)
+        R, steps = action_seq_shape(tuple(actions.shape), self.A, self.N, hold, steps,
+                                    None if weights is None else tuple(weights.shape))
+        if on_torch and not isinstance(actions, torch.Tensor):
+            actions = torch.as_tensor(actions)
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
+                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        if on_torch:
+            dev = torch.device("cuda", self.device)
+            act = actions.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if R == 0:   # (an empty tensor has no address to hand over)
+                act = torch.zeros((1, self.A, self.N), dtype=torch.float32, device=dev)
+            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
+            ret = torch.empty((self.A, self.N), dtype=torch.float32, device=dev) if returns else None
+            fd = torch.empty((self.A,), dtype=torch.int32, device=dev) if first_done else None
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+            if not act.is_cuda:
+                raise RuntimeError("rollout_actions: use_torch=True needs a device")
+        else:
+            if torch is not None and isinstance(actions, torch.Tensor):
+                actions = actions.detach().cpu().numpy()
+            if torch is not None and isinstance(weights, torch.Tensor):
+                weights = weights.detach().cpu().numpy()
+            act = self._actseq_host("actions", (max(R, 1), self.A, self.N), np.float32)
+            act[:R] = np.asarray(actions, np.float32)
+            w = None
+            if weights is not None:
+                w = self._actseq_host("weights", (max(steps, 1),), np.float32)
+                w[:steps] = np.asarray(weights, np.float32)
+            ret = self._actseq_host("returns", (self.A, self.N), np.float32) if returns else None
+            fd = self._actseq_host("first_done", (self.A,), np.int32) if first_done else None
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        nbytes = lambda t, n: 0 if t is None else n * 4
+        seq = _lib.ActionSeq(actions=ptr(act), actions_bytes=R * self.A * self.N * 4, hold=hold,
+                             weights=ptr(w) if steps else None, weights_bytes=nbytes(w, steps),
+                             returns=ptr(ret), returns_bytes=nbytes(ret, self.A * self.N),
+                             first_done=ptr(fd), first_done_bytes=nbytes(fd, self.A))
+        self._call("ca_rollout_actions", self.h, steps, flags, C.byref(seq))
+        if not on_torch:
+            self.sync()
+            ret = None if ret is None else np.array(ret)
+            fd = None if fd is None else np.array(fd)
+        return dict(returns=ret, first_done=fd, obs=self._obs_out() if with_obs else None)
+
+    def step_repeat(self, actions, k, with_obs=True, stats=False, autoreset=False):
+        """step(actions) k times in one call (frame skip; rollout_actions with one row held for k steps).  Returns (obs,
+        summed_rewards [A,N], dones [A], {"first_done": [A]}): the rewards of the k steps added up in float32 in step order,
+        dones[a] true if an episode of arena a ended inside the k steps, first_done the step at which it did (-1: none)."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("step_repeat: k=%d, must be at least 1" % k)
+        if self.use_torch and isinstance(actions, torch.Tensor):
+            a = actions.reshape(1, self.A, self.N)
+        else:
+            a = np.asarray(actions, np.float32).reshape(1, self.A, self.N)
+        out = self.rollout_actions(a, hold=k, returns=True, first_done=True, with_obs=with_obs, stats=stats, autoreset=autoreset)
+        return out["obs"], out["returns"], out["first_done"] >= 0, {"first_done": out["first_done"]}
 
     # ---- ALAN online learning (ALAN_true.py:569-628) -----------------------------------------------
     def alan_configure(self, actions, temp=0.2, timewindow=2.0, time_step=1 / 60.):

@@ -586,6 +586,46 @@ typedef struct ca_trace {
 int ca_rollout_trace(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
 int ca_alan_rollout_trace(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
 
+/* Action-sequence rollouts: `steps` consecutive ca_step calls under a [R, A, N] action tensor the caller already holds, without
+ * returning to the host -- the second step of a planner's round (ca_arena_gather: copy the real arena into every slot; roll each
+ * copy out under its own actions; pick; ca_snapshot_load: rewind) and an agent that holds every action for `hold` steps (frame skip).
+ *   Definition: the state, every field and every statistic the call leaves are, bit for bit, those of `steps` consecutive
+ *   ca_step(env, actions + (t / hold) * A * N, flags) calls, t = 0 .. steps - 1.  R = ceil(steps / hold): the last row may be held
+ *   for fewer than `hold` steps.
+ *   returns[a, i] starts at +0.0f and takes, in step order, ret = ret + r_t (weights NULL) or ret = ret + weights[t] * r_t (two fp32
+ *   operations, each rounded once, never contracted), r_t the value step t writes to CA_FLD_REWARD.  A step that did not advance
+ *   the arena adds nothing: under CA_F_FREEZE every step once arena_done is set, all of them for an arena frozen at entry.  An absent
+ *   row of ca_set_agent_counts stays 0.  Under CA_F_AUTORESET the sum RUNS ACROSS the episode boundary: it is the sum over the steps
+ *   of the call, not of an episode (first_done says where the boundary fell).
+ *   first_done[a] is the smallest t for which arena_done[a] != 0 after step t of this call, -1 if there is none; an arena frozen at
+ *   entry reads -1 (its flag was there to see before the call).
+ * Flags: CA_F_STATS, CA_F_AUTORESET and CA_F_FREEZE apply per step as in ca_step; CA_F_OBS and CA_F_CONTACT each add ONE launch
+ * behind the last step, for the state the call leaves (both are pure functions of that state: what the `steps` calls leave);
+ * CA_F_NODONE or an unknown bit -> CA_EINVAL.
+ * Checks, all before anything is launched (a failure advances nothing): a NULL env, seq or seq->actions, steps < 0, hold < 1 ->
+ * CA_EINVAL; a buffer smaller than its layout -> CA_ESIZE (ca_last_error names the buffer and the size it needs).  steps == 0
+ * advances nothing and still writes zeros to returns and -1 to first_done where given.  The sticky overflow error works as in
+ * ca_rollout.
+ * Asynchronous on the handle's stream: the buffers are the caller's and must stay alive until the stream has passed the call; the
+ * ca_action_seq struct itself is read before the call returns, as ca_trace is.
+ * Where ca_rollout is one launch per 256 steps (ca_solver_info: rollout_one_launch; ALAN-configured handles included) so is this:
+ * the four-lanes kernel reads each step's action element itself, keeps the return in a register and writes returns, first_done and
+ * the last reward once per launch; sums and row indices carry on across launches, also in the middle of a hold.  Everywhere else --
+ * one- and two-lanes kernels, wide lists, per-agent parameters, counts, sensing, tiled handles -- every step is the launch (sequence)
+ * of ca_step with that step's row and a small accumulate kernel behind it; ca_profile counts the small kernels under kind 3. */
+typedef struct ca_action_seq {
+    const float* actions;    /* DEVICE f32 [R, A, N], R = ceil(steps / hold): row t / hold drives step t */
+    size_t   actions_bytes;
+    int32_t  hold;           /* >= 1: every row is held for `hold` consecutive steps (frame skip) */
+    const float* weights;    /* DEVICE f32 [steps], or NULL = 1 for every step (discounts: the caller's gamma^t) */
+    size_t   weights_bytes;
+    float*   returns;        /* DEVICE f32 [A, N], or NULL: not wanted */
+    size_t   returns_bytes;
+    int32_t* first_done;     /* DEVICE i32 [A], or NULL: not wanted */
+    size_t   first_done_bytes;
+} ca_action_seq;
+int ca_rollout_actions(ca_env* env, int32_t steps, uint32_t flags, const ca_action_seq* seq);
+
 /* The reference's simulator keeps EVERY obstacle edge within range of an agent (sim.getAgentNumObstacleNeighbors /
  * getAgentObstacleNeighbor, env.py:249, 301-318, iterate them all); this library's lists hold max_obst_neighbors and drop the
  * farthest edges beyond that.  So that such a deviation cannot pass unnoticed, an overflow is a sticky error of the handle:
