@@ -39,7 +39,10 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_contacts", "ca_get_contacts", "ca_contacts_ptr",
            "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info",
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
-           "ca_fork_bytes_per_arena", "ca_rollout_actions")
+           "ca_fork_bytes_per_arena", "ca_rollout_actions",
+           "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy")
+POLICY_OUT_IDENTITY, POLICY_OUT_CLIP = 0, 1   # out_mode of a policy (struct ca_policy_desc)
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 128
 
 
 class Config(C.Structure):
@@ -77,6 +80,21 @@ class ActionSeq(C.Structure):
     _fields_ = [("actions", C.c_void_p), ("actions_bytes", C.c_size_t), ("hold", C.c_int32),
                 ("weights", C.c_void_p), ("weights_bytes", C.c_size_t), ("returns", C.c_void_p), ("returns_bytes", C.c_size_t),
                 ("first_done", C.c_void_p), ("first_done_bytes", C.c_size_t)]
+
+
+class PolicyDesc(C.Structure):
+    """struct ca_policy_desc (include/ca_env.h): the layers of a policy as ca_policy_configure takes them."""
+    _fields_ = [("n_layers", C.c_int32), ("width", C.c_int32 * 5), ("weights", C.c_void_p * 4), ("weights_bytes", C.c_size_t * 4),
+                ("bias", C.c_void_p * 4), ("bias_bytes", C.c_size_t * 4), ("src_is_device", C.c_int32), ("n_sets", C.c_int32),
+                ("set_of_arena", C.c_void_p), ("set_of_arena_bytes", C.c_size_t), ("out_mode", C.c_int32), ("out_limit", C.c_float)]
+
+
+class PolicySeq(C.Structure):
+    """struct ca_policy_seq (include/ca_env.h): the caller's buffers of a policy rollout."""
+    _fields_ = [("hold", C.c_int32), ("noise", C.c_void_p), ("noise_bytes", C.c_size_t), ("weights", C.c_void_p), ("weights_bytes", C.c_size_t),
+                ("returns", C.c_void_p), ("returns_bytes", C.c_size_t), ("first_done", C.c_void_p), ("first_done_bytes", C.c_size_t),
+                ("obs_out", C.c_void_p), ("obs_out_bytes", C.c_size_t), ("actions_out", C.c_void_p), ("actions_out_bytes", C.c_size_t),
+                ("rewards_out", C.c_void_p), ("rewards_out_bytes", C.c_size_t), ("done_out", C.c_void_p), ("done_out_bytes", C.c_size_t)]
 
 
 class EdgeGridDesc(C.Structure):
@@ -145,6 +163,11 @@ def load():
     L.ca_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
     L.ca_alan_rollout_trace.argtypes = [vp, i32, u32, C.POINTER(Trace)]
     L.ca_rollout_actions.argtypes = [vp, i32, u32, C.POINTER(ActionSeq)]
+    L.ca_policy_configure.argtypes = [vp, C.POINTER(PolicyDesc)]
+    L.ca_policy_clear.argtypes = [vp]
+    L.ca_policy_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32 * 5), C.POINTER(i32)]
+    L.ca_policy_actions.argtypes = [vp, vp, vp]
+    L.ca_rollout_policy.argtypes = [vp, i32, u32, C.POINTER(PolicySeq)]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]

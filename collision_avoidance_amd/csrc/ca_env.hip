@@ -98,6 +98,18 @@ struct ca_env {
     ActSeqDev* d_actseq = nullptr;   // the action-sequence block behind StepCold::actseq, rewritten in front of every ActionSeq launch of the four-lanes kernel
     bool actseq_on = false;          // ca_rollout_actions: the launch in flight is an ActionSeq instantiation
     int* actseq_words = nullptr;     // [2][A] first_done of a caller that gave none | frozen at entry (the per-step form); allocated on first use
+    // the policy (ca_policy_configure; ca_policy.h): configuration, like the ALAN action sets.  d_wp / d_bp hold the P sets' weights in
+    // the order the kernel's B operand reads them and their biases, d_set the arenas' set indices (P > 1), act the [A*N] actions a
+    // policy rollout steps under
+    struct Policy {
+        bool on = false;
+        int L = 0, P = 0, out_mode = 0, maxw = 0;
+        int width[CA_POLICY_MAX_LAYERS + 1] = {0, 0, 0, 0, 0};
+        float limit = 0.0f;
+        unsigned wp_off[CA_POLICY_MAX_LAYERS] = {0, 0, 0, 0}, bp_off[CA_POLICY_MAX_LAYERS] = {0, 0, 0, 0}, wset = 0, bset = 0;
+        float *d_wp = nullptr, *d_bp = nullptr, *act = nullptr;
+        int* d_set = nullptr;
+    } pol;
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -285,7 +297,7 @@ static FieldInfo field_info(ca_env* e, int f) {
         case CA_FLD_NB_IDX: return {e->nb_idx, an * 4 * (size_t)(e->K > 0 ? e->K : 1), true};
         case CA_FLD_OBST_COUNT: return {e->counts, an * 4, true};
         case CA_FLD_OBST_IDX: return {e->obst_idx, an * 4 * (size_t)e->S, true};
-        case CA_FLD_OBS: return {e->obs, an * CA_OBS_DIM * 4, false};
+        case CA_FLD_OBS: return {e->obs, an * CA_OBS_DIM * 4, true};   // (writable: ca_policy_actions reads the buffer as it stands)
         case CA_FLD_STEP_COUNT: return {e->step_count, A * 4, true};
         case CA_FLD_ARENA_DONE: return {e->arena_done, A * 4, true};
         case CA_FLD_EPISODE: return {e->episode, A * 4, true};
@@ -1156,6 +1168,7 @@ int ca_destroy(ca_env* e) {
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
+                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -2759,6 +2772,243 @@ int ca_rollout_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action
         }
     }
     if (steps > 0) e->orient_valid = true;
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+// ---- the policy and its rollouts (include/ca_env.h ca_policy_desc, ca_policy_seq) ---------------------------------------------------
+int ca_policy_configure(ca_env* e, const ca_policy_desc* d) {
+    const char* who = "ca_policy_configure";
+    if (!e || !d) return fail(e, CA_EINVAL, "%s: null argument", who);
+    const int L = d->n_layers, A = e->cfg.n_arenas;
+    if (L < 2 || L > CA_POLICY_MAX_LAYERS) return fail(e, CA_EINVAL, "%s: n_layers=%d, must be 2 .. %d", who, L, CA_POLICY_MAX_LAYERS);
+    if (d->width[0] != CA_OBS_DIM) return fail(e, CA_EINVAL, "%s: width[0]=%d, must be CA_OBS_DIM = %d", who, d->width[0], CA_OBS_DIM);
+    for (int l = 1; l < L; ++l)
+        if (d->width[l] < 16 || d->width[l] > CA_POLICY_MAX_WIDTH || d->width[l] % 16 != 0)
+            return fail(e, CA_EINVAL, "%s: width[%d]=%d, a hidden width is a multiple of 16 in 16 .. %d", who, l, d->width[l], CA_POLICY_MAX_WIDTH);
+    if (d->width[L] != 1) return fail(e, CA_EINVAL, "%s: width[%d]=%d, the output layer has one unit", who, L, d->width[L]);
+    if (d->out_mode != CA_POLICY_OUT_IDENTITY && d->out_mode != CA_POLICY_OUT_CLIP)
+        return fail(e, CA_EINVAL, "%s: out_mode=%d", who, d->out_mode);
+    if (d->out_mode == CA_POLICY_OUT_CLIP && !(d->out_limit >= 0.0f && std::isfinite(d->out_limit)))
+        return fail(e, CA_EINVAL, "%s: out_limit=%g, must be finite and not negative", who, (double)d->out_limit);
+    const int P = d->n_sets;
+    if (P < 1) return fail(e, CA_EINVAL, "%s: n_sets=%d, must be at least 1", who, P);
+    if (P > 1 && !d->set_of_arena) return fail(e, CA_EINVAL, "%s: n_sets=%d needs set_of_arena", who, P);
+    for (int l = 0; l < L; ++l) {
+        if (!d->weights[l] || !d->bias[l]) return fail(e, CA_EINVAL, "%s: weights[%d] or bias[%d] is null", who, l, l);
+        const size_t wb = (size_t)P * d->width[l + 1] * d->width[l] * 4, bb = (size_t)P * d->width[l + 1] * 4;
+        if (d->weights_bytes[l] < wb)
+            return fail(e, CA_ESIZE, "%s: weights[%d] needs %zu bytes (f32 [P=%d, %d, %d]), got %zu", who, l, wb, P, d->width[l + 1], d->width[l], d->weights_bytes[l]);
+        if (d->bias_bytes[l] < bb)
+            return fail(e, CA_ESIZE, "%s: bias[%d] needs %zu bytes (f32 [P=%d, %d]), got %zu", who, l, bb, P, d->width[l + 1], d->bias_bytes[l]);
+    }
+    if (d->set_of_arena) {
+        if (d->set_of_arena_bytes < (size_t)A * 4)
+            return fail(e, CA_ESIZE, "%s: set_of_arena needs %zu bytes (i32 [A=%d]), got %zu", who, (size_t)A * 4, A, d->set_of_arena_bytes);
+        for (int a = 0; a < A; ++a)
+            if (d->set_of_arena[a] < 0 || d->set_of_arena[a] >= P)
+                return fail(e, CA_ERANGE, "%s: arena %d asks for set %d of %d", who, a, d->set_of_arena[a], P);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // the caller's arrays on the host, checked; then the kernel's layout: a set is its layers one behind the other, a layer its
+    // 16-column tiles (the output layer: one tile, columns 1 .. 15 zero), a tile its k-steps, a k-step 64 lanes
+    std::vector<float> hw[CA_POLICY_MAX_LAYERS], hb[CA_POLICY_MAX_LAYERS];
+    ca_env::Policy n;
+    n.L = L; n.P = P; n.out_mode = d->out_mode; n.limit = d->out_limit;
+    for (int l = 0; l <= L; ++l) { n.width[l] = d->width[l]; if (l < L && d->width[l] > n.maxw) n.maxw = d->width[l]; }
+    for (int l = 0; l < L; ++l) {
+        const size_t nw = (size_t)P * d->width[l + 1] * d->width[l], nb = (size_t)P * d->width[l + 1];
+        hw[l].resize(nw); hb[l].resize(nb);
+        if (d->src_is_device) {
+            HIPCHK(e, download(e, hw[l].data(), d->weights[l], nw * 4));
+            HIPCHK(e, download(e, hb[l].data(), d->bias[l], nb * 4));
+        } else {
+            memcpy(hw[l].data(), d->weights[l], nw * 4);
+            memcpy(hb[l].data(), d->bias[l], nb * 4);
+        }
+        const size_t per = (size_t)d->width[l + 1] * d->width[l];
+        for (size_t k = 0; k < nw; ++k)
+            if (!std::isfinite(hw[l][k]))
+                return fail(e, CA_ERANGE, "%s: layer %d, set %zu: weight [%zu, %zu] is not finite", who, l, k / per, (k % per) / d->width[l], k % d->width[l]);
+        for (size_t k = 0; k < nb; ++k)
+            if (!std::isfinite(hb[l][k]))
+                return fail(e, CA_ERANGE, "%s: layer %d, set %zu: bias [%zu] is not finite", who, l, k / d->width[l + 1], k % d->width[l + 1]);
+        const unsigned opad = l == L - 1 ? 16u : (unsigned)d->width[l + 1];
+        n.wp_off[l] = n.wset; n.bp_off[l] = n.bset;
+        n.wset += opad * (unsigned)d->width[l]; n.bset += opad;
+    }
+    std::vector<float> wp((size_t)P * n.wset, 0.0f), bp((size_t)P * n.bset, 0.0f);
+    for (int p = 0; p < P; ++p)
+        for (int l = 0; l < L; ++l) {
+            const int K = d->width[l], O = d->width[l + 1], opad = l == L - 1 ? 16 : O;
+            const float* W = hw[l].data() + (size_t)p * O * K;
+            float* dst = wp.data() + (size_t)p * n.wset + n.wp_off[l];
+            for (int jt = 0; jt < opad / 16; ++jt)
+                for (int s = 0; s < K / 4; ++s)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int j = jt * 16 + (lane & 15), k = 4 * s + (lane >> 4);
+                        dst[((size_t)jt * (K / 4) + s) * 64 + lane] = j < O ? W[(size_t)j * K + k] : 0.0f;
+                    }
+            for (int j = 0; j < O; ++j) bp[(size_t)p * n.bset + n.bp_off[l] + j] = hb[l][(size_t)p * O + j];
+        }
+    hipError_t r = hipMalloc((void**)&n.d_wp, wp.size() * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&n.d_bp, bp.size() * 4);
+    if (r == hipSuccess && P > 1) r = hipMalloc((void**)&n.d_set, (size_t)A * 4);
+    if (r == hipSuccess) r = upload(e, n.d_wp, wp.data(), wp.size() * 4);
+    if (r == hipSuccess) r = upload(e, n.d_bp, bp.data(), bp.size() * 4);
+    if (r == hipSuccess && P > 1) r = upload(e, n.d_set, d->set_of_arena, (size_t)A * 4);
+    n.act = e->pol.act;
+    if (r == hipSuccess && !n.act) r = dalloc(e, &n.act, AN(e));
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    if (r != hipSuccess) {
+        if (n.d_wp) hipFree(n.d_wp);
+        if (n.d_bp) hipFree(n.d_bp);
+        if (n.d_set) hipFree(n.d_set);
+        if (n.act && !e->pol.act) hipFree(n.act);
+        return fail(e, CA_EHIP, "%s: installing the weights failed: %s", who, hipGetErrorString(r));
+    }
+    if (e->pol.d_wp) hipFree(e->pol.d_wp);
+    if (e->pol.d_bp) hipFree(e->pol.d_bp);
+    if (e->pol.d_set) hipFree(e->pol.d_set);
+    n.on = true;
+    e->pol = n;
+    return CA_OK;
+}
+
+int ca_policy_clear(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->pol.d_wp) hipFree(e->pol.d_wp);
+    if (e->pol.d_bp) hipFree(e->pol.d_bp);
+    if (e->pol.d_set) hipFree(e->pol.d_set);
+    float* act = e->pol.act;   // (kept for the next policy)
+    e->pol = ca_env::Policy();
+    e->pol.act = act;
+    return CA_OK;
+}
+
+int ca_policy_info(ca_env* e, int32_t* configured, int32_t* n_layers, int32_t* width, int32_t* n_sets) {
+    if (!e) return CA_EINVAL;
+    if (configured) *configured = e->pol.on ? 1 : 0;
+    if (n_layers) *n_layers = e->pol.on ? e->pol.L : 0;
+    if (n_sets) *n_sets = e->pol.on ? e->pol.P : 0;
+    if (width) for (int l = 0; l <= CA_POLICY_MAX_LAYERS; ++l) width[l] = e->pol.on && l <= e->pol.L ? e->pol.width[l] : 0;
+    return CA_OK;
+}
+
+// the policy launch (kind 3 for ca_profile): the handle's observation buffer -> actions, and the records of a rollout's row
+static hipError_t launch_policy(ca_env* e, const float* noise, float* actions, float* actions_rec, float* obs_rec) {
+    const ca_env::Policy& q = e->pol;
+    PolicyArgs p;
+    p.obs = e->obs; p.wp = q.d_wp; p.bp = q.d_bp; p.set_of_arena = q.P > 1 ? q.d_set : nullptr;
+    p.noise = noise; p.actions = actions; p.actions_rec = actions_rec; p.obs_rec = obs_rec;
+    for (int l = 0; l < POLICY_MAX_LAYERS; ++l) { p.wp_off[l] = q.wp_off[l]; p.bp_off[l] = q.bp_off[l]; }
+    for (int l = 0; l <= POLICY_MAX_LAYERS; ++l) p.width[l] = q.width[l];
+    p.wset = q.wset; p.bset = q.bset;
+    p.an = (unsigned)AN(e); p.N = e->cfg.n_agents;
+    // one set: tiles of consecutive rows across arenas; a set per arena: a tile holds rows of one arena, padded (the same bits)
+    p.tpa = q.P > 1 ? (p.N + POLICY_ROWS - 1) / POLICY_ROWS : 0;
+    p.n_layers = q.L; p.stride = q.maxw + POLICY_PAD;
+    p.clip = q.out_mode == CA_POLICY_OUT_CLIP ? 1 : 0; p.limit = q.limit;
+    const unsigned grid = p.tpa ? (unsigned)e->cfg.n_arenas * (unsigned)p.tpa : (p.an + POLICY_ROWS - 1) / POLICY_ROWS;
+    const size_t lds = (size_t)2 * POLICY_ROWS * p.stride * 4;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, policy_kernel, dim3(grid), dim3(64), lds, e->stream, p);
+    return hipGetLastError();
+}
+
+int ca_policy_actions(ca_env* e, const float* noise, float* actions_out) {
+    if (!e) return CA_EINVAL;
+    if (!e->pol.on) return fail(e, CA_EINVAL, "ca_policy_actions: call ca_policy_configure first");
+    if (!actions_out) return fail(e, CA_EINVAL, "ca_policy_actions: actions_out is null");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_policy(e, noise, actions_out, nullptr, nullptr));
+    return CA_OK;
+}
+
+// every refusal of ca_rollout_policy, before anything is launched
+static int policy_seq_check(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
+    const char* who = "ca_rollout_policy";
+    if (!seq) return fail(e, CA_EINVAL, "%s: the sequence is null", who);
+    if (!e->pol.on) return fail(e, CA_EINVAL, "%s: call ca_policy_configure first", who);
+    if (steps < 0) return fail(e, CA_EINVAL, "%s: steps=%d", who, steps);
+    if (seq->hold < 1) return fail(e, CA_EINVAL, "%s: hold=%d, must be at least 1", who, seq->hold);
+    if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "%s: CA_F_NODONE applies to ca_orca_step only", who);
+    if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE | CA_F_CONTACT))
+        return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
+    if (seq->obs_out && ((uintptr_t)seq->obs_out & 15) != 0) return fail(e, CA_EINVAL, "%s: the obs_out buffer must be 16-byte aligned", who);
+    const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold, A = (size_t)e->cfg.n_arenas, an = AN(e), T = (size_t)steps;
+    const int Ai = e->cfg.n_arenas, Ni = e->cfg.n_agents;
+    if (seq->noise && seq->noise_bytes < R * an * 4)
+        return fail(e, CA_ESIZE, "%s: the noise buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d], R = ceil(steps / hold)), got %zu", who, R * an * 4, R, Ai, Ni, seq->noise_bytes);
+    if (seq->weights && seq->weights_bytes < T * 4)
+        return fail(e, CA_ESIZE, "%s: the weights buffer needs %zu bytes (f32 [steps=%d]), got %zu", who, T * 4, steps, seq->weights_bytes);
+    if (seq->returns && seq->returns_bytes < an * 4)
+        return fail(e, CA_ESIZE, "%s: the returns buffer needs %zu bytes (f32 [A=%d, N=%d]), got %zu", who, an * 4, Ai, Ni, seq->returns_bytes);
+    if (seq->first_done && seq->first_done_bytes < A * 4)
+        return fail(e, CA_ESIZE, "%s: the first_done buffer needs %zu bytes (i32 [A=%d]), got %zu", who, A * 4, Ai, seq->first_done_bytes);
+    if (seq->obs_out && seq->obs_out_bytes < R * an * CA_OBS_DIM * 4)
+        return fail(e, CA_ESIZE, "%s: the obs_out buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d, %d]), got %zu", who, R * an * CA_OBS_DIM * 4, R, Ai, Ni, CA_OBS_DIM, seq->obs_out_bytes);
+    if (seq->actions_out && seq->actions_out_bytes < R * an * 4)
+        return fail(e, CA_ESIZE, "%s: the actions_out buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d]), got %zu", who, R * an * 4, R, Ai, Ni, seq->actions_out_bytes);
+    if (seq->rewards_out && seq->rewards_out_bytes < T * an * 4)
+        return fail(e, CA_ESIZE, "%s: the rewards_out buffer needs %zu bytes (f32 [steps=%d, A=%d, N=%d]), got %zu", who, T * an * 4, steps, Ai, Ni, seq->rewards_out_bytes);
+    if (seq->done_out && seq->done_out_bytes < T * A * 4)
+        return fail(e, CA_ESIZE, "%s: the done_out buffer needs %zu bytes (i32 [steps=%d, A=%d]), got %zu", who, T * A * 4, steps, Ai, seq->done_out_bytes);
+    return CA_OK;
+}
+// behind the launches of step t: the return, first_done and the step's records
+static hipError_t launch_policy_record(ca_env* e, const ca_policy_seq* seq, const ActSeqPlan& pl, uint32_t flags, int t) {
+    PolicyRecArgs c;
+    c.reward = e->reward; c.arena_done = e->arena_done; c.entry_frozen = pl.entry_frozen;
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.weight = seq->weights ? seq->weights + t : nullptr;
+    c.returns = seq->returns; c.first_done = pl.first_done;
+    c.rewards_rec = seq->rewards_out ? seq->rewards_out + (size_t)t * AN(e) : nullptr;
+    c.done_rec = seq->done_out ? seq->done_out + (size_t)t * e->cfg.n_arenas : nullptr;
+    c.an = (unsigned)AN(e); c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents; c.t = t; c.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, policy_record_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
+    return hipGetLastError();
+}
+
+int ca_rollout_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
+    if (!e) return CA_EINVAL;
+    { const int rc = policy_seq_check(e, steps, flags, seq); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, "ca_rollout_policy"); if (rs) return rs; }
+    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
+    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
+    ActSeqPlan pl;
+    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
+    pl.entry_frozen = e->actseq_words + A;
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
+    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    {   // zeros, -1, the arenas frozen at entry: the set-up launch of ca_rollout_actions
+        ActSeqBeginArgs b;
+        b.arena_done = e->arena_done; b.returns = seq->returns; b.first_done = pl.first_done; b.entry_frozen = pl.entry_frozen;
+        b.an = (unsigned)an; b.A = e->cfg.n_arenas; b.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+        const unsigned n = b.an > (unsigned)b.A ? b.an : (unsigned)b.A;
+        ProfScope ps(e, KIND_RESET);
+        launch_k(ps, actseq_begin_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, b);
+        HIPCHK(e, hipGetLastError());
+    }
+    for (int t = 0; t < steps; ++t) {
+        if (t % seq->hold == 0) {   // a row starts: what ca_observe launches, then the policy on what it left
+            const size_t r = (size_t)(t / seq->hold);
+            if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+            HIPCHK(e, launch_obs(e));
+            HIPCHK(e, launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act,
+                                    seq->actions_out ? seq->actions_out + r * an : nullptr,
+                                    seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr));
+        }
+        const int rc = do_step(e, e->pol.act, sf);
+        if (rc) return rc;
+        HIPCHK(e, launch_policy_record(e, seq, pl, flags, t));
+    }
     if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
     if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
     return CA_OK;

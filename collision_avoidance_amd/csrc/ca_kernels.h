@@ -33,7 +33,8 @@
 // reset kernels), ca_quad.h (four-lanes solve), ca_pair.h (two-lanes solve), ca_tiled.h (tiled solve: three launches),
 // ca_alan.h (ALAN bandit kernels), ca_obs.h (laser observation), ca_trace.h (the record kernels of a recording rollout),
 // ca_contact.h (the per-agent contact report), ca_fork.h (the arena copy behind ca_arena_gather / ca_snapshot_*),
-// ca_actseq.h (the small kernels of ca_rollout_actions and the rule of its return).
+// ca_actseq.h (the small kernels of ca_rollout_actions and the rule of its return), ca_policy.h (the MLP policy kernel on the f32
+// MFMA and the record kernel of ca_rollout_policy).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -46,6 +47,7 @@
 #include "ca_contact.h"
 #include "ca_fork.h"
 #include "ca_actseq.h"
+#include "ca_policy.h"
 
 namespace ca {
 

@@ -1,0 +1,175 @@
+// ca_policy.h -- the kernels of a closed-loop policy rollout (ca_policy_actions, ca_rollout_policy)
+// Part of the HIP kernels of libcaenv.so (see ca_kernels.h for the overview and the numerics contract).
+//
+// A policy is a ReLU MLP over an agent's 64-float observation with one output, the heading offset ca_step takes (include/ca_env.h
+// ca_policy_desc).  Its definition is a k-ordered chain of fused multiply-adds that starts from the bias,
+//     acc = b[j];  for k ascending: acc = fmaf(x[k], W[j][k], acc)
+// which is what v_mfma_f32_16x16x4_f32 computes with the bias in C and successive instructions taking ascending k: the products of
+// one instruction are added in the order k = 0 .. 3 of its lane groups.  policy_kernel runs on it:
+//   * one wave per workgroup owns POLICY_ROWS = 32 rows (agents): two 16-row tiles, i.e. two independent accumulators per output tile,
+//     which covers the instruction's dependent latency, and every weight fragment loaded serves both;
+//   * the rows' observations are staged into LDS with 128-bit loads (and go to the obs record from the same registers); a layer reads
+//     its A operand from LDS -- lane l holds x[row l & 15][4 s + (l >> 4)] of k-step s -- and writes its activations back to a second
+//     LDS image in [row][column] order, so the next layer again walks k in ascending order: nothing is ever permuted along k;
+//   * the weights come from global memory in the order the B operand wants them (the host packs them: [16-column tile][k-step][lane],
+//     lane l holding W[16 jt + (l & 15)][4 s + (l >> 4)]), one coalesced 256-byte load per instruction; the output layer is a tile whose
+//     columns 1 .. 15 are zero, and column 0 -- lanes 0, 16, 32, 48 -- holds the rows' means;
+//   * an LDS row is width + 4 floats long: the A reads of a k-step and the D writes of a tile then touch 64 different banks.
+// A row's result depends on its own observation and its arena's weight set only: not on the tiling, not on the rows beside it.
+// policy_record_kernel is the accumulate kernel of a policy rollout: actseq_accumulate_kernel's rule (ca_actseq.h) plus the reward and
+// done records.
+#pragma once
+#include "ca_common.h"
+#include "ca_actseq.h"
+
+namespace ca {
+
+enum { POLICY_ROWS = 32, POLICY_MAX_LAYERS = 4, POLICY_PAD = 4 };
+
+struct PolicyArgs {
+    const float* obs;           // [A*N][64], 16-byte aligned
+    const float* wp;            // packed weights: [P][wset]
+    const float* bp;            // biases: [P][bset]
+    const int* set_of_arena;    // [A], or null: set 0 for every arena
+    const float* noise;         // [A*N], or null
+    float* actions;             // [A*N]
+    float* actions_rec;         // [A*N] the action record's row, or null
+    float* obs_rec;             // [A*N][64] the observation record's row, or null
+    unsigned wp_off[POLICY_MAX_LAYERS], bp_off[POLICY_MAX_LAYERS];   // a layer's place inside a set
+    unsigned wset, bset;        // floats per set
+    unsigned an;                // A * N
+    int N;
+    int tpa;                    // tiles per arena (a tile holds rows of one arena), or 0: tiles of consecutive rows across arenas
+    int n_layers;
+    int width[POLICY_MAX_LAYERS + 1];
+    int stride;                 // floats per LDS row: the largest width + POLICY_PAD
+    int clip;                   // CA_POLICY_OUT_CLIP
+    float limit;
+};
+
+typedef float policy_f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(64) void policy_kernel(const PolicyArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float policy_lds[];   // [2][POLICY_ROWS][stride]
+    const int lane = (int)threadIdx.x;
+    unsigned g0;
+    int nvalid, set = 0;
+    if (p.tpa > 0) {
+        const unsigned arena = blockIdx.x / (unsigned)p.tpa;
+        const int i0 = (int)(blockIdx.x - arena * (unsigned)p.tpa) * POLICY_ROWS;
+        g0 = arena * (unsigned)p.N + (unsigned)i0;
+        nvalid = p.N - i0 < POLICY_ROWS ? p.N - i0 : POLICY_ROWS;
+        if (p.set_of_arena != nullptr) set = p.set_of_arena[arena];
+    } else {
+        g0 = blockIdx.x * (unsigned)POLICY_ROWS;
+        nvalid = p.an - g0 < (unsigned)POLICY_ROWS ? (int)(p.an - g0) : POLICY_ROWS;
+    }
+    const int stride = p.stride;
+    float* in = policy_lds;
+    float* out = policy_lds + POLICY_ROWS * stride;
+    // the tile's observations: 32 rows x 16 float4, eight per lane; rows past the end are zeros nobody reads back
+#pragma unroll
+    for (int it = 0; it < POLICY_ROWS * 16 / 64; ++it) {
+        const int q = it * 64 + lane, row = q >> 4, c = (q & 15) * 4;
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (row < nvalid) {
+            const size_t at = (size_t)(g0 + (unsigned)row) * CA_OBS_DIM + (size_t)c;
+            v = *(const float4*)(p.obs + at);
+            if (p.obs_rec != nullptr) *(float4*)(p.obs_rec + at) = v;
+        }
+        *(float4*)(in + row * stride + c) = v;
+    }
+    __syncthreads();
+    const float* wset = p.wp + (size_t)set * p.wset;
+    const float* bset = p.bp + (size_t)set * p.bset;
+    const int col = lane & 15, grp = lane >> 4;
+    for (int l = 0; l < p.n_layers; ++l) {
+        const bool last = l == p.n_layers - 1;
+        const int K = p.width[l], tiles = last ? 1 : p.width[l + 1] >> 4;
+        const float* W = wset + p.wp_off[l];
+        const float* B = bset + p.bp_off[l];
+        const float* a0p = in + col * stride + grp;
+        const float* a1p = a0p + 16 * stride;
+        for (int jt = 0; jt < tiles; ++jt) {
+            const float bias = B[jt * 16 + col];
+            policy_f32x4 acc0 = {bias, bias, bias, bias}, acc1 = {bias, bias, bias, bias};
+            const float* wj = W + (size_t)jt * (size_t)K * 16 + lane;
+            for (int s0 = 0; s0 < (K >> 2); s0 += 4) {   // (K is a multiple of 16: four k-steps at a time, their loads in front)
+                float b[4], x0[4], x1[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    b[u] = wj[(s0 + u) * 64];
+                    x0[u] = a0p[(s0 + u) * 4];
+                    x1[u] = a1p[(s0 + u) * 4];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[u], b[u], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[u], b[u], acc1, 0, 0, 0);
+                }
+            }
+            if (!last) {   // D: column = lane & 15, row = 4 (lane >> 4) + register
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = grp * 4 + r;
+                    out[row * stride + jt * 16 + col] = acc0[r] > 0.0f ? acc0[r] : 0.0f;
+                    out[(row + 16) * stride + jt * 16 + col] = acc1[r] > 0.0f ? acc1[r] : 0.0f;
+                }
+            } else if (col == 0) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const int row = grp * 4 + (r & 3) + (r >> 2) * 16;
+                    if (row < nvalid) {
+                        const unsigned g = g0 + (unsigned)row;
+                        float v = r < 4 ? acc0[r & 3] : acc1[r & 3];
+                        if (p.noise != nullptr) v = __fadd_rn(v, p.noise[g]);
+                        if (p.clip) v = fminf(fmaxf(v, -p.limit), p.limit);
+                        p.actions[g] = v;
+                        if (p.actions_rec != nullptr) p.actions_rec[g] = v;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        float* t = in; in = out; out = t;
+    }
+}
+
+struct PolicyRecArgs {
+    const float* reward;
+    const int* arena_done;
+    const int* entry_frozen;
+    const int* agent_counts;   // [A] (ca_set_agent_counts), or null
+    const float* weight;       // &weights[t], or null
+    float* returns;            // or null
+    int* first_done;
+    float* rewards_rec;        // [A*N] row t of the reward record, or null
+    int* done_rec;             // [A] row t of the done record, or null
+    unsigned an;
+    int A, N;
+    int t;
+    int freeze;
+};
+
+// behind the launches of step t: the records of every row and arena first, then actseq_accumulate_kernel's rule word for word (the
+// return through actseq_add, first_done stored by the lane of agent 0; see there for why every lane of an arena decides alike)
+__global__ __launch_bounds__(256) void policy_record_kernel(const PolicyRecArgs s) {
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= s.an) return;
+    const int a = (int)(g / (unsigned)s.N), i = (int)(g - (unsigned)a * (unsigned)s.N);
+    const float r = s.reward[g];
+    const float ret = s.returns != nullptr ? s.returns[g] : 0.0f;
+    const int fd = s.first_done[a];
+    const int done = s.arena_done[a];
+    const int frozen0 = s.freeze ? s.entry_frozen[a] : 0;
+    const int count = s.agent_counts != nullptr ? s.agent_counts[a] : s.N;
+    const float w = s.weight != nullptr ? *s.weight : 1.0f;
+    if (s.rewards_rec != nullptr) s.rewards_rec[g] = r;
+    if (s.done_rec != nullptr && i == 0) s.done_rec[a] = done;
+    const bool advanced = !(s.freeze && (frozen0 != 0 || (fd >= 0 && fd < s.t)));
+    if (!advanced) return;
+    if (s.returns != nullptr && i < count) s.returns[g] = actseq_add(ret, w, r);
+    if (i == 0 && fd < 0 && done != 0) s.first_done[a] = s.t;
+}
+
+}  // namespace ca

@@ -109,6 +109,75 @@ def action_seq_shape(actions_shape, A, N, hold=1, steps=None, weights_shape=None
     return R, steps
 
 
+def policy_seq_shape(A, N, steps, hold=1, noise_shape=None, weights_shape=None):
+    """The buffers of rollout_policy() without a device: dict(R=, noise=, weights=, returns=, first_done=, obs=, actions=, rewards=,
+    dones=) with R = ceil(steps / hold) and the shape of every array the call reads or writes.  Raises ValueError for what the library
+    would refuse or misread: hold < 1, steps < 0, noise of a shape other than [R, A, N], weights other than [steps]."""
+    hold, steps, A, N = int(hold), int(steps), int(A), int(N)
+    if hold < 1:
+        raise ValueError("rollout_policy: hold=%d, must be at least 1" % hold)
+    if steps < 0:
+        raise ValueError("rollout_policy: steps=%d" % steps)
+    R = (steps + hold - 1) // hold
+    if noise_shape is not None and tuple(int(d) for d in noise_shape) != (R, A, N):
+        raise ValueError("rollout_policy: noise must be [R=%d, A=%d, N=%d] (R = ceil(steps / hold)), got shape %s" %
+                         (R, A, N, tuple(noise_shape)))
+    if weights_shape is not None and tuple(int(d) for d in weights_shape) != (steps,):
+        raise ValueError("rollout_policy: weights must be [steps=%d], got shape %s" % (steps, tuple(weights_shape)))
+    return dict(R=R, noise=(R, A, N), weights=(steps,), returns=(A, N), first_done=(A,), obs=(R, A, N, _lib.OBS_DIM),
+                actions=(R, A, N), rewards=(steps, A, N), dones=(steps, A))
+
+
+def policy_layers(layers):
+    """The layers of set_policy() as the library takes them, without a device: (widths [w0 .. wL], P, [W_l float32 [P, out, in]],
+    [b_l float32 [P, out]]), C-contiguous host arrays.  `layers` is a list of (W, b) pairs -- numpy arrays or torch tensors, W
+    [out, in] and b [out] (one set) or W [P, out, in] and b [P, out] (P sets) -- or a torch.nn.Sequential of Linear modules with a
+    ReLU between every two.  Raises ValueError for what ca_policy_configure would refuse: fewer than 2 or more than 4 layers, a first
+    width other than 64, a hidden width that is no multiple of 16 in 16 .. 128, an output width other than 1, layers that do not
+    chain, sets of different sizes, a value that is not finite."""
+    if torch is not None and isinstance(layers, torch.nn.Module):
+        mods = list(layers.children()) if isinstance(layers, torch.nn.Sequential) else None
+        if mods is None:
+            raise ValueError("set_policy: a module must be a torch.nn.Sequential of Linear and ReLU")
+        pairs = []
+        for k, m in enumerate(mods):
+            if k % 2 == 0 and isinstance(m, torch.nn.Linear) and m.bias is not None:
+                pairs.append((m.weight, m.bias))
+            elif not (k % 2 == 1 and isinstance(m, torch.nn.ReLU) and k < len(mods) - 1):
+                raise ValueError("set_policy: module %d of the Sequential is %s; expected Linear (with bias), ReLU, ..., Linear" %
+                                 (k, type(m).__name__))
+        layers = pairs
+    host = lambda t: t.detach().cpu().numpy() if torch is not None and isinstance(t, torch.Tensor) else t
+    layers = [(np.asarray(host(W), np.float32), np.asarray(host(b), np.float32)) for W, b in layers]
+    if not 2 <= len(layers) <= _lib.POLICY_MAX_LAYERS:
+        raise ValueError("set_policy: %d layers, must be 2 .. %d" % (len(layers), _lib.POLICY_MAX_LAYERS))
+    Ws, bs, widths, P = [], [], [], None
+    for l, (W, b) in enumerate(layers):
+        if W.ndim == 2 and b.ndim == 1:
+            W, b = W[None], b[None]
+        if W.ndim != 3 or b.ndim != 2 or b.shape != W.shape[:2]:
+            raise ValueError("set_policy: layer %d: W %s and b %s are not [out, in] and [out] (or [P, out, in] and [P, out])" %
+                             (l, W.shape, b.shape))
+        if P is None:
+            P, widths = W.shape[0], [W.shape[2]]
+        if W.shape[0] != P:
+            raise ValueError("set_policy: layer %d holds %d sets, layer 0 holds %d" % (l, W.shape[0], P))
+        if W.shape[2] != widths[-1]:
+            raise ValueError("set_policy: layer %d reads %d values, the layer before it writes %d" % (l, W.shape[2], widths[-1]))
+        if not (np.isfinite(W).all() and np.isfinite(b).all()):
+            raise ValueError("set_policy: layer %d holds a value that is not finite" % l)
+        widths.append(W.shape[1])
+        Ws.append(np.ascontiguousarray(W)); bs.append(np.ascontiguousarray(b))
+    if widths[0] != _lib.OBS_DIM:
+        raise ValueError("set_policy: the first layer reads %d values, an observation has %d" % (widths[0], _lib.OBS_DIM))
+    for l, w in enumerate(widths[1:-1], 1):
+        if w % 16 or not 16 <= w <= _lib.POLICY_MAX_WIDTH:
+            raise ValueError("set_policy: hidden width %d of layer %d, must be a multiple of 16 in 16 .. %d" % (w, l, _lib.POLICY_MAX_WIDTH))
+    if widths[-1] != 1:
+        raise ValueError("set_policy: the output layer has %d units, must be 1" % widths[-1])
+    return [int(w) for w in widths], int(P), Ws, bs
+
+
 class Snapshot:
     """A second set of the state buffers on the environment's device (ca_snapshot_*): made and filled by
     VecCollisionAvoidanceEnv.snapshot(), read by restore().  close() destroys it; the environment's close() invalidates every
@@ -999,6 +1068,135 @@ class VecCollisionAvoidanceEnv:
             a = np.asarray(actions, np.float32).reshape(1, self.A, self.N)
         out = self.rollout_actions(a, hold=k, returns=True, first_done=True, with_obs=with_obs, stats=stats, autoreset=autoreset)
         return out["obs"], out["returns"], out["first_done"] >= 0, {"first_done": out["first_done"]}
+
+    # ---- the policy on the device (ca_policy_*, ca_rollout_policy) ---------------------------------------
+    def set_policy(self, layers, sets=None, out="identity", limit=np.pi):
+        """Install a ReLU MLP policy over the 64-float observation with one output per agent, the heading offset step() takes
+        (ca_policy_configure).  layers: a list of (W, b) -- W [out, in], b [out], numpy or torch; with a leading P axis: P weight
+        sets -- or a torch.nn.Sequential of Linear and ReLU; 2 .. 4 layers, hidden widths multiples of 16 in 16 .. 128 (policy_layers
+        above).  sets [A] int: the set arena a plays (required with P > 1), so a population is evaluated side by side.  out="clip"
+        clamps the action to [-limit, limit].  The result is defined bit for bit (include/ca_env.h); calling it again replaces the
+        policy.  Configuration: it survives resets and stays with the slot under fork() / restore()."""
+        if out not in ("identity", "clip"):
+            raise ValueError("set_policy: out=%r, must be 'identity' or 'clip'" % (out,))
+        widths, P, Ws, bs = policy_layers(layers)
+        d = _lib.PolicyDesc(n_layers=len(Ws), src_is_device=0, n_sets=P, out_mode=_lib.POLICY_OUT_CLIP if out == "clip" else _lib.POLICY_OUT_IDENTITY,
+                            out_limit=float(limit))
+        for l, (W, b) in enumerate(zip(Ws, bs)):
+            d.width[l] = widths[l]
+            d.weights[l], d.weights_bytes[l] = W.ctypes.data, W.nbytes
+            d.bias[l], d.bias_bytes[l] = b.ctypes.data, b.nbytes
+        d.width[len(Ws)] = widths[-1]
+        if sets is not None:
+            if torch is not None and isinstance(sets, torch.Tensor):
+                sets = sets.detach().cpu().numpy()
+            s = np.asarray(sets)
+            if s.dtype.kind not in "iu" or s.shape != (self.A,):
+                raise ValueError("set_policy: sets must be an integer [A=%d] array, got %s %s" % (self.A, s.dtype, s.shape))
+            s = np.ascontiguousarray(s, np.int32)
+            d.set_of_arena, d.set_of_arena_bytes = s.ctypes.data, s.nbytes
+        elif P > 1:
+            raise ValueError("set_policy: %d weight sets need sets=[A] (the set every arena plays)" % P)
+        self._call("ca_policy_configure", self.h, C.byref(d))
+
+    def clear_policy(self):
+        self._call("ca_policy_clear", self.h)
+
+    def policy_info(self):
+        """dict(configured=, n_layers=, widths=[w0 .. wL], n_sets=) of the installed policy (ca_policy_info)."""
+        on, L, P, w = C.c_int32(0), C.c_int32(0), C.c_int32(0), (C.c_int32 * 5)()
+        self._call("ca_policy_info", self.h, C.byref(on), C.byref(L), C.byref(w), C.byref(P))
+        return dict(configured=bool(on.value), n_layers=L.value, widths=list(w)[:L.value + 1] if on.value else [], n_sets=P.value)
+
+    def _policy_bufs(self, specs, on_torch):
+        """{name: array} for the (name, shape, dtype) of specs: device tensors, or the handle's page-locked host arrays"""
+        if on_torch:
+            dev = torch.device("cuda", self.device)
+            tdt = {np.float32: torch.float32, np.int32: torch.int32}
+            return {n: torch.empty(tuple(max(int(d), 0) for d in shape), dtype=tdt[dt], device=dev) for n, shape, dt in specs}
+        return {n: self._actseq_host("policy_" + n, tuple(max(int(d), 1) if k == 0 else int(d) for k, d in enumerate(shape)), dt)
+                for n, shape, dt in specs}
+
+    def policy_actions(self, noise=None):
+        """The policy's actions [A, N] for the observation buffer as it stands (ca_policy_actions: one launch; observe() or a step
+        with_obs=True fills the buffer).  noise [A, N] float32 or None is added to the mean before the output mode."""
+        on_torch = self.use_torch
+        ptr = (lambda t: t.data_ptr()) if on_torch else (lambda a: a.ctypes.data)
+        out = self._policy_bufs([("act1", (self.A, self.N), np.float32)], on_torch)["act1"]
+        nz = None
+        if noise is not None:
+            if on_torch:
+                nz = torch.as_tensor(noise).detach().to(device=out.device, dtype=torch.float32).contiguous()
+            else:
+                if torch is not None and isinstance(noise, torch.Tensor):
+                    noise = noise.detach().cpu().numpy()
+                nz = self._actseq_host("policy_noise1", (self.A, self.N), np.float32)
+                nz[...] = np.asarray(noise, np.float32).reshape(self.A, self.N)
+            if tuple(nz.shape) != (self.A, self.N):
+                raise ValueError("policy_actions: noise must be [A=%d, N=%d], got %s" % (self.A, self.N, tuple(nz.shape)))
+        self._call("ca_policy_actions", self.h, ptr(nz) if nz is not None else None, ptr(out))
+        if on_torch:
+            return out
+        self.sync()
+        return np.array(out)
+
+    def rollout_policy(self, steps, hold=1, noise=None, weights=None, record=("obs", "actions", "rewards", "dones"), returns=True,
+                       first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False):
+        """`steps` steps under the installed policy without returning to the host (ca_rollout_policy): at every hold-th step
+        observe(), the policy on that observation (plus noise[t // hold] where given), then step() under the action for `hold`
+        steps.  The state, fields and statistics left are those of that loop, bit for bit.  noise [R, A, N] (R = ceil(steps /
+        hold)): exploration noise the caller drew; weights [steps]: as for rollout_actions().  record: which of the trajectory
+        records to write -- "obs" [R, A, N, 64] and "actions" [R, A, N], what the policy read and emitted per row; "rewards"
+        [steps, A, N] and "dones" [steps, A] (int32, the arenas' done flags) per step.  Returns a dict with those, returns [A, N],
+        first_done [A] and obs_last (with_obs=True: the observation of the final state); what was not asked for is None.  With
+        use_torch the arrays are device tensors filled on the handle's stream, else numpy arrays (the call synchronises).  Shapes:
+        policy_seq_shape."""
+        on_torch = self.use_torch
+        record = (record,) if isinstance(record, str) else tuple(record or ())
+        for r in record:
+            if r not in ("obs", "actions", "rewards", "dones"):
+                raise ValueError("rollout_policy: record holds %r; it may hold 'obs', 'actions', 'rewards', 'dones'" % (r,))
+        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
+        sh = policy_seq_shape(self.A, self.N, steps, hold, None if noise is None else tuple(noise.shape if is_t(noise) else np.shape(noise)),
+                              None if weights is None else tuple(weights.shape if is_t(weights) else np.shape(weights)))
+        steps, hold, R = int(steps), int(hold), sh["R"]
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
+                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        specs = [(n, sh[n], np.int32 if n in ("first_done", "dones") else np.float32)
+                 for n, want in (("returns", returns), ("first_done", first_done), ("obs", "obs" in record), ("actions", "actions" in record),
+                                 ("rewards", "rewards" in record), ("dones", "dones" in record)) if want]
+        bufs = self._policy_bufs(specs, on_torch)
+        if on_torch:
+            dev = torch.device("cuda", self.device)
+            nz = None if noise is None else torch.as_tensor(noise).detach().to(device=dev, dtype=torch.float32).contiguous()
+            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        else:
+            nz = w = None
+            if noise is not None:
+                nz = self._actseq_host("policy_noise", (max(R, 1), self.A, self.N), np.float32)
+                nz[:R] = np.asarray(noise.detach().cpu().numpy() if is_t(noise) else noise, np.float32)
+            if weights is not None:
+                w = self._actseq_host("policy_weights", (max(steps, 1),), np.float32)
+                w[:steps] = np.asarray(weights.detach().cpu().numpy() if is_t(weights) else weights, np.float32)
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        size = lambda n: int(np.prod(sh[n])) * 4
+        b = bufs.get
+        seq = _lib.PolicySeq(hold=hold, noise=ptr(nz) if R else None, noise_bytes=size("noise") if nz is not None else 0,
+                             weights=ptr(w) if steps else None, weights_bytes=size("weights") if w is not None else 0,
+                             returns=ptr(b("returns")), returns_bytes=size("returns") if returns else 0,
+                             first_done=ptr(b("first_done")), first_done_bytes=size("first_done") if first_done else 0,
+                             obs_out=ptr(b("obs")) if R else None, obs_out_bytes=size("obs") if "obs" in bufs else 0,
+                             actions_out=ptr(b("actions")) if R else None, actions_out_bytes=size("actions") if "actions" in bufs else 0,
+                             rewards_out=ptr(b("rewards")) if steps else None, rewards_out_bytes=size("rewards") if "rewards" in bufs else 0,
+                             done_out=ptr(b("dones")) if steps else None, done_out_bytes=size("dones") if "dones" in bufs else 0)
+        self._call("ca_rollout_policy", self.h, steps, flags, C.byref(seq))
+        if not on_torch:
+            self.sync()
+            bufs = {n: np.array(a[:sh[n][0]]) if n in ("obs", "actions", "rewards", "dones") else np.array(a) for n, a in bufs.items()}
+        out = {n: bufs.get(n) for n in ("returns", "first_done", "obs", "actions", "rewards", "dones")}
+        out["obs_last"] = self._obs_out() if with_obs else None
+        return out
 
     # ---- ALAN online learning (ALAN_true.py:569-628) -----------------------------------------------
     def alan_configure(self, actions, temp=0.2, timewindow=2.0, time_step=1 / 60.):

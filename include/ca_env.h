@@ -626,6 +626,95 @@ typedef struct ca_action_seq {
 } ca_action_seq;
 int ca_rollout_actions(ca_env* env, int32_t steps, uint32_t flags, const ca_action_seq* seq);
 
+/* A policy on the device: the reference's model is a shared-weights 64-64 ReLU MLP over the 64-float laser observation that emits
+ * one heading offset per agent (run_rllib.py:35-52), stepped in a loop (run_rllib.py:103-125).  Here the policy is configuration of
+ * the handle and observation -> MLP -> action -> step runs for `steps` steps in one call.
+ *   Definition, bit for bit.  L linear layers, 2 <= L <= 4, widths w[0] = CA_OBS_DIM, hidden widths w[1 .. L-1] each a multiple of 16
+ *   in 16 .. 128, w[L] = 1.  Layer l has W_l f32 [w[l], w[l-1]] and b_l f32 [w[l]] (the torch.nn.Linear layout).  For a row x (one
+ *   agent's observation), layer l and output j, in fp32:
+ *       acc = b_l[j];  for k = 0 .. w[l-1]-1 ascending: acc = fmaf(x[k], W_l[j][k], acc)        (one rounding per step)
+ *       hidden layers: y[j] = acc > 0 ? acc : +0.0f            output layer: mean = acc
+ *       action = out(mean + noise)                               (the add only where noise is given, one fp32 add)
+ *       out = identity (CA_POLICY_OUT_IDENTITY) | fminf(fmaxf(v, -limit), limit) (CA_POLICY_OUT_CLIP)
+ *   A row's result depends on its observation and its arena's weight set only.
+ * ca_policy_configure: n_sets = P >= 1 weight sets, weights[l] f32 [P, w[l+1], w[l]] and bias[l] f32 [P, w[l+1]] (host memory, or
+ * device memory with src_is_device), set_of_arena i32 [A] HOST memory (NULL with P = 1: set 0 everywhere): arena a plays set
+ * set_of_arena[a], so a population is evaluated side by side.  Every value is checked before anything changes: n_layers, a width,
+ * out_mode, n_sets < 1, a NULL array, a NaN or negative out_limit under CA_POLICY_OUT_CLIP, a NULL set_of_arena with P > 1 ->
+ * CA_EINVAL; an array smaller than its layout -> CA_ESIZE; a non-finite weight or bias (ca_last_error names the layer, the set and
+ * the element) or a set index outside 0 .. P-1 (names the arena) -> CA_ERANGE.  The call repacks the weights for the kernel and
+ * drains the stream; calling it again replaces the policy.  Configuration, like the ALAN action sets: no ca_field, it persists across
+ * resets and stays with the SLOT under ca_arena_gather and ca_snapshot_load (fork arena 0 into every slot: each slot plays its own set).
+ * ca_policy_clear removes it; ca_policy_info reports *configured, and where configured *n_layers, width[0 .. L] and *n_sets (any
+ * pointer may be NULL).
+ * ca_policy_actions: ONE launch that reads the handle's observation buffer as it stands (what ca_observe / CA_F_OBS / ca_set left, a
+ * buffer bound with ca_bind_obs included) and writes actions_out, DEVICE f32 [A, N]; noise DEVICE f32 [A, N] or NULL.  No policy, or a
+ * NULL actions_out -> CA_EINVAL.  Asynchronous on the handle's stream. */
+#define CA_POLICY_OUT_IDENTITY 0
+#define CA_POLICY_OUT_CLIP 1
+#define CA_POLICY_MAX_LAYERS 4
+#define CA_POLICY_MAX_WIDTH 128
+typedef struct ca_policy_desc {
+    int32_t  n_layers;                           /* L: 2 .. CA_POLICY_MAX_LAYERS */
+    int32_t  width[CA_POLICY_MAX_LAYERS + 1];    /* w[0 .. L] */
+    const float* weights[CA_POLICY_MAX_LAYERS];  /* layer l: f32 [P, w[l+1], w[l]] */
+    size_t   weights_bytes[CA_POLICY_MAX_LAYERS];
+    const float* bias[CA_POLICY_MAX_LAYERS];     /* layer l: f32 [P, w[l+1]] */
+    size_t   bias_bytes[CA_POLICY_MAX_LAYERS];
+    int32_t  src_is_device;                      /* weights and bias lie in device memory */
+    int32_t  n_sets;                             /* P >= 1 */
+    const int32_t* set_of_arena;                 /* HOST i32 [A], or NULL when P = 1 */
+    size_t   set_of_arena_bytes;
+    int32_t  out_mode;                           /* CA_POLICY_OUT_* */
+    float    out_limit;                          /* CA_POLICY_OUT_CLIP: actions are clamped to [-out_limit, out_limit] */
+} ca_policy_desc;
+int ca_policy_configure(ca_env* env, const ca_policy_desc* desc);
+int ca_policy_clear(ca_env* env);
+int ca_policy_info(ca_env* env, int32_t* configured, int32_t* n_layers, int32_t* width, int32_t* n_sets);
+int ca_policy_actions(ca_env* env, const float* noise, float* actions_out);
+
+/* Closed-loop policy rollouts: `steps` steps under the configured policy without returning to the host.
+ *   Definition: the state, every field, every statistic, returns and first_done are bit for bit those of the loop
+ *       for t in 0 .. steps-1:
+ *           if t % hold == 0: ca_observe; ca_policy_actions(noise row t / hold) -> act       (record obs row t / hold, action row t / hold)
+ *           ca_step(env, act, flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE))            (record reward_t, done_t)
+ *   with returns and first_done as ca_rollout_actions defines them (weights, freezing, absent rows, the sum across a respawn: the
+ *   rules above apply verbatim).  R = ceil(steps / hold).  The handle's observation buffer is left holding the last row's observation
+ *   (CA_F_OBS: that of the final state).
+ *   Records, all optional DEVICE buffers, written for every row, arena and step: obs_out f32 [R, A, N, 64] (16-byte aligned) and
+ *   actions_out f32 [R, A, N] -- what the policy read and emitted at the start of row r --, rewards_out f32 [steps, A, N] -- what
+ *   CA_FLD_REWARD holds after step t -- and done_out i32 [steps, A] -- arena_done after step t.  An arena frozen under CA_F_FREEZE
+ *   repeats its unchanged observation and the reward the field holds; an absent row of ca_set_agent_counts records the policy of its
+ *   zero observation, which nothing reads.
+ * Flags as for ca_rollout_actions: CA_F_OBS and CA_F_CONTACT each add ONE launch behind the last step; CA_F_NODONE or an unknown bit
+ * -> CA_EINVAL.  Checks, all before anything is launched (a failure advances nothing): a NULL env or seq, steps < 0, hold < 1, no
+ * policy configured, a misaligned obs_out -> CA_EINVAL; a buffer smaller than its layout -> CA_ESIZE (ca_last_error names the buffer
+ * and the size it needs).  steps == 0 writes zeros to returns and -1 to first_done where given, and nothing else.  The sticky
+ * overflow error works as in ca_rollout.  Asynchronous on the handle's stream; the struct itself is read before the call returns.
+ * Every kind of handle takes the same form: per row one observation launch and one policy launch (which stores the obs and action
+ * records itself), per step the launch (sequence) of ca_step and a small accumulate-and-record kernel; ca_profile counts the policy
+ * kernel and the record kernel under kind 3. */
+typedef struct ca_policy_seq {
+    int32_t  hold;            /* >= 1: every action row is held for `hold` consecutive steps */
+    const float* noise;       /* DEVICE f32 [R, A, N], or NULL: exploration noise added to the mean, drawn by the caller */
+    size_t   noise_bytes;
+    const float* weights;     /* DEVICE f32 [steps], or NULL = 1 for every step */
+    size_t   weights_bytes;
+    float*   returns;         /* DEVICE f32 [A, N], or NULL */
+    size_t   returns_bytes;
+    int32_t* first_done;      /* DEVICE i32 [A], or NULL */
+    size_t   first_done_bytes;
+    float*   obs_out;         /* DEVICE f32 [R, A, N, 64], or NULL */
+    size_t   obs_out_bytes;
+    float*   actions_out;     /* DEVICE f32 [R, A, N], or NULL */
+    size_t   actions_out_bytes;
+    float*   rewards_out;     /* DEVICE f32 [steps, A, N], or NULL */
+    size_t   rewards_out_bytes;
+    int32_t* done_out;        /* DEVICE i32 [steps, A], or NULL */
+    size_t   done_out_bytes;
+} ca_policy_seq;
+int ca_rollout_policy(ca_env* env, int32_t steps, uint32_t flags, const ca_policy_seq* seq);
+
 /* The reference's simulator keeps EVERY obstacle edge within range of an agent (sim.getAgentNumObstacleNeighbors /
  * getAgentObstacleNeighbor, env.py:249, 301-318, iterate them all); this library's lists hold max_obst_neighbors and drop the
  * farthest edges beyond that.  So that such a deviation cannot pass unnoticed, an overflow is a sticky error of the handle:
@@ -664,7 +753,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
