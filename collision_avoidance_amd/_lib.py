@@ -40,9 +40,13 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info",
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
            "ca_fork_bytes_per_arena", "ca_rollout_actions",
-           "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy")
+           "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy",
+           "ca_nav_configure", "ca_nav_clear", "ca_nav_info", "ca_nav_get_field", "ca_nav_pref", "ca_rollout_nav", "ca_nav_mask_build")
 POLICY_OUT_IDENTITY, POLICY_OUT_CLIP = 0, 1   # out_mode of a policy (struct ca_policy_desc)
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 128
+NAV_MAX_CELLS, NAV_MAX_GOALS, NAV_MAX_LOOKAHEAD = 32768, 16, 8   # limits of a navigation (struct ca_nav_desc)
+NAV_STAY, NAV_NONE = 8, 9   # `next` of the source cell / of a cell nothing leads out of
+NAV_OFFSETS = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))   # (dx, dy) of pointer k = 0 .. 7
 
 
 class Config(C.Structure):
@@ -95,6 +99,13 @@ class PolicySeq(C.Structure):
                 ("returns", C.c_void_p), ("returns_bytes", C.c_size_t), ("first_done", C.c_void_p), ("first_done_bytes", C.c_size_t),
                 ("obs_out", C.c_void_p), ("obs_out_bytes", C.c_size_t), ("actions_out", C.c_void_p), ("actions_out_bytes", C.c_size_t),
                 ("rewards_out", C.c_void_p), ("rewards_out_bytes", C.c_size_t), ("done_out", C.c_void_p), ("done_out_bytes", C.c_size_t)]
+
+
+class NavDesc(C.Structure):
+    """struct ca_nav_desc (include/ca_env.h): the grid, the targets and the agents' classes of a navigation."""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("gx", C.c_int32), ("gy", C.c_int32), ("clearance", C.c_float),
+                ("n_goals", C.c_int32), ("per_arena", C.c_int32), ("targets", C.c_void_p), ("targets_bytes", C.c_size_t),
+                ("agent_class", C.c_void_p), ("class_bytes", C.c_size_t), ("lookahead", C.c_int32)]
 
 
 class EdgeGridDesc(C.Structure):
@@ -168,6 +179,13 @@ def load():
     L.ca_policy_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32 * 5), C.POINTER(i32)]
     L.ca_policy_actions.argtypes = [vp, vp, vp]
     L.ca_rollout_policy.argtypes = [vp, i32, u32, C.POINTER(PolicySeq)]
+    L.ca_nav_configure.argtypes = [vp, C.POINTER(NavDesc)]
+    L.ca_nav_clear.argtypes = [vp]
+    L.ca_nav_info.argtypes = [vp] + [C.POINTER(i32)] * 6
+    L.ca_nav_get_field.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    L.ca_nav_pref.argtypes = [vp, vp, u32]
+    L.ca_rollout_nav.argtypes = [vp, i32, u32, C.POINTER(Trace)]
+    L.ca_nav_mask_build.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, i32, i32, C.c_float, vp, i32]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]
@@ -216,6 +234,18 @@ def edge_grid_build(edges_pq, rng):
     check(L, None, L.ca_edge_grid_build(ptr, len(pq), float(rng), C.byref(d), cs.ctypes.data_as(C.c_void_p), len(cs),
                                         en.ctypes.data_as(C.c_void_p), len(en)), "ca_edge_grid_build")
     return d, cs, en[:d.n_entries]
+
+
+def nav_mask_build(edges_pq, x0, y0, cell, gx, gy, clearance):
+    """The blocked mask of a navigation grid, built on the host (ca_nav_mask_build; no device): edges_pq [n, 4] = (px, py, qx, qy).
+    Returns uint8 [gy, gx], 1 where the cell's centre lies within `clearance` of an edge; a refusal raises RuntimeError."""
+    import numpy as np
+    L = load()
+    pq = np.ascontiguousarray(edges_pq, np.float32).reshape(-1, 4)
+    out = np.zeros((max(int(gy), 0), max(int(gx), 0)), np.uint8)
+    check(L, None, L.ca_nav_mask_build(pq.ctypes.data_as(C.c_void_p) if len(pq) else None, len(pq), float(x0), float(y0), float(cell),
+                                       int(gx), int(gy), float(clearance), out.ctypes.data_as(C.c_void_p), out.size), "ca_nav_mask_build")
+    return out
 
 
 def check(L, handle, rc, what):

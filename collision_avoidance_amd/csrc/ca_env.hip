@@ -17,6 +17,7 @@
 
 #include "ca_kernels.h"
 #include "ca_edge_grid_host.h"
+#include "ca_nav_host.h"
 
 using namespace ca;
 
@@ -110,6 +111,17 @@ struct ca_env {
         float *d_wp = nullptr, *d_bp = nullptr, *act = nullptr;
         int* d_set = nullptr;
     } pol;
+    // the navigation fields (ca_nav_configure; ca_nav.h, ca_nav_host.h): configuration, like the policy.  d_dist / d_next hold the
+    // fields of `sets` x G targets over gx x gy cells, d_class the agents' targets, h_blocked the sets' masks (a byte per cell)
+    struct Nav {
+        bool on = false;
+        float x0 = 0.0f, y0 = 0.0f, cell = 0.0f, ics = 0.0f, clearance = 0.0f;
+        int gx = 0, gy = 0, G = 0, sets = 0, per_arena = 0, lookahead = 0, sweeps_max = 0, block = 0;
+        float* d_dist = nullptr;
+        unsigned char* d_next = nullptr;
+        int* d_class = nullptr;
+        std::vector<unsigned char> h_blocked;
+    } nav;
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -121,7 +133,7 @@ struct ca_env {
     int LS = 1, apb = 1, linv = 65536, dense = 0;   // lanes per arena, arenas per workgroup, ceil(2^16 / LS), packed back to back (ca_common.h StepArgs)
     // diagnostic environment switches, read ONCE by ca_create (a handle never changes behaviour because the environment did):
     // -1 = unset, else the first character's digit
-    struct { int reg_lines = -1, pair = -1, alan_fused = -1, nbr_seed = -1; } sw;
+    struct { int reg_lines = -1, pair = -1, alan_fused = -1, nbr_seed = -1, nav_block = 0; } sw;
     int ST = 0, KT = 16;  // solve-kernel variant: ST > 0 = register lines with ST obstacle slots; KT = KMAX
     int SMX = 4;          // ... and the capacity of its obstacle-neighbour list (4, or 16: agents with more than ST are solved apart;
                           // SWIDE = 64 with ST = 0: the wide LDS-table kernel of a handle with max_obst_neighbors > 16)
@@ -968,6 +980,8 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
         auto digit = [](const char* name) { const char* v = getenv(name); return (v && v[0] >= '0' && v[0] <= '9') ? v[0] - '0' : -1; };
         e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.pair = digit("CA_PAIR"); e->sw.alan_fused = digit("CA_ALAN_FUSED");
         e->sw.nbr_seed = digit("CA_NBR_SEED");
+        const char* nb = getenv("CA_NAV_BLOCK");   // 256 / 1024 forces the field kernel's block (tools/nav_cost.py measures both)
+        e->sw.nav_block = nb ? atoi(nb) : 0;
     }
     e->tiled = tiled;
     e->twide = twide;
@@ -1168,7 +1182,7 @@ int ca_destroy(ca_env* e) {
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
-                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set,
+                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->nav.d_dist, e->nav.d_next, e->nav.d_class,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -1313,6 +1327,14 @@ static int make_edge_grids(ca_env* e, const std::vector<ObstDev>& all, const std
     return CA_OK;
 }
 
+// drops the navigation (ca_nav_clear; install_tables: fields of the old tables would be stale).  The stream is idle.
+static void nav_release(ca_env* e) {
+    if (e->nav.d_dist) hipFree(e->nav.d_dist);
+    if (e->nav.d_next) hipFree(e->nav.d_next);
+    if (e->nav.d_class) hipFree(e->nav.d_class);
+    e->nav = ca_env::Nav();
+}
+
 // installs the table(s): `all` = every table concatenated, `offs` empty (one table for all arenas) or [A + 1].
 // The new tables are allocated and uploaded first and swapped in only when everything succeeded: a failure leaves the
 // handle as it was.  The obstacle-neighbour lists left by the last step refer to the old tables, so their counts are
@@ -1379,6 +1401,7 @@ static int install_tables(ca_env* e, std::vector<ObstDev>& all, std::vector<int>
         free_edge_grids(e->eg);
         e->eg = n_eg;
     }
+    nav_release(e);   // (the fields were relaxed round the old tables' edges)
     return alan_pick(e);   // (the form of the ALAN step follows the solve kernel)
 }
 
@@ -3008,6 +3031,231 @@ int ca_rollout_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_
         const int rc = do_step(e, e->pol.act, sf);
         if (rc) return rc;
         HIPCHK(e, launch_policy_record(e, seq, pl, flags, t));
+    }
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+// ---- navigation fields (include/ca_env.h ca_nav_desc; ca_nav.h, ca_nav_host.h) --------------------------------------
+// the field kernel's block: one workgroup relaxes a whole grid, so a large grid wants every lane a workgroup can have, and many small
+// grids want several workgroups per CU (profiles/nav_cost.txt has the two measured)
+enum { NAV_BIG_CELLS = 4096 };
+static int nav_block_for(const ca_env* e, int cells) {
+    if (e->sw.nav_block == 256 || e->sw.nav_block == 1024) return e->sw.nav_block;
+    return cells > NAV_BIG_CELLS ? 1024 : 256;
+}
+static hipError_t launch_nav_field(ca_env* e, const NavFieldArgs& f, int fields, int block) {
+    const size_t lds = ((size_t)f.cells + (size_t)f.mw) * 4;
+    void (*fn)(NavFieldArgs) = block == 1024 ? nav_field_kernel<1024> : nav_field_kernel<256>;
+    if (lds > 48 * 1024) {
+        const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (r != hipSuccess) return r;
+    }
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, fn, dim3((unsigned)fields), dim3((unsigned)block), lds, e->stream, f);
+    return hipGetLastError();
+}
+
+int ca_nav_mask_build(const float* edges_pq, int32_t n_edges, float x0, float y0, float cell, int32_t gx, int32_t gy, float clearance,
+                      uint8_t* blocked, int32_t cells_cap) {
+    const char* who = "ca_nav_mask_build";
+    if (!blocked || n_edges < 0 || (n_edges > 0 && !edges_pq)) return fail(nullptr, CA_EINVAL, "%s: bad argument", who);
+    if (!ca_nav::grid_ok(gx, gy))
+        return fail(nullptr, CA_EINVAL, "%s: a grid of %d x %d cells (1 .. %d per axis, at most %d in all)", who, (int)gx, (int)gy, (int)ca_nav::MAX_SIDE,
+                    (int)ca_nav::MAX_CELLS);
+    if (cells_cap < gx * gy) return fail(nullptr, CA_ESIZE, "%s: blocked needs %d bytes (cells_cap=%d)", who, (int)(gx * gy), (int)cells_cap);
+    ca_nav::mask_build(edges_pq, n_edges, x0, y0, cell, gx, gy, clearance, blocked);
+    return CA_OK;
+}
+
+int ca_nav_configure(ca_env* e, const ca_nav_desc* d) {
+    const char* who = "ca_nav_configure";
+    static_assert(NAV_STAY == ca_nav::STAY && NAV_NONE == ca_nav::NONE, "one pointer code");
+    if (!e || !d || !d->targets || !d->agent_class) return fail(e, CA_EINVAL, "%s: null argument", who);
+    const int A = e->cfg.n_arenas, N = e->cfg.n_agents, G = d->n_goals;
+    const bool per = d->per_arena != 0;
+    if (d->per_arena != 0 && d->per_arena != 1) return fail(e, CA_EINVAL, "%s: per_arena=%d (0 or 1)", who, (int)d->per_arena);
+    if (!per && !e->h_tab_off.empty())
+        return fail(e, CA_EINVAL, "%s: per_arena=0 asks for one field set, but the handle holds an obstacle table per arena (ca_set_obstacles_per_arena): "
+                    "configure with per_arena=1 and targets [A, G, 2]", who);
+    if (G < 1 || G > ca_nav::MAX_GOALS) return fail(e, CA_EINVAL, "%s: n_goals=%d (1 .. %d)", who, G, (int)ca_nav::MAX_GOALS);
+    if (d->lookahead < 1 || d->lookahead > ca_nav::MAX_LOOKAHEAD) return fail(e, CA_EINVAL, "%s: lookahead=%d (1 .. %d)", who, (int)d->lookahead, (int)ca_nav::MAX_LOOKAHEAD);
+    if (!ca_nav::grid_ok(d->gx, d->gy))
+        return fail(e, CA_EINVAL, "%s: a grid of %d x %d cells (1 .. %d per axis, at most %d in all)", who, (int)d->gx, (int)d->gy, (int)ca_nav::MAX_SIDE,
+                    (int)ca_nav::MAX_CELLS);
+    const int sets = per ? A : 1, gx = d->gx, gy = d->gy, cells = gx * gy, fields = sets * G;
+    const size_t an = AN(e);
+    if (d->targets_bytes != (size_t)fields * 2 * 4)
+        return fail(e, CA_ESIZE, "%s: targets holds %zu bytes (f32 %s), got %zu", who, (size_t)fields * 2 * 4, per ? "[A, G, 2]" : "[G, 2]", d->targets_bytes);
+    if (d->class_bytes != an * 4) return fail(e, CA_ESIZE, "%s: agent_class holds %zu bytes (i32 [A=%d, N=%d]), got %zu", who, an * 4, A, N, d->class_bytes);
+    if (!(d->cell >= CA_MIN_LENGTH && d->cell <= CA_MAX_LENGTH))   // (also false for NaN)
+        return fail(e, CA_ERANGE, "%s: cell=%g is outside [%g, %g] or not a number", who, (double)d->cell, (double)CA_MIN_LENGTH, (double)CA_MAX_LENGTH);
+    if (!(d->clearance == 0.0f || (d->clearance >= CA_MIN_LENGTH && d->clearance <= CA_MAX_LENGTH)))
+        return fail(e, CA_ERANGE, "%s: clearance=%g is neither 0 nor inside [%g, %g]", who, (double)d->clearance, (double)CA_MIN_LENGTH, (double)CA_MAX_LENGTH);
+    if (!(fabsf(d->x0) <= CA_MAX_COORD && fabsf(d->y0) <= CA_MAX_COORD))
+        return fail(e, CA_ERANGE, "%s: the origin (%g, %g) is beyond %g or not a number", who, (double)d->x0, (double)d->y0, (double)CA_MAX_COORD);
+    for (size_t q = 0; q < an; ++q)
+        if (d->agent_class[q] < -1 || d->agent_class[q] >= G)
+            return fail(e, CA_ERANGE, "%s: agent_class=%d of arena %zu, agent %zu is outside -1 .. %d", who, (int)d->agent_class[q], q / (size_t)N, q % (size_t)N, G - 1);
+    const float cs = d->cell, ics = 1.0f / cs;
+    // the masks and the sources, on the host
+    std::vector<unsigned char> blocked((size_t)sets * cells);
+    std::vector<float> pq;
+    for (int s = 0; s < sets; ++s) {
+        const int t0 = e->h_tab_off.empty() ? 0 : e->h_tab_off[s], n = e->h_tab_off.empty() ? (int)e->h_obst.size() : e->h_tab_off[s + 1] - e->h_tab_off[s];
+        pq.resize((size_t)4 * n);
+        for (int i = 0; i < n; ++i) {
+            const ObstDev& o = e->h_obst[(size_t)t0 + i];
+            pq[4 * i] = o.px; pq[4 * i + 1] = o.py; pq[4 * i + 2] = o.qx; pq[4 * i + 3] = o.qy;
+        }
+        ca_nav::mask_build(pq.data(), n, d->x0, d->y0, cs, gx, gy, d->clearance, blocked.data() + (size_t)s * cells);
+    }
+    std::vector<int> source((size_t)fields);
+    const double bx1 = (double)d->x0 + (double)gx * (double)cs, by1 = (double)d->y0 + (double)gy * (double)cs;
+    for (int f = 0; f < fields; ++f) {
+        const float tx = d->targets[2 * f], ty = d->targets[2 * f + 1];
+        const int s = f / G, g = f % G;
+        if (!(tx >= d->x0 && (double)tx <= bx1 && ty >= d->y0 && (double)ty <= by1))   // (also false for NaN)
+            return fail(e, CA_ERANGE, "%s: target (%g, %g) of arena %d, goal %d is outside the grid box [%g, %g] x [%g, %g] or not a number", who,
+                        (double)tx, (double)ty, per ? s : -1, g, (double)d->x0, bx1, (double)d->y0, by1);
+        const int c = ca_nav::cell(ty, d->y0, ics, gy) * gx + ca_nav::cell(tx, d->x0, ics, gx);
+        if (blocked[(size_t)s * cells + c])
+            return fail(e, CA_ERANGE, "%s: target (%g, %g) of arena %d, goal %d lies in a blocked cell (%d, %d): within clearance %g of an obstacle edge", who,
+                        (double)tx, (double)ty, per ? s : -1, g, c % gx, c / gx, (double)d->clearance);
+        source[f] = c;
+    }
+    const int mw = (cells + 31) / 32;
+    std::vector<unsigned> bits((size_t)sets * mw, 0u);
+    for (int s = 0; s < sets; ++s)
+        for (int c = 0; c < cells; ++c)
+            if (blocked[(size_t)s * cells + c]) bits[(size_t)s * mw + (c >> 5)] |= 1u << (c & 31);
+    // the new buffers, the upload, the relaxation; swapped in only when all of it succeeded
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    ca_env::Nav n;
+    unsigned* d_bits = nullptr;
+    int *d_src = nullptr, *d_sweeps = nullptr;
+    std::vector<int> sweeps((size_t)fields, 0);
+    hipError_t r = hipMalloc((void**)&n.d_dist, (size_t)fields * cells * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&n.d_next, (size_t)fields * cells);
+    if (r == hipSuccess) r = hipMalloc((void**)&n.d_class, an * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&d_bits, bits.size() * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&d_src, (size_t)fields * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&d_sweeps, (size_t)fields * 4);
+    if (r == hipSuccess) r = hipMemcpyAsync(n.d_class, d->agent_class, an * 4, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(d_bits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, e->stream);
+    if (r == hipSuccess) r = hipMemcpyAsync(d_src, source.data(), (size_t)fields * 4, hipMemcpyHostToDevice, e->stream);
+    n.block = nav_block_for(e, cells);
+    if (r == hipSuccess) {
+        NavFieldArgs f;
+        f.mask = d_bits; f.source = d_src; f.dist = n.d_dist; f.next = n.d_next; f.sweeps = d_sweeps;
+        f.gx = gx; f.gy = gy; f.cells = cells; f.mw = mw; f.G = G;
+        f.w_axis = cs; f.w_diag = cs * 1.41421354f;
+        r = launch_nav_field(e, f, fields, n.block);
+    }
+    if (r == hipSuccess) r = hipMemcpyAsync(sweeps.data(), d_sweeps, (size_t)fields * 4, hipMemcpyDeviceToHost, e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    if (d_bits) hipFree(d_bits);
+    if (d_src) hipFree(d_src);
+    if (d_sweeps) hipFree(d_sweeps);
+    if (r != hipSuccess) {
+        if (n.d_dist) hipFree(n.d_dist);
+        if (n.d_next) hipFree(n.d_next);
+        if (n.d_class) hipFree(n.d_class);
+        return fail(e, CA_EHIP, "%s: %s (the handle's navigation is as it was)", who, hipGetErrorString(r));
+    }
+    n.on = true;
+    n.x0 = d->x0; n.y0 = d->y0; n.cell = cs; n.ics = ics; n.clearance = d->clearance;
+    n.gx = gx; n.gy = gy; n.G = G; n.sets = sets; n.per_arena = per ? 1 : 0; n.lookahead = d->lookahead;
+    for (int f = 0; f < fields; ++f) n.sweeps_max = std::max(n.sweeps_max, sweeps[f]);
+    n.h_blocked.swap(blocked);
+    nav_release(e);
+    e->nav = std::move(n);
+    return CA_OK;
+}
+
+int ca_nav_clear(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    nav_release(e);
+    return CA_OK;
+}
+
+int ca_nav_info(ca_env* e, int32_t* configured, int32_t* gx, int32_t* gy, int32_t* n_goals, int32_t* n_sets, int32_t* sweeps_max) {
+    if (!e) return CA_EINVAL;
+    const ca_env::Nav& n = e->nav;
+    if (configured) *configured = n.on ? 1 : 0;
+    if (gx) *gx = n.gx;
+    if (gy) *gy = n.gy;
+    if (n_goals) *n_goals = n.G;
+    if (n_sets) *n_sets = n.sets;
+    if (sweeps_max) *sweeps_max = n.sweeps_max;
+    return CA_OK;
+}
+
+int ca_nav_get_field(ca_env* e, int32_t arena, int32_t goal, float* dist, uint8_t* next, uint8_t* blocked, int32_t cells_cap) {
+    const char* who = "ca_nav_get_field";
+    if (!e) return CA_EINVAL;
+    const ca_env::Nav& n = e->nav;
+    if (!n.on) return fail(e, CA_EINVAL, "%s: call ca_nav_configure first", who);
+    if (arena < 0 || arena >= e->cfg.n_arenas) return fail(e, CA_ERANGE, "%s: arena %d of %d", who, (int)arena, e->cfg.n_arenas);
+    if (goal < 0 || goal >= n.G) return fail(e, CA_ERANGE, "%s: goal %d of %d", who, (int)goal, n.G);
+    const int cells = n.gx * n.gy, set = n.per_arena ? arena : 0;
+    if (cells_cap < cells) return fail(e, CA_ESIZE, "%s: a field holds %d cells (cells_cap=%d)", who, cells, (int)cells_cap);
+    const size_t f = (size_t)set * n.G + (size_t)goal;
+    HIPCHK(e, hipSetDevice(e->device));
+    if (dist) HIPCHK(e, hipMemcpyAsync(dist, n.d_dist + f * cells, (size_t)cells * 4, hipMemcpyDeviceToHost, e->stream));
+    if (next) HIPCHK(e, hipMemcpyAsync(next, n.d_next + f * cells, (size_t)cells, hipMemcpyDeviceToHost, e->stream));
+    if (dist || next) HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (blocked) memcpy(blocked, n.h_blocked.data() + (size_t)set * cells, (size_t)cells);
+    return CA_OK;
+}
+
+// the preferred-velocity launch (kind 3 for ca_profile)
+static hipError_t launch_nav_pref(ca_env* e, float* dist_out, bool freeze) {
+    const ca_env::Nav& n = e->nav;
+    NavPrefArgs p;
+    p.pos_x = e->pos_x; p.pos_y = e->pos_y; p.goal_x = e->goal_x; p.goal_y = e->goal_y;
+    p.agent_done = e->agent_done; p.arena_done = e->arena_done; p.agent_counts = e->ac ? e->d_counts : nullptr;
+    p.cls = n.d_class; p.dist = n.d_dist; p.next = n.d_next;
+    p.pref_x = e->pref_x; p.pref_y = e->pref_y; p.dist_out = dist_out;
+    p.an = (unsigned)AN(e); p.N = e->cfg.n_agents; p.G = n.G; p.gx = n.gx; p.gy = n.gy; p.cells = n.gx * n.gy;
+    p.per_arena = n.per_arena; p.lookahead = n.lookahead; p.freeze = freeze ? 1 : 0;
+    p.x0 = n.x0; p.y0 = n.y0; p.cell = n.cell; p.ics = n.ics;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, nav_pref_kernel, dim3((p.an + 255) / 256), dim3(256), 0, e->stream, p);
+    return hipGetLastError();
+}
+
+int ca_nav_pref(ca_env* e, float* dist_out, uint32_t flags) {
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "ca_nav_pref: call ca_nav_configure first");
+    if (flags & ~CA_F_FREEZE) return fail(e, CA_EINVAL, "ca_nav_pref: flags=0x%x (0 or CA_F_FREEZE)", flags);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_nav_pref(e, dist_out, (flags & CA_F_FREEZE) != 0));
+    return CA_OK;
+}
+
+int ca_rollout_nav(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr) {
+    const char* who = "ca_rollout_nav";
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "%s: call ca_nav_configure first", who);
+    if (steps < 0) return fail(e, CA_EINVAL, "%s: steps=%d", who, (int)steps);
+    if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_NODONE | CA_F_FREEZE | CA_F_CONTACT))
+        return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
+    TracePlan pl = {0, 0};
+    if (tr) { const int rc = trace_check(e, who, steps, tr, &pl); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, who); if (rs) return rs; }
+    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, below)
+    for (int s = 0; s < steps; ++s) {   // the launch of ca_nav_pref, the launches of ca_orca_step, the record kernel behind every `every`-th
+        if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+        HIPCHK(e, launch_nav_pref(e, nullptr, (flags & CA_F_FREEZE) != 0));
+        const int rc = do_step(e, nullptr, sf);
+        if (rc) return rc;
+        if (tr && (s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
     }
     if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
     if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));

@@ -944,8 +944,9 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_get_contacts", self.h, *[_ptr(out[name]) for name, _ in self._CONTACT_PLANES], self.A * self.N * 4, 0)
         return out
 
-    def _traced(self, name, steps, flags, trace):
-        """ca_rollout_trace / ca_alan_rollout_trace into torch tensors on the handle's device; returns dict(agents, arenas)."""
+    def _trace_bufs(self, steps, trace):
+        """(agents, arenas, struct ca_trace or None) for trace=dict(...): torch tensors on the handle's device; None when `steps`
+        holds no record (an empty tensor has no address to hand over)."""
         if torch is None or not torch.cuda.is_available():
             raise RuntimeError("trace= needs PyTorch with a device: the records are written into device tensors")
         unknown = set(trace) - {"every", "channels", "arenas"}
@@ -956,13 +957,19 @@ class VecCollisionAvoidanceEnv:
         dev = torch.device("cuda", self.device)
         agents = torch.empty(ag_shape, dtype=torch.float32, device=dev)
         arenas = torch.empty(ar_shape, dtype=torch.int32, device=dev) if trace.get("arenas", True) else None
-        if ag_shape[0] == 0:   # fewer steps than `every`: no record, and an empty tensor has no address to hand over
+        if ag_shape[0] == 0:
+            return agents, arenas, None
+        return agents, arenas, _lib.Trace(agents=agents.data_ptr(), agents_bytes=agents.numel() * 4,
+                                          arenas=arenas.data_ptr() if arenas is not None else None,
+                                          arenas_bytes=arenas.numel() * 4 if arenas is not None else 0,
+                                          every=every, channels=_trace_channels(channels))
+
+    def _traced(self, name, steps, flags, trace):
+        """ca_rollout_trace / ca_alan_rollout_trace into torch tensors on the handle's device; returns dict(agents, arenas)."""
+        agents, arenas, tr = self._trace_bufs(steps, trace)
+        if tr is None:   # fewer steps than `every`: no record
             self._call(name[:-len("_trace")], self.h, int(steps), flags)
         else:
-            tr = _lib.Trace(agents=agents.data_ptr(), agents_bytes=agents.numel() * 4,
-                            arenas=arenas.data_ptr() if arenas is not None else None,
-                            arenas_bytes=arenas.numel() * 4 if arenas is not None else 0,
-                            every=every, channels=_trace_channels(channels))
             self._call(name, self.h, int(steps), flags, C.byref(tr))
         if not self.use_torch:   # the handle runs on a stream of its own: the records are complete before torch's stream reads them
             self.sync()
@@ -1197,6 +1204,110 @@ class VecCollisionAvoidanceEnv:
         out = {n: bufs.get(n) for n in ("returns", "first_done", "obs", "actions", "rewards", "dones")}
         out["obs_last"] = self._obs_out() if with_obs else None
         return out
+
+    # ---- navigation fields (ca_nav_*) ------------------------------------------------------------------
+    def set_navigation(self, targets, agent_class, cell, origin=None, shape=None, clearance=None, lookahead=2):
+        """Shortest-path fields towards a few shared targets, to steer agents round obstacles (ca_nav_configure; include/ca_env.h has
+        the definition, bit for bit).  targets [G, 2]: one set of fields for all arenas (needs one common obstacle table), or
+        [A, G, 2]: a set per arena, relaxed round the arena's own table.  agent_class int [A, N] (or a scalar / [N], broadcast): the
+        target an agent walks to, -1: not navigated.  cell: the grid's cell size; origin (x0, y0) and shape (gx, gy) default to the
+        bounding box of the obstacle table(s); clearance (how near an edge a cell centre may lie) to the radius; lookahead: pointer
+        steps per nav_pref().  Configuration: it survives resets and scenarios and stays with the slot under fork() / restore();
+        set_obstacles*() clears it."""
+        t = np.ascontiguousarray(np.asarray(targets.detach().cpu().numpy() if torch is not None and isinstance(targets, torch.Tensor) else targets,
+                                            np.float32))
+        if t.ndim not in (2, 3) or t.shape[-1] != 2 or (t.ndim == 3 and t.shape[0] != self.A):
+            raise ValueError("set_navigation: targets must be [G, 2] or [A=%d, G, 2], got %s" % (self.A, t.shape))
+        cls = np.ascontiguousarray(np.broadcast_to(np.asarray(agent_class, np.int32), (self.A, self.N)))
+        cell = float(cell)
+        if origin is None or shape is None:
+            tabs = [self.obstacle_table(a)["verts"] for a in (range(self.A) if t.ndim == 3 else (0,))]
+            v = np.concatenate(tabs) if tabs else np.zeros((0, 2), np.float32)
+            if len(v) == 0:
+                raise ValueError("set_navigation: no obstacle table to take the grid's box from: give origin= and shape=")
+            lo, hi = v.min(axis=0), v.max(axis=0)
+            if origin is None:
+                origin = (float(lo[0]), float(lo[1]))
+            if shape is None:
+                shape = tuple(max(1, int(np.ceil((float(hi[k]) - float(origin[k])) / cell))) for k in (0, 1))
+        d = _lib.NavDesc(x0=float(origin[0]), y0=float(origin[1]), cell=cell, gx=int(shape[0]), gy=int(shape[1]),
+                         clearance=float(self.cfg.radius if clearance is None else clearance), n_goals=int(t.shape[-2]),
+                         per_arena=1 if t.ndim == 3 else 0, targets=_ptr(t), targets_bytes=t.nbytes, agent_class=_ptr(cls),
+                         class_bytes=cls.nbytes, lookahead=int(lookahead))
+        self._call("ca_nav_configure", self.h, C.byref(d))
+
+    def clear_navigation(self):
+        self._call("ca_nav_clear", self.h)
+
+    def navigation_info(self):
+        """dict(configured=, gx=, gy=, n_goals=, n_sets=, sweeps_max=) of the installed navigation (ca_nav_info)."""
+        v = [C.c_int32(0) for _ in range(6)]
+        self._call("ca_nav_info", self.h, *[C.byref(x) for x in v])
+        return dict(configured=bool(v[0].value), gx=v[1].value, gy=v[2].value, n_goals=v[3].value, n_sets=v[4].value, sweeps_max=v[5].value)
+
+    def nav_field(self, arena=0, goal=0):
+        """(dist float32 [gy, gx], next uint8, blocked uint8) of one field, as host arrays (ca_nav_get_field): the distance to the
+        target (inf: blocked or unreachable), the pointer per cell (_lib.NAV_OFFSETS[k], _lib.NAV_STAY, _lib.NAV_NONE) and the mask."""
+        i = self.navigation_info()
+        gx, gy = max(i["gx"], 1), max(i["gy"], 1)
+        dist, nxt, blk = np.empty((gy, gx), np.float32), np.empty((gy, gx), np.uint8), np.empty((gy, gx), np.uint8)
+        self._call("ca_nav_get_field", self.h, int(arena), int(goal), _ptr(dist), _ptr(nxt), _ptr(blk), gx * gy)
+        return dist, nxt, blk
+
+    def _nav_dist_buf(self, dist):
+        """(buffer the kernel writes, its address) for dist=True or an [A, N] array / tensor whose rows that are not navigated keep
+        their values: a device tensor with use_torch, else the handle's page-locked array."""
+        given = dist is not True
+        if self.use_torch:
+            dev = torch.device("cuda", self.device)
+            if given:
+                buf = torch.as_tensor(dist).detach().to(device=dev, dtype=torch.float32).reshape(self.A, self.N).contiguous()
+            else:
+                buf = torch.full((self.A, self.N), float("inf"), dtype=torch.float32, device=dev)
+            return buf, buf.data_ptr()
+        buf = self._actseq_host("nav_dist", (self.A, self.N), np.float32)
+        buf[...] = np.asarray(dist.detach().cpu().numpy() if torch is not None and isinstance(dist, torch.Tensor) else dist,
+                              np.float32).reshape(self.A, self.N) if given else np.inf
+        return buf, buf.ctypes.data
+
+    def nav_pref(self, dist=False, freeze=False):
+        """Write the preferred velocities (PREF_X / PREF_Y) of the navigated agents from the fields (ca_nav_pref: one launch); the
+        next orca_step() steers by them.  freeze: the agents of arenas whose episode is over are not written.  dist=True: returns
+        the distance to go [A, N] (inf in a blocked cell and for rows that are not navigated); dist=an [A, N] array: the same with
+        that array's values kept for rows that are not navigated.  A device tensor with use_torch, else a numpy array."""
+        if dist is False or dist is None:
+            self._call("ca_nav_pref", self.h, None, _lib.F_FREEZE if freeze else 0)
+            return None
+        buf, addr = self._nav_dist_buf(dist)
+        self._call("ca_nav_pref", self.h, C.c_void_p(addr), _lib.F_FREEZE if freeze else 0)
+        if self.use_torch:
+            return buf
+        self.sync()
+        return np.array(buf)
+
+    def rollout_nav(self, steps, with_obs=False, stats=False, autoreset=False, freeze=False, trace=None, contacts=False, dist=False):
+        """`steps` navigated ORCA-only steps without returning to the host (ca_rollout_nav): per step nav_pref(freeze=freeze), then
+        orca_step(...) -- the state, fields and statistics left are those of that loop, bit for bit.  with_obs / contacts: one
+        launch behind the last step.  trace=dict(...): as for rollout(); returns its dict.  dist=True (not together with trace): the
+        last step is made as nav_pref(dist=True) + orca_step(), the same launches, and the distances to go seen in front of it are
+        returned."""
+        steps = int(steps)
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | \
+                (_lib.F_AUTORESET if autoreset else 0) | (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        if trace is not None:
+            if dist:
+                raise ValueError("rollout_nav: dist=True does not go together with trace=")
+            agents, arenas, tr = self._trace_bufs(steps, trace)
+            self._call("ca_rollout_nav", self.h, steps, flags, C.byref(tr) if tr is not None else None)
+            if not self.use_torch:
+                self.sync()
+            return dict(agents=agents, arenas=arenas)
+        if dist and steps > 0:
+            self._call("ca_rollout_nav", self.h, steps - 1, flags & ~(_lib.F_OBS | _lib.F_CONTACT), None)
+            out = self.nav_pref(dist=True, freeze=freeze)
+            self._call("ca_orca_step", self.h, flags)
+            return out
+        self._call("ca_rollout_nav", self.h, steps, flags, None)
 
     # ---- ALAN online learning (ALAN_true.py:569-628) -----------------------------------------------
     def alan_configure(self, actions, temp=0.2, timewindow=2.0, time_step=1 / 60.):

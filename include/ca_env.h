@@ -753,7 +753,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
@@ -832,6 +832,82 @@ typedef struct ca_edge_grid_desc {
 } ca_edge_grid_desc;
 int ca_edge_grid_build(const float* edges_pq, int32_t n_edges, float range, ca_edge_grid_desc* desc, uint32_t* cell_start, int32_t cell_cap,
                        uint32_t* entries, int32_t entry_cap);
+/* Navigation fields: steering round obstacles on the device.  Every ORCA-only step steers an agent straight at its goal (the
+ * preferred velocity is the unit vector towards it), and ORCA avoids only locally: an agent whose goal lies behind a wall walks into
+ * the wall and stays there.  A navigation is, per target, a shortest-path distance field over a caller-given grid and a pointer per
+ * cell; ca_nav_pref writes CA_FLD_PREF_X / _Y from it in front of an ORCA-only step, which reads them as its input.  No solve kernel
+ * knows about it.  Every value is defined bit for bit (fp32, one rounding per operation):
+ *   - Grid: origin (x0, y0), cell size `cell`, gx x gy cells (1 .. 256 per axis, gx * gy <= CA_NAV_MAX_CELLS), ics = 1.0f / cell.  The
+ *     cell of a coordinate is the edge grid's expression above, cell(v) = (int)fminf(fmaxf(floorf((v - x0) * ics), 0.0f), (float)(g - 1)):
+ *     a position outside the box is clamped into the outermost cell.  Cell index = cy * gx + cx; the centre of column cx is
+ *     x0 + ((float)cx + 0.5f) * cell, rows alike.
+ *   - Blocked: cell c is blocked iff some edge (p, q) of the obstacle table has distSqPointSegment(p, q, centre(c)) < clearance *
+ *     clearance (csrc/ca_math.h; strictly, like the wall test).  Edges only, no inside test.
+ *   - Field per (set, target): the target's cell is the source, d = 0.  Neighbours k = 0 .. 7 are offset by (1,0) (0,1) (-1,0) (0,-1)
+ *     (1,1) (-1,1) (-1,-1) (1,-1); w_k = cell for k < 4, cell * 1.41421354f (one multiply) for k >= 4; a diagonal move is allowed only
+ *     if both axis cells it passes between are in the grid and unblocked.  For an unblocked cell that is not the source,
+ *     d[c] = min over in-grid, unblocked, allowed neighbours of (d[u_k] + w_k), +inf without any; a blocked cell holds +inf.  These
+ *     equations have one solution, whatever order a kernel relaxes in.
+ *   - Pointers, `next`, one byte per cell: the smallest k with d[u_k] + w_k == d[c] in an unblocked cell of finite distance;
+ *     CA_NAV_STAY in the source; CA_NAV_NONE in an unblocked cell of infinite distance; in a blocked cell the escape pointer, the
+ *     smallest (d[u_k], k) over all in-grid neighbours of finite distance (all eight, no corner rule), CA_NAV_NONE without one.
+ *   - Per step: agent (a, i) is navigated if its row is present (ca_set_agent_counts), agent_done == 0, its class g =
+ *     agent_class[a, i] is >= 0 and, with CA_F_FREEZE, arena_done[a] == 0.  Every other row is not written at all.  For a navigated
+ *     agent: w = cell(pos); repeat `lookahead` times: k = next[w]; stop if k >= 8; else move w by offset k.  If the walk never moved
+ *     or stopped on CA_NAV_STAY: pref = the unit vector towards the agent's own goal; otherwise towards the centre of w (as a double).
+ *     Both through the one direction function of the step kernels (env.py:156-162).  dist_out[a, i] = d[g][cell(pos)], +inf in a
+ *     blocked cell.  Nothing else is written.
+ * ca_nav_configure: builds the masks on the host from the installed obstacle table(s), uploads them, relaxes every field in one launch
+ * (one workgroup per field, the grid in LDS) and drains the stream.  per_arena = 0: one set of fields for all arenas, targets [G, 2];
+ * needs one common table.  per_arena = 1: a set per arena from the arena's own table (or the common one), targets [A, G, 2].  Calling
+ * it again replaces the navigation.  All checks run before anything changes, and a failure leaves the handle as it was:
+ *   - a null argument, per_arena = 0 on a handle with tables per arena, n_goals outside 1 .. CA_NAV_MAX_GOALS, lookahead outside
+ *     1 .. CA_NAV_MAX_LOOKAHEAD, a grid outside the limits -> CA_EINVAL;
+ *   - targets_bytes or class_bytes not exactly the array's size -> CA_ESIZE;
+ *   - cell or clearance outside [CA_MIN_LENGTH, CA_MAX_LENGTH] (clearance may also be 0) or not finite; |x0| or |y0| above CA_MAX_COORD;
+ *     a target that is not finite, lies outside the box [x0, x0 + gx * cell] x [y0, y0 + gy * cell] or in a blocked cell; a class
+ *     outside -1 .. n_goals - 1 -> CA_ERANGE (ca_last_error names the arena, goal or agent).
+ * Navigation is configuration, like the policy and the obstacle tables: no ca_field, it survives ca_reset*, CA_F_AUTORESET and
+ * ca_init_scenario, and stays with the slot under ca_arena_gather / ca_snapshot_load.  ca_set_obstacles and
+ * ca_set_obstacles_per_arena CLEAR it when they install their tables: the fields were relaxed round the old edges.
+ * ca_nav_info: *configured, the grid's sides, n_goals, the number of field sets (1 or n_arenas) and the largest number of sweeps a
+ * field's relaxation made (below gx * gy + 1, the bound that makes the loop finite); zeros while nothing is configured.
+ * ca_nav_get_field: host copies of one field -- dist f32 [gy * gx], next u8, blocked u8 (0 / 1) -- of `arena`'s set (any arena names the
+ * one set of per_arena = 0); any pointer may be NULL; cells_cap < gx * gy -> CA_ESIZE.  Synchronises.
+ * ca_nav_pref: one small launch; flags 0 or CA_F_FREEZE (anything else -> CA_EINVAL).  dist_out: DEVICE f32 [A, N] or NULL.
+ * ca_rollout_nav(env, T, flags, tr) is the loop  for each step: ca_nav_pref(env, NULL, flags & CA_F_FREEZE); ca_orca_step(env, flags)
+ * without the returns to the host, always as launches per step (also where ca_rollout is one launch).  Flags are ca_rollout's; CA_F_OBS
+ * and CA_F_CONTACT each add one launch behind the last step.  tr != NULL: ca_rollout_trace's checks and records (record r = the state
+ * after (r + 1) * every steps).  The sticky overflow status works as in ca_rollout.  Without a navigation -> CA_EINVAL; a refusal
+ * advances nothing.
+ * ca_nav_mask_build: the mask builder itself, handle-free and without a device (tests, tools), for the n_edges edges
+ * edges_pq[n_edges][4] = (px, py, qx, qy): blocked[gy * gx] = 0 / 1.  cells_cap < gx * gy -> CA_ESIZE; a grid outside the limits ->
+ * CA_EINVAL; messages through ca_last_error(NULL). */
+#define CA_NAV_MAX_CELLS 32768
+#define CA_NAV_MAX_GOALS 16
+#define CA_NAV_MAX_LOOKAHEAD 8
+#define CA_NAV_STAY 8
+#define CA_NAV_NONE 9
+typedef struct ca_nav_desc {
+    float x0, y0, cell;            /* the grid's origin and cell size */
+    int32_t gx, gy;                /* its sides */
+    float clearance;               /* >= 0: how near an edge a cell centre may lie (a caller's usual choice: ca_config.radius) */
+    int32_t n_goals;               /* G: 1 .. CA_NAV_MAX_GOALS */
+    int32_t per_arena;             /* 0: one field set, targets [G, 2]; 1: a set per arena, targets [A, G, 2] */
+    const float* targets;          /* HOST f32 (x, y) */
+    size_t targets_bytes;
+    const int32_t* agent_class;    /* HOST i32 [A, N]: the target an agent walks to, or -1: not navigated */
+    size_t class_bytes;
+    int32_t lookahead;             /* pointer steps per ca_nav_pref: 1 .. CA_NAV_MAX_LOOKAHEAD */
+} ca_nav_desc;
+int ca_nav_configure(ca_env* env, const ca_nav_desc* desc);
+int ca_nav_clear(ca_env* env);
+int ca_nav_info(ca_env* env, int32_t* configured, int32_t* gx, int32_t* gy, int32_t* n_goals, int32_t* n_sets, int32_t* sweeps_max);
+int ca_nav_get_field(ca_env* env, int32_t arena, int32_t goal, float* dist, uint8_t* next, uint8_t* blocked, int32_t cells_cap);
+int ca_nav_pref(ca_env* env, float* dist_out, uint32_t flags);
+int ca_rollout_nav(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
+int ca_nav_mask_build(const float* edges_pq, int32_t n_edges, float x0, float y0, float cell, int32_t gx, int32_t gy, float clearance,
+                      uint8_t* blocked, int32_t cells_cap);
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
 const char* ca_source_sha(void);
