@@ -37,7 +37,7 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_set_agent_counts", "ca_get_agent_counts", "ca_agent_counts_info", "ca_create_ex", "ca_tiled_info", "ca_tiled_grid_info",
            "ca_rollout_trace", "ca_alan_rollout_trace", "ca_tiled_edge_grid", "ca_tiled_edge_grid_info", "ca_edge_grid_build",
            "ca_contacts", "ca_get_contacts", "ca_contacts_ptr",
-           "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info",
+           "ca_set_agent_sensing", "ca_get_agent_sensing", "ca_agent_sensing_info", "ca_nbr_seed_info", "ca_lp3_pairs_info",
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
            "ca_fork_bytes_per_arena", "ca_rollout_actions",
            "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy",
@@ -205,6 +205,7 @@ def load():
     L.ca_get_agent_sensing.argtypes = [vp, vp, vp, sz, i32]
     L.ca_agent_sensing_info.argtypes = [vp, C.POINTER(i32)]
     L.ca_nbr_seed_info.argtypes = [vp, C.POINTER(i32)]
+    L.ca_lp3_pairs_info.argtypes = [vp, C.POINTER(i32)]
     L.ca_arena_gather.argtypes = [vp, vp, sz, i32, u32]
     L.ca_snapshot_create.argtypes = [vp, C.POINTER(vp)]
     L.ca_snapshot_save.argtypes = [vp, vp]

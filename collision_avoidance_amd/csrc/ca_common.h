@@ -41,6 +41,10 @@ struct ActionSeq;
 // ArenaCounts kernels have a seeded twin; the AgentParams, AgentSensing and wide-list kernels do not, and every instantiation
 // without the tag keeps its name, its text and its resources (they serve CA_NBR_SEED=0 in the environment).
 struct SeededScan;
+// Tag of the one-wave register-line kernels whose LP3 pool round takes 17 to 32 waiting lanes at once, two lanes per agent with the
+// projected lines in registers (step_kernel<KMAX, 64, 4, 4, false, SeededScan, PairedLp3>; ca_lp.h lp3_pair_lds, CA_LP3_PAIRS).  It
+// stands behind SeededScan; every instantiation without the tag keeps its name, its text and its resources.
+struct PairedLp3;
 
 namespace ca {
 

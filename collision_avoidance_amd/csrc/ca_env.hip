@@ -133,7 +133,7 @@ struct ca_env {
     int LS = 1, apb = 1, linv = 65536, dense = 0;   // lanes per arena, arenas per workgroup, ceil(2^16 / LS), packed back to back (ca_common.h StepArgs)
     // diagnostic environment switches, read ONCE by ca_create (a handle never changes behaviour because the environment did):
     // -1 = unset, else the first character's digit
-    struct { int reg_lines = -1, pair = -1, alan_fused = -1, nbr_seed = -1, nav_block = 0; } sw;
+    struct { int reg_lines = -1, pair = -1, alan_fused = -1, nbr_seed = -1, lp3_pairs = -1, nav_block = 0; } sw;
     int ST = 0, KT = 16;  // solve-kernel variant: ST > 0 = register lines with ST obstacle slots; KT = KMAX
     int SMX = 4;          // ... and the capacity of its obstacle-neighbour list (4, or 16: agents with more than ST are solved apart;
                           // SWIDE = 64 with ST = 0: the wide LDS-table kernel of a handle with max_obst_neighbors > 16)
@@ -388,15 +388,25 @@ static void fill_args(ca_env* e, StepArgs& a, const float* actions, uint32_t fla
 // The one place where the variant the handle chose (pick_variant, alan_pick, the quad switches of ca_create) becomes a kernel
 // instantiation, a grid, a block and a dynamic LDS size: launch_step launches what solve_launch returns, apply_variant_attributes
 // and alan_pick raise the dynamic-LDS limit of exactly these kernels, and ca_launch_info reports the plain single-step form.
-struct SolveLaunch { const void* fn; dim3 grid, block; size_t lds; bool seeded = false; };   // seeded: fn is a SeededScan kernel (ca_nbr.h)
+struct SolveLaunch { const void* fn; dim3 grid, block; size_t lds; bool seeded = false, paired = false; };   // seeded: fn is a SeededScan kernel (ca_nbr.h); paired: ... and a PairedLp3 one (ca_lp.h)
 template <class F> static const void* fn_ptr(F* f) { return reinterpret_cast<const void*>(f); }
 // one lane per agent: register lines (ST = 4) or the LDS line table (ST = 0); the ALAN instantiations exist for one and two waves
 // seed: the handle asks for the seeded agent scan, which the one-wave kernels have a twin for under the SeededScan tag (ca_nbr.h:
 // the untagged kernels, their ALAN forms -- with an action set per arena too -- and the ArenaCounts kernels below); *seeded: a twin it is
+// pairs: the handle asks for the paired LP3 round, which the seeded register-line kernels with obstacle lists of 4 have a twin for
+// under the PairedLp3 tag (ca_lp.h); *paired: that twin it is
 template <int KMAX, int ST, int SMX, bool ALAN, class... PER>
-static const void* step_fn_for(int BS, bool seed, bool* seeded) {
+static const void* step_fn_for(int BS, bool seed, bool* seeded, bool pairs = false, bool* paired = nullptr) {
 #if CA_NBR_SEED
-    if (seed && BS == 64) { *seeded = true; return fn_ptr(&step_kernel<KMAX, 64, ST, SMX, ALAN, PER..., SeededScan>); }
+    if (seed && BS == 64) {
+        *seeded = true;
+#if CA_LP3_PAIRS
+        if constexpr (ST > 0 && SMX == ST && !ALAN && sizeof...(PER) == 0) {
+            if (pairs && paired) { *paired = true; return fn_ptr(&step_kernel<KMAX, 64, ST, SMX, false, SeededScan, PairedLp3>); }
+        }
+#endif
+        return fn_ptr(&step_kernel<KMAX, 64, ST, SMX, ALAN, PER..., SeededScan>);
+    }
 #endif
     if constexpr (ALAN) {
         return BS == 64 ? fn_ptr(&step_kernel<KMAX, 64, ST, SMX, true, PER...>) : fn_ptr(&step_kernel<KMAX, 128, ST, SMX, true, PER...>);
@@ -472,14 +482,15 @@ static const void* sens_fn_of(const ca_env* e) {
 // the lane kernel of the handle's KMAX and line storage: register lines with obstacle lists of 4, or of 16 (the rare agent with
 // more than 4 is solved apart), else the LDS line table; K = 16 has the table only, and no ALAN form
 template <bool ALAN, class... PER>
-static const void* lane_fn_for(const ca_env* e, bool* seeded) {
+static const void* lane_fn_for(const ca_env* e, bool* seeded, bool* paired) {
     const bool sd = e->sw.nbr_seed != 0;   // (CA_NBR_SEED=0 in the environment, latched by ca_create: the unseeded agent scan)
+    const bool pl = e->sw.lp3_pairs < 0 ? CA_LP3_PAIRS_DEFAULT != 0 : e->sw.lp3_pairs != 0;   // (CA_LP3_PAIRS=0 / 1 in the environment, latched by ca_create)
     if (e->sens) return e->ac ? sens_fn_of<ArenaCounts, AgentSensing>(e) : sens_fn_of<AgentSensing>(e);   // (ap is on with it; no ALAN form either)
     if (e->ac) return e->KT == 5 ? ac_fn_for<5>(e->BS, sd, seeded) : (e->KT == 16 ? ac_fn_for<16>(e->BS, sd, seeded) : ac_fn_for<10>(e->BS, sd, seeded));   // (refused by the ALAN calls)
     if (e->ap) return e->KT == 5 ? ap_fn_for<5>(e->BS) : (e->KT == 16 ? ap_fn_for<16>(e->BS) : ap_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->SMX > SMAX) return e->KT == 5 ? wide_fn_for<5>(e->BS) : (e->KT == 16 ? wide_fn_for<16>(e->BS) : wide_fn_for<10>(e->BS));   // (alan_pick never asks for an ALAN form of it)
     if (e->ST > 0 && e->SMX > 4) return e->KT == 5 ? step_fn_for<5, 4, 16, ALAN, PER...>(e->BS, sd, seeded) : step_fn_for<10, 4, 16, ALAN, PER...>(e->BS, sd, seeded);
-    if (e->ST > 0) return e->KT == 5 ? step_fn_for<5, 4, 4, ALAN, PER...>(e->BS, sd, seeded) : step_fn_for<10, 4, 4, ALAN, PER...>(e->BS, sd, seeded);
+    if (e->ST > 0) return e->KT == 5 ? step_fn_for<5, 4, 4, ALAN, PER...>(e->BS, sd, seeded, pl, paired) : step_fn_for<10, 4, 4, ALAN, PER...>(e->BS, sd, seeded, pl, paired);
     if (e->KT == 5) return step_fn_for<5, 0, SMAX, ALAN, PER...>(e->BS, sd, seeded);
     if constexpr (!ALAN) { if (e->KT == 16) return step_fn_for<16, 0, SMAX, false>(e->BS, sd, seeded); }
     return step_fn_for<10, 0, SMAX, ALAN, PER...>(e->BS, sd, seeded);
@@ -544,9 +555,9 @@ static SolveLaunch solve_launch(const ca_env* e, bool alan, bool rollout, bool t
     }
     if (e->pair)   // two lanes per agent (ca_pair.h): one arena per workgroup of 2 P lanes
         return {e->KT == 5 ? pair_fn_for<5>(e->BS) : pair_fn_for<10>(e->BS), dim3(e->grid), dim3(2 * e->BS), e->lds_p};
-    bool seeded = false;
-    const void* f = per ? lane_fn_for<true, AlanArenaSets>(e, &seeded) : (alan ? lane_fn_for<true>(e, &seeded) : lane_fn_for<false>(e, &seeded));
-    return {f, dim3(e->grid), dim3(e->BS), e->lds, seeded};
+    bool seeded = false, paired = false;
+    const void* f = per ? lane_fn_for<true, AlanArenaSets>(e, &seeded, &paired) : (alan ? lane_fn_for<true>(e, &seeded, &paired) : lane_fn_for<false>(e, &seeded, &paired));
+    return {f, dim3(e->grid), dim3(e->BS), e->lds, seeded, paired};
 }
 // (above the 48 KiB that every kernel may take, a kernel's dynamic LDS needs its limit raised before the launch)
 static hipError_t allow_lds(const SolveLaunch& s) {
@@ -979,7 +990,7 @@ int ca_create_ex(const ca_config* cfg, uint32_t create_flags, int device, void* 
     {   // the diagnostic switches, once
         auto digit = [](const char* name) { const char* v = getenv(name); return (v && v[0] >= '0' && v[0] <= '9') ? v[0] - '0' : -1; };
         e->sw.reg_lines = digit("CA_REG_LINES"); e->sw.pair = digit("CA_PAIR"); e->sw.alan_fused = digit("CA_ALAN_FUSED");
-        e->sw.nbr_seed = digit("CA_NBR_SEED");
+        e->sw.nbr_seed = digit("CA_NBR_SEED"); e->sw.lp3_pairs = digit("CA_LP3_PAIRS");
         const char* nb = getenv("CA_NAV_BLOCK");   // 256 / 1024 forces the field kernel's block (tools/nav_cost.py measures both)
         e->sw.nav_block = nb ? atoi(nb) : 0;
     }
@@ -1870,6 +1881,12 @@ int ca_agent_sensing_info(ca_env* e, int32_t* per_agent) {
 int ca_nbr_seed_info(ca_env* e, int32_t* seeded) {
     if (!e) return CA_EINVAL;
     if (seeded) *seeded = solve_launch(e, false, false).seeded ? 1 : 0;   // (the plain single-step form, as ca_launch_info reports it)
+    return CA_OK;
+}
+
+int ca_lp3_pairs_info(ca_env* e, int32_t* paired) {
+    if (!e) return CA_EINVAL;
+    if (paired) *paired = solve_launch(e, false, false).paired ? 1 : 0;   // (the plain single-step form, as above)
     return CA_OK;
 }
 

@@ -6,7 +6,8 @@
 //     (ca_nbr.h); the ORCA half-planes live in REGISTER slots (4 obstacle + KMAX neighbour slots, LP2 / LP1 fully
 //     unrolled; every configuration with K <= 10 and <= 4 obstacle neighbours) or, for larger K / S, in an LDS line
 //     table laid out [line][lane]; the lanes whose LP2 is infeasible solve LP3 four lanes per agent in a per-wave LDS
-//     pool (ca_lp.h lp3_coop).
+//     pool (ca_lp.h lp3_coop); the PairedLp3 twins of the one-wave kernels take a wave with 17 to 32 such lanes in one round,
+//     two lanes per agent with the projected lines in registers (ca_lp.h lp3_pair_lds).
 //   * quad kernel (ca_quad.h): FOUR lanes per agent for small arenas (a chip of 1024 SIMDs is otherwise left with a
 //     few hundred waves): candidates, edges, lines and LP1 clips are dealt over the quad and merged with DPP moves;
 //     one launch can advance T ORCA-only steps with the arena resident in registers / LDS (ca_rollout).

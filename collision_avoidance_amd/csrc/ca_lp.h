@@ -342,4 +342,120 @@ __device__ __forceinline__ void lp3_coop(float4* pool, int ML, int nslots, float
     lp3_coop_lds((lp3_lds_v4f*)pool, ML, nslots, radius, stride);
 }
 
+// App. A.5 LP3, TWO LANES PER AGENT, 32 agents at once (the PairedLp3 kernels, ca_step.h; CA_LP3_PAIRS, build switch: 0 = there are
+// none).  A settled dense crowd leaves 17 to 32 lanes of nearly every second wave infeasible after LP2: with POOL_SLOTS four-lane
+// slots they take two rounds of lp3_coop, the second a fifth full, and a round is a lock-step chain whose length hardly depends on
+// how many slots are live.  Here lanes 2 s and 2 s + 1 work for slot s:
+//   * the wave's pool bytes hold the ORIGINAL lines only, [ML][PAIR_SLOTS] (ML * 32 rows = 2 ML * 16); the headers lie apart (hdr);
+//   * the projected lines of a violated line i live in REGISTERS: position p (the contract's order: the obstacle copies, then line
+//     numObst .. i - 1) is held by lane p & 1 of the pair in register slot p >> 1, and a bit per position says whether it exists -- a
+//     line skipped as parallel and same-direction is never tested and never clips, the order of the rest is what the compaction of
+//     lp3_coop leaves, so LP2 visits the same lines in the same order;
+//   * LP2 over the positions is unrolled (every register index a constant); line ii reaches both lanes by one quad_perm DPP move per
+//     component, each lane clips it against its own earlier positions, and tLeft / tRight / failed merge in one quad_xor<0xB1> step
+//     -- a maximum, a minimum and an OR, so the values are those of the serial loop bit for bit (the argument of lp3_coop above).
+// No LDS access inside LP2, no LDS write before the result: the round needs no synchronisation of its own.
+#ifndef CA_LP3_PAIRS
+#define CA_LP3_PAIRS 1
+#endif
+#ifndef CA_LP3_PAIRS_DEFAULT   // what a handle launches when CA_LP3_PAIRS is not in its environment (ca_env.hip lane_fn_for)
+#define CA_LP3_PAIRS_DEFAULT 1
+#endif
+constexpr int PAIR_SLOTS = 32;  // two-lane LP3 slots per wave
+// value of lane 0 (EVEN: quad_perm [0,0,2,2]) or lane 1 ([1,1,3,3]) of the pair, in both of its lanes
+template <bool ODD>
+__device__ __forceinline__ float lp3_pair_bcast(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ODD ? 0xF5 : 0xA0, 0xF, 0xF, false));
+}
+template <int ML>
+__device__ __forceinline__ void lp3_pair_lds(lp3_lds_v4f* pool, lp3_lds_v4f* hdr, int nslots, float radius) {
+    constexpr int NP = ML - 1;         // positions of projected lines at most (line n - 1 against the n - 1 before it)
+    constexpr int NR = (NP + 1) / 2;   // register slots per lane
+    const int lane = threadIdx.x & 63, slot = lane >> 1, hh = lane & 1;
+    Lds3Lines ls; ls.base = pool + slot; ls.stride = PAIR_SLOTS;
+    const bool live = slot < nslots;
+    lp3_v4f h = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (live) h = hdr[slot];
+    const int packed = __float_as_int(h.z);
+    const int n = live ? (packed & 0xFF) : 0, numObst = (packed >> 8) & 0xFF, begin = (packed >> 16) & 0xFF;
+    V2 result = mk(h.x, h.y);
+    float distance = 0.0f;
+    for (int i = begin; i < n; ++i) {
+        const Line Li = ls.get(i);
+        if (det(Li.dir, Li.point - result) > distance) {
+            lp3_v4f P[NR];
+            unsigned own = 0u;   // bit p: position p exists (this lane's positions)
+            static_for<NR>([&](auto sc) __attribute__((always_inline)) {
+                constexpr int s = decltype(sc)::value;
+                const int p = 2 * s + hh;
+                lp3_v4f v = {0.0f, 0.0f, 1.0f, 0.0f};
+                bool valid = p < numObst || p < i;
+                if (valid) {
+                    const Line Lj = ls.get(p);
+                    Line l = Lj;   // (an obstacle line is taken as it is)
+                    if (p >= numObst) {
+                        const float d = det(Li.dir, Lj.dir);
+                        if (fabsf(d) <= EPS) {
+                            if (dot(Li.dir, Lj.dir) > 0.0f) valid = false;
+                            else l.point = 0.5f * (Li.point + Lj.point);
+                        } else {
+                            l.point = Li.point + div_ir(det(Lj.dir, Li.point - Lj.point), d) * Li.dir;   // (|d| > EPS here)
+                        }
+                        l.dir = normalize_ir(Lj.dir - Li.dir);   // (unit vectors that are not parallel: |difference| in [1e-5, 2]; parallel ones are skipped or opposite)
+                    }
+                    if (valid) { v.x = l.point.x; v.y = l.point.y; v.z = l.dir.x; v.w = l.dir.y; }
+                }
+                P[s] = v;
+                own |= valid ? (1u << p) : 0u;
+            });
+            const unsigned have = own | (unsigned)quad_xor<0xB1>((int)own);   // the pair's positions
+            const V2 opt = mk(-Li.dir.y, Li.dir.x);
+            V2 res = opt * radius;  // lp2(..., dirOpt = true)
+            bool ok = true;
+            static_for<NP>([&](auto ic) __attribute__((always_inline)) {
+                constexpr int ii = decltype(ic)::value;
+                if (ok && ((have >> ii) & 1u)) {   // (the same in both lanes of the pair)
+                    Line L;
+                    L.point = mk(lp3_pair_bcast<(ii & 1) != 0>(P[ii >> 1].x), lp3_pair_bcast<(ii & 1) != 0>(P[ii >> 1].y));
+                    L.dir = mk(lp3_pair_bcast<(ii & 1) != 0>(P[ii >> 1].z), lp3_pair_bcast<(ii & 1) != 0>(P[ii >> 1].w));
+                    if (det(L.dir, L.point - res) > 0.0f) {
+                        const float dp = dot(L.point, L.dir);
+                        const float disc = sqr(dp) + sqr(radius) - absSq(L.point);
+                        int failed = disc < 0.0f ? 1 : 0;
+                        const float sq = sqrt_ir(disc);   // (disc = 0 or >= an ulp of O(1) terms; negative: the lane has failed already / fails below)
+                        float tLeft = -dp - sq;
+                        float tRight = -dp + sq;
+                        static_for<(ii + 1) / 2>([&](auto jc) __attribute__((always_inline)) {
+                            constexpr int sj = decltype(jc)::value;
+                            const int jj = 2 * sj + hh;
+                            const bool on = (jj < ii) & (((own >> jj) & 1u) != 0u);
+                            const Line M = unpack_line(make_float4(P[sj].x, P[sj].y, P[sj].z, P[sj].w));
+                            const float den = det(L.dir, M.dir);
+                            const float num = det(M.dir, L.point - M.point);
+                            const bool par = fabsf(den) <= EPS;
+                            const float t = div_ir(num, den);   // (used only where |den| > EPS: den in (1e-5, 1], num = 0 or in [1e-21, 5e7])
+                            const bool pos = den >= 0.0f;
+                            const bool right = on & !par & pos, left = on & !par & !pos;
+                            tRight = (right & (t < tRight)) ? t : tRight;
+                            tLeft = (left & (tLeft < t)) ? t : tLeft;
+                            failed |= (on & par & (num < 0.0f)) ? 1 : 0;
+                        });
+                        {
+                            const float oR = quad_xor<0xB1>(tRight), oL = quad_xor<0xB1>(tLeft);
+                            tRight = (oR < tRight) ? oR : tRight;
+                            tLeft = (tLeft < oL) ? oL : tLeft;
+                            failed |= quad_xor<0xB1>(failed);
+                        }
+                        if (failed || tLeft > tRight) ok = false;  // lp2 stops here and LP3 keeps its previous result
+                        else res = (dot(opt, L.dir) > 0.0f) ? L.point + tRight * L.dir : L.point + tLeft * L.dir;
+                    }
+                }
+            });
+            if (ok) result = res;
+            distance = det(Li.dir, Li.point - result);
+        }
+    }
+    if (live && hh == 0) { const lp3_v4f o = {result.x, result.y, h.z, 0.0f}; hdr[slot] = o; }
+}
+
 }  // namespace ca

@@ -99,6 +99,8 @@ __device__ __noinline__ void solve_many_obstacles(CA_AS(3) char* tbl3, int MLX, 
 //   instantiations scans the arena (below), so it never reasons from a list.
 //   SeededScan (one wave, alone in the pack, ALAN or not) = the agent scan of the neighbour search starts from last step's list
 //   (ca_nbr.h); nothing else of the kernel reads the tag.
+//   PairedLp3 (behind SeededScan; one wave, register lines with SMX == ST, no ALAN form) = a pool round with more than POOL_SLOTS
+//   waiting lanes solves up to PAIR_SLOTS of them at once, two lanes per agent (ca_lp.h lp3_pair_lds); 16 or fewer take lp3_coop as ever.
 template <int KMAX, int BS, int ST, int SMX = (ST > 0 ? ST : SMAX), bool ALAN = false, class... PER>
 __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void step_kernel(const StepArgs p) {
     constexpr int AM = !ALAN ? 0 : (has_tag<AlanArenaSets, PER...> ? 2 : 1);   // the set mode of alan_count / alan_cs
@@ -106,6 +108,9 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
     constexpr bool AS = has_tag<AgentSensing, PER...>;        // neighbor_dist and max_neighbors per agent: the neighbour search's alone (ca_nbr.h)
     constexpr bool AP = has_tag<AgentParams, PER...> || AC || AS;   // (ArenaCounts and AgentSensing include AgentParams: the tag names the instantiation)
     static_assert(!AP || (ST == 0 && !ALAN && SMX <= SMAX), "per-agent parameters: the LDS line table with lists of up to 16, no ALAN form");
+    constexpr bool PL = has_tag<PairedLp3, PER...>;           // the LP3 pool round takes 17 .. 32 waiting lanes at once (ca_lp.h lp3_pair_lds)
+    static_assert(!PL || (CA_LP3_PAIRS && BS == 64 && ST > 0 && SMX == ST && !ALAN && !AP),
+                  "the paired LP3 round: one wave, register lines, no many-obstacle stage (it reads the staged velocities the headers overwrite), no ALAN form");
     extern __shared__ float4 smem4[];
     constexpr bool LISTP = BS > 64 && !AP;   // the pair count of the statistics goes through the neighbour lists (arenas within one wave: the
     //                                   scan of the staged arena is as fast -- round 5 measured the lists there: 57.7 against 57.3 us)
@@ -253,9 +258,15 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             }
         }
 #if defined(CA_STAMPS) && CA_STAMPS == 3
-        if ((tid & 63) == 0 && p.dbg) p.dbg[((size_t)blockIdx.x * (BS / 64) + (tid >> 6)) * 16 + 4] = 0;  // LP3 rounds | lanes << 32
+        if ((tid & 63) == 0 && p.dbg) p.dbg[((size_t)blockIdx.x * (BS / 64) + (tid >> 6)) * 16 + 4] = 0;  // LP3 rounds | paired rounds << 16 | lanes << 32
 #else
         CA_STAMP(4);
+#endif
+#if defined(CA_STAMPS) && CA_STAMPS < 3   // ... and beside the phase stamps: slot 2 of the wave's row behind them (ca_nbr.h; tools/lp3_rounds.py)
+        unsigned long long* const lp3_cnt = p.dbg ? p.dbg + ((size_t)((p.A + p.apb - 1) / p.apb + blockIdx.x) * (BS / 64) + (tid >> 6)) * 16 + 2 : nullptr;
+        if ((tid & 63) == 0 && lp3_cnt) *lp3_cnt = 0;
+#elif defined(CA_STAMPS) && CA_STAMPS == 3   // (cleared above; the timeline variant, 4, counts nothing)
+        unsigned long long* const lp3_cnt = p.dbg ? p.dbg + ((size_t)blockIdx.x * (BS / 64) + (tid >> 6)) * 16 + 4 : nullptr;
 #endif
         CA_PRIO_POINT(2);
         {
@@ -295,10 +306,13 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
             const unsigned long long below = (1ull << (tid & 63)) - 1ull;
             while (true) {
                 const unsigned long long m = __ballot(need);
-#if defined(CA_STAMPS) && CA_STAMPS == 3
-                if ((tid & 63) == 0 && p.dbg) p.dbg[((size_t)blockIdx.x * (BS / 64) + (tid >> 6)) * 16 + 4] += 1 + ((unsigned long long)__popcll(m) << 32);
+#if defined(CA_STAMPS) && CA_STAMPS <= 3
+                if ((tid & 63) == 0 && lp3_cnt) *lp3_cnt += 1 + ((unsigned long long)__popcll(m) << 32);
 #endif
                 if (__builtin_expect(!m, 1)) break;
+                if constexpr (PL) {   // 17 .. PAIR_SLOTS lanes wait: they leave for the paired round below
+                    if (__popcll(m) > POOL_SLOTS && __popcll(m) <= PAIR_SLOTS) break;
+                }
                 const int rank = __popcll(m & below);
                 const bool mine = need && rank < POOL_SLOTS;
                 if (mine) {
@@ -318,6 +332,36 @@ __global__ __launch_bounds__(BS, ST > 0 ? (BS == 512 ? CA_LB512 : 4) : 1) void s
                     const float4 h = hdr[rank];
                     nv = mk(h.x, h.y);
                     need = false;
+                }
+            }
+            if constexpr (PL) {
+                // More lanes wait than the pool has four-lane slots: ALL of them in one round, two lanes each (ca_lp.h lp3_pair_lds).
+                // The pool bytes hold their lines [ML][PAIR_SLOTS]; the headers lie over the staged velocities, which nothing of
+                // this instantiation reads behind the agent lines.  The round comes last (more than PAIR_SLOTS waiting lanes give
+                // the first POOL_SLOTS a four-lane round above until the rest fits: the solutions do not depend on the order), so
+                // the line registers are dead from here on and the solver has them.
+                const unsigned long long m = __ballot(need);
+                if (m != 0ull) {
+#if defined(CA_STAMPS) && CA_STAMPS <= 3
+                    if ((tid & 63) == 0 && lp3_cnt) *lp3_cnt += 1ull << 16;   // paired rounds: bits 16 .. 31
+#endif
+                    float4* hdr2 = reinterpret_cast<float4*>(s_vx);
+                    const int rank = __popcll(m & below);
+                    if (need) {
+                        static_for<ML>([&](auto kc) __attribute__((always_inline)) {
+                            constexpr int k = decltype(kc)::value;
+                            const bool valid = (k < ST) ? (k < no) : (k - ST < ncnt);
+                            if (valid) pool[((k < ST) ? k : no + (k - ST)) * PAIR_SLOTS + rank] = L[k];
+                        });
+                        hdr2[rank] = make_float4(nv.x, nv.y, __int_as_float(nl | (no << 8) | (fail << 16)), 0.0f);
+                    }
+                    wave_lds_sync();
+                    lp3_pair_lds<ML>((lp3_lds_v4f*)pool, (lp3_lds_v4f*)hdr2, __popcll(m), p.max_speed);
+                    wave_lds_sync();
+                    if (need) {
+                        const float4 h = hdr2[rank];
+                        nv = mk(h.x, h.y);
+                    }
                 }
             }
             if constexpr (SMX > ST) {   // the agents with more than ST obstacle neighbours, GX at a time (rare in small worlds; every

@@ -646,6 +646,14 @@ class VecCollisionAvoidanceEnv:
         self._call("ca_nbr_seed_info", self.h, C.byref(v))
         return bool(v.value)
 
+    def lp3_pairs_info(self):
+        """True if a plain step of this handle launches a PairedLp3 solve kernel: a wave with 17 to 32 infeasible agents solves
+        them in one LP3 round, two lanes per agent (ca_lp3_pairs_info; CA_LP3_PAIRS=0 / 1 in the environment at construction
+        selects the kernel without / with the tag)."""
+        v = C.c_int32()
+        self._call("ca_lp3_pairs_info", self.h, C.byref(v))
+        return bool(v.value)
+
     def tiled_info(self):
         """dict(tiled, tile_agents, tiles_per_arena, launches_per_step) of the tiled solve path (ca_tiled_info); zeros on an
         ordinary handle."""

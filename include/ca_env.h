@@ -374,6 +374,13 @@ int ca_agent_sensing_info(ca_env* env, int32_t* per_agent);
  * (a diagnostic switch, like CA_QUAD) keeps the handle on the unseeded kernels. */
 int ca_nbr_seed_info(ca_env* env, int32_t* seeded);
 
+/* The LP3 stage of the one-wave register-line solve kernels (arenas of at most 64 agents, K <= 10, obstacle lists of 4) solves a wave's
+ * infeasible agents cooperatively, 16 at a time with four lanes each.  The PairedLp3 kernels take a wave with 17 to 32 of them in one
+ * round instead, two lanes per agent; the results are the same bits.  *paired = 1 if a plain ca_step of this handle launches such a
+ * kernel, else 0.  CA_LP3_PAIRS=0 / 1 in the environment when the handle is made (a diagnostic switch, like CA_NBR_SEED) selects the
+ * kernel without / with the tag on one library. */
+int ca_lp3_pairs_info(ca_env* env, int32_t* paired);
+
 /* Replaces _init_world's agent loop (env.py:86-97) / ALAN's scenario generators (ALAN:175-457).  Runs on the device: every
  * agent's heading, start and targets come from the handle's counter-based streams (keyed by the global arena id) or, for
  * the layouts that do not depend on the arena, from a per-agent table made once on the host (its cos / sin / sqrt are
