@@ -41,7 +41,8 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
            "ca_fork_bytes_per_arena", "ca_rollout_actions",
            "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy",
-           "ca_nav_configure", "ca_nav_clear", "ca_nav_info", "ca_nav_get_field", "ca_nav_pref", "ca_rollout_nav", "ca_nav_mask_build")
+           "ca_nav_configure", "ca_nav_clear", "ca_nav_info", "ca_nav_get_field", "ca_nav_pref", "ca_rollout_nav", "ca_nav_mask_build",
+           "ca_nav_act", "ca_nav_step", "ca_rollout_nav_actions", "ca_rollout_nav_policy")
 POLICY_OUT_IDENTITY, POLICY_OUT_CLIP = 0, 1   # out_mode of a policy (struct ca_policy_desc)
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 128
 NAV_MAX_CELLS, NAV_MAX_GOALS, NAV_MAX_LOOKAHEAD = 32768, 16, 8   # limits of a navigation (struct ca_nav_desc)
@@ -186,6 +187,10 @@ def load():
     L.ca_nav_pref.argtypes = [vp, vp, u32]
     L.ca_rollout_nav.argtypes = [vp, i32, u32, C.POINTER(Trace)]
     L.ca_nav_mask_build.argtypes = [vp, i32, C.c_float, C.c_float, C.c_float, i32, i32, C.c_float, vp, i32]
+    L.ca_nav_act.argtypes = [vp, vp, vp, vp, u32]
+    L.ca_nav_step.argtypes = [vp, vp, u32]
+    L.ca_rollout_nav_actions.argtypes = [vp, i32, u32, C.POINTER(ActionSeq)]
+    L.ca_rollout_nav_policy.argtypes = [vp, i32, u32, C.POINTER(PolicySeq)]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]

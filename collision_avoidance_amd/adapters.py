@@ -63,6 +63,16 @@ def _episode_info(st, ended, n_agents):
     return dict(arena=idx, length=steps, arrived=arrived, truncated=arrived < np.broadcast_to(n_agents, ended.shape)[idx])
 
 
+def _step_fn(vec, navigate, who):
+    """vec.step, or with navigate=True vec.step_nav: actions are offsets from the navigation heading (set_navigation), not from the
+    straight line to the goal"""
+    if not navigate:
+        return vec.step
+    if not vec.navigation_info()["configured"]:
+        raise ValueError("%s: navigate=True needs a navigation on the vector env (set_navigation)" % who)
+    return vec.step_nav
+
+
 def _agent_counts(vec):
     """[A] agents per arena of a vector env (N everywhere where it has no per-arena counts, set_agent_counts)."""
     get = getattr(vec, "agent_counts", None)
@@ -89,10 +99,13 @@ class AgentVectorEnv(object):
       "agent_contact" [A*N]     bool: the agent overlaps another agent of its arena or a wall
       "agent_touching" [A*N]    int: how many other agents it overlaps
       "agent_nearest_d2" [A*N]  float: squared distance to the nearest other agent of its arena (inf alone)
+    navigate=True: the step is vec.step_nav -- an action is an offset from the heading of the navigation fields (set_navigation must
+    have been called: ValueError otherwise), and the reward counts progress along that heading.
     """
 
-    def __init__(self, vec, new_step_api=False, collect_stats=True, contacts=False):
+    def __init__(self, vec, new_step_api=False, collect_stats=True, contacts=False, navigate=False):
         self.vec, self.A, self.N = vec, vec.A, vec.N
+        self._step = _step_fn(vec, navigate, "AgentVectorEnv")
         self.contacts = bool(contacts)
         self.num_envs = self.A * self.N
         self.new_step_api, self.collect_stats = bool(new_step_api), bool(collect_stats)
@@ -112,7 +125,7 @@ class AgentVectorEnv(object):
     def step(self, actions):
         a = actions.reshape(self.A, self.N) if hasattr(actions, "reshape") else np.asarray(actions, np.float32).reshape(self.A, self.N)
         kw = dict(contacts=True) if self.contacts else {}
-        obs, rew, done, vinfo = self.vec.step(a, with_obs=True, stats=self.collect_stats, autoreset=True, **kw)
+        obs, rew, done, vinfo = self._step(a, with_obs=True, stats=self.collect_stats, autoreset=True, **kw)
         if torch is not None and isinstance(done, torch.Tensor):
             done_agents = done.reshape(self.A, 1).expand(self.A, self.N).reshape(self.num_envs) != 0
             ended = done.cpu().numpy() != 0 if self.collect_stats else None
@@ -165,10 +178,12 @@ class MultiAgentVectorEnv(object):
     only, and an action dictionary need not contain the absent ids.
     contacts=True: infos[env]['agent_<i>'] carries `contact` (the agent overlaps another agent of its arena or a wall) and
     `nearest_d2` (squared distance to the nearest other agent, inf alone) from the contact report of the state the step leaves.
+    navigate=True: the step is vec.step_nav, as for AgentVectorEnv.
     """
 
-    def __init__(self, vec, per_agent_dones=True, common_info=True, contacts=False):
+    def __init__(self, vec, per_agent_dones=True, common_info=True, contacts=False, navigate=False):
         self.vec, self.num_envs, self.N = vec, vec.A, vec.N
+        self._step = _step_fn(vec, navigate, "MultiAgentVectorEnv")
         self.contacts = bool(contacts)
         self.per_agent_dones, self.common_info = bool(per_agent_dones), bool(common_info)
         self.agent_ids = ['agent_%d' % i for i in range(self.N)]
@@ -217,7 +232,7 @@ class MultiAgentVectorEnv(object):
     def vector_step(self, actions):
         act = self._actions(actions)
         kw = dict(contacts=True) if self.contacts else {}
-        obs, rew, done, vinfo = self.vec.step(act, with_obs=True, stats=True, autoreset=False, **kw)
+        obs, rew, done, vinfo = self._step(act, with_obs=True, stats=True, autoreset=False, **kw)
         obs, rew, done = self._host(obs), self._host(rew), self._host(done) != 0
         if self.contacts:
             c = vinfo["contacts"]

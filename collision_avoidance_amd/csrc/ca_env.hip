@@ -122,6 +122,10 @@ struct ca_env {
         int* d_class = nullptr;
         std::vector<unsigned char> h_blocked;
     } nav;
+    // the navigated action step (ca_nav_act, ca_nav_step; ca_nav.h): [4][A*N] the direction and the rotated direction nav_act_kernel
+    // keeps for nav_reward_kernel, [A] whether the step between them advances the arena.  Allocated on first use; no field and no state
+    float* nav_keep = nullptr;
+    int* nav_advance = nullptr;
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -1193,7 +1197,7 @@ int ca_destroy(ca_env* e) {
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
-                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->nav.d_dist, e->nav.d_next, e->nav.d_class,
+                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->nav.d_dist, e->nav.d_next, e->nav.d_class, e->nav_keep, e->nav_advance,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -3230,8 +3234,8 @@ int ca_nav_get_field(ca_env* e, int32_t arena, int32_t goal, float* dist, uint8_
     return CA_OK;
 }
 
-// the preferred-velocity launch (kind 3 for ca_profile)
-static hipError_t launch_nav_pref(ca_env* e, float* dist_out, bool freeze) {
+// what the per-step kernels read of the state and the navigation
+static NavPrefArgs nav_pref_args(ca_env* e, float* dist_out, bool freeze) {
     const ca_env::Nav& n = e->nav;
     NavPrefArgs p;
     p.pos_x = e->pos_x; p.pos_y = e->pos_y; p.goal_x = e->goal_x; p.goal_y = e->goal_y;
@@ -3241,6 +3245,11 @@ static hipError_t launch_nav_pref(ca_env* e, float* dist_out, bool freeze) {
     p.an = (unsigned)AN(e); p.N = e->cfg.n_agents; p.G = n.G; p.gx = n.gx; p.gy = n.gy; p.cells = n.gx * n.gy;
     p.per_arena = n.per_arena; p.lookahead = n.lookahead; p.freeze = freeze ? 1 : 0;
     p.x0 = n.x0; p.y0 = n.y0; p.cell = n.cell; p.ics = n.ics;
+    return p;
+}
+// the preferred-velocity launch (kind 3 for ca_profile)
+static hipError_t launch_nav_pref(ca_env* e, float* dist_out, bool freeze) {
+    const NavPrefArgs p = nav_pref_args(e, dist_out, freeze);
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, nav_pref_kernel, dim3((p.an + 255) / 256), dim3(256), 0, e->stream, p);
     return hipGetLastError();
@@ -3273,6 +3282,145 @@ int ca_rollout_nav(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr)
         const int rc = do_step(e, nullptr, sf);
         if (rc) return rc;
         if (tr && (s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
+    }
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+// ---- action steps steered by the navigation (include/ca_env.h ca_nav_act, ca_nav_step; ca_nav.h) -----------------------
+static hipError_t nav_step_buffers(ca_env* e) {
+    if (!e->nav_keep) { const hipError_t r = dalloc(e, &e->nav_keep, 4 * AN(e)); if (r != hipSuccess) return r; }
+    if (!e->nav_advance) { const hipError_t r = dalloc(e, &e->nav_advance, (size_t)e->cfg.n_arenas); if (r != hipSuccess) return r; }
+    return hipSuccess;
+}
+// the launch in front of the step (kind 3 for ca_profile)
+static hipError_t launch_nav_act(ca_env* e, const float* actions, float* heading_out, float* dist_out, bool freeze) {
+    NavActArgs q;
+    q.n = nav_pref_args(e, dist_out, freeze);
+    q.actions = actions; q.keep = e->nav_keep; q.heading_out = heading_out; q.advance = e->nav_advance;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, nav_act_kernel, dim3((q.n.an + 255) / 256), dim3(256), 0, e->stream, q);
+    return hipGetLastError();
+}
+// what a rollout hands the launch behind its step t (null members: not wanted)
+struct NavStepRec { const ActSeqPlan* pl; const float* weights; float* returns; float* rewards_out; int32_t* done_out; int t; uint32_t flags; };
+// the launch behind the step (kind 3): the reward, the arena's sum under CA_F_STATS, a rollout's return, first_done and records
+static hipError_t launch_nav_reward(ca_env* e, uint32_t flags, const NavStepRec* rec) {
+    NavRewardArgs c;
+    c.vel_x = e->vel_x; c.vel_y = e->vel_y; c.keep = e->nav_keep; c.advance = e->nav_advance;
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.reward = e->reward; c.arena_stats = (flags & CA_F_STATS) ? e->arena_stats : nullptr;
+    c.reward_scale = e->cfg.reward_scale;
+    c.arena_done = e->arena_done;
+    c.entry_frozen = rec ? rec->pl->entry_frozen : nullptr;
+    c.weight = rec && rec->weights ? rec->weights + rec->t : nullptr;
+    c.returns = rec ? rec->returns : nullptr;
+    c.first_done = rec ? rec->pl->first_done : nullptr;
+    c.rewards_rec = rec && rec->rewards_out ? rec->rewards_out + (size_t)rec->t * AN(e) : nullptr;
+    c.done_rec = rec && rec->done_out ? (int*)rec->done_out + (size_t)rec->t * e->cfg.n_arenas : nullptr;
+    c.an = (unsigned)AN(e); c.N = e->cfg.n_agents; c.t = rec ? rec->t : 0; c.freeze = rec && (rec->flags & CA_F_FREEZE) ? 1 : 0;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, nav_reward_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
+    return hipGetLastError();
+}
+// one navigated action step: nav_act_kernel, the launches of the ORCA-only step, nav_reward_kernel
+static int nav_do_step(ca_env* e, const float* actions, uint32_t sf, const NavStepRec* rec) {
+    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    HIPCHK(e, launch_nav_act(e, actions, nullptr, nullptr, (sf & CA_F_FREEZE) != 0));
+    const int rc = do_step(e, nullptr, sf);
+    if (rc) return rc;
+    HIPCHK(e, launch_nav_reward(e, sf, rec));
+    return CA_OK;
+}
+
+int ca_nav_act(ca_env* e, const float* actions, float* heading_out, float* dist_out, uint32_t flags) {
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "ca_nav_act: call ca_nav_configure first");
+    if (!actions) return fail(e, CA_EINVAL, "ca_nav_act: actions is null");
+    if (flags & ~CA_F_FREEZE) return fail(e, CA_EINVAL, "ca_nav_act: flags=0x%x (0 or CA_F_FREEZE)", flags);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, nav_step_buffers(e));
+    HIPCHK(e, launch_nav_act(e, actions, heading_out, dist_out, (flags & CA_F_FREEZE) != 0));
+    return CA_OK;
+}
+
+int ca_nav_step(ca_env* e, const float* actions, uint32_t flags) {
+    const char* who = "ca_nav_step";
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "%s: call ca_nav_configure first", who);
+    if (!actions) return fail(e, CA_EINVAL, "%s: actions is null (ca_rollout_nav is the ORCA-only navigated step)", who);
+    if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "%s: CA_F_NODONE applies to ca_orca_step only", who);
+    if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE | CA_F_CONTACT))
+        return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, who); if (rs) return rs; }
+    HIPCHK(e, nav_step_buffers(e));
+    { const int rc = nav_do_step(e, actions, flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE), nullptr); if (rc) return rc; }
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+int ca_rollout_nav_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "ca_rollout_nav_actions: call ca_nav_configure first");
+    { const int rc = actseq_check(e, steps, flags, seq); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, "ca_rollout_nav_actions"); if (rs) return rs; }
+    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
+    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
+    HIPCHK(e, nav_step_buffers(e));
+    ActSeqPlan pl;
+    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
+    pl.entry_frozen = e->actseq_words + A;
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);   // (observation and contacts: one launch behind the last step, below)
+    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    HIPCHK(e, launch_actseq_begin(e, seq, pl, flags));
+    NavStepRec rec = {&pl, seq->weights, seq->returns, nullptr, nullptr, 0, flags};
+    for (int t = 0; t < steps; ++t) {   // always the per-step form, as ca_rollout_nav
+        rec.t = t;
+        const int rc = nav_do_step(e, seq->actions + (size_t)(t / seq->hold) * an, sf, &rec);
+        if (rc) return rc;
+    }
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+
+int ca_rollout_nav_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
+    if (!e) return CA_EINVAL;
+    if (!e->nav.on) return fail(e, CA_EINVAL, "ca_rollout_nav_policy: call ca_nav_configure first");
+    { const int rc = policy_seq_check(e, steps, flags, seq); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, "ca_rollout_nav_policy"); if (rs) return rs; }
+    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
+    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
+    HIPCHK(e, nav_step_buffers(e));
+    ActSeqPlan pl;
+    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
+    pl.entry_frozen = e->actseq_words + A;
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
+    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    {   // zeros, -1, the arenas frozen at entry: the set-up launch of ca_rollout_actions
+        ca_action_seq b;
+        memset(&b, 0, sizeof b);
+        b.returns = seq->returns;
+        HIPCHK(e, launch_actseq_begin(e, &b, pl, flags));
+    }
+    NavStepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
+    for (int t = 0; t < steps; ++t) {
+        if (t % seq->hold == 0) {   // a row starts: what ca_observe launches, then the policy on what it left
+            const size_t r = (size_t)(t / seq->hold);
+            if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+            HIPCHK(e, launch_obs(e));
+            HIPCHK(e, launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act,
+                                    seq->actions_out ? seq->actions_out + r * an : nullptr,
+                                    seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr));
+        }
+        rec.t = t;
+        const int rc = nav_do_step(e, e->pol.act, sf, &rec);
+        if (rc) return rc;
     }
     if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
     if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));

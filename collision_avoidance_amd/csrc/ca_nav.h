@@ -22,9 +22,20 @@
 // nav_pref_kernel: one lane per agent row; the row's cell, `lookahead` pointer steps through next, and goal_dir (ca_rules.h) towards the
 // centre of the cell reached -- or towards the agent's own goal when the walk never moved or ended on STAY.  It writes PREF_X / PREF_Y
 // (and dist_out) of navigated rows and nothing else.
+// The navigated action step (ca_nav_act, ca_nav_step, ca_rollout_nav_actions / _policy) is two more small kernels round the
+// launches of an ORCA-only step, which reads PREF as its input and leaves VEL alone across a respawn:
+//   * nav_act_kernel, in front: one lane per agent row; the point T the row heads for -- nav_pref_kernel's for a row it would navigate
+//     (the same walk, nav_walk below), the agent's own goal for every other present row --, then action_pref (ca_rules.h: the function of
+//     the solve kernels) towards T.  PREF = the rotated direction; the direction and the rotated direction are kept in a buffer of the
+//     handle's for the kernel behind the step, and the lane of agent 0 notes whether the arena is advanced at all (CA_F_FREEZE);
+//   * nav_reward_kernel, behind: REWARD = step_reward (ca_rules.h) of the velocity the step left and the two kept directions, for
+//     the present rows of the arenas that were advanced; under CA_F_STATS the arena's sum in f64 (a segmented sum inside the wave, one
+//     atomic per arena and wave); and, for the rollouts, the return, first_done and the reward / done records by the rule of
+//     actseq_accumulate_kernel / policy_record_kernel word for word, so that no second launch follows.
 #pragma once
 #include "ca_common.h"
 #include "ca_rules.h"
+#include "ca_actseq.h"
 
 namespace ca {
 
@@ -146,6 +157,24 @@ struct NavPrefArgs {
 // the grid's cell expression (ca_nav_host.h; the edge grid's)
 __device__ __forceinline__ int nav_cell(float v, float x0, float ics, int g) { return (int)fminf(fmaxf(floorf((v - x0) * ics), 0.0f), (float)(g - 1)); }
 
+// the pointer walk from cell (wx, wy): `lookahead` steps through next, (ox, oy) the cell reached.  True: the walk never moved or ended on
+// STAY -- the row heads for the agent's own goal; false: for the centre of (ox, oy).  (The cell by value, the order of the locals and
+// the sense of the result are what leaves nav_pref_kernel's instruction text as it was with the loop written out in it:
+// profiles/nav_step_kernel_resources.txt.)
+__device__ __forceinline__ bool nav_walk(int wx, int wy, const NavPrefArgs& p, const unsigned char* next, int& ox, int& oy) {
+    int k = NAV_NONE;
+    bool moved = false;
+    for (int l = 0; l < p.lookahead; ++l) {
+        k = (int)next[wy * p.gx + wx];
+        if (k >= 8) break;
+        const int ux = wx + nav_dx(k), uy = wy + nav_dy(k);
+        if (ux < 0 || ux >= p.gx || uy < 0 || uy >= p.gy) break;   // (a pointer never leaves the grid; this keeps the read in bounds whatever the table holds)
+        wx = ux; wy = uy; moved = true;
+    }
+    ox = wx; oy = wy;
+    return !moved || k == NAV_STAY;
+}
+
 __global__ __launch_bounds__(256) void nav_pref_kernel(const NavPrefArgs p) {
     const unsigned g = blockIdx.x * 256u + threadIdx.x;
     if (g >= p.an) return;
@@ -155,28 +184,121 @@ __global__ __launch_bounds__(256) void nav_pref_kernel(const NavPrefArgs p) {
     if (i >= count || cls < 0 || cls >= p.G || p.agent_done[g] != 0) return;
     if (p.freeze && p.arena_done[a] != 0) return;
     const V2 pos = mk(p.pos_x[g], p.pos_y[g]);
-    int wx = nav_cell(pos.x, p.x0, p.ics, p.gx), wy = nav_cell(pos.y, p.y0, p.ics, p.gy);
+    const int wx = nav_cell(pos.x, p.x0, p.ics, p.gx), wy = nav_cell(pos.y, p.y0, p.ics, p.gy);
     const size_t f = ((size_t)(p.per_arena ? a : 0) * (size_t)p.G + (size_t)cls) * (size_t)p.cells;
     const unsigned char* next = p.next + f;
     if (p.dist_out != nullptr) p.dist_out[g] = p.dist[f + (size_t)(wy * p.gx + wx)];
-    bool moved = false;
-    int k = NAV_NONE;
-    for (int l = 0; l < p.lookahead; ++l) {
-        k = (int)next[wy * p.gx + wx];
-        if (k >= 8) break;
-        const int ux = wx + nav_dx(k), uy = wy + nav_dy(k);
-        if (ux < 0 || ux >= p.gx || uy < 0 || uy >= p.gy) break;   // (a pointer never leaves the grid; this keeps the read in bounds whatever the table holds)
-        wx = ux; wy = uy; moved = true;
-    }
+    int ox, oy;
     V2 dir;
-    if (!moved || k == NAV_STAY) {
+    if (nav_walk(wx, wy, p, next, ox, oy)) {
         dir = goal_dir(pos, p.goal_x[g], p.goal_y[g]);
     } else {
-        const float tx = p.x0 + ((float)wx + 0.5f) * p.cell, ty = p.y0 + ((float)wy + 0.5f) * p.cell;
+        const float tx = p.x0 + ((float)ox + 0.5f) * p.cell, ty = p.y0 + ((float)oy + 0.5f) * p.cell;
         dir = goal_dir(pos, (double)tx, (double)ty);
     }
     p.pref_x[g] = dir.x;
     p.pref_y[g] = dir.y;
+}
+
+struct NavActArgs {
+    NavPrefArgs n;           // the state, the navigation, pref_x / pref_y, dist_out (or null), freeze
+    const float* actions;    // [A*N]
+    float* keep;             // [4][A*N] the handle's: dir.x | dir.y | rot.x | rot.y for nav_reward_kernel
+    float* heading_out;      // [2][A*N] dir, or null
+    int* advance;            // [A] 1: the step behind this launch advances the arena, 0: frozen
+};
+
+__global__ __launch_bounds__(256) void nav_act_kernel(const NavActArgs q) {
+    const NavPrefArgs& p = q.n;
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= p.an) return;
+    const int a = (int)(g / (unsigned)p.N), i = (int)(g - (unsigned)a * (unsigned)p.N);
+    const bool frozen = p.freeze && p.arena_done[a] != 0;
+    if (i == 0) q.advance[a] = frozen ? 0 : 1;
+    const int count = p.agent_counts != nullptr ? p.agent_counts[a] : p.N;
+    if (i >= count || frozen) return;
+    const V2 pos = mk(p.pos_x[g], p.pos_y[g]);
+    double tx = p.goal_x[g], ty = p.goal_y[g];
+    const int cls = p.cls[g];
+    if (cls >= 0 && cls < p.G && p.agent_done[g] == 0) {   // a row nav_pref_kernel navigates: its cell, its walk, its centre
+        const int wx = nav_cell(pos.x, p.x0, p.ics, p.gx), wy = nav_cell(pos.y, p.y0, p.ics, p.gy);
+        const size_t f = ((size_t)(p.per_arena ? a : 0) * (size_t)p.G + (size_t)cls) * (size_t)p.cells;
+        if (p.dist_out != nullptr) p.dist_out[g] = p.dist[f + (size_t)(wy * p.gx + wx)];
+        int ox, oy;
+        if (!nav_walk(wx, wy, p, p.next + f, ox, oy)) {
+            const float cx = p.x0 + ((float)ox + 0.5f) * p.cell, cy = p.y0 + ((float)oy + 0.5f) * p.cell;
+            tx = (double)cx; ty = (double)cy;
+        }
+    }
+    V2 dir, rot;
+    action_pref(pos, tx, ty, q.actions[g], dir, rot);
+    p.pref_x[g] = rot.x;
+    p.pref_y[g] = rot.y;
+    const size_t an = (size_t)p.an;
+    q.keep[g] = dir.x; q.keep[an + g] = dir.y; q.keep[2 * an + g] = rot.x; q.keep[3 * an + g] = rot.y;
+    if (q.heading_out != nullptr) { q.heading_out[g] = dir.x; q.heading_out[an + g] = dir.y; }
+}
+
+struct NavRewardArgs {
+    const float *vel_x, *vel_y;
+    const float* keep;             // [4][A*N] what nav_act_kernel kept
+    const int* advance;            // [A]
+    const int* agent_counts;       // [A] (ca_set_agent_counts), or null
+    float* reward;                 // [A*N] CA_FLD_REWARD
+    unsigned long long* arena_stats;   // CA_F_STATS: the per-arena rows (ST_SUMREW), else null
+    double reward_scale;
+    // a rollout's step t (first_done != null), as ActSeqAccArgs / PolicyRecArgs
+    const int* arena_done;
+    const int* entry_frozen;
+    const float* weight;           // &weights[t], or null
+    float* returns;                // or null
+    int* first_done;               // the caller's or the handle's own; null: a single ca_nav_step
+    float* rewards_rec;            // [A*N] row t of the reward record, or null
+    int* done_rec;                 // [A] row t of the done record, or null
+    unsigned an;
+    int N, t, freeze;
+};
+
+__global__ __launch_bounds__(256) void nav_reward_kernel(const NavRewardArgs s) {
+    const unsigned g = blockIdx.x * 256u + threadIdx.x;
+    const bool row = g < s.an;   // (no lane leaves before the wave's sum)
+    const int a = row ? (int)(g / (unsigned)s.N) : -1, i = row ? (int)(g - (unsigned)a * (unsigned)s.N) : 0;
+    const int count = row ? (s.agent_counts != nullptr ? s.agent_counts[a] : s.N) : 0;
+    const bool stepped = row && s.advance[a] == 1 && i < count;
+    float r = 0.0f;
+    if (stepped) {
+        const size_t an = (size_t)s.an;
+        r = step_reward(s.reward_scale, mk(s.vel_x[g], s.vel_y[g]), mk(s.keep[g], s.keep[an + g]), mk(s.keep[2 * an + g], s.keep[3 * an + g]));
+        s.reward[g] = r;
+    } else if (row) {
+        r = s.reward[g];
+    }
+    if (s.arena_stats != nullptr) {
+        // the rows of an arena are consecutive lanes: a suffix sum that stops at the arena's last lane, its first lane of this wave adds
+        double sum = stepped ? (double)r : 0.0;
+        const int lane = (int)(threadIdx.x & 63u);
+        for (int off = 1; off < 64; off <<= 1) {
+            const double ts = __shfl_down(sum, off, 64);
+            const int ta = __shfl_down(a, off, 64);
+            if (lane + off < 64 && ta == a) sum += ts;
+        }
+        const int pa = __shfl_up(a, 1, 64);
+        if (row && (lane == 0 || pa != a) && s.advance[a] == 1)
+            atomicAdd(reinterpret_cast<double*>(&s.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), sum);
+    }
+    if (!row || s.first_done == nullptr) return;
+    // actseq_accumulate_kernel / policy_record_kernel, word for word (r: what CA_FLD_REWARD holds behind this step)
+    const float ret = s.returns != nullptr ? s.returns[g] : 0.0f;
+    const int fd = s.first_done[a];
+    const int done = s.arena_done[a];
+    const int frozen0 = s.freeze ? s.entry_frozen[a] : 0;
+    const float w = s.weight != nullptr ? *s.weight : 1.0f;
+    if (s.rewards_rec != nullptr) s.rewards_rec[g] = r;
+    if (s.done_rec != nullptr && i == 0) s.done_rec[a] = done;
+    const bool advanced = !(s.freeze && (frozen0 != 0 || (fd >= 0 && fd < s.t)));
+    if (!advanced) return;
+    if (s.returns != nullptr && i < count) s.returns[g] = actseq_add(ret, w, r);
+    if (i == 0 && fd < 0 && done != 0) s.first_done[a] = s.t;
 }
 
 }  // namespace ca

@@ -1006,7 +1006,7 @@ class VecCollisionAvoidanceEnv:
         return bufs[key]
 
     def rollout_actions(self, actions, hold=1, weights=None, returns=True, first_done=False, with_obs=False, stats=False,
-                        autoreset=False, freeze=False, contacts=False, steps=None):
+                        autoreset=False, freeze=False, contacts=False, steps=None, _entry="ca_rollout_actions"):
         """`steps` step() calls under the action tensor `actions` [R, A, N] without returning to the host (ca_rollout_actions): row
         t // hold drives step t, so every row is held for `hold` steps (frame skip) and steps = R * hold; steps= gives a shorter
         last row (R == ceil(steps / hold)).  The state, fields and statistics left are those of the step() calls, bit for bit.
@@ -1063,7 +1063,7 @@ class VecCollisionAvoidanceEnv:
                              weights=ptr(w) if steps else None, weights_bytes=nbytes(w, steps),
                              returns=ptr(ret), returns_bytes=nbytes(ret, self.A * self.N),
                              first_done=ptr(fd), first_done_bytes=nbytes(fd, self.A))
-        self._call("ca_rollout_actions", self.h, steps, flags, C.byref(seq))
+        self._call(_entry, self.h, steps, flags, C.byref(seq))
         if not on_torch:
             self.sync()
             ret = None if ret is None else np.array(ret)
@@ -1156,7 +1156,8 @@ class VecCollisionAvoidanceEnv:
         return np.array(out)
 
     def rollout_policy(self, steps, hold=1, noise=None, weights=None, record=("obs", "actions", "rewards", "dones"), returns=True,
-                       first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False):
+                       first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False,
+                       _entry="ca_rollout_policy"):
         """`steps` steps under the installed policy without returning to the host (ca_rollout_policy): at every hold-th step
         observe(), the policy on that observation (plus noise[t // hold] where given), then step() under the action for `hold`
         steps.  The state, fields and statistics left are those of that loop, bit for bit.  noise [R, A, N] (R = ceil(steps /
@@ -1205,7 +1206,7 @@ class VecCollisionAvoidanceEnv:
                              actions_out=ptr(b("actions")) if R else None, actions_out_bytes=size("actions") if "actions" in bufs else 0,
                              rewards_out=ptr(b("rewards")) if steps else None, rewards_out_bytes=size("rewards") if "rewards" in bufs else 0,
                              done_out=ptr(b("dones")) if steps else None, done_out_bytes=size("dones") if "dones" in bufs else 0)
-        self._call("ca_rollout_policy", self.h, steps, flags, C.byref(seq))
+        self._call(_entry, self.h, steps, flags, C.byref(seq))
         if not on_torch:
             self.sync()
             bufs = {n: np.array(a[:sh[n][0]]) if n in ("obs", "actions", "rewards", "dones") else np.array(a) for n, a in bufs.items()}
@@ -1316,6 +1317,94 @@ class VecCollisionAvoidanceEnv:
             self._call("ca_orca_step", self.h, flags)
             return out
         self._call("ca_rollout_nav", self.h, steps, flags, None)
+
+    # ---- action steps steered by the navigation fields (ca_nav_act, ca_nav_step, ca_rollout_nav_*) -------------------
+    def nav_act(self, actions, heading=False, dist=False, freeze=False):
+        """Write the preferred velocities (PREF_X / PREF_Y) of every present agent as the navigation heading rotated by actions [A, N]
+        (ca_nav_act: one launch): the heading is nav_pref()'s for a navigated agent and the direction to its own goal for every
+        other one (class -1, or arrived and walking on).  The next orca_step() steers by them.  freeze: the agents of arenas whose
+        episode is over are not written.  Returns None, or a dict of what was asked for: heading [2, A, N] (the unrotated
+        direction; heading=True: zeros for rows that were not written, heading=an array: that array's values) and dist [A, N] as
+        nav_pref(dist=...) gives it (navigated rows only).  Device tensors with use_torch, else numpy arrays."""
+        flags = _lib.F_FREEZE if freeze else 0
+        want_dist = not (dist is False or dist is None)
+        head_given = None if heading is True or heading is False or heading is None else heading
+        heading = heading is True or head_given is not None
+        if head_given is not None and torch is not None and isinstance(head_given, torch.Tensor) and not self.use_torch:
+            head_given = head_given.detach().cpu().numpy()
+        if self.use_torch:
+            dev = torch.device("cuda", self.device)
+            act = torch.as_tensor(actions).detach().to(device=dev, dtype=torch.float32).reshape(self.A, self.N).contiguous()
+            head = torch.zeros((2, self.A, self.N), dtype=torch.float32, device=dev) if heading else None
+            if head_given is not None:
+                head.copy_(torch.as_tensor(head_given).to(device=dev, dtype=torch.float32).reshape(2, self.A, self.N))
+            a_addr, h_addr = act.data_ptr(), head.data_ptr() if heading else None
+        else:
+            if torch is not None and isinstance(actions, torch.Tensor):
+                actions = actions.detach().cpu().numpy()
+            act = self._actseq_host("nav_actions", (self.A, self.N), np.float32)
+            act[...] = np.asarray(actions, np.float32).reshape(self.A, self.N)
+            head = None
+            if heading:
+                head = self._actseq_host("nav_heading", (2, self.A, self.N), np.float32)
+                head[...] = 0.0 if head_given is None else np.asarray(head_given, np.float32).reshape(2, self.A, self.N)
+            a_addr, h_addr = act.ctypes.data, head.ctypes.data if heading else None
+        dbuf, d_addr = self._nav_dist_buf(dist) if want_dist else (None, None)
+        self._call("ca_nav_act", self.h, C.c_void_p(a_addr), C.c_void_p(h_addr) if heading else None,
+                   C.c_void_p(d_addr) if want_dist else None, flags)
+        if not (heading or want_dist):
+            if not self.use_torch:
+                self.sync()       # (the action buffer is the handle's own: the next call may overwrite it)
+            return None
+        if not self.use_torch:
+            self.sync()
+            head, dbuf = (None if head is None else np.array(head)), (None if dbuf is None else np.array(dbuf))
+        return dict(heading=head, dist=dbuf)
+
+    def step_nav(self, actions, with_obs=True, stats=False, autoreset=False, freeze=False, copy=True, contacts=False):
+        """step(actions) with the actions taken as offsets from the navigation heading (ca_nav_step): nav_act(actions), the
+        launches of orca_step(), and a small kernel that writes the reference's reward from the velocity the step left and the two
+        directions nav_act kept -- progress along the navigation heading and along the rotated one.  Returns what step() returns.
+        An agent that is not navigated steps exactly as under step(); arrive_step counts the ORCA-only way and PREF afterwards is
+        the direction to the goal (include/ca_env.h).  Needs set_navigation()."""
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
+                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        if self.use_torch:
+            if not isinstance(actions, torch.Tensor):
+                actions = torch.as_tensor(np.asarray(actions, np.float32).reshape(self.A, self.N))
+            if actions.is_cuda and actions.dtype == torch.float32 and actions.is_contiguous() and \
+                    actions.numel() == self.A * self.N and actions.device.index == self.device:
+                src = actions
+            else:
+                self._act_t.copy_(actions.reshape(self.A, self.N), non_blocking=True)
+                src = self._act_t
+            self._call("ca_nav_step", self.h, C.c_void_p(src.data_ptr()), flags)
+            return (self._obs_t if with_obs else None), self._rew_t, self._done_t, \
+                ({"contacts": self.last_contacts()} if contacts else {})
+        if torch is not None and isinstance(actions, torch.Tensor):
+            actions = actions.detach().cpu().numpy()
+        a = self._actseq_host("nav_actions", (self.A, self.N), np.float32)   # page-locked and device-visible: read where it lies
+        a[...] = np.asarray(actions, np.float32).reshape(self.A, self.N)
+        self._call("ca_nav_step", self.h, C.c_void_p(a.ctypes.data), flags)
+        infos = {"contacts": self.last_contacts()} if contacts else {}
+        if not copy:
+            return (self.get(_lib.FLD_OBS, self.host_buffer(_lib.FLD_OBS)) if with_obs else None), \
+                self.get(_lib.FLD_REWARD, self.host_buffer(_lib.FLD_REWARD)), \
+                self.get(_lib.FLD_ARENA_DONE, self.host_buffer(_lib.FLD_ARENA_DONE)), infos
+        return (self.get(_lib.FLD_OBS) if with_obs else None), self.get(_lib.FLD_REWARD), \
+            self.get(_lib.FLD_ARENA_DONE), infos
+
+    def rollout_nav_actions(self, actions, hold=1, weights=None, returns=True, first_done=False, with_obs=False, stats=False,
+                            autoreset=False, freeze=False, contacts=False, steps=None):
+        """rollout_actions() with step_nav() in place of step() (ca_rollout_nav_actions): the same arguments, the same dict."""
+        return self.rollout_actions(actions, hold, weights, returns, first_done, with_obs, stats, autoreset, freeze, contacts, steps,
+                                    _entry="ca_rollout_nav_actions")
+
+    def rollout_nav_policy(self, steps, hold=1, noise=None, weights=None, record=("obs", "actions", "rewards", "dones"), returns=True,
+                           first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False):
+        """rollout_policy() with step_nav() in place of step() (ca_rollout_nav_policy): the same arguments, the same dict."""
+        return self.rollout_policy(steps, hold, noise, weights, record, returns, first_done, with_obs, stats, autoreset, freeze, contacts,
+                                   _entry="ca_rollout_nav_policy")
 
     # ---- ALAN online learning (ALAN_true.py:569-628) -----------------------------------------------
     def alan_configure(self, actions, temp=0.2, timewindow=2.0, time_step=1 / 60.):

@@ -760,7 +760,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
@@ -915,6 +915,64 @@ int ca_nav_pref(ca_env* env, float* dist_out, uint32_t flags);
 int ca_rollout_nav(ca_env* env, int32_t steps, uint32_t flags, const ca_trace* tr);
 int ca_nav_mask_build(const float* edges_pq, int32_t n_edges, float x0, float y0, float cell, int32_t gx, int32_t gy, float clearance,
                       uint8_t* blocked, int32_t cells_cap);
+
+/* Action steps steered by the navigation fields.  ca_step, ca_rollout_actions and ca_rollout_policy rotate the straight line to the
+ * agent's own goal by the action, so behind a wall an action of 0 walks into the wall and the reward's progress term pays for pushing
+ * against it.  Here the action rotates the navigation heading instead, and the reward counts progress along that heading.  No solve
+ * kernel knows about it: every solve family reads CA_FLD_PREF_X / _Y as its input when no actions are given and leaves CA_FLD_VEL_*
+ * unchanged across a respawn, so a navigated action step is a small kernel in front of the launches of ca_orca_step and a small kernel
+ * behind them.  Every value is defined bit for bit: fp32 / fp64 exactly as written, one rounding per operation, no contraction.
+ *
+ * ca_nav_act(env, actions, heading_out, dist_out, flags): ONE launch (nav_act_kernel), one lane per agent row.  actions DEVICE f32
+ * [A, N]; heading_out DEVICE f32 [2, A, N] or NULL; dist_out DEVICE f32 [A, N] or NULL; flags 0 or CA_F_FREEZE.
+ *   - A row is STEERED if it is present (i < counts[a] under ca_set_agent_counts) and not (CA_F_FREEZE and arena_done[a] != 0).  A
+ *     row that is not steered is not written at all.
+ *   - The point T a steered row heads for: if ca_nav_pref would navigate the row (agent_done == 0, class in 0 .. G-1), T is what
+ *     ca_nav_pref heads for -- the centre of the cell reached after `lookahead` pointer steps (x0 + ((float)cx + 0.5f) * cell, as a
+ *     double), or the agent's own goal when the walk never moved or ended on CA_NAV_STAY.  Otherwise (class -1, or a done agent
+ *     walking to its second goal) T is the agent's own goal (CA_FLD_GOAL_X / _Y).
+ *   - For a steered row, the function of the solve kernels (csrc/ca_rules.h action_pref; env.py:371-383):
+ *         (pf_x, pf_y) = pref_dir64(pos, T)                       the fp64 unit vector pos -> T (env.py:156-162)
+ *         (sn, cs) = sincos64((double)action)
+ *         rl_x = pf_x * cs - pf_y * sn;   rl_y = pf_x * sn + pf_y * cs        (fp64)
+ *         dir = ((float)pf_x, (float)pf_y);   rot = ((float)rl_x, (float)rl_y)
+ *     It writes CA_FLD_PREF_X / _Y = rot, heading_out = dir where given, and dir and rot into a buffer of the handle's ([4, A, N],
+ *     allocated on first use, freed by ca_destroy; no ca_field and no state: ca_arena_gather and ca_snapshot_* do not move it).  For
+ *     navigated rows only, dist_out follows ca_nav_pref's rule.  The lane of agent 0 notes per arena whether it is steered (1) or
+ *     frozen (0) for the kernel behind the step.
+ *   Without a navigation, NULL actions or any other flag -> CA_EINVAL.
+ *
+ * ca_nav_step(env, actions, flags) is, by definition,
+ *     1. ca_nav_act(env, actions, NULL, NULL, flags & CA_F_FREEZE)
+ *     2. ca_orca_step(env, flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE))
+ *     3. one launch of nav_reward_kernel: for every present row of an arena that step 1 noted as steered,
+ *            CA_FLD_REWARD = step_reward(reward_scale, (VEL_X, VEL_Y) as step 2 left them, dir, rot)          (csrc/ca_rules.h; env.py:389-400)
+ *            = scale * (vel.x * dir.x + vel.y * dir.y) + (1.0f - scale) * (vel.x * rot.x + vel.y * rot.y),  scale = (float)reward_scale, in fp32.
+ *        Under CA_F_AUTORESET the velocity survives the respawn, so the step that ends an episode is rewarded like any other.  Rows
+ *        of a frozen arena keep their reward.  Under CA_F_STATS the arena's rewards are added into the arena's sum_reward in f64; the
+ *        order of that sum is not defined: it agrees with a sequential sum to 1e-9 relative, the tolerance of tiled handles.
+ *     4. one observation launch (CA_F_OBS) and one contact launch (CA_F_CONTACT) for the state left, if asked for.
+ *   Everything else is what ca_orca_step leaves: the step counter, the done test, arrive_step (counted the ORCA-only way: the counter
+ *   is incremented before the done test, so an arrival reads one more than under ca_step), the collision statistics, the PREF field
+ *   afterwards (the unit vector from the new position to the goal, not the rotated direction ca_step leaves), and the observation
+ *   frame.  With no row navigated, POS, VEL, REWARD, the goals, the done flags and the counters are ca_step's, bit for bit.
+ *   CA_F_NODONE or an unknown bit, NULL actions, no navigation -> CA_EINVAL; a refusal advances nothing.  The sticky overflow status
+ *   works as in ca_rollout.
+ *
+ * ca_rollout_nav_actions(env, steps, flags, seq) is the loop of ca_nav_step(env, actions + (t / hold) * A * N, flags); returns and
+ * first_done follow exactly the rules of ca_rollout_actions (ret = ret + w * r in two fp32 operations, freezing, absent rows, the
+ * sum running across a respawn), and it takes ca_rollout_actions's checks, messages and steps == 0 behaviour; CA_F_OBS / CA_F_CONTACT
+ * are one launch behind the last step.  ca_rollout_nav_policy(env, steps, flags, seq) is the loop of ca_rollout_policy's definition
+ * with ca_nav_step in place of ca_step: the same records, the same checks.  Both -> CA_EINVAL without a navigation, before anything else
+ * is looked at.  Both always take the per-step form, also where ca_rollout is one launch (as ca_rollout_nav and ca_rollout_policy do):
+ * per step nav_act_kernel, the launches of the ORCA-only step, and ONE kernel behind them -- nav_reward_kernel takes the return,
+ * first_done and the reward / done records as optional arguments, so no second accumulate launch follows.  A held action is re-rotated
+ * every step about that step's heading, as ca_step re-derives the goal direction every step.  ca_profile counts both kernels under kind 3. */
+int ca_nav_act(ca_env* env, const float* actions, float* heading_out, float* dist_out, uint32_t flags);
+int ca_nav_step(ca_env* env, const float* actions, uint32_t flags);
+int ca_rollout_nav_actions(ca_env* env, int32_t steps, uint32_t flags, const ca_action_seq* seq);
+int ca_rollout_nav_policy(ca_env* env, int32_t steps, uint32_t flags, const ca_policy_seq* seq);
+
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
 const char* ca_source_sha(void);

@@ -6,7 +6,10 @@
       scenarios.pillar_hall(300, 40, 1.0), and 4096 sets x 1 goal x 32 x 32 cells in scenarios.blocks_worlds(4096, 16);
   (b) nav_pref_kernel per launch at 4096 x 64 and at 1 x 16384 (tiled, grid), beside the launches of the ORCA-only step it precedes;
   (c) rollout_nav(64) against what a caller could do before: a Python loop that computes the same preferred velocities with torch
-      gathers on the device, writes them into PREF_X / PREF_Y and calls orca_step -- at 1024 x 16 and 4096 x 64.
+      gathers on the device, writes them into PREF_X / PREF_Y and calls orca_step -- at 1024 x 16 and 4096 x 64;
+  (e) the navigated action step (ca_nav_step): rollout_nav_policy(64) against (i) the Python loop of observe /
+      policy_actions / step_nav and (ii) rollout_policy(64) on the same handle, at 1024 x 16 and 4096 x 64, and the two new kernels'
+      own times (ca_profile).  Not among the default parts: --only e --out profiles/nav_step_cost.txt.
 
   python tools/nav_cost.py [--repeat 5] [--seconds 0.5] [--only a,b,c] [--out FILE]
 """
@@ -180,6 +183,53 @@ def part_c(args, say):
         env.close()
 
 
+# ---- (e) -------------------------------------------------------------------------------------------------------------------------------
+def part_e(args, say):
+    say("")
+    say("(e) %d policy steps (64-64-1): rollout_nav_policy | the Python loop observe / policy_actions / step_nav | rollout_policy -- "
+        "G agent-steps/s: median  min .. max  (every repeat)" % T)
+    rs = np.random.RandomState(0)
+    layers = [((rs.standard_normal((o, i)) / np.sqrt(i)).astype(np.float32), np.zeros(o, np.float32)) for i, o in ((64, 64), (64, 64), (64, 1))]
+    for A, N in ((1024, 16), (4096, 64)):
+        env, nav = crowd_env(A, N)
+        env.set_policy(layers, out="clip", limit=float(np.pi / 4))
+
+        def loop():
+            for _ in range(T):
+                env.observe()
+                env.step_nav(env.policy_actions(), with_obs=False)
+        vs = [("rollout_nav_policy(T): one call", lambda: env.rollout_nav_policy(T, record=(), returns=False)),
+              ("T x (observe, policy_actions, step_nav)", loop),
+              ("rollout_policy(T): one call", lambda: env.rollout_policy(T, record=(), returns=False))]
+        res = {n: [] for n, _ in vs}
+        for _, c in vs:
+            c(); env.sync()
+        for _ in range(args.repeat):
+            for n, c in vs:
+                res[n].append(timed(env, c, args.seconds))
+        say("  %d x %d agents, grid %d x %d, 4 targets" % (A, N, nav["side"], nav["side"]))
+        for n, _ in vs:
+            say("    %-42s %s" % (n, stat(res[n], 1e9, "%.4f")))
+        med = {n: sorted(v)[len(v) // 2] for n, v in res.items()}
+        say("    one call / loop (medians): %.2f;  navigated / straight-line policy rollout (medians): %.2f"
+            % (med[vs[0][0]] / med[vs[1][0]], med[vs[0][0]] / med[vs[2][0]]))
+        # the two kernels on their own dispatches: nav_act alone, then both round the step (the mean of the two: reward = 2 x mean - act)
+        act = torch.zeros((A, N), dtype=torch.float32, device=torch.device("cuda", env.device))
+        env.profile(1); env.profile_read()
+        for _ in range(40):
+            env.nav_act(act)
+        n_a, ms_a = env.profile_read()["reset_kernels"]
+        for _ in range(40):
+            env.step_nav(act, with_obs=False, stats=True)
+        prof = env.profile_read(); env.profile(0)
+        n_b, ms_b = prof["reset_kernels"]
+        sn, sms = prof["step_kernel"]
+        assert n_a == 40 and n_b == 80, (n_a, n_b)
+        say("    nav_act_kernel %d x %.2f us; nav_reward_kernel (CA_F_STATS) %d x %.2f us; solve launches %d x %.2f us = %.2f us per step"
+            % (n_a, ms_a * 1e3, n_b - n_a, (2 * ms_b - ms_a) * 1e3, sn, sms * 1e3, sn * sms * 1e3 / 40))
+        env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=5)
@@ -194,7 +244,7 @@ def main():
     def say(text=""):
         print(text, flush=True)
         lines.append(text)
-    for part, fn in (("a", part_a), ("b", part_b), ("c", part_c)):
+    for part, fn in (("a", part_a), ("b", part_b), ("c", part_c), ("e", part_e)):
         if part in args.only.split(","):
             try:
                 fn(args, say)
