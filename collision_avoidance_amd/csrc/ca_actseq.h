@@ -52,25 +52,37 @@ struct ActSeqAccArgs {
     int freeze;
 };
 
-// behind the launches of step t, one lane per agent, agent fastest.  Under CA_F_FREEZE the step advanced arena a unless it was frozen
-// at entry or an earlier step of the call left its flag set (first_done[a] in 0 .. t - 1).  The lane of agent 0 stores first_done[a] = t
-// in this very launch at most; a lane of the same arena that reads it sees -1 or t, and decides the same either way.
+// The accounting behind step t of a sequence call, for lane g = agent i of arena a whose reward of the step is r: the one statement of
+// the rule for actseq_accumulate_kernel, policy_record_kernel (ca_policy.h) and nav_reward_kernel (ca_nav.h), each of which hands over
+// the members of its argument block by value.  agent_counts / n_rows: the arena holds agent_counts[a] agents, n_rows where the pointer
+// is null (a caller that has the count already passes it as n_rows); rewards_rec / done_rec: row t of a policy rollout's records, or
+// null.  Under CA_F_FREEZE the step advanced arena a unless it was frozen at entry or an earlier step of the call left its flag set
+// (first_done[a] in 0 .. t - 1).  The lane of agent 0 stores first_done[a] = t in this very launch at most; a lane of the same arena
+// that reads it sees -1 or t, and decides the same either way.
+__device__ __forceinline__ void actseq_account(unsigned g, int a, int i, float r, const int* agent_counts, int n_rows, const int* arena_done,
+                                               const int* entry_frozen, const float* weight, float* returns, int* first_done,
+                                               float* rewards_rec, int* done_rec, int t, int freeze) {
+    // (every load is issued before anything is decided: the kernel is one memory latency long, not a chain of them)
+    const float ret = returns != nullptr ? returns[g] : 0.0f;
+    const int fd = first_done[a];
+    const int done = arena_done[a];
+    const int frozen0 = freeze ? entry_frozen[a] : 0;
+    const int count = agent_counts != nullptr ? agent_counts[a] : n_rows;
+    const float w = weight != nullptr ? *weight : 1.0f;
+    if (rewards_rec != nullptr) rewards_rec[g] = r;   // (the records of every row and arena, frozen or not)
+    if (done_rec != nullptr && i == 0) done_rec[a] = done;
+    const bool advanced = !(freeze && (frozen0 != 0 || (fd >= 0 && fd < t)));
+    if (!advanced) return;
+    if (returns != nullptr && i < count) { float* const dst = returns + g; *dst = actseq_add(ret, w, r); }   // (the address first: the kernels' instruction order of before)
+    if (i == 0 && fd < 0 && done != 0) first_done[a] = t;
+}
+
+// behind the launches of step t, one lane per agent, agent fastest
 __global__ __launch_bounds__(256) void actseq_accumulate_kernel(const ActSeqAccArgs s) {
     const unsigned g = blockIdx.x * 256u + threadIdx.x;
     if (g >= s.an) return;
     const int a = (int)(g / (unsigned)s.N), i = (int)(g - (unsigned)a * (unsigned)s.N);
-    // (every load is issued before anything is decided: the kernel is one memory latency long, not a chain of them)
-    const float r = s.reward[g];
-    const float ret = s.returns != nullptr ? s.returns[g] : 0.0f;
-    const int fd = s.first_done[a];
-    const int done = s.arena_done[a];
-    const int frozen0 = s.freeze ? s.entry_frozen[a] : 0;
-    const int count = s.agent_counts != nullptr ? s.agent_counts[a] : s.N;
-    const float w = s.weight != nullptr ? *s.weight : 1.0f;
-    const bool advanced = !(s.freeze && (frozen0 != 0 || (fd >= 0 && fd < s.t)));
-    if (!advanced) return;
-    if (s.returns != nullptr && i < count) s.returns[g] = actseq_add(ret, w, r);
-    if (i == 0 && fd < 0 && done != 0) s.first_done[a] = s.t;
+    actseq_account(g, a, i, s.reward[g], s.agent_counts, s.N, s.arena_done, s.entry_frozen, s.weight, s.returns, s.first_done, nullptr, nullptr, s.t, s.freeze);
 }
 
 // the block of the next ActionSeq launch of the four-lanes kernel, by value through the kernel arguments: ordered on the stream like

@@ -285,6 +285,12 @@ static void launch_k(const ProfScope& ps, void (*kernel)(Args...), dim3 grid, di
     else hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
 }
 
+// The sampling cadence of ca_profile(period > 1): the launches that follow are timed when the handle's step count, in units of `unit`
+// steps, is a multiple of the period.  unit = 1: a step; CA_ROLLOUT_MAX_T: a launch of the one-launch rollout.
+static void prof_cadence(ca_env* e, int unit) {
+    if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)unit) % (uint64_t)e->prof_period == 0;
+}
+
 static size_t AN(const ca_env* e) { return (size_t)e->cfg.n_arenas * e->cfg.n_agents; }
 
 struct FieldInfo {
@@ -710,6 +716,14 @@ static hipError_t launch_contacts(ca_env* e) {
 static int contacts_behind(ca_env* e, int rc) {
     if (rc) return rc;
     HIPCHK(e, launch_contacts(e));
+    return CA_OK;
+}
+// The tail of a call that strips CA_F_OBS and CA_F_CONTACT from its steps' flags: the observation and the contact report of the state
+// its last step left, one launch each.  (The entry points above these -- the steps, the resets, ca_rollout, ca_alan_rollout and the two
+// trace calls -- consume CA_F_CONTACT through contacts_behind instead, ahead of their own refusals: DESIGN.md 7q.)
+static int launch_tail(ca_env* e, uint32_t flags) {
+    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
+    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
     return CA_OK;
 }
 
@@ -2252,7 +2266,7 @@ int ca_reset_masked(ca_env* e, const int32_t* mask, int32_t mask_is_device, uint
 
 static int do_step(ca_env* e, const float* actions, uint32_t flags) {
     { const int rs = overflow_status(e, "step"); if (rs) return rs; }
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    prof_cadence(e, 1);
     StepArgs a;
     fill_args(e, a, actions, flags);
     HIPCHK(e, launch_step(e, a));
@@ -2261,6 +2275,28 @@ static int do_step(ca_env* e, const float* actions, uint32_t flags) {
     e->steps_done += 1;
     return CA_OK;
 }
+
+// The one-launch rollout's loop, for every call that has one (DESIGN.md 7q lists them and their conditions): `steps` steps in launches
+// of at most CA_ROLLOUT_MAX_T, the workgroup that owns an arena keeping it in registers / LDS for all the steps of a launch
+// (ca_quad.h).  Bounded, so that a long rollout stays a sequence of kernels of a few milliseconds (a kernel cannot be interrupted, and
+// a watchdog may reset a GPU over one that runs for seconds).  chunk(done) launches a.T steps behind the `done` the call has made;
+// lone(done) makes a last launch of one step, which is a step and not a rollout: the caller passes `chunk` again where the same launch
+// serves.  Both return a CA_ code.  The loop owns the sampling cadence, a.T, steps_done and orient_valid.
+extern "C++" {   // (templates)
+template <class Chunk, class Lone>
+static int rollout_chunks(ca_env* e, StepArgs& a, int steps, const Chunk& chunk, const Lone& lone) {
+    const uint64_t before = e->steps_done;
+    for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
+        prof_cadence(e, CA_ROLLOUT_MAX_T);
+        a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
+        const int rc = a.T == 1 ? lone(done) : chunk(done);
+        if (rc) return rc;
+        e->steps_done = before + (uint64_t)(done + a.T);   // (set, not added: a lone step that went through ca_alan_step has counted itself)
+        e->orient_valid = true;
+    }
+    return CA_OK;
+}
+}  // extern "C++"
 
 int ca_step(ca_env* e, const float* actions, uint32_t flags) {
     if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_step(e, actions, flags & ~CA_F_CONTACT));
@@ -2433,13 +2469,19 @@ int ca_alan_actions_arena(ca_env* e, int32_t arena, double* cs_xy, int32_t cap, 
     return CA_OK;
 }
 
+// the refusals of an ALAN step, for the calls that make them up front (ca_alan_rollout makes the first alone and leaves the others to
+// the steps it falls back to)
+static int alan_refusals(ca_env* e, const char* who, uint32_t flags) {
+    if (e->ac) return fail(e, CA_EINVAL, "%s: ALAN is not supported while per-arena agent counts are set", who);
+    if (e->n_actions <= 0) return fail(e, CA_EINVAL, "%s: call ca_alan_configure first", who);
+    if (flags & (CA_F_AUTORESET | CA_F_NODONE)) return fail(e, CA_EINVAL, "%s: CA_F_AUTORESET / CA_F_NODONE do not apply (ALAN:106-123)", who);
+    return CA_OK;
+}
+
 int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags) {
     if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_step(e, u, u_is_device, flags & ~CA_F_CONTACT));
     if (!e) return CA_EINVAL;
-    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_step: ALAN is not supported while per-arena agent counts are set");
-    if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_step: call ca_alan_configure first");
-    if (flags & (CA_F_AUTORESET | CA_F_NODONE))
-        return fail(e, CA_EINVAL, "ca_alan_step: CA_F_AUTORESET / CA_F_NODONE do not apply (ALAN:106-123)");
+    { const int rc = alan_refusals(e, "ca_alan_step", flags); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_alan_step"); if (rs) return rs; }
     if (u && !u_is_device) {  // stage the caller's host uniforms
@@ -2447,7 +2489,7 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
         HIPCHK(e, hipStreamSynchronize(e->stream));
         u = e->alan_u;
     }
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+    prof_cadence(e, 1);
     if ((e->alan_fused && e->quad) || e->alan_lane) {   // ONE launch: the bandit runs inside the solve kernel (ca_quad.h / ca_step.h)
         StepArgs a;
         fill_args(e, a, nullptr, flags);
@@ -2492,6 +2534,14 @@ int ca_alan_step(ca_env* e, const double* u, int32_t u_is_device, uint32_t flags
     return CA_OK;
 }
 
+// a lone last step of a fused ALAN rollout (a.T == 1) is a step, not a rollout: the handle's step kernel takes it -- ca_alan_step, unless
+// that kernel is the four-lanes one the rollout runs on anyway
+static int alan_lone_step(ca_env* e, const StepArgs& a, uint32_t flags) {
+    if (!e->quad) return ca_alan_step(e, nullptr, 0, flags);
+    HIPCHK(e, launch_step(e, a));
+    return CA_OK;
+}
+
 int ca_alan_rollout(ca_env* e, int32_t steps, uint32_t flags) {
     if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_rollout(e, steps, flags & ~CA_F_CONTACT));
     if (!e || steps < 0) return fail(e, CA_EINVAL, "ca_alan_rollout: bad argument");
@@ -2504,19 +2554,8 @@ int ca_alan_rollout(ca_env* e, int32_t steps, uint32_t flags) {
         StepArgs a;
         fill_args(e, a, nullptr, flags);
         a.alan = e->d_alan;
-        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
-            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
-            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
-            if (a.T == 1 && !e->quad) {   // (a lone last step is a step, not a rollout: the handle's step kernel takes it)
-                const int rc = ca_alan_step(e, nullptr, 0, flags);
-                if (rc) return rc;
-                continue;
-            }
-            HIPCHK(e, launch_step(e, a));   // (the four-lanes kernel: alan_fused)
-            e->steps_done += (uint64_t)a.T;
-        }
-        e->orient_valid = true;
-        return CA_OK;
+        return rollout_chunks(e, a, steps, [&](int) -> int { HIPCHK(e, launch_step(e, a)); return CA_OK; },   // (the four-lanes kernel: alan_fused)
+                              [&](int) -> int { return alan_lone_step(e, a, flags); });
     }
     for (int s = 0; s < steps; ++s) {
         const int rc = ca_alan_step(e, nullptr, 0, flags);
@@ -2571,20 +2610,11 @@ int ca_rollout(ca_env* e, int32_t steps, uint32_t flags) {
     if (!e || steps < 0) return fail(e, CA_EINVAL, "ca_rollout: bad argument");
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout"); if (rs) return rs; }
-    if (e->quad_roll && !(flags & CA_F_OBS) && steps > 1) {
-        // ONE launch per CA_ROLLOUT_MAX_T steps: the workgroup that owns an arena keeps it in registers / LDS for all of
-        // them (ca_quad.h).  Bounded, so that a long rollout stays a sequence of kernels of a few milliseconds (a kernel
-        // cannot be interrupted, and a watchdog may reset a GPU over one that runs for seconds).
+    if (e->quad_roll && !(flags & CA_F_OBS) && steps > 1) {   // ONE launch per CA_ROLLOUT_MAX_T steps (rollout_chunks)
         StepArgs a;
         fill_args(e, a, nullptr, flags);
-        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
-            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
-            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
-            HIPCHK(e, launch_step(e, a));
-            e->steps_done += (uint64_t)a.T;
-        }
-        e->orient_valid = true;
-        return CA_OK;
+        const auto chunk = [&](int) -> int { HIPCHK(e, launch_step(e, a)); return CA_OK; };
+        return rollout_chunks(e, a, steps, chunk, chunk);
     }
     for (int s = 0; s < steps; ++s) {
         const int rc = do_step(e, nullptr, flags);
@@ -2629,6 +2659,10 @@ static hipError_t launch_trace_record(ca_env* e, const ca_trace* tr, const Trace
     launch_k(ps, trace_record_kernel, dim3((t.an + 255) / 256), dim3(256), 0, e->stream, t);
     return hipGetLastError();
 }
+// behind the launches of step s of a call that makes a step at a time: the record kernel behind every `every`-th
+static hipError_t launch_trace_behind(ca_env* e, const ca_trace* tr, const TracePlan& pl, int s) {
+    return (s + 1) % tr->every == 0 ? launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1) : hipSuccess;
+}
 // the cursor of a Trace launch of the four-lanes kernel that follows `done` steps of the rollout
 static hipError_t launch_trace_setup(ca_env* e, const ca_trace* tr, const TracePlan& pl, int done) {
     TraceDev v;
@@ -2658,24 +2692,17 @@ int ca_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* t
     if (e->quad_roll && !(flags & CA_F_OBS) && steps > 1) {   // ca_rollout's one-launch form, its Trace instantiation
         StepArgs a;
         fill_args(e, a, nullptr, flags);
-        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
-            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
-            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
-            if (a.T == 1) {   // (a lone last step is the launch ca_rollout makes, and the record kernel behind it)
-                HIPCHK(e, launch_step(e, a));
-                if ((done + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (done + 1) / tr->every - 1));
-            } else {
-                HIPCHK(e, launch_step_traced(e, a, tr, pl, done));
-            }
-            e->steps_done += (uint64_t)a.T;
-        }
-        e->orient_valid = true;
-        return CA_OK;
+        return rollout_chunks(e, a, steps, [&](int done) -> int { HIPCHK(e, launch_step_traced(e, a, tr, pl, done)); return CA_OK; },
+                              [&](int done) -> int {   // (a lone last step is the launch ca_rollout makes, and the record kernel behind it)
+                                  HIPCHK(e, launch_step(e, a));
+                                  HIPCHK(e, launch_trace_behind(e, tr, pl, done));
+                                  return CA_OK;
+                              });
     }
     for (int s = 0; s < steps; ++s) {   // a sequence of launches per step: the record kernel behind those of every `every`-th
         const int rc = do_step(e, nullptr, flags);
         if (rc) return rc;
-        if ((s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
+        HIPCHK(e, launch_trace_behind(e, tr, pl, s));
     }
     return CA_OK;
 }
@@ -2684,10 +2711,7 @@ int ca_alan_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_tra
     if (e && (flags & CA_F_CONTACT)) return contacts_behind(e, ca_alan_rollout_trace(e, steps, flags & ~CA_F_CONTACT, tr));
     TracePlan pl;
     { const int rc = trace_check(e, "ca_alan_rollout_trace", steps, tr, &pl); if (rc) return rc; }
-    if (e->ac) return fail(e, CA_EINVAL, "ca_alan_rollout_trace: ALAN is not supported while per-arena agent counts are set");
-    if (e->n_actions <= 0) return fail(e, CA_EINVAL, "ca_alan_rollout_trace: call ca_alan_configure first");
-    if (flags & (CA_F_AUTORESET | CA_F_NODONE))
-        return fail(e, CA_EINVAL, "ca_alan_rollout_trace: CA_F_AUTORESET / CA_F_NODONE do not apply (ALAN:106-123)");
+    { const int rc = alan_refusals(e, "ca_alan_rollout_trace", flags); if (rc) return rc; }
     { const int rs = overflow_status(e, "ca_alan_rollout_trace"); if (rs) return rs; }
     // (an action set per arena records in the per-step form: no Trace twin of the AlanArenaSets instantiations)
     if (e->alan_fused && e->quad_roll && !e->alan_per && !(flags & CA_F_OBS) && steps > 1) {
@@ -2695,71 +2719,100 @@ int ca_alan_rollout_trace(ca_env* e, int32_t steps, uint32_t flags, const ca_tra
         StepArgs a;
         fill_args(e, a, nullptr, flags);
         a.alan = e->d_alan;
-        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
-            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
-            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
-            if (a.T == 1) {   // (a lone last step: what ca_alan_rollout does with it, and the record kernel behind it)
-                if (!e->quad) { const int rc = ca_alan_step(e, nullptr, 0, flags); if (rc) return rc; }
-                else { HIPCHK(e, launch_step(e, a)); e->steps_done += 1; }
-                if ((done + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (done + 1) / tr->every - 1));
-                continue;
-            }
-            HIPCHK(e, launch_step_traced(e, a, tr, pl, done));
-            e->steps_done += (uint64_t)a.T;
-        }
-        e->orient_valid = true;
-        return CA_OK;
+        return rollout_chunks(e, a, steps, [&](int done) -> int { HIPCHK(e, launch_step_traced(e, a, tr, pl, done)); return CA_OK; },
+                              [&](int done) -> int {   // (a lone last step: what ca_alan_rollout does with it, and the record kernel behind it)
+                                  const int rc = alan_lone_step(e, a, flags);
+                                  if (rc) return rc;
+                                  HIPCHK(e, launch_trace_behind(e, tr, pl, done));
+                                  return CA_OK;
+                              });
     }
     for (int s = 0; s < steps; ++s) {
         const int rc = ca_alan_step(e, nullptr, 0, flags);
         if (rc) return rc;
-        if ((s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
+        HIPCHK(e, launch_trace_behind(e, tr, pl, s));
     }
     return CA_OK;
 }
 
 // ---- action-sequence rollouts (include/ca_env.h ca_action_seq) --------------------------------------------------------------
 struct ActSeqPlan { int* first_done; int* entry_frozen; };
-// every refusal of the call, before anything is launched
-static int actseq_check(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
-    const char* who = "ca_rollout_actions";
-    if (!seq || !seq->actions) return fail(e, CA_EINVAL, "%s: the sequence or its actions buffer is null", who);
+// The refusals that the sequence calls share -- ca_rollout_actions, ca_rollout_policy and their navigated forms, `who` -- in the two
+// groups and the order that all of them make them in; Seq is ca_action_seq or ca_policy_seq, whose members of one name mean one thing.
+extern "C++" {   // (templates)
+template <class Seq>
+static int seq_check_call(ca_env* e, const char* who, int32_t steps, uint32_t flags, const Seq* seq) {
     if (steps < 0) return fail(e, CA_EINVAL, "%s: steps=%d", who, steps);
     if (seq->hold < 1) return fail(e, CA_EINVAL, "%s: hold=%d, must be at least 1", who, seq->hold);
     if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "%s: CA_F_NODONE applies to ca_orca_step only", who);
     if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE | CA_F_CONTACT))
         return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
-    const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold, A = (size_t)e->cfg.n_arenas;
+    return CA_OK;
+}
+template <class Seq>
+static int seq_check_results(ca_env* e, const char* who, int32_t steps, const Seq* seq) {
+    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e), T = (size_t)steps;
+    const int Ai = e->cfg.n_arenas, Ni = e->cfg.n_agents;
+    if (seq->weights && seq->weights_bytes < T * 4)
+        return fail(e, CA_ESIZE, "%s: the weights buffer needs %zu bytes (f32 [steps=%d]), got %zu", who, T * 4, steps, seq->weights_bytes);
+    if (seq->returns && seq->returns_bytes < an * 4)
+        return fail(e, CA_ESIZE, "%s: the returns buffer needs %zu bytes (f32 [A=%d, N=%d]), got %zu", who, an * 4, Ai, Ni, seq->returns_bytes);
+    if (seq->first_done && seq->first_done_bytes < A * 4)
+        return fail(e, CA_ESIZE, "%s: the first_done buffer needs %zu bytes (i32 [A=%d]), got %zu", who, A * 4, Ai, seq->first_done_bytes);
+    return CA_OK;
+}
+}  // extern "C++"
+// every refusal of an action-sequence call, before anything is launched
+static int actseq_check(ca_env* e, const char* who, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
+    if (!seq || !seq->actions) return fail(e, CA_EINVAL, "%s: the sequence or its actions buffer is null", who);
+    { const int rc = seq_check_call(e, who, steps, flags, seq); if (rc) return rc; }
+    const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold;
     if (seq->actions_bytes < R * AN(e) * 4)
         return fail(e, CA_ESIZE, "%s: the actions buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d], R = ceil(steps / hold)), got %zu", who,
                     R * AN(e) * 4, R, e->cfg.n_arenas, e->cfg.n_agents, seq->actions_bytes);
-    if (seq->weights && seq->weights_bytes < (size_t)steps * 4)
-        return fail(e, CA_ESIZE, "%s: the weights buffer needs %zu bytes (f32 [steps=%d]), got %zu", who, (size_t)steps * 4, steps, seq->weights_bytes);
-    if (seq->returns && seq->returns_bytes < AN(e) * 4)
-        return fail(e, CA_ESIZE, "%s: the returns buffer needs %zu bytes (f32 [A=%d, N=%d]), got %zu", who, AN(e) * 4, e->cfg.n_arenas,
-                    e->cfg.n_agents, seq->returns_bytes);
-    if (seq->first_done && seq->first_done_bytes < A * 4)
-        return fail(e, CA_ESIZE, "%s: the first_done buffer needs %zu bytes (i32 [A=%d]), got %zu", who, A * 4, e->cfg.n_arenas, seq->first_done_bytes);
-    return CA_OK;
+    return seq_check_results(e, who, steps, seq);
 }
-// in front of the first step: zeros, -1, the arenas frozen at entry (kind 3 for ca_profile, like the record kernel)
-static hipError_t launch_actseq_begin(ca_env* e, const ca_action_seq* seq, const ActSeqPlan& pl, uint32_t flags) {
+// In front of the first step of a sequence call: the handle's words on first use, the plan -- first_done is the caller's or the handle's
+// own, entry_frozen only where a launch behind each step reads it --, the sampling cadence and the set-up launch: returns = +0,
+// first_done = -1, the arenas frozen at entry (kind 3 for ca_profile, like the record kernel).
+static int actseq_prologue(ca_env* e, uint32_t flags, float* returns, int32_t* first_done, bool entry_frozen, ActSeqPlan* pl) {
+    const size_t A = (size_t)e->cfg.n_arenas;
+    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
+    pl->first_done = first_done ? (int*)first_done : e->actseq_words;
+    pl->entry_frozen = entry_frozen ? e->actseq_words + A : nullptr;
+    prof_cadence(e, 1);
     ActSeqBeginArgs b;
-    b.arena_done = e->arena_done; b.returns = seq->returns; b.first_done = pl.first_done; b.entry_frozen = pl.entry_frozen;
+    b.arena_done = e->arena_done; b.returns = returns; b.first_done = pl->first_done; b.entry_frozen = pl->entry_frozen;
     b.an = (unsigned)AN(e); b.A = e->cfg.n_arenas; b.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
     const unsigned n = b.an > (unsigned)b.A ? b.an : (unsigned)b.A;
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, actseq_begin_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, b);
-    return hipGetLastError();
+    HIPCHK(e, hipGetLastError());
+    return CA_OK;
 }
-// behind the launches of step t of the per-step form
-static hipError_t launch_actseq_accumulate(ca_env* e, const ca_action_seq* seq, const ActSeqPlan& pl, uint32_t flags, int t) {
-    ActSeqAccArgs c;
-    c.reward = e->reward; c.arena_done = e->arena_done; c.entry_frozen = pl.entry_frozen;
+// What a sequence call hands the launch behind its step t, whichever kernel that is (null members: not wanted): the one description
+// that actseq_accumulate_kernel, policy_record_kernel and nav_reward_kernel take their share of the arguments of actseq_account from.
+struct StepRec { const ActSeqPlan* pl; const float* weights; float* returns; float* rewards_out; int32_t* done_out; int t; uint32_t flags; };
+extern "C++" {   // (templates)
+template <class Args>   // (rec null: the launch behind a single step -- nav_reward_kernel knows it by a null first_done)
+static void fill_step_rec(const ca_env* e, const StepRec* rec, Args& c) {
+    c.arena_done = e->arena_done; c.entry_frozen = rec ? rec->pl->entry_frozen : nullptr;
     c.agent_counts = e->ac ? e->d_counts : nullptr;
-    c.weight = seq->weights ? seq->weights + t : nullptr;
-    c.returns = seq->returns; c.first_done = pl.first_done;
-    c.an = (unsigned)AN(e); c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents; c.t = t; c.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    c.weight = rec && rec->weights ? rec->weights + rec->t : nullptr;
+    c.returns = rec ? rec->returns : nullptr; c.first_done = rec ? rec->pl->first_done : nullptr;
+    c.an = (unsigned)AN(e); c.N = e->cfg.n_agents; c.t = rec ? rec->t : 0; c.freeze = rec && (rec->flags & CA_F_FREEZE) ? 1 : 0;
+}
+template <class Args>   // (the kernels with the records of a policy rollout)
+static void fill_step_records(const ca_env* e, const StepRec& rec, Args& c) {
+    c.rewards_rec = rec.rewards_out ? rec.rewards_out + (size_t)rec.t * AN(e) : nullptr;
+    c.done_rec = rec.done_out ? (int*)rec.done_out + (size_t)rec.t * e->cfg.n_arenas : nullptr;
+}
+}  // extern "C++"
+// behind the launches of step t of the per-step form
+static hipError_t launch_actseq_accumulate(ca_env* e, const StepRec& rec) {
+    ActSeqAccArgs c;
+    fill_step_rec(e, &rec, c);
+    c.reward = e->reward; c.A = e->cfg.n_arenas;
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, actseq_accumulate_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
     return hipGetLastError();
@@ -2785,40 +2838,29 @@ static hipError_t launch_step_actseq(ca_env* e, const StepArgs& a, const ca_acti
 
 int ca_rollout_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
     if (!e) return CA_EINVAL;
-    { const int rc = actseq_check(e, steps, flags, seq); if (rc) return rc; }
+    { const int rc = actseq_check(e, "ca_rollout_actions", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_actions"); if (rs) return rs; }
-    const size_t A = (size_t)e->cfg.n_arenas;
-    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
     const bool one_launch = e->quad_roll;   // (ca_solver_info: rollout_one_launch; an ALAN-configured handle steps without the bandit here)
     ActSeqPlan pl;
-    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
-    pl.entry_frozen = one_launch ? nullptr : e->actseq_words + A;
-    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, below)
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-    HIPCHK(e, launch_actseq_begin(e, seq, pl, flags));
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, !one_launch, &pl); if (rc) return rc; }
+    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, launch_tail)
     if (one_launch) {
         // one launch per CA_ROLLOUT_MAX_T steps, as ca_rollout: the arena stays in registers / LDS, each step reads its own action
         StepArgs a;
         fill_args(e, a, seq->actions, sf);
-        for (int done = 0; done < steps; done += CA_ROLLOUT_MAX_T) {
-            if (e->prof_period > 1) e->profiling = (e->steps_done / (uint64_t)CA_ROLLOUT_MAX_T) % (uint64_t)e->prof_period == 0;
-            a.T = steps - done < CA_ROLLOUT_MAX_T ? steps - done : CA_ROLLOUT_MAX_T;
-            HIPCHK(e, launch_step_actseq(e, a, seq, pl, done));
-            e->steps_done += (uint64_t)a.T;
-        }
+        const auto chunk = [&](int done) -> int { HIPCHK(e, launch_step_actseq(e, a, seq, pl, done)); return CA_OK; };
+        const int rc = rollout_chunks(e, a, steps, chunk, chunk);
+        if (rc) return rc;
     } else {
-        const size_t an = AN(e);
-        for (int t = 0; t < steps; ++t) {   // the launches of ca_step with this step's row, the accumulate kernel behind them
-            const int rc = do_step(e, seq->actions + (size_t)(t / seq->hold) * an, sf);
+        StepRec rec = {&pl, seq->weights, seq->returns, nullptr, nullptr, 0, flags};
+        for (rec.t = 0; rec.t < steps; ++rec.t) {   // the launches of ca_step with this step's row, the accumulate kernel behind them
+            const int rc = do_step(e, seq->actions + (size_t)(rec.t / seq->hold) * AN(e), sf);
             if (rc) return rc;
-            HIPCHK(e, launch_actseq_accumulate(e, seq, pl, flags, t));
+            HIPCHK(e, launch_actseq_accumulate(e, rec));
         }
     }
-    if (steps > 0) e->orient_valid = true;
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 // ---- the policy and its rollouts (include/ca_env.h ca_policy_desc, ca_policy_seq) ---------------------------------------------------
@@ -2973,27 +3015,17 @@ int ca_policy_actions(ca_env* e, const float* noise, float* actions_out) {
     return CA_OK;
 }
 
-// every refusal of ca_rollout_policy, before anything is launched
-static int policy_seq_check(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
-    const char* who = "ca_rollout_policy";
+// every refusal of a policy-rollout call, before anything is launched
+static int policy_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
     if (!seq) return fail(e, CA_EINVAL, "%s: the sequence is null", who);
     if (!e->pol.on) return fail(e, CA_EINVAL, "%s: call ca_policy_configure first", who);
-    if (steps < 0) return fail(e, CA_EINVAL, "%s: steps=%d", who, steps);
-    if (seq->hold < 1) return fail(e, CA_EINVAL, "%s: hold=%d, must be at least 1", who, seq->hold);
-    if (flags & CA_F_NODONE) return fail(e, CA_EINVAL, "%s: CA_F_NODONE applies to ca_orca_step only", who);
-    if (flags & ~(CA_F_OBS | CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE | CA_F_CONTACT))
-        return fail(e, CA_EINVAL, "%s: flags=0x%x holds a bit this call does not know", who, flags);
+    { const int rc = seq_check_call(e, who, steps, flags, seq); if (rc) return rc; }
     if (seq->obs_out && ((uintptr_t)seq->obs_out & 15) != 0) return fail(e, CA_EINVAL, "%s: the obs_out buffer must be 16-byte aligned", who);
     const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold, A = (size_t)e->cfg.n_arenas, an = AN(e), T = (size_t)steps;
     const int Ai = e->cfg.n_arenas, Ni = e->cfg.n_agents;
     if (seq->noise && seq->noise_bytes < R * an * 4)
         return fail(e, CA_ESIZE, "%s: the noise buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d], R = ceil(steps / hold)), got %zu", who, R * an * 4, R, Ai, Ni, seq->noise_bytes);
-    if (seq->weights && seq->weights_bytes < T * 4)
-        return fail(e, CA_ESIZE, "%s: the weights buffer needs %zu bytes (f32 [steps=%d]), got %zu", who, T * 4, steps, seq->weights_bytes);
-    if (seq->returns && seq->returns_bytes < an * 4)
-        return fail(e, CA_ESIZE, "%s: the returns buffer needs %zu bytes (f32 [A=%d, N=%d]), got %zu", who, an * 4, Ai, Ni, seq->returns_bytes);
-    if (seq->first_done && seq->first_done_bytes < A * 4)
-        return fail(e, CA_ESIZE, "%s: the first_done buffer needs %zu bytes (i32 [A=%d]), got %zu", who, A * 4, Ai, seq->first_done_bytes);
+    { const int rc = seq_check_results(e, who, steps, seq); if (rc) return rc; }
     if (seq->obs_out && seq->obs_out_bytes < R * an * CA_OBS_DIM * 4)
         return fail(e, CA_ESIZE, "%s: the obs_out buffer needs %zu bytes (f32 [R=%zu, A=%d, N=%d, %d]), got %zu", who, R * an * CA_OBS_DIM * 4, R, Ai, Ni, CA_OBS_DIM, seq->obs_out_bytes);
     if (seq->actions_out && seq->actions_out_bytes < R * an * 4)
@@ -3004,16 +3036,22 @@ static int policy_seq_check(ca_env* e, int32_t steps, uint32_t flags, const ca_p
         return fail(e, CA_ESIZE, "%s: the done_out buffer needs %zu bytes (i32 [steps=%d, A=%d]), got %zu", who, T * A * 4, steps, Ai, seq->done_out_bytes);
     return CA_OK;
 }
+// the row of actions that starts at step t (t a multiple of hold): what ca_observe launches, then the policy on what it left, into the
+// handle's action buffer and the row's records
+static hipError_t launch_policy_row(ca_env* e, const ca_policy_seq* seq, int t) {
+    const size_t r = (size_t)(t / seq->hold), an = AN(e);
+    prof_cadence(e, 1);
+    const hipError_t rc = launch_obs(e);
+    if (rc != hipSuccess) return rc;
+    return launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act, seq->actions_out ? seq->actions_out + r * an : nullptr,
+                         seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr);
+}
 // behind the launches of step t: the return, first_done and the step's records
-static hipError_t launch_policy_record(ca_env* e, const ca_policy_seq* seq, const ActSeqPlan& pl, uint32_t flags, int t) {
+static hipError_t launch_policy_record(ca_env* e, const StepRec& rec) {
     PolicyRecArgs c;
-    c.reward = e->reward; c.arena_done = e->arena_done; c.entry_frozen = pl.entry_frozen;
-    c.agent_counts = e->ac ? e->d_counts : nullptr;
-    c.weight = seq->weights ? seq->weights + t : nullptr;
-    c.returns = seq->returns; c.first_done = pl.first_done;
-    c.rewards_rec = seq->rewards_out ? seq->rewards_out + (size_t)t * AN(e) : nullptr;
-    c.done_rec = seq->done_out ? seq->done_out + (size_t)t * e->cfg.n_arenas : nullptr;
-    c.an = (unsigned)AN(e); c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents; c.t = t; c.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    fill_step_rec(e, &rec, c);
+    fill_step_records(e, rec, c);
+    c.reward = e->reward; c.A = e->cfg.n_arenas;
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, policy_record_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
     return hipGetLastError();
@@ -3021,41 +3059,20 @@ static hipError_t launch_policy_record(ca_env* e, const ca_policy_seq* seq, cons
 
 int ca_rollout_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
     if (!e) return CA_EINVAL;
-    { const int rc = policy_seq_check(e, steps, flags, seq); if (rc) return rc; }
+    { const int rc = policy_seq_check(e, "ca_rollout_policy", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_policy"); if (rs) return rs; }
-    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
-    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
     ActSeqPlan pl;
-    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
-    pl.entry_frozen = e->actseq_words + A;
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
     const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-    {   // zeros, -1, the arenas frozen at entry: the set-up launch of ca_rollout_actions
-        ActSeqBeginArgs b;
-        b.arena_done = e->arena_done; b.returns = seq->returns; b.first_done = pl.first_done; b.entry_frozen = pl.entry_frozen;
-        b.an = (unsigned)an; b.A = e->cfg.n_arenas; b.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
-        const unsigned n = b.an > (unsigned)b.A ? b.an : (unsigned)b.A;
-        ProfScope ps(e, KIND_RESET);
-        launch_k(ps, actseq_begin_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, b);
-        HIPCHK(e, hipGetLastError());
-    }
-    for (int t = 0; t < steps; ++t) {
-        if (t % seq->hold == 0) {   // a row starts: what ca_observe launches, then the policy on what it left
-            const size_t r = (size_t)(t / seq->hold);
-            if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-            HIPCHK(e, launch_obs(e));
-            HIPCHK(e, launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act,
-                                    seq->actions_out ? seq->actions_out + r * an : nullptr,
-                                    seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr));
-        }
+    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
+    for (rec.t = 0; rec.t < steps; ++rec.t) {
+        if (rec.t % seq->hold == 0) HIPCHK(e, launch_policy_row(e, seq, rec.t));
         const int rc = do_step(e, e->pol.act, sf);
         if (rc) return rc;
-        HIPCHK(e, launch_policy_record(e, seq, pl, flags, t));
+        HIPCHK(e, launch_policy_record(e, rec));
     }
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 // ---- navigation fields (include/ca_env.h ca_nav_desc; ca_nav.h, ca_nav_host.h) --------------------------------------
@@ -3275,17 +3292,15 @@ int ca_rollout_nav(ca_env* e, int32_t steps, uint32_t flags, const ca_trace* tr)
     if (tr) { const int rc = trace_check(e, who, steps, tr, &pl); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, who); if (rs) return rs; }
-    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, below)
+    const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, launch_tail)
     for (int s = 0; s < steps; ++s) {   // the launch of ca_nav_pref, the launches of ca_orca_step, the record kernel behind every `every`-th
-        if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+        prof_cadence(e, 1);
         HIPCHK(e, launch_nav_pref(e, nullptr, (flags & CA_F_FREEZE) != 0));
         const int rc = do_step(e, nullptr, sf);
         if (rc) return rc;
-        if (tr && (s + 1) % tr->every == 0) HIPCHK(e, launch_trace_record(e, tr, pl, (s + 1) / tr->every - 1));
+        if (tr) HIPCHK(e, launch_trace_behind(e, tr, pl, s));
     }
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 // ---- action steps steered by the navigation (include/ca_env.h ca_nav_act, ca_nav_step; ca_nav.h) -----------------------
@@ -3303,30 +3318,21 @@ static hipError_t launch_nav_act(ca_env* e, const float* actions, float* heading
     launch_k(ps, nav_act_kernel, dim3((q.n.an + 255) / 256), dim3(256), 0, e->stream, q);
     return hipGetLastError();
 }
-// what a rollout hands the launch behind its step t (null members: not wanted)
-struct NavStepRec { const ActSeqPlan* pl; const float* weights; float* returns; float* rewards_out; int32_t* done_out; int t; uint32_t flags; };
 // the launch behind the step (kind 3): the reward, the arena's sum under CA_F_STATS, a rollout's return, first_done and records
-static hipError_t launch_nav_reward(ca_env* e, uint32_t flags, const NavStepRec* rec) {
-    NavRewardArgs c;
+static hipError_t launch_nav_reward(ca_env* e, uint32_t flags, const StepRec* rec) {
+    NavRewardArgs c = {};
+    fill_step_rec(e, rec, c);
+    if (rec) fill_step_records(e, *rec, c);
     c.vel_x = e->vel_x; c.vel_y = e->vel_y; c.keep = e->nav_keep; c.advance = e->nav_advance;
-    c.agent_counts = e->ac ? e->d_counts : nullptr;
     c.reward = e->reward; c.arena_stats = (flags & CA_F_STATS) ? e->arena_stats : nullptr;
     c.reward_scale = e->cfg.reward_scale;
-    c.arena_done = e->arena_done;
-    c.entry_frozen = rec ? rec->pl->entry_frozen : nullptr;
-    c.weight = rec && rec->weights ? rec->weights + rec->t : nullptr;
-    c.returns = rec ? rec->returns : nullptr;
-    c.first_done = rec ? rec->pl->first_done : nullptr;
-    c.rewards_rec = rec && rec->rewards_out ? rec->rewards_out + (size_t)rec->t * AN(e) : nullptr;
-    c.done_rec = rec && rec->done_out ? (int*)rec->done_out + (size_t)rec->t * e->cfg.n_arenas : nullptr;
-    c.an = (unsigned)AN(e); c.N = e->cfg.n_agents; c.t = rec ? rec->t : 0; c.freeze = rec && (rec->flags & CA_F_FREEZE) ? 1 : 0;
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, nav_reward_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
     return hipGetLastError();
 }
 // one navigated action step: nav_act_kernel, the launches of the ORCA-only step, nav_reward_kernel
-static int nav_do_step(ca_env* e, const float* actions, uint32_t sf, const NavStepRec* rec) {
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
+static int nav_do_step(ca_env* e, const float* actions, uint32_t sf, const StepRec* rec) {
+    prof_cadence(e, 1);
     HIPCHK(e, launch_nav_act(e, actions, nullptr, nullptr, (sf & CA_F_FREEZE) != 0));
     const int rc = do_step(e, nullptr, sf);
     if (rc) return rc;
@@ -3357,74 +3363,44 @@ int ca_nav_step(ca_env* e, const float* actions, uint32_t flags) {
     { const int rs = overflow_status(e, who); if (rs) return rs; }
     HIPCHK(e, nav_step_buffers(e));
     { const int rc = nav_do_step(e, actions, flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE), nullptr); if (rc) return rc; }
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 int ca_rollout_nav_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action_seq* seq) {
     if (!e) return CA_EINVAL;
     if (!e->nav.on) return fail(e, CA_EINVAL, "ca_rollout_nav_actions: call ca_nav_configure first");
-    { const int rc = actseq_check(e, steps, flags, seq); if (rc) return rc; }
+    { const int rc = actseq_check(e, "ca_rollout_nav_actions", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_nav_actions"); if (rs) return rs; }
-    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
-    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
     HIPCHK(e, nav_step_buffers(e));
     ActSeqPlan pl;
-    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
-    pl.entry_frozen = e->actseq_words + A;
-    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);   // (observation and contacts: one launch behind the last step, below)
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-    HIPCHK(e, launch_actseq_begin(e, seq, pl, flags));
-    NavStepRec rec = {&pl, seq->weights, seq->returns, nullptr, nullptr, 0, flags};
-    for (int t = 0; t < steps; ++t) {   // always the per-step form, as ca_rollout_nav
-        rec.t = t;
-        const int rc = nav_do_step(e, seq->actions + (size_t)(t / seq->hold) * an, sf, &rec);
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);   // (observation and contacts: one launch behind the last step, launch_tail)
+    StepRec rec = {&pl, seq->weights, seq->returns, nullptr, nullptr, 0, flags};
+    for (rec.t = 0; rec.t < steps; ++rec.t) {   // always the per-step form, as ca_rollout_nav
+        const int rc = nav_do_step(e, seq->actions + (size_t)(rec.t / seq->hold) * AN(e), sf, &rec);
         if (rc) return rc;
     }
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 int ca_rollout_nav_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
     if (!e) return CA_EINVAL;
     if (!e->nav.on) return fail(e, CA_EINVAL, "ca_rollout_nav_policy: call ca_nav_configure first");
-    { const int rc = policy_seq_check(e, steps, flags, seq); if (rc) return rc; }
+    { const int rc = policy_seq_check(e, "ca_rollout_nav_policy", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_nav_policy"); if (rs) return rs; }
-    const size_t A = (size_t)e->cfg.n_arenas, an = AN(e);
-    if (!e->actseq_words) HIPCHK(e, dalloc(e, &e->actseq_words, 2 * A));
     HIPCHK(e, nav_step_buffers(e));
     ActSeqPlan pl;
-    pl.first_done = seq->first_done ? (int*)seq->first_done : e->actseq_words;
-    pl.entry_frozen = e->actseq_words + A;
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
     const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
-    if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-    {   // zeros, -1, the arenas frozen at entry: the set-up launch of ca_rollout_actions
-        ca_action_seq b;
-        memset(&b, 0, sizeof b);
-        b.returns = seq->returns;
-        HIPCHK(e, launch_actseq_begin(e, &b, pl, flags));
-    }
-    NavStepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
-    for (int t = 0; t < steps; ++t) {
-        if (t % seq->hold == 0) {   // a row starts: what ca_observe launches, then the policy on what it left
-            const size_t r = (size_t)(t / seq->hold);
-            if (e->prof_period > 1) e->profiling = (e->steps_done % (uint64_t)e->prof_period) == 0;
-            HIPCHK(e, launch_obs(e));
-            HIPCHK(e, launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act,
-                                    seq->actions_out ? seq->actions_out + r * an : nullptr,
-                                    seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr));
-        }
-        rec.t = t;
+    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
+    for (rec.t = 0; rec.t < steps; ++rec.t) {
+        if (rec.t % seq->hold == 0) HIPCHK(e, launch_policy_row(e, seq, rec.t));
         const int rc = nav_do_step(e, e->pol.act, sf, &rec);
         if (rc) return rc;
     }
-    if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
-    if (flags & CA_F_CONTACT) HIPCHK(e, launch_contacts(e));
-    return CA_OK;
+    return launch_tail(e, flags);
 }
 
 int ca_sync(ca_env* e) {

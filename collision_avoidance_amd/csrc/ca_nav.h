@@ -287,18 +287,8 @@ __global__ __launch_bounds__(256) void nav_reward_kernel(const NavRewardArgs s) 
             atomicAdd(reinterpret_cast<double*>(&s.arena_stats[(size_t)a * ST_STRIDE + ST_SUMREW]), sum);
     }
     if (!row || s.first_done == nullptr) return;
-    // actseq_accumulate_kernel / policy_record_kernel, word for word (r: what CA_FLD_REWARD holds behind this step)
-    const float ret = s.returns != nullptr ? s.returns[g] : 0.0f;
-    const int fd = s.first_done[a];
-    const int done = s.arena_done[a];
-    const int frozen0 = s.freeze ? s.entry_frozen[a] : 0;
-    const float w = s.weight != nullptr ? *s.weight : 1.0f;
-    if (s.rewards_rec != nullptr) s.rewards_rec[g] = r;
-    if (s.done_rec != nullptr && i == 0) s.done_rec[a] = done;
-    const bool advanced = !(s.freeze && (frozen0 != 0 || (fd >= 0 && fd < s.t)));
-    if (!advanced) return;
-    if (s.returns != nullptr && i < count) s.returns[g] = actseq_add(ret, w, r);
-    if (i == 0 && fd < 0 && done != 0) s.first_done[a] = s.t;
+    // (r: what CA_FLD_REWARD holds behind this step; the count is in a register already)
+    actseq_account(g, a, i, r, nullptr, count, s.arena_done, s.entry_frozen, s.weight, s.returns, s.first_done, s.rewards_rec, s.done_rec, s.t, s.freeze);
 }
 
 }  // namespace ca

@@ -16,8 +16,8 @@
 //     columns 1 .. 15 are zero, and column 0 -- lanes 0, 16, 32, 48 -- holds the rows' means;
 //   * an LDS row is width + 4 floats long: the A reads of a k-step and the D writes of a tile then touch 64 different banks.
 // A row's result depends on its own observation and its arena's weight set only: not on the tiling, not on the rows beside it.
-// policy_record_kernel is the accumulate kernel of a policy rollout: actseq_accumulate_kernel's rule (ca_actseq.h) plus the reward and
-// done records.
+// policy_record_kernel is the accumulate kernel of a policy rollout: the rule of actseq_account (ca_actseq.h) with the reward and done
+// records.
 #pragma once
 #include "ca_common.h"
 #include "ca_actseq.h"
@@ -151,25 +151,13 @@ struct PolicyRecArgs {
     int freeze;
 };
 
-// behind the launches of step t: the records of every row and arena first, then actseq_accumulate_kernel's rule word for word (the
-// return through actseq_add, first_done stored by the lane of agent 0; see there for why every lane of an arena decides alike)
+// behind the launches of step t: the step's records and the rule of the return and first_done (actseq_account, ca_actseq.h)
 __global__ __launch_bounds__(256) void policy_record_kernel(const PolicyRecArgs s) {
     const unsigned g = blockIdx.x * 256u + threadIdx.x;
     if (g >= s.an) return;
     const int a = (int)(g / (unsigned)s.N), i = (int)(g - (unsigned)a * (unsigned)s.N);
-    const float r = s.reward[g];
-    const float ret = s.returns != nullptr ? s.returns[g] : 0.0f;
-    const int fd = s.first_done[a];
-    const int done = s.arena_done[a];
-    const int frozen0 = s.freeze ? s.entry_frozen[a] : 0;
-    const int count = s.agent_counts != nullptr ? s.agent_counts[a] : s.N;
-    const float w = s.weight != nullptr ? *s.weight : 1.0f;
-    if (s.rewards_rec != nullptr) s.rewards_rec[g] = r;
-    if (s.done_rec != nullptr && i == 0) s.done_rec[a] = done;
-    const bool advanced = !(s.freeze && (frozen0 != 0 || (fd >= 0 && fd < s.t)));
-    if (!advanced) return;
-    if (s.returns != nullptr && i < count) s.returns[g] = actseq_add(ret, w, r);
-    if (i == 0 && fd < 0 && done != 0) s.first_done[a] = s.t;
+    actseq_account(g, a, i, s.reward[g], s.agent_counts, s.N, s.arena_done, s.entry_frozen, s.weight, s.returns, s.first_done, s.rewards_rec, s.done_rec, s.t,
+                   s.freeze);
 }
 
 }  // namespace ca

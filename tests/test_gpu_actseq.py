@@ -107,18 +107,28 @@ def _case(g, twin, orc, what, steps, hold, weights=None, seed=3, one_launch=None
 
 
 # ---- the four-lanes kernel: the T-step launch with actions ----------------------------------------------------------------------------
-def test_quad_two_launches_boundary_inside_a_hold(monkeypatch):
-    """259 steps are two launches (256 + 3); hold = 3: step 255 is the first of row 85's three, so the boundary falls inside a hold,
-    and row 86 is held for one step; weights 0.99^t"""
+def _two_launches(monkeypatch, steps, hold, n_rows):
     monkeypatch.setenv("CA_QUAD", "1")
-    A, N, steps, hold = 37, 16, 259, 3
+    A, N = 37, 16
     p = H.scenario_params("crowd", N, neighbor_dist=1.5, max_neighbors=5)
     g, twin = (H.make_gpu(A, N, "crowd", p, seed=11) for _ in range(2))
     orc = H.make_oracle(A, N, "crowd", p, seed=11)
     w = (f32(0.99) ** np.arange(steps)).astype(f32)
     out, ret, fd, _ = _case(g, twin, orc, "37x16", steps, hold, weights=w, one_launch=True, stats=True)
-    assert np.abs(ret).max() > 1.0 and S.rows(steps, hold)[0] == 87
+    assert np.abs(ret).max() > 1.0 and S.rows(steps, hold)[0] == n_rows
     g.close(); twin.close()
+
+
+def test_quad_two_launches_boundary_inside_a_hold(monkeypatch):
+    """259 steps are two launches (256 + 3); hold = 3: step 255 is the first of row 85's three, so the boundary falls inside a hold,
+    and row 86 is held for one step; weights 0.99^t"""
+    _two_launches(monkeypatch, 259, 3, 87)
+
+
+def test_quad_two_launches_remainder_of_one(monkeypatch):
+    """257 steps are two launches (256 + 1), the second of a single step: its block starts at row 128 with a full countdown (hold = 2),
+    and the row is held for that one step; the same comparison"""
+    _two_launches(monkeypatch, 257, 2, 129)
 
 
 @pytest.mark.parametrize("scenario,A,N", [("circle", 5, 12), ("crowd", 70, 1)], ids=["circle5x12", "crowd70x1"])
@@ -340,6 +350,9 @@ def test_refusals_advance_nothing(monkeypatch, quad):
         rc = g.L.ca_rollout_actions(g.h, n_steps, flags, C.byref(seq) if seq is not None else None)
         assert rc == code, (n_steps, flags, kw, rc)
         assert word in g.L.ca_last_error(g.h).decode(), (kw, g.L.ca_last_error(g.h))
+        # the refusal names the call that was made, and none of the calls that share its checks
+        msg = g.L.ca_last_error(g.h).decode()
+        assert "ca_rollout_actions:" in msg and not any(n in msg for n in ("ca_rollout_nav_actions:", "ca_rollout_policy:", "ca_rollout_nav_policy:")), msg
     g.sync()
     for n in fields:
         H._eq(g.get(getattr(_lib, "FLD_" + n)), before[n], "after the refusals: %s" % n)

@@ -341,13 +341,16 @@ def test_every_refusal_leaves_the_handle_working():
         full_p[n], full_p[n + "_bytes"] = b.ctypes.data, b.nbytes
     roll_a = lambda n, fl, kw: g.L.ca_rollout_nav_actions(g.h, n, fl, C.byref(_lib.ActionSeq(**kw)) if kw is not None else None)   # noqa: E731
     roll_p = lambda n, fl, kw: g.L.ca_rollout_nav_policy(g.h, n, fl, C.byref(_lib.PolicySeq(**kw)) if kw is not None else None)    # noqa: E731
-    for roll, full in ((roll_a, full_a), (roll_p, full_p)):
+    names = ("ca_rollout_nav_actions", "ca_rollout_nav_policy", "ca_rollout_actions", "ca_rollout_policy")
+    for roll, full, own in ((roll_a, full_a, names[0]), (roll_p, full_p, names[1])):
         cases = [(steps, 0, None, EINVAL), (steps, 0, dict(full, hold=0), EINVAL), (-1, 0, full, EINVAL), (steps, _lib.F_NODONE, full, EINVAL),
                  (steps, 64, full, EINVAL)]
         cases += [(steps, 0, dict(full, **{n: v - 1}), ESIZE) for n, v in full.items() if n.endswith("_bytes")]      # every undersized buffer
         cases += [(steps + 2, 0, full, ESIZE)]
         for n_steps, flags, kw, code in cases:
             assert roll(n_steps, flags, kw) == code, (roll is roll_a, n_steps, flags, kw and {k: v for k, v in kw.items() if k.endswith("_bytes")}, err())
+            # the refusal names the call that was made, and no other call that shares its checks
+            assert (own + ":") in err() and not any((n + ":") in err() for n in names if n != own), (own, n_steps, flags, err())
     assert roll_a(steps, 0, dict(full_a, actions=None)) == EINVAL
     unchanged(before, "a refused call")
     assert not bufs["returns"].any() and not bufs["rewards_out"].any() and not bufs["first_done"].any()

@@ -366,6 +366,8 @@ def test_refusals_advance_nothing_and_zero_steps():
     for n_steps, flags, kw, code, word in cases:
         rc = roll(n_steps, flags, kw)
         assert rc == code and word in err(), (n_steps, flags, word, rc, err())
+        # the refusal names the call that was made, and none of the calls that share its checks
+        assert "ca_rollout_policy:" in err() and not any(n in err() for n in ("ca_rollout_nav_policy:", "ca_rollout_actions:", "ca_rollout_nav_actions:")), err()
     g.sync()
     for n in fields:
         H._eq(g.get(getattr(_lib, "FLD_" + n)), before[n], "after the refusals: %s" % n)

@@ -234,6 +234,46 @@ def test_fused_alan_rollout_records(monkeypatch):
         e.close()
 
 
+def test_lone_last_step_behind_a_full_launch(monkeypatch):
+    """257 = 256 + 1 steps: the second launch is a single step, which is a step and not a rollout -- the handle's step launch, with the
+    record kernel behind it.  every = 1: record 256 is that step's; every = 257: it is the only record.  The ORCA-only rollout and the
+    fused ALAN rollout (the handle's own draws) on a handle whose single step is the four-lanes kernel, with and without a trace,
+    against a twin's 257 single steps.  (A handle with a one-launch rollout whose single step is another kernel exists at exactly 1024
+    lane-waves only -- thousands of arenas: that branch of the lone step is not reached here.)"""
+    monkeypatch.setenv("CA_QUAD", "1")
+    A, N, steps = 3, 12, 257
+    p = H.scenario_params("circle", N)
+    moved = PLANES + WORDS + ("PREF_X", "PREF_Y", "AGENT_DONE")
+    for bandit in (False, True):
+        what = "ALAN" if bandit else "ORCA"
+
+        def make():
+            g = H.make_gpu(A, N, "circle", p, seed=5)
+            if bandit:
+                g.alan_configure(alan.DEFAULT_ACTIONS)
+            return g
+
+        def roll(g, **kw):
+            return g.alan_rollout(steps, freeze=True, **kw) if bandit else g.rollout(steps, **kw)
+        twin = make()
+        li = twin.launch_info()
+        assert li["rollout_one_launch"] == 1 and li["lanes_per_agent"] == 4, li
+        want = _records((lambda: twin.alan_step(freeze=True)) if bandit else twin.orca_step, twin, _lib, steps, 1)
+        for every in (1, steps):
+            traced = make()
+            tr = roll(traced, trace=dict(every=every))
+            assert tr["agents"].shape[0] == steps // every
+            _assert_records(tr, want[every - 1::every], "%s, every=%d" % (what, every))
+            _assert_same_handles(traced, twin, "%s, every=%d: the final state" % (what, every), fields=moved)
+            traced.close()
+        plain = make()
+        roll(plain)
+        _assert_same_handles(plain, twin, "%s without a trace: the final state" % what, fields=moved)
+        if bandit:
+            _alan_equal(plain, twin, _lib, _lib, "ALAN without a trace")
+        plain.close(); twin.close()
+
+
 def test_alan_rollout_records_with_an_action_set_per_arena(monkeypatch):
     """Two arenas whose action sets differ in size (the per-step form: select / solve / update or the fused single step, then the
     record kernel); each arena against an oracle of its own."""
