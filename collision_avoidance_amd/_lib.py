@@ -41,10 +41,12 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_arena_gather", "ca_snapshot_create", "ca_snapshot_save", "ca_snapshot_load", "ca_snapshot_destroy",
            "ca_fork_bytes_per_arena", "ca_rollout_actions",
            "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy",
+           "ca_policy_set_heads", "ca_policy_clear_heads", "ca_policy_heads_info", "ca_policy_evaluate", "ca_rollout_policy_sample", "ca_gae",
            "ca_nav_configure", "ca_nav_clear", "ca_nav_info", "ca_nav_get_field", "ca_nav_pref", "ca_rollout_nav", "ca_nav_mask_build",
            "ca_nav_act", "ca_nav_step", "ca_rollout_nav_actions", "ca_rollout_nav_policy")
 POLICY_OUT_IDENTITY, POLICY_OUT_CLIP = 0, 1   # out_mode of a policy (struct ca_policy_desc)
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 128
+POLICY_LOGSTD_MIN, POLICY_LOGSTD_MAX = -20.0, 2.0   # the clamp of a log-std head (ca_policy_set_heads)
 NAV_MAX_CELLS, NAV_MAX_GOALS, NAV_MAX_LOOKAHEAD = 32768, 16, 8   # limits of a navigation (struct ca_nav_desc)
 NAV_STAY, NAV_NONE = 8, 9   # `next` of the source cell / of a cell nothing leads out of
 NAV_OFFSETS = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))   # (dx, dy) of pointer k = 0 .. 7
@@ -100,6 +102,31 @@ class PolicySeq(C.Structure):
                 ("returns", C.c_void_p), ("returns_bytes", C.c_size_t), ("first_done", C.c_void_p), ("first_done_bytes", C.c_size_t),
                 ("obs_out", C.c_void_p), ("obs_out_bytes", C.c_size_t), ("actions_out", C.c_void_p), ("actions_out_bytes", C.c_size_t),
                 ("rewards_out", C.c_void_p), ("rewards_out_bytes", C.c_size_t), ("done_out", C.c_void_p), ("done_out_bytes", C.c_size_t)]
+
+
+class PolicyHeads(C.Structure):
+    """struct ca_policy_heads (include/ca_env.h): the value and log-std rows as ca_policy_set_heads takes them."""
+    _fields_ = [("value_w", C.c_void_p), ("value_w_bytes", C.c_size_t), ("value_b", C.c_void_p), ("value_b_bytes", C.c_size_t),
+                ("logstd_w", C.c_void_p), ("logstd_w_bytes", C.c_size_t), ("logstd_b", C.c_void_p), ("logstd_b_bytes", C.c_size_t)]
+
+
+class PolicyEval(C.Structure):
+    """struct ca_policy_eval (include/ca_env.h): the optional outputs of ca_policy_evaluate."""
+    _fields_ = [("actions", C.c_void_p), ("logp", C.c_void_p), ("value", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
+
+
+class PolicySampleSeq(C.Structure):
+    """struct ca_policy_sample_seq (include/ca_env.h): the members of ca_policy_seq and the records of a PPO batch."""
+    _fields_ = list(PolicySeq._fields_) + \
+        [(n + s, t) for n in ("logp_out", "dist_out", "values_out", "row_rewards_out", "row_done_out", "row_valid_out", "advantages_out",
+                              "targets_out") for s, t in (("", C.c_void_p), ("_bytes", C.c_size_t))] + \
+        [("gamma", C.c_float), ("lambda", C.c_float)]
+
+
+class GaeDesc(C.Structure):
+    """struct ca_gae_desc (include/ca_env.h): the caller's buffers of ca_gae."""
+    _fields_ = [(n + s, t) for n in ("rewards", "values", "done", "valid", "advantages", "targets")
+                for s, t in (("", C.c_void_p), ("_bytes", C.c_size_t))] + [("gamma", C.c_float), ("lambda", C.c_float)]
 
 
 class NavDesc(C.Structure):
@@ -180,6 +207,12 @@ def load():
     L.ca_policy_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32 * 5), C.POINTER(i32)]
     L.ca_policy_actions.argtypes = [vp, vp, vp]
     L.ca_rollout_policy.argtypes = [vp, i32, u32, C.POINTER(PolicySeq)]
+    L.ca_policy_set_heads.argtypes = [vp, C.POINTER(PolicyHeads)]
+    L.ca_policy_clear_heads.argtypes = [vp]
+    L.ca_policy_heads_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.ca_policy_evaluate.argtypes = [vp, vp, C.POINTER(PolicyEval)]
+    L.ca_rollout_policy_sample.argtypes = [vp, i32, u32, C.POINTER(PolicySampleSeq)]
+    L.ca_gae.argtypes = [vp, i32, C.POINTER(GaeDesc)]
     L.ca_nav_configure.argtypes = [vp, C.POINTER(NavDesc)]
     L.ca_nav_clear.argtypes = [vp]
     L.ca_nav_info.argtypes = [vp] + [C.POINTER(i32)] * 6

@@ -111,6 +111,16 @@ struct ca_env {
         float *d_wp = nullptr, *d_bp = nullptr, *act = nullptr;
         int* d_set = nullptr;
     } pol;
+    // the heads of the policy (ca_policy_set_heads; ca_policy.h): d_wp / d_bp are copies of the policy's whose output tile also holds the
+    // log-std row (column 1) and the value row (column 2); rr / words: the row records of a sampling rollout that wants its GAE
+    // but gave no buffers for them ([cap_rows][A*N] floats, [2][cap_rows][A] words)
+    struct Heads {
+        bool on = false, has_value = false, has_logstd = false;
+        float *d_wp = nullptr, *d_bp = nullptr;
+        float* rr = nullptr;
+        int* words = nullptr;
+        size_t rr_rows = 0, words_rows = 0;
+    } heads;
     // the navigation fields (ca_nav_configure; ca_nav.h, ca_nav_host.h): configuration, like the policy.  d_dist / d_next hold the
     // fields of `sets` x G targets over gx x gy cells, d_class the agents' targets, h_blocked the sets' masks (a byte per cell)
     struct Nav {
@@ -1211,7 +1221,7 @@ int ca_destroy(ca_env* e) {
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
-                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->nav.d_dist, e->nav.d_next, e->nav.d_class, e->nav_keep, e->nav_advance,
+                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->heads.d_wp, e->heads.d_bp, e->heads.rr, e->heads.words, e->nav.d_dist, e->nav.d_next, e->nav.d_class, e->nav_keep, e->nav_advance,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -2864,6 +2874,13 @@ int ca_rollout_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action
 }
 
 // ---- the policy and its rollouts (include/ca_env.h ca_policy_desc, ca_policy_seq) ---------------------------------------------------
+// the heads go with the policy they were packed for (the stream is drained where this is called); the row-record buffers stay
+static void drop_heads(ca_env* e) {
+    if (e->heads.d_wp) hipFree(e->heads.d_wp);
+    if (e->heads.d_bp) hipFree(e->heads.d_bp);
+    e->heads.d_wp = e->heads.d_bp = nullptr;
+    e->heads.on = e->heads.has_value = e->heads.has_logstd = false;
+}
 int ca_policy_configure(ca_env* e, const ca_policy_desc* d) {
     const char* who = "ca_policy_configure";
     if (!e || !d) return fail(e, CA_EINVAL, "%s: null argument", who);
@@ -2960,6 +2977,7 @@ int ca_policy_configure(ca_env* e, const ca_policy_desc* d) {
     if (e->pol.d_set) hipFree(e->pol.d_set);
     n.on = true;
     e->pol = n;
+    drop_heads(e);
     return CA_OK;
 }
 
@@ -2973,6 +2991,7 @@ int ca_policy_clear(ca_env* e) {
     float* act = e->pol.act;   // (kept for the next policy)
     e->pol = ca_env::Policy();
     e->pol.act = act;
+    drop_heads(e);
     return CA_OK;
 }
 
@@ -3016,7 +3035,9 @@ int ca_policy_actions(ca_env* e, const float* noise, float* actions_out) {
 }
 
 // every refusal of a policy-rollout call, before anything is launched
-static int policy_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
+extern "C++" {   // (a template: Seq is ca_policy_seq or ca_policy_sample_seq, whose members of one name mean one thing)
+template <class Seq>
+static int policy_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t flags, const Seq* seq) {
     if (!seq) return fail(e, CA_EINVAL, "%s: the sequence is null", who);
     if (!e->pol.on) return fail(e, CA_EINVAL, "%s: call ca_policy_configure first", who);
     { const int rc = seq_check_call(e, who, steps, flags, seq); if (rc) return rc; }
@@ -3036,6 +3057,7 @@ static int policy_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t 
         return fail(e, CA_ESIZE, "%s: the done_out buffer needs %zu bytes (i32 [steps=%d, A=%d]), got %zu", who, T * A * 4, steps, Ai, seq->done_out_bytes);
     return CA_OK;
 }
+}  // extern "C++"
 // the row of actions that starts at step t (t a multiple of hold): what ca_observe launches, then the policy on what it left, into the
 // handle's action buffer and the row's records
 static hipError_t launch_policy_row(ca_env* e, const ca_policy_seq* seq, int t) {
@@ -3073,6 +3095,241 @@ int ca_rollout_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_
         HIPCHK(e, launch_policy_record(e, rec));
     }
     return launch_tail(e, flags);
+}
+
+// ---- PPO sample collection (include/ca_env.h ca_policy_heads, ca_policy_sample_seq, ca_gae_desc) -------------------
+int ca_policy_set_heads(ca_env* e, const ca_policy_heads* d) {
+    const char* who = "ca_policy_set_heads";
+    if (!e || !d) return fail(e, CA_EINVAL, "%s: null argument", who);
+    if (!e->pol.on) return fail(e, CA_EINVAL, "%s: call ca_policy_configure first", who);
+    const ca_env::Policy& q = e->pol;
+    const int P = q.P, K = q.width[q.L - 1];
+    if (!d->value_b && !d->logstd_b) return fail(e, CA_EINVAL, "%s: neither head is given (value_b and logstd_b are null)", who);
+    if (d->value_b && !d->value_w) return fail(e, CA_EINVAL, "%s: value_b without value_w", who);
+    if (d->value_w && !d->value_b) return fail(e, CA_EINVAL, "%s: value_w without value_b", who);
+    if (d->logstd_w && !d->logstd_b) return fail(e, CA_EINVAL, "%s: logstd_w without logstd_b", who);
+    const size_t wb = (size_t)P * K * 4, bb = (size_t)P * 4;
+    struct { const char* name; const float* w; size_t w_bytes; const float* b; size_t b_bytes; int col; } hd[2] = {
+        {"value", d->value_w, d->value_w_bytes, d->value_b, d->value_b_bytes, 2}, {"logstd", d->logstd_w, d->logstd_w_bytes, d->logstd_b, d->logstd_b_bytes, 1}};
+    for (const auto& h : hd) {
+        if (!h.b) continue;
+        if (h.w && h.w_bytes < wb) return fail(e, CA_ESIZE, "%s: %s_w needs %zu bytes (f32 [P=%d, %d]), got %zu", who, h.name, wb, P, K, h.w_bytes);
+        if (h.b_bytes < bb) return fail(e, CA_ESIZE, "%s: %s_b needs %zu bytes (f32 [P=%d]), got %zu", who, h.name, bb, P, h.b_bytes);
+        for (size_t k = 0; h.w && k < (size_t)P * K; ++k)
+            if (!std::isfinite(h.w[k])) return fail(e, CA_ERANGE, "%s: %s head, set %zu: weight [%zu] is not finite", who, h.name, k / K, k % K);
+        for (int p = 0; p < P; ++p)
+            if (!std::isfinite(h.b[p])) return fail(e, CA_ERANGE, "%s: %s head, set %d: the bias is not finite", who, h.name, p);
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    // the policy's own packed sets, and into the output tile of each: lane l of k-step s holds W[column l & 15][4 s + (l >> 4)]
+    std::vector<float> wp((size_t)P * q.wset), bp((size_t)P * q.bset);
+    HIPCHK(e, download(e, wp.data(), q.d_wp, wp.size() * 4));
+    HIPCHK(e, download(e, bp.data(), q.d_bp, bp.size() * 4));
+    for (const auto& h : hd) {
+        if (!h.b) continue;
+        for (int p = 0; p < P; ++p) {
+            float* dst = wp.data() + (size_t)p * q.wset + q.wp_off[q.L - 1];
+            for (int k = 0; k < K; ++k) dst[(size_t)(k >> 2) * 64 + (size_t)(k & 3) * 16 + h.col] = h.w ? h.w[(size_t)p * K + k] : 0.0f;
+            bp[(size_t)p * q.bset + q.bp_off[q.L - 1] + h.col] = h.b[p];
+        }
+    }
+    float *nw = nullptr, *nb = nullptr;
+    hipError_t r = hipMalloc((void**)&nw, wp.size() * 4);
+    if (r == hipSuccess) r = hipMalloc((void**)&nb, bp.size() * 4);
+    if (r == hipSuccess) r = upload(e, nw, wp.data(), wp.size() * 4);
+    if (r == hipSuccess) r = upload(e, nb, bp.data(), bp.size() * 4);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    if (r != hipSuccess) {
+        if (nw) hipFree(nw);
+        if (nb) hipFree(nb);
+        return fail(e, CA_EHIP, "%s: installing the heads failed: %s", who, hipGetErrorString(r));
+    }
+    drop_heads(e);
+    e->heads.d_wp = nw; e->heads.d_bp = nb;
+    e->heads.has_value = d->value_b != nullptr; e->heads.has_logstd = d->logstd_b != nullptr;
+    e->heads.on = true;
+    return CA_OK;
+}
+
+int ca_policy_clear_heads(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    drop_heads(e);
+    return CA_OK;
+}
+
+int ca_policy_heads_info(ca_env* e, int32_t* has_value, int32_t* has_logstd) {
+    if (!e) return CA_EINVAL;
+    if (has_value) *has_value = e->heads.on && e->heads.has_value ? 1 : 0;
+    if (has_logstd) *has_logstd = e->heads.on && e->heads.has_logstd ? 1 : 0;
+    return CA_OK;
+}
+
+// the heads launch (kind 3 for ca_profile): launch_policy's geometry on the sets with the heads' output tile
+static hipError_t launch_heads(ca_env* e, const float* noise, float* actions, float* actions_rec, float* obs_rec, const ca_policy_eval& o, bool values_only) {
+    const ca_env::Policy& q = e->pol;
+    ActorCriticArgs c;
+    PolicyArgs& p = c.p;
+    p.obs = e->obs; p.wp = e->heads.d_wp; p.bp = e->heads.d_bp; p.set_of_arena = q.P > 1 ? q.d_set : nullptr;
+    p.noise = noise; p.actions = actions; p.actions_rec = actions_rec; p.obs_rec = obs_rec;
+    for (int l = 0; l < POLICY_MAX_LAYERS; ++l) { p.wp_off[l] = q.wp_off[l]; p.bp_off[l] = q.bp_off[l]; }
+    for (int l = 0; l <= POLICY_MAX_LAYERS; ++l) p.width[l] = q.width[l];
+    p.wset = q.wset; p.bset = q.bset;
+    p.an = (unsigned)AN(e); p.N = e->cfg.n_agents;
+    p.tpa = q.P > 1 ? (p.N + POLICY_ROWS - 1) / POLICY_ROWS : 0;
+    p.n_layers = q.L; p.stride = q.maxw + POLICY_PAD;
+    p.clip = q.out_mode == CA_POLICY_OUT_CLIP ? 1 : 0; p.limit = q.limit;
+    c.logp = o.logp; c.value = o.value; c.mean = o.mean; c.log_std = o.log_std;
+    c.has_logstd = e->heads.has_logstd ? 1 : 0; c.values_only = values_only ? 1 : 0;
+    const unsigned grid = p.tpa ? (unsigned)e->cfg.n_arenas * (unsigned)p.tpa : (p.an + POLICY_ROWS - 1) / POLICY_ROWS;
+    const size_t lds = (size_t)2 * POLICY_ROWS * p.stride * 4;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, actor_critic_kernel, dim3(grid), dim3(64), lds, e->stream, c);
+    return hipGetLastError();
+}
+
+int ca_policy_evaluate(ca_env* e, const float* noise, const ca_policy_eval* out) {
+    if (!e) return CA_EINVAL;
+    if (!e->pol.on) return fail(e, CA_EINVAL, "ca_policy_evaluate: call ca_policy_configure first");
+    if (!e->heads.on) return fail(e, CA_EINVAL, "ca_policy_evaluate: call ca_policy_set_heads first");
+    if (!out) return fail(e, CA_EINVAL, "ca_policy_evaluate: out is null");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_heads(e, noise, out->actions, nullptr, nullptr, *out, false));
+    return CA_OK;
+}
+
+static hipError_t launch_gae(ca_env* e, int R, const float* rewards, const float* values, const int* done, const int* valid, float gamma, float lambda,
+                             float* adv, float* target) {
+    GaeArgs g;
+    g.rewards = rewards; g.values = values; g.done = done; g.valid = valid; g.adv = adv; g.target = target;
+    g.an = (unsigned)AN(e); g.A = e->cfg.n_arenas; g.N = e->cfg.n_agents; g.R = R;
+    g.gamma = gamma; g.gl = gamma * lambda;   // (one fp32 multiply: the library is built without contraction)
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, gae_kernel, dim3((g.an + 255) / 256), dim3(256), 0, e->stream, g);
+    return hipGetLastError();
+}
+
+int ca_gae(ca_env* e, int32_t rows, const ca_gae_desc* d) {
+    const char* who = "ca_gae";
+    if (!e) return CA_EINVAL;
+    if (!d) return fail(e, CA_EINVAL, "%s: the description is null", who);
+    if (rows < 0) return fail(e, CA_EINVAL, "%s: rows=%d", who, rows);
+    if (!d->rewards || !d->values || !d->done) return fail(e, CA_EINVAL, "%s: rewards, values or done is null", who);
+    const size_t R = (size_t)rows, A = (size_t)e->cfg.n_arenas, an = AN(e);
+    const int Ai = e->cfg.n_arenas, Ni = e->cfg.n_agents;
+    if (d->rewards_bytes < R * an * 4)
+        return fail(e, CA_ESIZE, "%s: the rewards buffer needs %zu bytes (f32 [R=%d, A=%d, N=%d]), got %zu", who, R * an * 4, rows, Ai, Ni, d->rewards_bytes);
+    if (d->values_bytes < (R + 1) * an * 4)
+        return fail(e, CA_ESIZE, "%s: the values buffer needs %zu bytes (f32 [R+1=%d, A=%d, N=%d]), got %zu", who, (R + 1) * an * 4, rows + 1, Ai, Ni, d->values_bytes);
+    if (d->done_bytes < R * A * 4)
+        return fail(e, CA_ESIZE, "%s: the done buffer needs %zu bytes (i32 [R=%d, A=%d]), got %zu", who, R * A * 4, rows, Ai, d->done_bytes);
+    if (d->valid && d->valid_bytes < R * A * 4)
+        return fail(e, CA_ESIZE, "%s: the valid buffer needs %zu bytes (i32 [R=%d, A=%d]), got %zu", who, R * A * 4, rows, Ai, d->valid_bytes);
+    if (d->advantages && d->advantages_bytes < R * an * 4)
+        return fail(e, CA_ESIZE, "%s: the advantages buffer needs %zu bytes (f32 [R=%d, A=%d, N=%d]), got %zu", who, R * an * 4, rows, Ai, Ni, d->advantages_bytes);
+    if (d->targets && d->targets_bytes < R * an * 4)
+        return fail(e, CA_ESIZE, "%s: the targets buffer needs %zu bytes (f32 [R=%d, A=%d, N=%d]), got %zu", who, R * an * 4, rows, Ai, Ni, d->targets_bytes);
+    if (rows == 0) return CA_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_gae(e, rows, d->rewards, d->values, (const int*)d->done, (const int*)d->valid, d->gamma, d->lambda, d->advantages, d->targets));
+    return CA_OK;
+}
+
+// every refusal of a sampling rollout, before anything is launched: those of a policy rollout, then the new records'
+static int sample_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t flags, const ca_policy_sample_seq* seq) {
+    { const int rc = policy_seq_check(e, who, steps, flags, seq); if (rc) return rc; }
+    if (!e->heads.on) return fail(e, CA_EINVAL, "%s: call ca_policy_set_heads first", who);
+    if ((seq->advantages_out || seq->targets_out) && !seq->values_out)
+        return fail(e, CA_EINVAL, "%s: advantages_out and targets_out need values_out", who);
+    const size_t R = ((size_t)steps + (size_t)seq->hold - 1) / (size_t)seq->hold, A = (size_t)e->cfg.n_arenas, an = AN(e);
+    const int Ai = e->cfg.n_arenas, Ni = e->cfg.n_agents;
+    const struct { const char* name; const void* p; size_t bytes, need; const char* layout; } bufs[] = {
+        {"logp_out", seq->logp_out, seq->logp_out_bytes, R * an * 4, "f32 [R, A, N]"},
+        {"dist_out", seq->dist_out, seq->dist_out_bytes, R * 2 * an * 4, "f32 [R, 2, A, N]"},
+        {"values_out", seq->values_out, seq->values_out_bytes, (R + 1) * an * 4, "f32 [R+1, A, N]"},
+        {"row_rewards_out", seq->row_rewards_out, seq->row_rewards_out_bytes, R * an * 4, "f32 [R, A, N]"},
+        {"row_done_out", seq->row_done_out, seq->row_done_out_bytes, R * A * 4, "i32 [R, A]"},
+        {"row_valid_out", seq->row_valid_out, seq->row_valid_out_bytes, R * A * 4, "i32 [R, A]"},
+        {"advantages_out", seq->advantages_out, seq->advantages_out_bytes, R * an * 4, "f32 [R, A, N]"},
+        {"targets_out", seq->targets_out, seq->targets_out_bytes, R * an * 4, "f32 [R, A, N]"}};
+    for (const auto& b : bufs)
+        if (b.p && b.bytes < b.need)
+            return fail(e, CA_ESIZE, "%s: the %s buffer needs %zu bytes (%s with R=%zu, A=%d, N=%d), got %zu", who, b.name, b.need, b.layout, R, Ai, Ni, b.bytes);
+    return CA_OK;
+}
+
+int ca_rollout_policy_sample(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_sample_seq* seq) {
+    const char* who = "ca_rollout_policy_sample";
+    if (!e) return CA_EINVAL;
+    { const int rc = sample_seq_check(e, who, steps, flags, seq); if (rc) return rc; }
+    HIPCHK(e, hipSetDevice(e->device));
+    { const int rs = overflow_status(e, who); if (rs) return rs; }
+    const size_t an = AN(e), A = (size_t)e->cfg.n_arenas;
+    const int hold = seq->hold, R = (int)(((size_t)steps + (size_t)hold - 1) / (size_t)hold);
+    const bool gae = (seq->advantages_out || seq->targets_out) && R > 0;
+    // the row records the GAE launch reads: the caller's, or the handle's own (they only grow)
+    float* rr = seq->row_rewards_out;
+    int *rd = (int*)seq->row_done_out, *rv = (int*)seq->row_valid_out;
+    if (gae && !rr) {
+        if (e->heads.rr_rows < (size_t)R) {
+            if (e->heads.rr) { HIPCHK(e, hipFree(e->heads.rr)); e->heads.rr = nullptr; e->heads.rr_rows = 0; }
+            HIPCHK(e, hipMalloc((void**)&e->heads.rr, (size_t)R * an * 4));
+            e->heads.rr_rows = (size_t)R;
+        }
+        rr = e->heads.rr;
+    }
+    if (gae && (!rd || !rv)) {
+        if (e->heads.words_rows < (size_t)R) {
+            if (e->heads.words) { HIPCHK(e, hipFree(e->heads.words)); e->heads.words = nullptr; e->heads.words_rows = 0; }
+            HIPCHK(e, hipMalloc((void**)&e->heads.words, 2 * (size_t)R * A * 4));
+            e->heads.words_rows = (size_t)R;
+        }
+        if (!rd) rd = e->heads.words;
+        if (!rv) rv = e->heads.words + e->heads.words_rows * A;
+    }
+    ActSeqPlan pl;
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
+    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
+    for (rec.t = 0; rec.t < steps; ++rec.t) {
+        const size_t r = (size_t)(rec.t / hold);
+        const bool first = rec.t % hold == 0;
+        if (first) {   // the row: what ca_observe launches, then the heads on what it left, into the handle's action buffer and the row's records
+            prof_cadence(e, 1);
+            HIPCHK(e, launch_obs(e));
+            ca_policy_eval o;
+            o.actions = nullptr;
+            o.logp = seq->logp_out ? seq->logp_out + r * an : nullptr;
+            o.value = seq->values_out ? seq->values_out + r * an : nullptr;
+            o.mean = seq->dist_out ? seq->dist_out + r * 2 * an : nullptr;
+            o.log_std = seq->dist_out ? seq->dist_out + r * 2 * an + an : nullptr;
+            HIPCHK(e, launch_heads(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act, seq->actions_out ? seq->actions_out + r * an : nullptr,
+                                   seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr, o, false));
+        }
+        const int rc = do_step(e, e->pol.act, sf);
+        if (rc) return rc;
+        SampleRecArgs c;
+        fill_step_rec(e, &rec, c.s);
+        fill_step_records(e, rec, c.s);
+        c.s.reward = e->reward; c.s.A = e->cfg.n_arenas;
+        c.row_rewards = rr ? rr + r * an : nullptr; c.row_done = rd ? rd + r * A : nullptr; c.row_valid = rv ? rv + r * A : nullptr;
+        c.first = first ? 1 : 0;
+        {
+            ProfScope ps(e, KIND_RESET);
+            launch_k(ps, sample_record_kernel, dim3((c.s.an + 255) / 256), dim3(256), 0, e->stream, c);
+        }
+        HIPCHK(e, hipGetLastError());
+    }
+    if (seq->values_out) {   // the bootstrap row: the value of the state the call leaves
+        HIPCHK(e, launch_obs(e));
+        ca_policy_eval o = {nullptr, nullptr, seq->values_out + (size_t)R * an, nullptr, nullptr};
+        HIPCHK(e, launch_heads(e, nullptr, nullptr, nullptr, nullptr, o, true));
+    }
+    if (gae) HIPCHK(e, launch_gae(e, R, rr, seq->values_out, rd, rv, seq->gamma, seq->lambda, seq->advantages_out, seq->targets_out));
+    const uint32_t tail = seq->values_out ? flags & ~(uint32_t)CA_F_OBS : flags;   // (the bootstrap's observation is CA_F_OBS's)
+    return launch_tail(e, tail);
 }
 
 // ---- navigation fields (include/ca_env.h ca_nav_desc; ca_nav.h, ca_nav_host.h) --------------------------------------

@@ -178,6 +178,66 @@ def policy_layers(layers):
     return [int(w) for w in widths], int(P), Ws, bs
 
 
+def policy_heads(width, P, value=None, log_std=None):
+    """The heads of set_policy_heads() as the library takes them, without a device: dict(value_w=, value_b=, logstd_w=, logstd_b=) of
+    C-contiguous float32 host arrays -- weights [P, width], biases [P] -- or None for what is absent (logstd_w None with logstd_b
+    given: a state-independent log-std).  width: the policy's last hidden width, P: its number of weight sets.  value = (w, b) or a
+    torch.nn.Linear(width, 1); log_std = (w_or_None, b) or a Linear; w [width], [1, width] or [P, width], b a scalar, [1] or [P].
+    Raises ValueError for what ca_policy_set_heads would refuse: no head at all, a shape that does not fit, a value that is not
+    finite."""
+    width, P = int(width), int(P)
+    host = lambda t: t.detach().cpu().numpy() if torch is not None and isinstance(t, torch.Tensor) else t
+
+    def one(name, head):
+        if head is None:
+            return None, None
+        if torch is not None and isinstance(head, torch.nn.Linear):
+            if head.bias is None or head.out_features != 1:
+                raise ValueError("set_policy_heads: the %s head must be a Linear(%d, 1) with a bias" % (name, width))
+            head = (head.weight, head.bias)
+        if not isinstance(head, (tuple, list)) or len(head) != 2:
+            raise ValueError("set_policy_heads: the %s head must be (w, b) or a torch.nn.Linear" % name)
+        w, b = head
+        if b is None:
+            raise ValueError("set_policy_heads: the %s head has no bias" % name)
+        if w is None and name == "value":
+            raise ValueError("set_policy_heads: the value head has no weights")
+        b = np.asarray(host(b), np.float32).reshape(-1)
+        if b.size == 1 and P > 1:
+            b = np.repeat(b, P)
+        if b.shape != (P,):
+            raise ValueError("set_policy_heads: the %s bias must hold one value per weight set (P=%d), got shape %s" % (name, P, b.shape))
+        if w is not None:
+            w = np.asarray(host(w), np.float32)
+            if w.ndim == 1:
+                w = w[None]
+            if w.ndim != 2 or w.shape[1] != width or w.shape[0] not in (1, P):
+                raise ValueError("set_policy_heads: the %s weights must be [%d] or [P=%d, %d] (the last hidden width), got shape %s" %
+                                 (name, width, P, width, w.shape))
+            w = np.ascontiguousarray(np.broadcast_to(w, (P, width)))
+            if not np.isfinite(w).all():
+                raise ValueError("set_policy_heads: the %s head holds a weight that is not finite" % name)
+        if not np.isfinite(b).all():
+            raise ValueError("set_policy_heads: the %s head holds a bias that is not finite" % name)
+        return w, np.ascontiguousarray(b)
+
+    vw, vb = one("value", value)
+    lw, lb = one("log_std", log_std)
+    if vb is None and lb is None:
+        raise ValueError("set_policy_heads: at least one head must be given")
+    return dict(value_w=vw, value_b=vb, logstd_w=lw, logstd_b=lb)
+
+
+def policy_sample_shape(A, N, steps, hold=1, noise_shape=None, weights_shape=None):
+    """The buffers of rollout_policy_sample() without a device: policy_seq_shape's dict plus logp (R, A, N), dist (R, 2, A, N), values
+    (R + 1, A, N), row_rewards (R, A, N), row_dones (R, A), row_valid (R, A), advantages and targets (R, A, N)."""
+    sh = policy_seq_shape(A, N, steps, hold, noise_shape, weights_shape)
+    R, A, N = sh["R"], int(A), int(N)
+    sh.update(logp=(R, A, N), dist=(R, 2, A, N), values=(R + 1, A, N), row_rewards=(R, A, N), row_dones=(R, A), row_valid=(R, A),
+              advantages=(R, A, N), targets=(R, A, N))
+    return sh
+
+
 class Snapshot:
     """A second set of the state buffers on the environment's device (ca_snapshot_*): made and filled by
     VecCollisionAvoidanceEnv.snapshot(), read by restore().  close() destroys it; the environment's close() invalidates every
@@ -1213,6 +1273,160 @@ class VecCollisionAvoidanceEnv:
         out = {n: bufs.get(n) for n in ("returns", "first_done", "obs", "actions", "rewards", "dones")}
         out["obs_last"] = self._obs_out() if with_obs else None
         return out
+
+    # ---- PPO sample collection (ca_policy_set_heads, ca_policy_evaluate, ca_rollout_policy_sample, ca_gae) ---------
+    def set_policy_heads(self, value=None, log_std=None):
+        """Install a value head and / or a log-std head on the installed policy (ca_policy_set_heads): two extra rows of the output
+        layer, read from the last hidden layer.  value=(w, b), log_std=(w_or_None, b) -- numpy or torch, per weight set or shared
+        -- or torch.nn.Linear modules (policy_heads above).  log-std is clamped to [-20, 2]; w None: a state-independent log-std.
+        Configuration like the policy; set_policy() and clear_policy() drop the heads."""
+        info = self.policy_info()
+        if not info["configured"]:
+            raise RuntimeError("set_policy_heads: call set_policy first")
+        h = policy_heads(info["widths"][-2], info["n_sets"], value, log_std)
+        d = _lib.PolicyHeads()
+        for n, a in h.items():
+            if a is not None:
+                setattr(d, n, a.ctypes.data)
+                setattr(d, n + "_bytes", a.nbytes)
+        self._call("ca_policy_set_heads", self.h, C.byref(d))
+
+    def clear_policy_heads(self):
+        self._call("ca_policy_clear_heads", self.h)
+
+    def policy_heads_info(self):
+        """dict(value=, log_std=): which heads are installed (ca_policy_heads_info)."""
+        v, s = C.c_int32(0), C.c_int32(0)
+        self._call("ca_policy_heads_info", self.h, C.byref(v), C.byref(s))
+        return dict(value=bool(v.value), log_std=bool(s.value))
+
+    def policy_evaluate(self, noise=None):
+        """The policy with its heads on the observation buffer as it stands (ca_policy_evaluate: one launch): dict(actions=, logp=,
+        value=, mean=, log_std=), each [A, N] float32.  noise [A, N] is eps: action = out(mean + exp(log_std) * eps), logp the
+        log-density of the unclipped sample (include/ca_env.h has the definition, bit for bit)."""
+        on_torch = self.use_torch
+        ptr = (lambda t: t.data_ptr()) if on_torch else (lambda a: a.ctypes.data)
+        names = ("actions", "logp", "value", "mean", "log_std")
+        bufs = self._policy_bufs([("eval_" + n, (self.A, self.N), np.float32) for n in names], on_torch)
+        nz = None
+        if noise is not None:
+            if on_torch:
+                nz = torch.as_tensor(noise).detach().to(device=bufs["eval_logp"].device, dtype=torch.float32).contiguous()
+            else:
+                if torch is not None and isinstance(noise, torch.Tensor):
+                    noise = noise.detach().cpu().numpy()
+                nz = self._actseq_host("policy_noise1", (self.A, self.N), np.float32)
+                nz[...] = np.asarray(noise, np.float32).reshape(self.A, self.N)
+            if tuple(nz.shape) != (self.A, self.N):
+                raise ValueError("policy_evaluate: noise must be [A=%d, N=%d], got %s" % (self.A, self.N, tuple(nz.shape)))
+        o = _lib.PolicyEval(**{n: ptr(bufs["eval_" + n]) for n in names})
+        self._call("ca_policy_evaluate", self.h, ptr(nz) if nz is not None else None, C.byref(o))
+        if on_torch:
+            return {n: bufs["eval_" + n] for n in names}
+        self.sync()
+        return {n: np.array(bufs["eval_" + n]) for n in names}
+
+    _SAMPLE_RECORDS = ("obs", "actions", "rewards", "dones", "logp", "dist", "values", "row_rewards", "row_dones", "row_valid",
+                       "advantages", "targets")
+
+    def rollout_policy_sample(self, steps, hold=1, noise=None, gamma=0.95, lam=1.0, weights=None,
+                              record=("obs", "actions", "logp", "dist", "values", "row_rewards", "row_dones", "row_valid", "advantages", "targets"),
+                              returns=True, first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False):
+        """rollout_policy() under the policy with its heads, handing back a PPO batch (ca_rollout_policy_sample).  noise [R, A, N]
+        is eps (R = ceil(steps / hold)).  record: rollout_policy's four records and "logp" [R, A, N], "dist" [R, 2, A, N] (mean,
+        clamped log-std), "values" [R + 1, A, N] (row R: the bootstrap value of the state the call leaves), "row_rewards"
+        [R, A, N] (the rewards of a row's steps added up), "row_dones" / "row_valid" [R, A] int32, "advantages" / "targets"
+        [R, A, N] (GAE under gamma and lam; they need "values").  Returns a dict as rollout_policy()'s; conventions as there.
+        Shapes: policy_sample_shape."""
+        on_torch = self.use_torch
+        record = (record,) if isinstance(record, str) else tuple(record or ())
+        for r in record:
+            if r not in self._SAMPLE_RECORDS:
+                raise ValueError("rollout_policy_sample: record holds %r; it may hold %s" % (r, ", ".join(repr(n) for n in self._SAMPLE_RECORDS)))
+        if ("advantages" in record or "targets" in record) and "values" not in record:
+            raise ValueError("rollout_policy_sample: 'advantages' and 'targets' need 'values' among the records")
+        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
+        sh = policy_sample_shape(self.A, self.N, steps, hold, None if noise is None else tuple(noise.shape if is_t(noise) else np.shape(noise)),
+                                 None if weights is None else tuple(weights.shape if is_t(weights) else np.shape(weights)))
+        steps, hold, R = int(steps), int(hold), sh["R"]
+        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
+                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        ints = ("first_done", "dones", "row_dones", "row_valid")
+        wanted = [n for n, want in (("returns", returns), ("first_done", first_done)) if want] + [n for n in self._SAMPLE_RECORDS if n in record]
+        bufs = self._policy_bufs([("sample_" + n, sh[n], np.int32 if n in ints else np.float32) for n in wanted], on_torch)
+        bufs = {n[len("sample_"):]: a for n, a in bufs.items()}
+        if on_torch:
+            dev = torch.device("cuda", self.device)
+            nz = None if noise is None else torch.as_tensor(noise).detach().to(device=dev, dtype=torch.float32).contiguous()
+            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        else:
+            nz = w = None
+            if noise is not None:
+                nz = self._actseq_host("policy_noise", (max(R, 1), self.A, self.N), np.float32)
+                nz[:R] = np.asarray(noise.detach().cpu().numpy() if is_t(noise) else noise, np.float32)
+            if weights is not None:
+                w = self._actseq_host("policy_weights", (max(steps, 1),), np.float32)
+                w[:steps] = np.asarray(weights.detach().cpu().numpy() if is_t(weights) else weights, np.float32)
+            ptr = lambda a: a.ctypes.data if a is not None else None
+        size = lambda n: int(np.prod(sh[n])) * 4
+        kw = dict(hold=hold, noise=ptr(nz) if R else None, noise_bytes=size("noise") if nz is not None else 0,
+                  weights=ptr(w) if steps else None, weights_bytes=size("weights") if w is not None else 0,
+                  gamma=float(gamma))
+        kw["lambda"] = float(lam)
+        member = dict(returns="returns", first_done="first_done", obs="obs_out", actions="actions_out", rewards="rewards_out", dones="done_out",
+                      logp="logp_out", dist="dist_out", values="values_out", row_rewards="row_rewards_out", row_dones="row_done_out",
+                      row_valid="row_valid_out", advantages="advantages_out", targets="targets_out")
+        for n, a in bufs.items():
+            empty = n != "values" and n not in ("returns", "first_done") and (steps == 0)
+            kw[member[n]] = None if empty else ptr(a)
+            kw[member[n] + "_bytes"] = size(n)
+        seq = _lib.PolicySampleSeq(**kw)
+        self._call("ca_rollout_policy_sample", self.h, steps, flags, C.byref(seq))
+        if not on_torch:
+            self.sync()
+            bufs = {n: np.array(a[:sh[n][0]]) if n not in ("returns", "first_done") else np.array(a) for n, a in bufs.items()}
+        out = {n: bufs.get(n) for n in ("returns", "first_done") + self._SAMPLE_RECORDS}
+        out["obs_last"] = self._obs_out() if with_obs else None
+        return out
+
+    def gae(self, rewards, values, done, valid=None, gamma=0.95, lam=1.0):
+        """Generalised advantage estimation on the device (ca_gae): rewards [R, A, N], values [R + 1, A, N], done [R, A], valid
+        [R, A] or None (all 1).  Returns (advantages, targets), each [R, A, N] float32; include/ca_env.h has the definition, bit for
+        bit.  Device tensors in and out under use_torch, else numpy (the call synchronises)."""
+        on_torch = self.use_torch
+        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
+        R = int(rewards.shape[0]) if is_t(rewards) else int(np.shape(rewards)[0])
+        want = dict(rewards=(R, self.A, self.N), values=(R + 1, self.A, self.N), done=(R, self.A), valid=(R, self.A))
+        given = dict(rewards=rewards, values=values, done=done, valid=valid)
+        for n, x in given.items():
+            if x is not None and tuple(x.shape if is_t(x) else np.shape(x)) != want[n]:
+                raise ValueError("gae: %s must be %s, got shape %s" % (n, list(want[n]), tuple(x.shape if is_t(x) else np.shape(x))))
+        out = self._policy_bufs([("gae_advantages", want["rewards"], np.float32), ("gae_targets", want["rewards"], np.float32)], on_torch)
+        ins = {}
+        for n, x in given.items():
+            if x is None:
+                continue
+            dt = np.float32 if n in ("rewards", "values") else np.int32
+            if on_torch:
+                ins[n] = torch.as_tensor(x).detach().to(device=torch.device("cuda", self.device),
+                                                       dtype=torch.float32 if dt is np.float32 else torch.int32).contiguous()
+            else:
+                ins[n] = self._actseq_host("gae_" + n, want[n][:0] + (max(want[n][0], 1),) + want[n][1:], dt)
+                ins[n][:want[n][0]] = np.asarray(x.detach().cpu().numpy() if is_t(x) else x, dt)
+        ptr = (lambda t: t.data_ptr() if t.numel() else None) if on_torch else (lambda a: a.ctypes.data)
+        kw = dict(gamma=float(gamma))
+        kw["lambda"] = float(lam)
+        for n in ins:
+            kw[n], kw[n + "_bytes"] = ptr(ins[n]), int(np.prod(want[n])) * 4
+        for n in ("advantages", "targets"):
+            kw[n], kw[n + "_bytes"] = ptr(out["gae_" + n]), int(np.prod(want["rewards"])) * 4
+        if R:
+            self._call("ca_gae", self.h, R, C.byref(_lib.GaeDesc(**kw)))
+        if on_torch:
+            return out["gae_advantages"], out["gae_targets"]
+        self.sync()
+        return np.array(out["gae_advantages"][:R]), np.array(out["gae_targets"][:R])
 
     # ---- navigation fields (ca_nav_*) ------------------------------------------------------------------
     def set_navigation(self, targets, agent_class, cell, origin=None, shape=None, clearance=None, lookahead=2):

@@ -722,6 +722,139 @@ typedef struct ca_policy_seq {
 } ca_policy_seq;
 int ca_rollout_policy(ca_env* env, int32_t steps, uint32_t flags, const ca_policy_seq* seq);
 
+/* PPO sample collection: heads on the installed policy, a rollout that hands back a PPO batch, and GAE.
+ * Heads.  Two optional extra rows of the output layer, read from the last hidden layer (width w[L-1]), one per weight set: the value
+ * head value_w f32 [P, w[L-1]] / value_b f32 [P], and the log-std head logstd_w f32 [P, w[L-1]] (NULL: all zeros -- a
+ * state-independent log-std carried by the bias) / logstd_b f32 [P]; HOST memory.  A head is given by its bias; at least one must be.
+ *   Definition, bit for bit.  Per agent row, in fp32, one rounding per operation, never contracted:
+ *       mean, ls_raw, value: each the k-ordered fmaf chain from its bias over the last hidden layer's activations (the rule of the mean)
+ *       ls  = fminf(fmaxf(ls_raw, CA_POLICY_LOGSTD_MIN), CA_POLICY_LOGSTD_MAX);  std = (float)exp64((double)ls)     (ca_debug_math op 5)
+ *             without a log-std head: ls = +0, std = 1;  without a value head: value = +0
+ *       eps = the noise element, +0 where noise is NULL
+ *       u   = mean + std * eps                                     (two operations)
+ *       action = out(u)                                            (the policy's out mode)
+ *       logp = ((-0.5f * (eps * eps)) - ls) - 0.918938533f         (left to right as written: the log-density of the UNCLIPPED u)
+ * ca_policy_set_heads repacks the output tile -- column 0 the installed mean row, column 1 the log-std, column 2 the value -- and
+ * drains the stream.  Refusals as ca_policy_configure's, all before anything changes: no policy installed, a NULL desc, no head at
+ * all, a weight array without its bias -> CA_EINVAL; an array smaller than its layout -> CA_ESIZE; a non-finite value -> CA_ERANGE
+ * (ca_last_error names the head, the set and the element).  Heads are configuration like the policy: they survive resets and stay
+ * with the SLOT under ca_arena_gather / ca_snapshot_load.  ca_policy_configure and ca_policy_clear drop them (the widths may have
+ * changed); ca_policy_clear_heads removes them alone; ca_policy_heads_info reports *has_value and *has_logstd (either may be NULL).
+ * ca_policy_actions and ca_rollout_policy are untouched by heads: they keep reading the tile whose columns 1 .. 15 are zero.
+ * ca_policy_evaluate: ONE launch on the observation buffer as it stands, the heads' counterpart of ca_policy_actions.  out holds
+ * optional DEVICE f32 [A, N] pointers; noise DEVICE f32 [A, N] or NULL.  No policy, no heads or a NULL out -> CA_EINVAL. */
+#define CA_POLICY_LOGSTD_MIN (-20.0f)
+#define CA_POLICY_LOGSTD_MAX 2.0f
+typedef struct ca_policy_heads {
+    const float* value_w;     /* HOST f32 [P, w[L-1]], or NULL: no value head */
+    size_t   value_w_bytes;
+    const float* value_b;     /* HOST f32 [P] */
+    size_t   value_b_bytes;
+    const float* logstd_w;    /* HOST f32 [P, w[L-1]], or NULL: zeros */
+    size_t   logstd_w_bytes;
+    const float* logstd_b;    /* HOST f32 [P], or NULL: no log-std head */
+    size_t   logstd_b_bytes;
+} ca_policy_heads;
+typedef struct ca_policy_eval {
+    float*   actions;         /* DEVICE f32 [A, N] each, or NULL: not wanted */
+    float*   logp;
+    float*   value;
+    float*   mean;
+    float*   log_std;         /* the clamped log-std */
+} ca_policy_eval;
+int ca_policy_set_heads(ca_env* env, const ca_policy_heads* heads);
+int ca_policy_clear_heads(ca_env* env);
+int ca_policy_heads_info(ca_env* env, int32_t* has_value, int32_t* has_logstd);
+int ca_policy_evaluate(ca_env* env, const float* noise, const ca_policy_eval* out);
+
+/* ca_rollout_policy_sample: the loop of ca_rollout_policy, verbatim, with ca_policy_evaluate in the place of ca_policy_actions:
+ *       for t in 0 .. steps-1:
+ *           if t % hold == 0: ca_observe; ca_policy_evaluate(noise row t / hold) -> act         (the row's records, r = t / hold)
+ *           ca_step(env, act, flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE))               (the step's and the row's records)
+ *       values_out given: ca_observe; the value of the state the call leaves -> values_out row R
+ *       advantages_out or targets_out given: ca_gae(R rows: row_rewards, values, row_done, row_valid; gamma, lambda)
+ * The state, fields, statistics, returns, first_done and the four records of ca_policy_seq are bit for bit those of
+ * ca_rollout_policy under the same effective actions.  Further optional DEVICE records, R = ceil(steps / hold):
+ *   logp_out f32 [R, A, N]; dist_out f32 [R, 2, A, N]: the mean and the clamped log-std; values_out f32 [R+1, A, N]: row R is the
+ *   bootstrap value, one observation launch and one heads launch behind the last step, made only where the buffer is given -- the
+ *   handle's observation buffer then holds the final state's observation, as under CA_F_OBS;
+ *   row_rewards_out f32 [R, A, N]: from +0, one fp32 add per step of the row that advanced the arena (ca_rollout_actions' freeze
+ *   rule), in step order, unweighted (`weights` is the business of `returns`); row_done_out i32 [R, A]: the OR of the row's done_out
+ *   entries; row_valid_out i32 [R, A]: 1 iff the row's first step advanced the arena;
+ *   advantages_out, targets_out f32 [R, A, N]: one ca_gae launch behind everything, under gamma and lambda; they need values_out,
+ *   else CA_EINVAL (row records that were not given are kept in buffers of the handle's).
+ * Checks, messages and steps == 0 as ca_rollout_policy (steps == 0 with values_out: the bootstrap row alone is written); a policy
+ * without heads and a misaligned obs_out are CA_EINVAL; a refusal advances nothing; the sticky overflow error works as before;
+ * ca_profile counts the new kernels under kind 3. */
+typedef struct ca_policy_sample_seq {
+    int32_t  hold;            /* the members of ca_policy_seq, with their meaning */
+    const float* noise;       /* DEVICE f32 [R, A, N], or NULL: eps */
+    size_t   noise_bytes;
+    const float* weights;
+    size_t   weights_bytes;
+    float*   returns;
+    size_t   returns_bytes;
+    int32_t* first_done;
+    size_t   first_done_bytes;
+    float*   obs_out;
+    size_t   obs_out_bytes;
+    float*   actions_out;
+    size_t   actions_out_bytes;
+    float*   rewards_out;
+    size_t   rewards_out_bytes;
+    int32_t* done_out;
+    size_t   done_out_bytes;
+    float*   logp_out;        /* DEVICE f32 [R, A, N], or NULL */
+    size_t   logp_out_bytes;
+    float*   dist_out;        /* DEVICE f32 [R, 2, A, N], or NULL */
+    size_t   dist_out_bytes;
+    float*   values_out;      /* DEVICE f32 [R+1, A, N], or NULL */
+    size_t   values_out_bytes;
+    float*   row_rewards_out; /* DEVICE f32 [R, A, N], or NULL */
+    size_t   row_rewards_out_bytes;
+    int32_t* row_done_out;    /* DEVICE i32 [R, A], or NULL */
+    size_t   row_done_out_bytes;
+    int32_t* row_valid_out;   /* DEVICE i32 [R, A], or NULL */
+    size_t   row_valid_out_bytes;
+    float*   advantages_out;  /* DEVICE f32 [R, A, N], or NULL */
+    size_t   advantages_out_bytes;
+    float*   targets_out;     /* DEVICE f32 [R, A, N], or NULL */
+    size_t   targets_out_bytes;
+    float    gamma;           /* of the GAE launch */
+    float    lambda;
+} ca_policy_sample_seq;
+int ca_rollout_policy_sample(ca_env* env, int32_t steps, uint32_t flags, const ca_policy_sample_seq* seq);
+
+/* ca_gae: generalised advantage estimation on buffers of the caller's, all DEVICE: rewards f32 [R, A, N], values f32 [R+1, A, N],
+ * done i32 [R, A], valid i32 [R, A] or NULL for all 1; advantages and targets f32 [R, A, N], each optional.  R = rows.
+ *   Definition, in fp32, gl = gamma * lambda one fp32 multiply; for r = R-1 .. 0 per (a, i):
+ *       nd     = done[r, a] == 0
+ *       next_v = nd ? values[r+1] : +0
+ *       delta  = (rewards[r] + gamma * next_v) - values[r]                  (three operations, in that order)
+ *       next_a = nd && r < R-1 ? adv[r+1] : +0
+ *       adv[r] = delta + gl * next_a;     valid[r, a] == 0: adv[r] = +0
+ *       target[r] = adv[r] + values[r]
+ * A pure function of its inputs, no special case for absent rows; the done flag alone ends an episode, the step cap included (the
+ * reference treats it as terminal, env.py:404-413).  rows == 0 launches nothing; rows < 0, a NULL desc, rewards, values or done ->
+ * CA_EINVAL; a buffer smaller than its layout -> CA_ESIZE.  One launch (kind 3), asynchronous on the handle's stream. */
+typedef struct ca_gae_desc {
+    const float* rewards;
+    size_t   rewards_bytes;
+    const float* values;
+    size_t   values_bytes;
+    const int32_t* done;
+    size_t   done_bytes;
+    const int32_t* valid;     /* or NULL */
+    size_t   valid_bytes;
+    float*   advantages;      /* or NULL */
+    size_t   advantages_bytes;
+    float*   targets;         /* or NULL */
+    size_t   targets_bytes;
+    float    gamma;
+    float    lambda;
+} ca_gae_desc;
+int ca_gae(ca_env* env, int32_t rows, const ca_gae_desc* desc);
+
 /* The reference's simulator keeps EVERY obstacle edge within range of an agent (sim.getAgentNumObstacleNeighbors /
  * getAgentObstacleNeighbor, env.py:249, 301-318, iterate them all); this library's lists hold max_obst_neighbors and drop the
  * farthest edges beyond that.  So that such a deviation cannot pass unnoticed, an overflow is a sticky error of the handle:
@@ -760,7 +893,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, actor_critic_kernel, sample_record_kernel and gae_kernel (ca_policy_evaluate, ca_rollout_policy_sample, ca_gae), nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
