@@ -43,12 +43,18 @@ EXPORTS = ("ca_create", "ca_destroy", "ca_last_error", "ca_set_stream", "ca_set_
            "ca_policy_configure", "ca_policy_clear", "ca_policy_info", "ca_policy_actions", "ca_rollout_policy",
            "ca_policy_set_heads", "ca_policy_clear_heads", "ca_policy_heads_info", "ca_policy_evaluate", "ca_rollout_policy_sample", "ca_gae",
            "ca_nav_configure", "ca_nav_clear", "ca_nav_info", "ca_nav_get_field", "ca_nav_pref", "ca_rollout_nav", "ca_nav_mask_build",
-           "ca_nav_act", "ca_nav_step", "ca_rollout_nav_actions", "ca_rollout_nav_policy")
+           "ca_nav_act", "ca_nav_step", "ca_rollout_nav_actions", "ca_rollout_nav_policy",
+           "ca_reward_configure", "ca_reward_clear", "ca_reward_info", "ca_reward_get_weights", "ca_reward_parts", "ca_get_reward_parts",
+           "ca_reward_parts_ptr")
 POLICY_OUT_IDENTITY, POLICY_OUT_CLIP = 0, 1   # out_mode of a policy (struct ca_policy_desc)
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 128
 POLICY_LOGSTD_MIN, POLICY_LOGSTD_MAX = -20.0, 2.0   # the clamp of a log-std head (ca_policy_set_heads)
 NAV_MAX_CELLS, NAV_MAX_GOALS, NAV_MAX_LOOKAHEAD = 32768, 16, 8   # limits of a navigation (struct ca_nav_desc)
 NAV_STAY, NAV_NONE = 8, 9   # `next` of the source cell / of a cell nothing leads out of
+REWARD_N_TERMS = 7   # the terms of a shaped reward (struct ca_reward_desc), in the order of their weights:
+REWARD_BASE, REWARD_COLLISION, REWARD_WALL, REWARD_NEAR, REWARD_WALL_NEAR, REWARD_ARRIVAL, REWARD_STEP = range(7)
+REWARD_TERMS = ("base", "collision", "wall", "near", "wall_near", "arrival", "step")
+MAX_LENGTH = 1e3   # CA_MAX_LENGTH: the largest length a handle takes (a reward margin among them)
 NAV_OFFSETS = ((1, 0), (0, 1), (-1, 0), (0, -1), (1, 1), (-1, 1), (-1, -1), (1, -1))   # (dx, dy) of pointer k = 0 .. 7
 
 
@@ -134,6 +140,11 @@ class NavDesc(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("cell", C.c_float), ("gx", C.c_int32), ("gy", C.c_int32), ("clearance", C.c_float),
                 ("n_goals", C.c_int32), ("per_arena", C.c_int32), ("targets", C.c_void_p), ("targets_bytes", C.c_size_t),
                 ("agent_class", C.c_void_p), ("class_bytes", C.c_size_t), ("lookahead", C.c_int32)]
+
+
+class RewardDesc(C.Structure):
+    """struct ca_reward_desc (include/ca_env.h): the weights and the comfort distance of the reward terms."""
+    _fields_ = [("weights", C.c_void_p), ("weights_bytes", C.c_size_t), ("per_arena", C.c_int32), ("margin", C.c_float)]
 
 
 class EdgeGridDesc(C.Structure):
@@ -224,6 +235,13 @@ def load():
     L.ca_nav_step.argtypes = [vp, vp, u32]
     L.ca_rollout_nav_actions.argtypes = [vp, i32, u32, C.POINTER(ActionSeq)]
     L.ca_rollout_nav_policy.argtypes = [vp, i32, u32, C.POINTER(PolicySeq)]
+    L.ca_reward_configure.argtypes = [vp, C.POINTER(RewardDesc)]
+    L.ca_reward_clear.argtypes = [vp]
+    L.ca_reward_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]
+    L.ca_reward_get_weights.argtypes = [vp, vp, sz]
+    L.ca_reward_parts.argtypes = [vp]
+    L.ca_get_reward_parts.argtypes = [vp, vp, vp, sz, sz, i32]
+    L.ca_reward_parts_ptr.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
     L.ca_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.ca_reset_stats.argtypes = [vp]
     L.ca_sync.argtypes = [vp]

@@ -101,10 +101,13 @@ class AgentVectorEnv(object):
       "agent_nearest_d2" [A*N]  float: squared distance to the nearest other agent of its arena (inf alone)
     navigate=True: the step is vec.step_nav -- an action is an offset from the heading of the navigation fields (set_navigation must
     have been called: ValueError otherwise), and the reward counts progress along that heading.
+    reward_terms=dict(...): handed to vec.set_reward_terms() -- the rewards are shaped on the device (collisions, walls, arrival, time).
     """
 
-    def __init__(self, vec, new_step_api=False, collect_stats=True, contacts=False, navigate=False):
+    def __init__(self, vec, new_step_api=False, collect_stats=True, contacts=False, navigate=False, reward_terms=None):
         self.vec, self.A, self.N = vec, vec.A, vec.N
+        if reward_terms:
+            vec.set_reward_terms(**reward_terms)
         self._step = _step_fn(vec, navigate, "AgentVectorEnv")
         self.contacts = bool(contacts)
         self.num_envs = self.A * self.N
@@ -178,11 +181,13 @@ class MultiAgentVectorEnv(object):
     only, and an action dictionary need not contain the absent ids.
     contacts=True: infos[env]['agent_<i>'] carries `contact` (the agent overlaps another agent of its arena or a wall) and
     `nearest_d2` (squared distance to the nearest other agent, inf alone) from the contact report of the state the step leaves.
-    navigate=True: the step is vec.step_nav, as for AgentVectorEnv.
+    navigate=True: the step is vec.step_nav, as for AgentVectorEnv.  reward_terms=dict(...): handed to vec.set_reward_terms().
     """
 
-    def __init__(self, vec, per_agent_dones=True, common_info=True, contacts=False, navigate=False):
+    def __init__(self, vec, per_agent_dones=True, common_info=True, contacts=False, navigate=False, reward_terms=None):
         self.vec, self.num_envs, self.N = vec, vec.A, vec.N
+        if reward_terms:
+            vec.set_reward_terms(**reward_terms)
         self._step = _step_fn(vec, navigate, "MultiAgentVectorEnv")
         self.contacts = bool(contacts)
         self.per_agent_dones, self.common_info = bool(per_agent_dones), bool(common_info)

@@ -6,7 +6,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcaenv.so")
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("ca_env.hip", "ca_kernels.h", "ca_common.h", "ca_lp.h", "ca_lines.h", "ca_nbr.h", "ca_rules.h", "ca_step.h", "ca_quad.h", "ca_pair.h", "ca_tiled.h", "ca_edge_grid_host.h",
-                                                    "ca_alan.h", "ca_obs.h", "ca_obs_chord.h", "ca_math.h", "ca_trace.h", "ca_contact.h", "ca_fork.h", "ca_actseq.h", "ca_policy.h", "ca_nav.h", "ca_nav_host.h")] + \
+                                                    "ca_alan.h", "ca_obs.h", "ca_obs_chord.h", "ca_math.h", "ca_trace.h", "ca_contact.h", "ca_fork.h", "ca_actseq.h", "ca_policy.h", "ca_nav.h", "ca_nav_host.h", "ca_reward.h")] + \
           [os.path.join(os.path.dirname(_HERE), "include", "ca_env.h")]
 # -ffp-contract=off: no FMA contraction -- the numerics contract shared with the parity oracle.
 # -fno-slp-vectorize: keeps the compiler from packing adjacent scalar fp32 adds / multiplies into v_pk_add_f32 /

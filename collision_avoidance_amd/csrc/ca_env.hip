@@ -136,6 +136,18 @@ struct ca_env {
     // keeps for nav_reward_kernel, [A] whether the step between them advances the arena.  Allocated on first use; no field and no state
     float* nav_keep = nullptr;
     int* nav_advance = nullptr;
+    // the reward terms (ca_reward_configure; ca_reward.h): configuration, like the policy and the navigation.  d_w / h_w hold the [A][7]
+    // weights as the kernel uses them (one row repeated when they were given once), need_mask bit k: some arena has w_k != 0.  saved /
+    // advance: [A*N] / [A] what reward_begin_kernel keeps for reward_terms_kernel; parts: [7][A*N] r_ref and the counts.  The three are
+    // allocated on first use; no field and no state.  parts_valid: parts have been computed on this handle (ca_get_reward_parts refuses before)
+    struct Reward {
+        bool on = false, parts_valid = false;
+        int per_arena = 0, need_mask = 0;
+        float margin = 0.0f;
+        float* d_w = nullptr;
+        std::vector<float> h_w;
+        int *saved = nullptr, *advance = nullptr, *parts = nullptr;
+    } rew;
     // obstacle-neighbour overflow made loud: a page-locked host word the kernels write (ca_common.h note_overflow); unless the
     // caller opted in (ca_allow_obstacle_overflow) it is the handle's sticky CA_ERANGE status (overflow_status below)
     unsigned long long* ovf_host = nullptr;
@@ -1221,7 +1233,7 @@ int ca_destroy(ca_env* e) {
                     e->goal2_x, e->goal2_y, e->slab, e->tmp_x, e->tmp_y, e->orient_x, e->orient_y,
                     e->agent_done, e->arrive_step,
                     e->regoal_count, e->counts, e->nb_idx, e->obst_idx, e->cvt_buf, e->d_tab_off, e->d_cold, e->d_trace, e->d_actseq, e->actseq_words, e->d_order,
-                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->heads.d_wp, e->heads.d_bp, e->heads.rr, e->heads.words, e->nav.d_dist, e->nav.d_next, e->nav.d_class, e->nav_keep, e->nav_advance,
+                    e->pol.d_wp, e->pol.d_bp, e->pol.act, e->pol.d_set, e->heads.d_wp, e->heads.d_bp, e->heads.rr, e->heads.words, e->nav.d_dist, e->nav.d_next, e->nav.d_class, e->nav_keep, e->nav_advance, e->rew.d_w, e->rew.saved, e->rew.advance, e->rew.parts,
                     e->episode, e->arena_stats, e->arena_steps, e->d_obst, e->dbg, e->dbg_obs,
                     e->alan_w, e->alan_t, e->alan_dirs, e->alan_u, e->alan_action, e->d_alan, e->mask_buf,
                     e->d_act_tab, e->d_act_n, e->d_ap[0], e->d_ap[1], e->d_ap[2], e->d_ap[3], e->d_ap_oct, e->d_counts, e->d_as_nd, e->d_as_k,
@@ -2274,12 +2286,64 @@ int ca_reset_masked(ca_env* e, const int32_t* mask, int32_t mask_is_device, uint
     return CA_OK;
 }
 
+// The reward terms round a step (ca_reward.h; kind 3 for ca_profile): reward_begin_kernel in front of its launches, reward_terms_kernel
+// behind them -- or, parts_only, the one launch of ca_reward_parts for the state as it stands.
+static hipError_t reward_buffers(ca_env* e) {
+    if (!e->rew.saved) { const hipError_t r = dalloc(e, &e->rew.saved, AN(e)); if (r != hipSuccess) return r; }
+    if (!e->rew.advance) { const hipError_t r = dalloc(e, &e->rew.advance, (size_t)e->cfg.n_arenas); if (r != hipSuccess) return r; }
+    if (!e->rew.parts) { const hipError_t r = dalloc(e, &e->rew.parts, (size_t)REWARD_N_TERMS * AN(e)); if (r != hipSuccess) return r; }
+    return hipSuccess;
+}
+static hipError_t launch_reward_begin(ca_env* e, uint32_t flags) {
+    const hipError_t r = reward_buffers(e);
+    if (r != hipSuccess) return r;
+    RewardBeginArgs b;
+    b.word = e->cfg.done_mode == CA_DONE_REGOAL ? e->regoal_count : e->agent_done;
+    b.arena_done = e->arena_done; b.saved = e->rew.saved; b.advance = e->rew.advance;
+    b.an = (unsigned)AN(e); b.N = e->cfg.n_agents; b.freeze = (flags & CA_F_FREEZE) ? 1 : 0;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, reward_begin_kernel, dim3((b.an + 255) / 256), dim3(256), 0, e->stream, b);
+    return hipGetLastError();
+}
+static hipError_t launch_reward_terms(ca_env* e, uint32_t flags, bool parts_only) {
+    hipError_t r = reward_buffers(e);
+    if (r != hipSuccess) return r;
+    RewardTermsArgs c;
+    c.pos_x = e->pos_x; c.pos_y = e->pos_y;
+    c.ap_radius = e->ap ? e->d_ap[0] : nullptr;      // (as launch_contacts)
+    c.agent_counts = e->ac ? e->d_counts : nullptr;
+    c.obst = e->d_obst; c.tab_off = e->d_tab_off;
+    c.an = (unsigned)AN(e);
+    c.n_obst = e->h_tab_off.empty() ? (int)e->h_obst.size() : 0; c.A = e->cfg.n_arenas; c.N = e->cfg.n_agents;
+    c.apb = c.N <= REWARD_BS ? REWARD_BS / c.N : 0;
+    c.tiles = c.N <= REWARD_BS ? 0 : (c.N + REWARD_BS - 1) / REWARD_BS;
+    c.radius = e->cfg.radius;
+    c.weights = e->rew.d_w; c.margin = e->rew.margin;
+    c.reward = e->reward; c.parts = e->rew.parts; c.saved = e->rew.saved; c.advance = e->rew.advance;
+    c.agent_done = e->agent_done; c.regoal_count = e->regoal_count; c.arena_done = e->arena_done; c.arena_stats = e->arena_stats;
+    c.regoal = e->cfg.done_mode == CA_DONE_REGOAL ? 1 : 0;
+    c.autoreset = (flags & CA_F_AUTORESET) ? 1 : 0; c.stats = (!parts_only && (flags & CA_F_STATS)) ? 1 : 0;
+    c.need_mask = e->rew.need_mask;
+    c.need_pairs = (c.need_mask & ((1 << CA_REWARD_COLLISION) | (1 << CA_REWARD_NEAR))) ? 1 : 0;
+    c.need_walls = (c.need_mask & ((1 << CA_REWARD_WALL) | (1 << CA_REWARD_WALL_NEAR))) ? 1 : 0;
+    c.parts_only = parts_only ? 1 : 0;
+    const unsigned grid = c.apb ? (unsigned)((c.A + c.apb - 1) / c.apb) : (unsigned)((size_t)c.A * c.tiles);
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, reward_terms_kernel, dim3(grid), dim3(REWARD_BS), 0, e->stream, c);
+    r = hipGetLastError();
+    if (r == hipSuccess) e->rew.parts_valid = true;
+    return r;
+}
+
 static int do_step(ca_env* e, const float* actions, uint32_t flags) {
     { const int rs = overflow_status(e, "step"); if (rs) return rs; }
     prof_cadence(e, 1);
+    const bool terms = actions != nullptr && e->rew.on;   // (a step that writes the reward from actions: ca_reward_configure)
+    if (terms) HIPCHK(e, launch_reward_begin(e, flags));
     StepArgs a;
     fill_args(e, a, actions, flags);
     HIPCHK(e, launch_step(e, a));
+    if (terms) HIPCHK(e, launch_reward_terms(e, flags, false));
     e->orient_valid = true;
     if (flags & CA_F_OBS) HIPCHK(e, launch_obs(e));
     e->steps_done += 1;
@@ -2851,7 +2915,7 @@ int ca_rollout_actions(ca_env* e, int32_t steps, uint32_t flags, const ca_action
     { const int rc = actseq_check(e, "ca_rollout_actions", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_actions"); if (rs) return rs; }
-    const bool one_launch = e->quad_roll;   // (ca_solver_info: rollout_one_launch; an ALAN-configured handle steps without the bandit here)
+    const bool one_launch = e->quad_roll && !e->rew.on;   // (ca_solver_info: rollout_one_launch; an ALAN-configured handle steps without the bandit here; reward terms need the state between steps)
     ActSeqPlan pl;
     { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, !one_launch, &pl); if (rc) return rc; }
     const uint32_t sf = flags & ~(CA_F_OBS | CA_F_CONTACT);   // (both: one launch behind the last step, launch_tail)
@@ -3590,10 +3654,19 @@ static hipError_t launch_nav_reward(ca_env* e, uint32_t flags, const StepRec* re
 // one navigated action step: nav_act_kernel, the launches of the ORCA-only step, nav_reward_kernel
 static int nav_do_step(ca_env* e, const float* actions, uint32_t sf, const StepRec* rec) {
     prof_cadence(e, 1);
+    const bool terms = e->rew.on;
+    if (terms) HIPCHK(e, launch_reward_begin(e, sf));
     HIPCHK(e, launch_nav_act(e, actions, nullptr, nullptr, (sf & CA_F_FREEZE) != 0));
     const int rc = do_step(e, nullptr, sf);
     if (rc) return rc;
-    HIPCHK(e, launch_nav_reward(e, sf, rec));
+    if (!terms) {
+        HIPCHK(e, launch_nav_reward(e, sf, rec));
+        return CA_OK;
+    }
+    // reward terms: nav_reward_kernel in its single-step form, the terms, then a rollout's ordinary accounting of the shaped reward
+    HIPCHK(e, launch_nav_reward(e, sf, nullptr));
+    HIPCHK(e, launch_reward_terms(e, sf, false));
+    if (rec) HIPCHK(e, (rec->rewards_out || rec->done_out) ? launch_policy_record(e, *rec) : launch_actseq_accumulate(e, *rec));
     return CA_OK;
 }
 
@@ -3658,6 +3731,98 @@ int ca_rollout_nav_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_pol
         if (rc) return rc;
     }
     return launch_tail(e, flags);
+}
+
+// ---- reward terms (include/ca_env.h ca_reward_desc; ca_reward.h) ------------------------------------------------------
+int ca_reward_configure(ca_env* e, const ca_reward_desc* d) {
+    const char* who = "ca_reward_configure";
+    if (!e) return CA_EINVAL;
+    if (!d || !d->weights) return fail(e, CA_EINVAL, "%s: the description or its weights are null", who);
+    if (d->per_arena != 0 && d->per_arena != 1) return fail(e, CA_EINVAL, "%s: per_arena=%d (0 or 1)", who, d->per_arena);
+    const size_t A = (size_t)e->cfg.n_arenas, rows = d->per_arena ? A : 1, need = rows * CA_REWARD_N_TERMS * 4;
+    if (d->weights_bytes != need)
+        return fail(e, CA_ESIZE, "%s: the weights hold %zu bytes (f32 [%s%d]), got %zu", who, need, d->per_arena ? "A, " : "", CA_REWARD_N_TERMS, d->weights_bytes);
+    for (size_t a = 0; a < rows; ++a)
+        for (int k = 0; k < CA_REWARD_N_TERMS; ++k)
+            if (!std::isfinite(d->weights[a * CA_REWARD_N_TERMS + k]))
+                return fail(e, CA_ERANGE, "%s: the weight of arena %zu, term %d is not finite", who, a, k);
+    if (!std::isfinite(d->margin) || d->margin < 0.0f || d->margin > CA_MAX_LENGTH)
+        return fail(e, CA_ERANGE, "%s: margin=%g outside [0, %g]", who, (double)d->margin, (double)CA_MAX_LENGTH);
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));   // (launches in flight read the weights being replaced)
+    if (!e->rew.d_w) HIPCHK(e, dalloc(e, &e->rew.d_w, A * CA_REWARD_N_TERMS));
+    std::vector<float> w(A * CA_REWARD_N_TERMS);
+    int mask = 0;
+    for (size_t a = 0; a < A; ++a)
+        for (int k = 0; k < CA_REWARD_N_TERMS; ++k) {
+            const float v = d->weights[(d->per_arena ? a : 0) * CA_REWARD_N_TERMS + k];
+            w[a * CA_REWARD_N_TERMS + k] = v;
+            if (v != 0.0f) mask |= 1 << k;
+        }
+    HIPCHK(e, upload(e, e->rew.d_w, w.data(), w.size() * 4));
+    e->rew.h_w.swap(w);
+    e->rew.need_mask = mask; e->rew.per_arena = d->per_arena; e->rew.margin = d->margin; e->rew.on = true;
+    return CA_OK;
+}
+
+int ca_reward_clear(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->rew.on = false;
+    return CA_OK;
+}
+
+int ca_reward_info(ca_env* e, int32_t* configured, int32_t* per_arena, float* margin) {
+    if (!e) return CA_EINVAL;
+    if (configured) *configured = e->rew.on ? 1 : 0;
+    if (per_arena) *per_arena = e->rew.on ? e->rew.per_arena : 0;
+    if (margin) *margin = e->rew.on ? e->rew.margin : 0.0f;
+    return CA_OK;
+}
+
+int ca_reward_get_weights(ca_env* e, float* weights, size_t bytes) {
+    if (!e) return CA_EINVAL;
+    if (!weights) return fail(e, CA_EINVAL, "ca_reward_get_weights: weights is null");
+    if (!e->rew.on) return fail(e, CA_EINVAL, "ca_reward_get_weights: no reward terms are configured (ca_reward_configure)");
+    if (bytes != e->rew.h_w.size() * 4)
+        return fail(e, CA_ESIZE, "ca_reward_get_weights: the weights hold %zu bytes (f32 [A, %d]), got %zu", e->rew.h_w.size() * 4, CA_REWARD_N_TERMS, bytes);
+    memcpy(weights, e->rew.h_w.data(), bytes);
+    return CA_OK;
+}
+
+int ca_reward_parts(ca_env* e) {
+    if (!e) return CA_EINVAL;
+    if (!e->rew.on) return fail(e, CA_EINVAL, "ca_reward_parts: no reward terms are configured (ca_reward_configure)");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, launch_reward_terms(e, 0, true));
+    return CA_OK;
+}
+
+int ca_get_reward_parts(ca_env* e, float* ref, int32_t* counts, size_t ref_bytes, size_t counts_bytes, int32_t dst_is_device) {
+    if (!e) return CA_EINVAL;
+    const size_t an = AN(e);
+    if (ref && ref_bytes != an * 4) return fail(e, CA_ESIZE, "ca_get_reward_parts: the reference plane holds %zu bytes, got %zu", an * 4, ref_bytes);
+    if (counts && counts_bytes != (CA_REWARD_N_TERMS - 1) * an * 4)
+        return fail(e, CA_ESIZE, "ca_get_reward_parts: the count planes hold %zu bytes, got %zu", (CA_REWARD_N_TERMS - 1) * an * 4, counts_bytes);
+    if (!e->rew.parts_valid)
+        return fail(e, CA_EINVAL, "ca_get_reward_parts: no reward parts have been computed on this handle (ca_reward_parts, or a step "
+                                  "under configured terms)");
+    HIPCHK(e, hipSetDevice(e->device));
+    const hipMemcpyKind kind = dst_is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (ref) HIPCHK(e, hipMemcpyAsync(ref, e->rew.parts, ref_bytes, kind, e->stream));
+    if (counts) HIPCHK(e, hipMemcpyAsync(counts, e->rew.parts + an, counts_bytes, kind, e->stream));
+    if (!dst_is_device) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return CA_OK;
+}
+
+int ca_reward_parts_ptr(ca_env* e, void** dev_ptr, size_t* bytes) {
+    if (!e || !dev_ptr) return fail(e, CA_EINVAL, "ca_reward_parts_ptr: null argument");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, reward_buffers(e));
+    *dev_ptr = e->rew.parts;
+    if (bytes) *bytes = (size_t)CA_REWARD_N_TERMS * AN(e) * 4;
+    return CA_OK;
 }
 
 int ca_sync(ca_env* e) {

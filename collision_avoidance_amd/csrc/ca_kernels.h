@@ -36,7 +36,8 @@
 // ca_contact.h (the per-agent contact report), ca_fork.h (the arena copy behind ca_arena_gather / ca_snapshot_*),
 // ca_actseq.h (the small kernels of ca_rollout_actions and the rule of its return), ca_policy.h (the MLP policy kernel on the f32
 // MFMA and the record kernel of ca_rollout_policy), ca_nav.h (the navigation fields: the LDS relaxation behind ca_nav_configure and the
-// preferred-velocity kernel of ca_nav_pref / ca_rollout_nav; its host parts are ca_nav_host.h).
+// preferred-velocity kernel of ca_nav_pref / ca_rollout_nav; its host parts are ca_nav_host.h), ca_reward.h (the reward terms: the two small
+// kernels round a step that writes the reward from actions).
 #pragma once
 #include "ca_rules.h"
 #include "ca_step.h"
@@ -51,6 +52,7 @@
 #include "ca_actseq.h"
 #include "ca_policy.h"
 #include "ca_nav.h"
+#include "ca_reward.h"
 
 namespace ca {
 

@@ -45,12 +45,13 @@ _bases = (_EnvBase,) if _MultiAgentEnv is object or _EnvBase is _MultiAgentEnv e
 class Collision_Avoidance_Env(*_bases):
     metadata = {'render.modes': ['human']}
 
-    def __init__(self, numAgents=10, device=0, seed=0, max_obst_neighbors=None, allow_obst_overflow=False, contacts=False):
+    def __init__(self, numAgents=10, device=0, seed=0, max_obst_neighbors=None, allow_obst_overflow=False, contacts=False, reward_terms=None):
         # (max_obst_neighbors / allow_obst_overflow: VecCollisionAvoidanceEnv's keywords, no reference counterpart -- the
         # reference's simulator keeps every obstacle edge in range; the defaults are the vector env's)
         # contacts=True (no reference counterpart either: its gym_infos stay empty, env.py:474): after step(),
         # gym_infos['agent_i'] = {'contact': the agent overlaps another agent or a wall, 'nearest_d2': squared distance to the
         # nearest other agent (inf alone)} from the contact report of the state the step leaves
+        # reward_terms=dict(...) (no reference counterpart): VecCollisionAvoidanceEnv.set_reward_terms's keywords; the rewards are shaped on the device
         # constants of env.py:27-44
         self.timeStep = 1 / 60.
         self.neighborDist = 1.5
@@ -69,6 +70,7 @@ class Collision_Avoidance_Env(*_bases):
                                      shape=(self.laser_num * 4,))                               # env.py:53
         self._device, self._seed = device, seed
         self._contacts = bool(contacts)
+        self._reward_terms = dict(reward_terms) if reward_terms else None
         self._max_obst_neighbors, self._allow_obst_overflow = max_obst_neighbors, allow_obst_overflow
         self._keys = ['agent_' + str(i) for i in range(numAgents)]                              # env.py:275, 373, 400
         self._make()
@@ -79,7 +81,8 @@ class Collision_Avoidance_Env(*_bases):
                                             seed=self._seed, use_torch=False, max_obst_neighbors=self._max_obst_neighbors,
                                             allow_obst_overflow=self._allow_obst_overflow,
                                             tiled=self.numAgents > _lib.MAX_AGENTS,   # (any numAgents, like the reference's)
-                                            tiled_wide=self.numAgents > _lib.MAX_AGENTS and (self._max_obst_neighbors or 0) > 16)
+                                            tiled_wide=self.numAgents > _lib.MAX_AGENTS and (self._max_obst_neighbors or 0) > 16,
+                                            reward_terms=self._reward_terms)
 
     @property
     def step_count(self):

@@ -6,7 +6,10 @@ advantages and value targets; torch is used for the gradient step
 again with set_policy() / set_policy_heads(), so the next collect() samples from the policy that was just trained.
 
 The log-probability the library records is defined as a k-ordered fmaf chain; torch's GEMM adds in another order, so the importance
-ratio of the first minibatch is 1 to rounding, not exactly."""
+ratio of the first minibatch is 1 to rounding, not exactly.
+
+With env.set_reward_terms(...) the rewards, advantages and value targets of the batch are those of the shaped reward -- collision,
+wall, arrival and time terms computed on the device between the steps --, and nothing here changes."""
 import math
 
 import numpy as np

@@ -238,6 +238,31 @@ def policy_sample_shape(A, N, steps, hold=1, noise_shape=None, weights_shape=Non
     return sh
 
 
+def reward_terms(A, base=1.0, collision=0.0, wall=0.0, near=0.0, wall_near=0.0, arrival=0.0, step=0.0, margin=0.0):
+    """The description of a shaped reward as ca_reward_configure takes it, without a device: (weights, per_arena, margin).  Each weight
+    is a scalar or [A]; weights is float32 [7] when all are scalars (per_arena 0), else [A, 7] (per_arena 1), in the order of
+    _lib.REWARD_TERMS.  Raises ValueError for what the library refuses: a weight that is not a scalar or [A] or is not finite, a
+    margin that is not finite, negative or above _lib.MAX_LENGTH."""
+    A = int(A)
+    vals = []
+    for name, v in zip(_lib.REWARD_TERMS, (base, collision, wall, near, wall_near, arrival, step)):
+        v = np.asarray(v.detach().cpu().numpy() if torch is not None and isinstance(v, torch.Tensor) else v, np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != A):
+            raise ValueError("reward terms: %s must be a scalar or [A=%d], got shape %s" % (name, A, v.shape))
+        if not np.isfinite(v).all() or (np.abs(v) > float(np.finfo(np.float32).max)).any():
+            raise ValueError("reward terms: %s holds a value that is not finite in float32" % name)
+        vals.append(v)
+    m = float(margin)
+    if not np.isfinite(np.float32(m)) or m < 0.0 or np.float32(m) > np.float32(_lib.MAX_LENGTH):
+        raise ValueError("reward terms: margin=%r outside [0, %g]" % (margin, _lib.MAX_LENGTH))
+    per_arena = any(v.ndim == 1 for v in vals)
+    if per_arena:
+        w = np.stack([np.broadcast_to(v, (A,)) for v in vals], 1).astype(np.float32)
+    else:
+        w = np.array([float(v) for v in vals], np.float32)
+    return np.ascontiguousarray(w), int(per_arena), m
+
+
 class Snapshot:
     """A second set of the state buffers on the environment's device (ca_snapshot_*): made and filled by
     VecCollisionAvoidanceEnv.snapshot(), read by restore().  close() destroys it; the environment's close() invalidates every
@@ -278,6 +303,8 @@ class VecCollisionAvoidanceEnv:
     agent_sensing: dict(neighbor_dist=, max_neighbors=) handed to set_agent_sensing() once the handle exists: how far every agent
                looks and how many others it attends to, with the two values of `params` as capacities.  On a tiled handle it
                follows the rule of agent_params=: only with tiled_params=True (ValueError).
+    reward_terms: dict(base=, collision=, wall=, near=, wall_near=, arrival=, step=, margin=) handed to set_reward_terms() once the
+               handle exists: the reward every step from actions writes is shaped on the device.
     agent_counts: [A] ints handed to set_agent_counts() before the scenario is initialised: arena a holds agent_counts[a] of its
                n_agents rows (n_agents becomes a capacity).  Only scenario "doorway" or None goes with it (ValueError otherwise).
     tiled:     True: the tiled solve path (ca_create_ex with CA_CREATE_TILED) -- n_agents up to _lib.MAX_AGENTS_LARGE (16384), an
@@ -304,7 +331,7 @@ class VecCollisionAvoidanceEnv:
     def __init__(self, n_arenas, n_agents, scenario="crowd", params=None, device=0, seed=0,
                  arena_offset=0, max_obst_neighbors=None, use_torch=None, obstacles="scenario", allow_obst_overflow=False,
                  agent_params=None, agent_counts=None, tiled=False, edge_grid=False, tiled_params=False, tiled_wide=False,
-                 agent_sensing=None):
+                 agent_sensing=None, reward_terms=None):
         if tiled not in (False, True, "grid", None, 0, 1):
             raise ValueError("tiled=%r: False, True or 'grid'" % (tiled,))
         if tiled_params and not tiled:
@@ -392,6 +419,8 @@ class VecCollisionAvoidanceEnv:
             self.set_agent_params(**agent_params)
         if agent_sensing:
             self.set_agent_sensing(**agent_sensing)
+        if reward_terms:
+            self.set_reward_terms(**reward_terms)
 
     # ---- plumbing -------------------------------------------------------------------------------
     def _call(self, name, *args):
@@ -1427,6 +1456,71 @@ class VecCollisionAvoidanceEnv:
             return out["gae_advantages"], out["gae_targets"]
         self.sync()
         return np.array(out["gae_advantages"][:R]), np.array(out["gae_targets"][:R])
+
+    # ---- reward terms (ca_reward_*) ---------------------------------------------------------------------
+    def set_reward_terms(self, base=1.0, collision=0.0, wall=0.0, near=0.0, wall_near=0.0, arrival=0.0, step=0.0, margin=0.0):
+        """Shape the reward on the device (ca_reward_configure; include/ca_env.h has the definition, bit for bit): while set, every
+        call that writes the reward from actions -- step, step_packed, rollout_actions, rollout_policy, rollout_policy_sample, step_nav
+        and the navigated rollouts -- leaves
+            r = base * r_ref + collision * (agents touched) + wall * (on a wall) + near * (agents within the radii + margin)
+                + wall_near * (a wall within the radius + margin) + arrival * (arrived in this step) + step * (was not done)
+        in the reward, so that returns, records, advantages and targets are computed from it.  A penalty is a negative weight.  Each
+        weight is a scalar or [A] (a curriculum over arenas); margin is the comfort distance of near / wall_near.  Configuration: it
+        survives resets and scenarios and stays with the slot under fork() / restore().  orca_step, rollout and alan_* are not
+        affected."""
+        w, per_arena, m = reward_terms(self.A, base, collision, wall, near, wall_near, arrival, step, margin)
+        d = _lib.RewardDesc(weights=_ptr(w), weights_bytes=w.nbytes, per_arena=per_arena, margin=m)
+        self._call("ca_reward_configure", self.h, C.byref(d))
+
+    def clear_reward_terms(self):
+        self._call("ca_reward_clear", self.h)
+
+    def reward_terms_info(self):
+        """dict(configured=, per_arena=, margin=, weights=) of the installed terms (ca_reward_info, ca_reward_get_weights): weights
+        float32 [A, 7] as the kernel uses them, None while nothing is configured."""
+        c, pa, m = C.c_int32(0), C.c_int32(0), C.c_float(0.0)
+        self._call("ca_reward_info", self.h, C.byref(c), C.byref(pa), C.byref(m))
+        w = None
+        if c.value:
+            w = np.empty((self.A, _lib.REWARD_N_TERMS), np.float32)
+            self._call("ca_reward_get_weights", self.h, _ptr(w), w.nbytes)
+        return dict(configured=bool(c.value), per_arena=bool(pa.value), margin=float(m.value), weights=w)
+
+    def reward_parts(self):
+        """The parts of a shaped reward for the current state (ca_reward_parts), a dict of seven [A,N] arrays: ref float32 -- the
+        reward field as it stands -- and collision, wall, near, wall_near, arrival (0 here), step (agent_done == 0) int32.  A count
+        that no arena has a weight for reads 0.  The reward is not written.  With use_torch the arrays are views of the handle's one
+        device buffer (rewritten by every step under terms); else host copies."""
+        self._call("ca_reward_parts", self.h)
+        return self.last_reward_parts()
+
+    def last_reward_parts(self):
+        """The parts last computed -- by reward_parts() or by a step under terms -- without recomputing them.  Raises if the handle
+        has computed none yet."""
+        names = ("ref",) + _lib.REWARD_TERMS[1:]
+        if self.use_torch:
+            planes = self.__dict__.get("_reward_parts_t")
+            if planes is None:
+                ptr, nbytes = C.c_void_p(), C.c_size_t()
+                self._call("ca_reward_parts_ptr", self.h, C.byref(ptr), C.byref(nbytes))
+
+                class _View(object):   # the CUDA array interface, as in field_tensor
+                    pass
+                v = _View()
+                v.__cuda_array_interface__ = {"shape": (_lib.REWARD_N_TERMS, self.A, self.N), "typestr": np.dtype(np.float32).str,
+                                              "data": (int(ptr.value), False), "version": 2, "strides": None}
+                t = torch.as_tensor(v, device=torch.device("cuda", self.device))
+                assert t.numel() * 4 == nbytes.value
+                planes = self._reward_parts_t = {name: (t[k] if k == 0 else t[k].view(torch.int32)) for k, name in enumerate(names)}
+            # (the library refuses a read before the first computation: asked for here, without a copy)
+            self._call("ca_get_reward_parts", self.h, None, None, 0, 0, 1)
+            return dict(planes)
+        ref = np.empty((self.A, self.N), np.float32)
+        cnt = np.empty((_lib.REWARD_N_TERMS - 1, self.A, self.N), np.int32)
+        self._call("ca_get_reward_parts", self.h, _ptr(ref), _ptr(cnt), ref.nbytes, cnt.nbytes, 0)
+        out = {"ref": ref}
+        out.update({name: cnt[k] for k, name in enumerate(names[1:])})
+        return out
 
     # ---- navigation fields (ca_nav_*) ------------------------------------------------------------------
     def set_navigation(self, targets, agent_class, cell, origin=None, shape=None, clearance=None, lookahead=2):

@@ -893,7 +893,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, actor_critic_kernel, sample_record_kernel and gae_kernel (ca_policy_evaluate, ca_rollout_policy_sample, ca_gae), nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, actor_critic_kernel, sample_record_kernel and gae_kernel (ca_policy_evaluate, ca_rollout_policy_sample, ca_gae), nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), reward_begin_kernel and reward_terms_kernel (every step from actions while ca_reward_configure's terms are set; ca_reward_parts), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);
@@ -1105,6 +1105,94 @@ int ca_nav_act(ca_env* env, const float* actions, float* heading_out, float* dis
 int ca_nav_step(ca_env* env, const float* actions, uint32_t flags);
 int ca_rollout_nav_actions(ca_env* env, int32_t steps, uint32_t flags, const ca_action_seq* seq);
 int ca_rollout_nav_policy(ca_env* env, int32_t steps, uint32_t flags, const ca_policy_seq* seq);
+
+/* Reward terms: collisions, walls, crowding, arrival and time, on the device.  The reward a step writes from actions is the reference's
+ * (env.py:389-400): progress along the goal direction and along the commanded direction.  While terms are configured, every such step
+ * runs one small kernel in front of its launches (reward_begin_kernel) and one behind them (reward_terms_kernel), and the kernel behind
+ * rewrites CA_FLD_REWARD as a weighted sum of the reference's reward r_ref and six per-agent counts, so that everything that reads the
+ * field afterwards -- returns, the reward records, row_rewards, advantages and targets of the rollouts, the packed copy of
+ * ca_step_packed -- is computed from the shaped reward.  No solve, observation, contact, record or policy kernel knows about it.
+ * All arithmetic is fp32, one rounding per operation, never contracted.
+ *
+ * The terms, CA_REWARD_N_TERMS = 7 with weights w[0 .. 6]; c_k for agent i of arena a, of the state the step leaves:
+ *   0 CA_REWARD_BASE       no count: it multiplies the reference reward r_ref that the step wrote
+ *   1 CA_REWARD_COLLISION  number of other present agents j with absSq(p_i - p_j) < sqr(r_i + r_j)   (the contact report's `agents`)
+ *   2 CA_REWARD_WALL       1 if distSqPointSegment(edge, p_i) < sqr(r_i) for any edge of the arena's table, else 0   (the report's `wall`)
+ *   3 CA_REWARD_NEAR       number of other present agents j with absSq(p_i - p_j) < sqr((r_i + r_j) + margin); the touching ones included
+ *   4 CA_REWARD_WALL_NEAR  1 if the smallest distSqPointSegment over the edges is < sqr(r_i + margin), else 0
+ *   5 CA_REWARD_ARRIVAL    1 if the agent arrived in this step (rule below), else 0
+ *   6 CA_REWARD_STEP       1 if the agent was not done in front of the step (agent_done == 0), else 0: the count of a time penalty.
+ *                          Under CA_DONE_REGOAL it is always 1.
+ * r_i is the agent's own radius under ca_set_agent_params, else ca_config.radius; j = i is left out by index, as in the contact
+ * report; no range limit applies; absent rows of ca_set_agent_counts are never a j and are not written.
+ *
+ * The shaped reward:  r = w0 * r_ref  (one multiply);  then for k = 1 .. 6 ascending, where w_k != 0:  r = r + w_k * (float)c_k  (one
+ * multiply and one add, each rounded).  A term whose weight is exactly 0 is skipped, so the weights (1, 0, 0, 0, 0, 0, 0) leave the
+ * reward's bits unchanged.
+ *
+ * Rows that are shaped: every present row of an arena that the step advanced.  Under CA_F_FREEZE an arena whose arena_done was set in
+ * front of the step keeps the reward it holds (the kernel in front notes this per arena); such rows, like absent ones, are written
+ * neither in CA_FLD_REWARD nor in the parts.
+ *
+ * Arrival.  The kernel in front saves one word per agent.  CA_DONE_XLESS / CA_DONE_GOAL: agent_done; arrived means saved == 0 and
+ * agent_done != 0 behind the step.  CA_DONE_REGOAL: regoal_count; arrived means regoal_count changed.
+ *
+ * A step that respawned its arena (CA_F_AUTORESET among the step's flags and arena_done[a] != 0 behind the step): the positions are
+ * the next episode's, so c1 .. c4 are 0 for that step, as the contact report documents for its own planes.  In modes 0 / 1 the done
+ * flags were cleared, and the arrival test reads the arena's last-episode word instead (CA_FLD_ARENA_STATS slot 7, length << 32 |
+ * agents that arrived, written by every solve kernel whenever an episode ends): an agent with saved == 0 arrived iff the word's low
+ * half equals the arena's agent count.  ONE CASE IS LEFT OUT: at an episode that the step cap ends with some agents still under way,
+ * an agent arriving in that very step is not credited.
+ *
+ * Statistics.  Under CA_F_STATS the kernel adds (double)r - (double)r_ref of the arena's shaped rows into the arena's sum_reward,
+ * which afterwards is the sum of the shaped rewards.  The order of that sum is not defined: it agrees with a sequential float64 sum
+ * to 1e-9 * sum(|r|) (n * 2^-53 for fewer than 10^6 addends; the tolerance of tiled handles and of ca_nav_step).
+ *
+ * Parts.  The kernel also leaves a buffer of the handle's, [7, A, N] words, allocated on first use: plane 0 is r_ref (f32), planes
+ * 1 .. 6 are c_1 .. c_6 (i32).  No ca_field and no state: ca_arena_gather and ca_snapshot_* do not move it.  A count whose weight is 0
+ * in every arena is stored as 0 (the pair scan is not made when no arena weighs term 1 or 3, the wall scan when none weighs 2 or 4).
+ * ca_reward_parts recomputes the buffer for the current state in one launch, like ca_contacts: plane 0 is the reward field as it
+ * stands, arrival is 0, step is agent_done == 0, every present row is written and the reward is not; CA_EINVAL without terms.
+ * ca_get_reward_parts copies the planes out (either pointer may be NULL; CA_ESIZE unless ref_bytes == A * N * 4 and counts_bytes ==
+ * 6 * A * N * 4; CA_EINVAL before anything was computed on the handle).  ca_reward_parts_ptr: the zero-copy view (allocates the buffer
+ * if needed; valid until ca_destroy).
+ *
+ * ca_reward_configure: all checks run before anything changes, and a failure leaves the handle as it was.  A NULL argument or per_arena
+ * outside 0 / 1 -> CA_EINVAL; weights_bytes not exactly the layout -> CA_ESIZE; a non-finite weight -> CA_ERANGE (ca_last_error names
+ * the arena and the term); a margin that is not finite, negative or above CA_MAX_LENGTH -> CA_ERANGE.  It drains the stream; calling it
+ * again replaces the terms.  The terms are configuration: they survive ca_reset*, CA_F_AUTORESET, ca_init_scenario and
+ * ca_set_obstacles*, and per-arena weights stay with the slot under ca_arena_gather / ca_snapshot_load.  ca_reward_clear removes them;
+ * ca_reward_get_weights returns [A, 7] as the kernel uses them (CA_EINVAL without terms).
+ *
+ * While configured, the terms apply to every call that writes the reward from actions: ca_step, ca_step_host, ca_step_packed (shaped
+ * before the packed copy); ca_rollout_actions, ca_rollout_policy, ca_rollout_policy_sample; ca_nav_step, ca_rollout_nav_actions,
+ * ca_rollout_nav_policy -- a navigated step then runs nav_reward_kernel in its single-step form, the terms kernel behind it, and for
+ * the two rollouts the ordinary accumulate / record launch last (three launches more per step than without terms, two for ca_nav_step).
+ * NOT AFFECTED: ORCA-only steps and ca_rollout* without actions, which write no reward, and ca_alan_*, whose fp64 reward lives inside
+ * the bandit's kernels.  On a handle whose ca_rollout_actions is one launch per 256 steps, the call takes the per-step form while terms
+ * are set -- the terms need the state between steps --; ca_solver_info does not change.  ca_profile counts the two kernels under
+ * kind 3; a handle without terms launches nothing new. */
+#define CA_REWARD_N_TERMS 7
+#define CA_REWARD_BASE 0
+#define CA_REWARD_COLLISION 1
+#define CA_REWARD_WALL 2
+#define CA_REWARD_NEAR 3
+#define CA_REWARD_WALL_NEAR 4
+#define CA_REWARD_ARRIVAL 5
+#define CA_REWARD_STEP 6
+typedef struct ca_reward_desc {
+    const float* weights;   /* HOST f32 [CA_REWARD_N_TERMS], or [A, CA_REWARD_N_TERMS] with per_arena = 1 */
+    size_t  weights_bytes;
+    int32_t per_arena;      /* 0 | 1 */
+    float   margin;         /* the comfort distance of terms 3 and 4: 0 .. CA_MAX_LENGTH */
+} ca_reward_desc;
+int ca_reward_configure(ca_env* env, const ca_reward_desc* desc);
+int ca_reward_clear(ca_env* env);
+int ca_reward_info(ca_env* env, int32_t* configured, int32_t* per_arena, float* margin);
+int ca_reward_get_weights(ca_env* env, float* weights, size_t bytes);   /* [A, 7] as the kernel uses them */
+int ca_reward_parts(ca_env* env);
+int ca_get_reward_parts(ca_env* env, float* ref, int32_t* counts /* [6, A, N] */, size_t ref_bytes, size_t counts_bytes, int32_t dst_is_device);
+int ca_reward_parts_ptr(ca_env* env, void** dev_ptr, size_t* bytes);
 
 /* Hash of the kernel sources and compiler flags this library was built from (collision_avoidance_amd/build.py compiles
  * it in): reports and counter profiles quote it, so that they name the code that ran.  No reference counterpart. */
