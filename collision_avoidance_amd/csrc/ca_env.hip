@@ -3068,12 +3068,16 @@ int ca_policy_info(ca_env* e, int32_t* configured, int32_t* n_layers, int32_t* w
     return CA_OK;
 }
 
-// the policy launch (kind 3 for ca_profile): the handle's observation buffer -> actions, and the records of a rollout's row
-static hipError_t launch_policy(ca_env* e, const float* noise, float* actions, float* actions_rec, float* obs_rec) {
+// the four rows of a policy launch (null members: not wanted; actions may be null for the heads only)
+struct PolicyRows { const float* noise; float* actions; float* actions_rec; float* obs_rec; };
+// The policy launch (kind 3 for ca_profile) for both instances of policy_kernel: the handle's observation buffer through the sets
+// wp / bp (the policy's own, or the ones with the heads' output tile) into the rows; c is the argument block, p the PolicyArgs in it.
+extern "C++" {   // (a template)
+template <class Args>
+static hipError_t launch_policy_args(ca_env* e, void (*kernel)(Args), Args& c, PolicyArgs& p, const float* wp, const float* bp, const PolicyRows& rows) {
     const ca_env::Policy& q = e->pol;
-    PolicyArgs p;
-    p.obs = e->obs; p.wp = q.d_wp; p.bp = q.d_bp; p.set_of_arena = q.P > 1 ? q.d_set : nullptr;
-    p.noise = noise; p.actions = actions; p.actions_rec = actions_rec; p.obs_rec = obs_rec;
+    p.obs = e->obs; p.wp = wp; p.bp = bp; p.set_of_arena = q.P > 1 ? q.d_set : nullptr;
+    p.noise = rows.noise; p.actions = rows.actions; p.actions_rec = rows.actions_rec; p.obs_rec = rows.obs_rec;
     for (int l = 0; l < POLICY_MAX_LAYERS; ++l) { p.wp_off[l] = q.wp_off[l]; p.bp_off[l] = q.bp_off[l]; }
     for (int l = 0; l <= POLICY_MAX_LAYERS; ++l) p.width[l] = q.width[l];
     p.wset = q.wset; p.bset = q.bset;
@@ -3085,8 +3089,20 @@ static hipError_t launch_policy(ca_env* e, const float* noise, float* actions, f
     const unsigned grid = p.tpa ? (unsigned)e->cfg.n_arenas * (unsigned)p.tpa : (p.an + POLICY_ROWS - 1) / POLICY_ROWS;
     const size_t lds = (size_t)2 * POLICY_ROWS * p.stride * 4;
     ProfScope ps(e, KIND_RESET);
-    launch_k(ps, policy_kernel, dim3(grid), dim3(64), lds, e->stream, p);
+    launch_k(ps, kernel, dim3(grid), dim3(64), lds, e->stream, c);
     return hipGetLastError();
+}
+}  // extern "C++"
+static hipError_t launch_policy(ca_env* e, const PolicyRows& rows) {
+    PolicyArgs p;
+    return launch_policy_args(e, policy_kernel<false>, p, p, e->pol.d_wp, e->pol.d_bp, rows);
+}
+// the same on the sets with the heads' output tile: the records of ca_policy_eval, or the value column alone
+static hipError_t launch_heads(ca_env* e, const PolicyRows& rows, const ca_policy_eval& o, bool values_only) {
+    ActorCriticArgs c;
+    c.logp = o.logp; c.value = o.value; c.mean = o.mean; c.log_std = o.log_std;
+    c.has_logstd = e->heads.has_logstd ? 1 : 0; c.values_only = values_only ? 1 : 0;
+    return launch_policy_args(e, policy_kernel<true>, c, c.p, e->heads.d_wp, e->heads.d_bp, rows);
 }
 
 int ca_policy_actions(ca_env* e, const float* noise, float* actions_out) {
@@ -3094,7 +3110,7 @@ int ca_policy_actions(ca_env* e, const float* noise, float* actions_out) {
     if (!e->pol.on) return fail(e, CA_EINVAL, "ca_policy_actions: call ca_policy_configure first");
     if (!actions_out) return fail(e, CA_EINVAL, "ca_policy_actions: actions_out is null");
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, launch_policy(e, noise, actions_out, nullptr, nullptr));
+    HIPCHK(e, launch_policy(e, {noise, actions_out, nullptr, nullptr}));
     return CA_OK;
 }
 
@@ -3122,43 +3138,72 @@ static int policy_seq_check(ca_env* e, const char* who, int32_t steps, uint32_t 
     return CA_OK;
 }
 }  // extern "C++"
-// the row of actions that starts at step t (t a multiple of hold): what ca_observe launches, then the policy on what it left, into the
-// handle's action buffer and the row's records
-static hipError_t launch_policy_row(ca_env* e, const ca_policy_seq* seq, int t) {
+// The row of actions that starts at step t (t a multiple of hold): what ca_observe launches, then the policy on what it left, into the
+// handle's action buffer and the row's records.  heads: row t / hold of the records of a sampling rollout, which launches the heads
+// (null: the policy alone).
+extern "C++" {   // (templates: Seq as for policy_seq_check; the record launches lie between them)
+template <class Seq>
+static hipError_t launch_policy_row(ca_env* e, const Seq* seq, int t, const ca_policy_eval* heads) {
     const size_t r = (size_t)(t / seq->hold), an = AN(e);
     prof_cadence(e, 1);
     const hipError_t rc = launch_obs(e);
     if (rc != hipSuccess) return rc;
-    return launch_policy(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act, seq->actions_out ? seq->actions_out + r * an : nullptr,
-                         seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr);
+    const PolicyRows rows = {seq->noise ? seq->noise + r * an : nullptr, e->pol.act, seq->actions_out ? seq->actions_out + r * an : nullptr,
+                             seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr};
+    return heads ? launch_heads(e, rows, *heads, false) : launch_policy(e, rows);
 }
-// behind the launches of step t: the return, first_done and the step's records
-static hipError_t launch_policy_record(ca_env* e, const StepRec& rec) {
-    PolicyRecArgs c;
+// behind the launches of step t: the return, first_done and the step's records (both record kernels take these)
+static void fill_policy_rec(const ca_env* e, const StepRec& rec, PolicyRecArgs& c) {
     fill_step_rec(e, &rec, c);
     fill_step_records(e, rec, c);
     c.reward = e->reward; c.A = e->cfg.n_arenas;
+}
+static hipError_t launch_policy_record(ca_env* e, const StepRec& rec) {
+    PolicyRecArgs c;
+    fill_policy_rec(e, rec, c);
     ProfScope ps(e, KIND_RESET);
     launch_k(ps, policy_record_kernel, dim3((c.an + 255) / 256), dim3(256), 0, e->stream, c);
     return hipGetLastError();
 }
+// the same behind a step of a sampling rollout, with row t / hold of the row records (null: not wanted)
+static hipError_t launch_sample_record(ca_env* e, const StepRec& rec, int hold, float* row_rewards, int* row_done, int* row_valid) {
+    const size_t r = (size_t)(rec.t / hold), an = AN(e), A = (size_t)e->cfg.n_arenas;
+    SampleRecArgs c;
+    fill_policy_rec(e, rec, c.s);
+    c.row_rewards = row_rewards ? row_rewards + r * an : nullptr; c.row_done = row_done ? row_done + r * A : nullptr;
+    c.row_valid = row_valid ? row_valid + r * A : nullptr; c.first = rec.t % hold == 0 ? 1 : 0;
+    ProfScope ps(e, KIND_RESET);
+    launch_k(ps, sample_record_kernel, dim3((c.s.an + 255) / 256), dim3(256), 0, e->stream, c);
+    return hipGetLastError();
+}
+// The loop of a policy rollout, for the three calls that have one: the set-up launch, then for every step the row where a row starts,
+// the step and the record behind it.  row(t) is launch_policy_row; step(sf, rec) launches step t on the handle's action buffer and
+// returns a CA_ code; record(rec) is the launch behind it.  The caller's launch_tail follows (the sampling rollout has launches in between).
+template <class Seq, class Row, class Step, class Record>
+static int policy_rollout_steps(ca_env* e, int steps, uint32_t flags, const Seq* seq, const Row& row, const Step& step, const Record& record) {
+    ActSeqPlan pl;
+    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
+    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);   // (observation and contacts: one launch behind the last step, launch_tail)
+    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
+    for (rec.t = 0; rec.t < steps; ++rec.t) {
+        if (rec.t % seq->hold == 0) HIPCHK(e, row(rec.t));
+        const int rc = step(sf, rec);
+        if (rc) return rc;
+        HIPCHK(e, record(rec));
+    }
+    return CA_OK;
+}
+}  // extern "C++"
 
 int ca_rollout_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_policy_seq* seq) {
     if (!e) return CA_EINVAL;
     { const int rc = policy_seq_check(e, "ca_rollout_policy", steps, flags, seq); if (rc) return rc; }
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_policy"); if (rs) return rs; }
-    ActSeqPlan pl;
-    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
-    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
-    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
-    for (rec.t = 0; rec.t < steps; ++rec.t) {
-        if (rec.t % seq->hold == 0) HIPCHK(e, launch_policy_row(e, seq, rec.t));
-        const int rc = do_step(e, e->pol.act, sf);
-        if (rc) return rc;
-        HIPCHK(e, launch_policy_record(e, rec));
-    }
-    return launch_tail(e, flags);
+    const int rc = policy_rollout_steps(e, steps, flags, seq, [&](int t) { return launch_policy_row(e, seq, t, nullptr); },
+                                        [&](uint32_t sf, const StepRec&) { return do_step(e, e->pol.act, sf); },
+                                        [&](const StepRec& rec) { return launch_policy_record(e, rec); });
+    return rc ? rc : launch_tail(e, flags);
 }
 
 // ---- PPO sample collection (include/ca_env.h ca_policy_heads, ca_policy_sample_seq, ca_gae_desc) -------------------
@@ -3231,36 +3276,13 @@ int ca_policy_heads_info(ca_env* e, int32_t* has_value, int32_t* has_logstd) {
     return CA_OK;
 }
 
-// the heads launch (kind 3 for ca_profile): launch_policy's geometry on the sets with the heads' output tile
-static hipError_t launch_heads(ca_env* e, const float* noise, float* actions, float* actions_rec, float* obs_rec, const ca_policy_eval& o, bool values_only) {
-    const ca_env::Policy& q = e->pol;
-    ActorCriticArgs c;
-    PolicyArgs& p = c.p;
-    p.obs = e->obs; p.wp = e->heads.d_wp; p.bp = e->heads.d_bp; p.set_of_arena = q.P > 1 ? q.d_set : nullptr;
-    p.noise = noise; p.actions = actions; p.actions_rec = actions_rec; p.obs_rec = obs_rec;
-    for (int l = 0; l < POLICY_MAX_LAYERS; ++l) { p.wp_off[l] = q.wp_off[l]; p.bp_off[l] = q.bp_off[l]; }
-    for (int l = 0; l <= POLICY_MAX_LAYERS; ++l) p.width[l] = q.width[l];
-    p.wset = q.wset; p.bset = q.bset;
-    p.an = (unsigned)AN(e); p.N = e->cfg.n_agents;
-    p.tpa = q.P > 1 ? (p.N + POLICY_ROWS - 1) / POLICY_ROWS : 0;
-    p.n_layers = q.L; p.stride = q.maxw + POLICY_PAD;
-    p.clip = q.out_mode == CA_POLICY_OUT_CLIP ? 1 : 0; p.limit = q.limit;
-    c.logp = o.logp; c.value = o.value; c.mean = o.mean; c.log_std = o.log_std;
-    c.has_logstd = e->heads.has_logstd ? 1 : 0; c.values_only = values_only ? 1 : 0;
-    const unsigned grid = p.tpa ? (unsigned)e->cfg.n_arenas * (unsigned)p.tpa : (p.an + POLICY_ROWS - 1) / POLICY_ROWS;
-    const size_t lds = (size_t)2 * POLICY_ROWS * p.stride * 4;
-    ProfScope ps(e, KIND_RESET);
-    launch_k(ps, actor_critic_kernel, dim3(grid), dim3(64), lds, e->stream, c);
-    return hipGetLastError();
-}
-
 int ca_policy_evaluate(ca_env* e, const float* noise, const ca_policy_eval* out) {
     if (!e) return CA_EINVAL;
     if (!e->pol.on) return fail(e, CA_EINVAL, "ca_policy_evaluate: call ca_policy_configure first");
     if (!e->heads.on) return fail(e, CA_EINVAL, "ca_policy_evaluate: call ca_policy_set_heads first");
     if (!out) return fail(e, CA_EINVAL, "ca_policy_evaluate: out is null");
     HIPCHK(e, hipSetDevice(e->device));
-    HIPCHK(e, launch_heads(e, noise, out->actions, nullptr, nullptr, *out, false));
+    HIPCHK(e, launch_heads(e, {noise, out->actions, nullptr, nullptr}, *out, false));
     return CA_OK;
 }
 
@@ -3353,43 +3375,22 @@ int ca_rollout_policy_sample(ca_env* e, int32_t steps, uint32_t flags, const ca_
         if (!rd) rd = e->heads.words;
         if (!rv) rv = e->heads.words + e->heads.words_rows * A;
     }
-    ActSeqPlan pl;
-    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
-    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
-    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
-    for (rec.t = 0; rec.t < steps; ++rec.t) {
-        const size_t r = (size_t)(rec.t / hold);
-        const bool first = rec.t % hold == 0;
-        if (first) {   // the row: what ca_observe launches, then the heads on what it left, into the handle's action buffer and the row's records
-            prof_cadence(e, 1);
-            HIPCHK(e, launch_obs(e));
-            ca_policy_eval o;
-            o.actions = nullptr;
-            o.logp = seq->logp_out ? seq->logp_out + r * an : nullptr;
-            o.value = seq->values_out ? seq->values_out + r * an : nullptr;
-            o.mean = seq->dist_out ? seq->dist_out + r * 2 * an : nullptr;
-            o.log_std = seq->dist_out ? seq->dist_out + r * 2 * an + an : nullptr;
-            HIPCHK(e, launch_heads(e, seq->noise ? seq->noise + r * an : nullptr, e->pol.act, seq->actions_out ? seq->actions_out + r * an : nullptr,
-                                   seq->obs_out ? seq->obs_out + r * an * CA_OBS_DIM : nullptr, o, false));
-        }
-        const int rc = do_step(e, e->pol.act, sf);
-        if (rc) return rc;
-        SampleRecArgs c;
-        fill_step_rec(e, &rec, c.s);
-        fill_step_records(e, rec, c.s);
-        c.s.reward = e->reward; c.s.A = e->cfg.n_arenas;
-        c.row_rewards = rr ? rr + r * an : nullptr; c.row_done = rd ? rd + r * A : nullptr; c.row_valid = rv ? rv + r * A : nullptr;
-        c.first = first ? 1 : 0;
-        {
-            ProfScope ps(e, KIND_RESET);
-            launch_k(ps, sample_record_kernel, dim3((c.s.an + 255) / 256), dim3(256), 0, e->stream, c);
-        }
-        HIPCHK(e, hipGetLastError());
-    }
+    const auto row = [&](int t) {   // (the heads, into row t / hold of the call's own records)
+        const size_t r = (size_t)(t / hold);
+        ca_policy_eval o;
+        o.actions = nullptr;
+        o.logp = seq->logp_out ? seq->logp_out + r * an : nullptr;
+        o.value = seq->values_out ? seq->values_out + r * an : nullptr;
+        o.mean = seq->dist_out ? seq->dist_out + r * 2 * an : nullptr;
+        o.log_std = seq->dist_out ? seq->dist_out + r * 2 * an + an : nullptr;
+        return launch_policy_row(e, seq, t, &o);
+    };
+    { const int rc = policy_rollout_steps(e, steps, flags, seq, row, [&](uint32_t sf, const StepRec&) { return do_step(e, e->pol.act, sf); },
+                                          [&](const StepRec& rec) { return launch_sample_record(e, rec, hold, rr, rd, rv); }); if (rc) return rc; }
     if (seq->values_out) {   // the bootstrap row: the value of the state the call leaves
         HIPCHK(e, launch_obs(e));
         ca_policy_eval o = {nullptr, nullptr, seq->values_out + (size_t)R * an, nullptr, nullptr};
-        HIPCHK(e, launch_heads(e, nullptr, nullptr, nullptr, nullptr, o, true));
+        HIPCHK(e, launch_heads(e, {nullptr, nullptr, nullptr, nullptr}, o, true));
     }
     if (gae) HIPCHK(e, launch_gae(e, R, rr, seq->values_out, rd, rv, seq->gamma, seq->lambda, seq->advantages_out, seq->targets_out));
     const uint32_t tail = seq->values_out ? flags & ~(uint32_t)CA_F_OBS : flags;   // (the bootstrap's observation is CA_F_OBS's)
@@ -3721,16 +3722,10 @@ int ca_rollout_nav_policy(ca_env* e, int32_t steps, uint32_t flags, const ca_pol
     HIPCHK(e, hipSetDevice(e->device));
     { const int rs = overflow_status(e, "ca_rollout_nav_policy"); if (rs) return rs; }
     HIPCHK(e, nav_step_buffers(e));
-    ActSeqPlan pl;
-    { const int rc = actseq_prologue(e, flags, seq->returns, seq->first_done, true, &pl); if (rc) return rc; }
-    const uint32_t sf = flags & (CA_F_STATS | CA_F_AUTORESET | CA_F_FREEZE);
-    StepRec rec = {&pl, seq->weights, seq->returns, seq->rewards_out, seq->done_out, 0, flags};
-    for (rec.t = 0; rec.t < steps; ++rec.t) {
-        if (rec.t % seq->hold == 0) HIPCHK(e, launch_policy_row(e, seq, rec.t));
-        const int rc = nav_do_step(e, e->pol.act, sf, &rec);
-        if (rc) return rc;
-    }
-    return launch_tail(e, flags);
+    const int rc = policy_rollout_steps(e, steps, flags, seq, [&](int t) { return launch_policy_row(e, seq, t, nullptr); },
+                                        [&](uint32_t sf, const StepRec& rec) { return nav_do_step(e, e->pol.act, sf, &rec); },
+                                        [](const StepRec&) { return hipSuccess; });   // (nav_do_step launches its record itself)
+    return rc ? rc : launch_tail(e, flags);
 }
 
 // ---- reward terms (include/ca_env.h ca_reward_desc; ca_reward.h) ------------------------------------------------------

@@ -5,7 +5,8 @@
 // ca_policy_desc).  Its definition is a k-ordered chain of fused multiply-adds that starts from the bias,
 //     acc = b[j];  for k ascending: acc = fmaf(x[k], W[j][k], acc)
 // which is what v_mfma_f32_16x16x4_f32 computes with the bias in C and successive instructions taking ascending k: the products of
-// one instruction are added in the order k = 0 .. 3 of its lane groups.  policy_kernel runs on it:
+// one instruction are added in the order k = 0 .. 3 of its lane groups.  policy_kernel<HEADS> runs on it, one kernel template with
+// two output stages (policy_kernel<false>: the mean alone; policy_kernel<true>: the heads of a PPO sample, below):
 //   * one wave per workgroup owns POLICY_ROWS = 32 rows (agents): two 16-row tiles, i.e. two independent accumulators per output tile,
 //     which covers the instruction's dependent latency, and every weight fragment loaded serves both;
 //   * the rows' observations are staged into LDS with 128-bit loads (and go to the obs record from the same registers); a layer reads
@@ -13,7 +14,7 @@
 //     LDS image in [row][column] order, so the next layer again walks k in ascending order: nothing is ever permuted along k;
 //   * the weights come from global memory in the order the B operand wants them (the host packs them: [16-column tile][k-step][lane],
 //     lane l holding W[16 jt + (l & 15)][4 s + (l >> 4)]), one coalesced 256-byte load per instruction; the output layer is a tile whose
-//     columns 1 .. 15 are zero, and column 0 -- lanes 0, 16, 32, 48 -- holds the rows' means;
+//     column 0 -- lanes 0, 16, 32, 48 -- holds the rows' means, and whose columns 1 .. 15 are zero (with heads: 3 .. 15);
 //   * an LDS row is width + 4 floats long: the A reads of a k-step and the D writes of a tile then touch 64 different banks.
 // A row's result depends on its own observation and its arena's weight set only: not on the tiling, not on the rows beside it.
 // policy_record_kernel is the accumulate kernel of a policy rollout: the rule of actseq_account (ca_actseq.h) with the reward and done
@@ -49,8 +50,32 @@ struct PolicyArgs {
 
 typedef float policy_f32x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(64) void policy_kernel(const PolicyArgs p) {
+// ---- the heads of a PPO sample (ca_policy_set_heads, ca_policy_evaluate, ca_rollout_policy_sample; include/ca_env.h) ----------------
+// The output tile of a policy with heads holds the mean row in column 0, the log-std row in column 1 and the value row in column 2:
+// three chains for the MFMAs that computed one.  policy_kernel<true> is the kernel on that tile: everything up to the last layer's
+// accumulators is policy_kernel<false>'s, and the output stage is its own: lanes col = 0, 1, 2 of every 16-lane group hold the three
+// results of the same four rows (twice: two row tiles), so they go through the LDS image the last layer leaves free, as [column][row],
+// and lane r < 32 picks up row r: one row per lane for the fp64 exponential, consecutive lanes on consecutive banks and consecutive
+// addresses of every record.
+struct ActorCriticArgs {
+    PolicyArgs p;               // as policy_kernel<false> takes it; wp / bp: the sets with the heads' output tile; actions may be null here
+    float* logp;                // [A*N], or null
+    float* value;               // [A*N], or null
+    float* mean;                // [A*N], or null
+    float* log_std;             // [A*N], or null
+    int has_logstd;             // a log-std head is installed (else ls = 0, std = 1)
+    int values_only;            // the bootstrap row: the value column alone
+};
+
+template <bool HEADS> struct PolicyKernelArgs { typedef PolicyArgs type; };
+template <> struct PolicyKernelArgs<true> { typedef ActorCriticArgs type; };
+__device__ __forceinline__ const PolicyArgs& policy_part(const PolicyArgs& q) { return q; }
+__device__ __forceinline__ const PolicyArgs& policy_part(const ActorCriticArgs& q) { return q.p; }
+
+template <bool HEADS>
+__global__ __launch_bounds__(64) void policy_kernel(const typename PolicyKernelArgs<HEADS>::type q) {
     extern __shared__ __attribute__((aligned(16))) float policy_lds[];   // [2][POLICY_ROWS][stride]
+    const PolicyArgs& p = policy_part(q);
     const int lane = (int)threadIdx.x;
     unsigned g0;
     int nvalid, set = 0;
@@ -70,7 +95,7 @@ __global__ __launch_bounds__(64) void policy_kernel(const PolicyArgs p) {
     // the tile's observations: 32 rows x 16 float4, eight per lane; rows past the end are zeros nobody reads back
 #pragma unroll
     for (int it = 0; it < POLICY_ROWS * 16 / 64; ++it) {
-        const int q = it * 64 + lane, row = q >> 4, c = (q & 15) * 4;
+        const int f4 = it * 64 + lane, row = f4 >> 4, c = (f4 & 15) * 4;
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (row < nvalid) {
             const size_t at = (size_t)(g0 + (unsigned)row) * CA_OBS_DIM + (size_t)c;
@@ -115,6 +140,14 @@ __global__ __launch_bounds__(64) void policy_kernel(const PolicyArgs p) {
                     out[row * stride + jt * 16 + col] = acc0[r] > 0.0f ? acc0[r] : 0.0f;
                     out[(row + 16) * stride + jt * 16 + col] = acc1[r] > 0.0f ? acc1[r] : 0.0f;
                 }
+            } else if constexpr (HEADS) {
+                if (col < 3) {   // -> [column][row] in the free image, 3 x 32 floats
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        out[col * POLICY_ROWS + grp * 4 + r] = acc0[r];
+                        out[col * POLICY_ROWS + grp * 4 + r + 16] = acc1[r];
+                    }
+                }
             } else if (col == 0) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
@@ -131,9 +164,32 @@ __global__ __launch_bounds__(64) void policy_kernel(const PolicyArgs p) {
             }
         }
         __syncthreads();
-        float* t = in; in = out; out = t;
+        if (!HEADS || !last) { float* t = in; in = out; out = t; }   // (the heads' three columns stay in `out` for the epilogue)
+    }
+    if constexpr (HEADS) {   // one row per lane: value; sample, log-probability and the row's records
+        if (lane >= nvalid) return;   // (nvalid <= 32: one row per lane)
+        const unsigned g = g0 + (unsigned)lane;
+        const float value = out[2 * POLICY_ROWS + lane];
+        if (q.value != nullptr) q.value[g] = value;
+        if (q.values_only) return;
+        const float mean = out[lane], ls_raw = out[POLICY_ROWS + lane];
+        float ls = 0.0f, sd = 1.0f;
+        if (q.has_logstd) {
+            ls = fminf(fmaxf(ls_raw, CA_POLICY_LOGSTD_MIN), CA_POLICY_LOGSTD_MAX);
+            sd = (float)exp64((double)ls);
+        }
+        const float eps = p.noise != nullptr ? p.noise[g] : 0.0f;
+        float u = __fadd_rn(mean, __fmul_rn(sd, eps));
+        if (p.clip) u = fminf(fmaxf(u, -p.limit), p.limit);
+        if (p.actions != nullptr) p.actions[g] = u;
+        if (p.actions_rec != nullptr) p.actions_rec[g] = u;
+        if (q.logp != nullptr) q.logp[g] = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps, eps)), ls), 0.918938533f);
+        if (q.mean != nullptr) q.mean[g] = mean;
+        if (q.log_std != nullptr) q.log_std[g] = ls;
     }
 }
+template __global__ void policy_kernel<false>(const PolicyArgs);
+template __global__ void policy_kernel<true>(const ActorCriticArgs);
 
 struct PolicyRecArgs {
     const float* reward;
@@ -158,121 +214,6 @@ __global__ __launch_bounds__(256) void policy_record_kernel(const PolicyRecArgs 
     const int a = (int)(g / (unsigned)s.N), i = (int)(g - (unsigned)a * (unsigned)s.N);
     actseq_account(g, a, i, s.reward[g], s.agent_counts, s.N, s.arena_done, s.entry_frozen, s.weight, s.returns, s.first_done, s.rewards_rec, s.done_rec, s.t,
                    s.freeze);
-}
-
-// ---- the heads of a PPO sample (ca_policy_set_heads, ca_policy_evaluate, ca_rollout_policy_sample; include/ca_env.h) ----------------
-// The output tile of a policy with heads holds the mean row in column 0, the log-std row in column 1 and the value row in column 2:
-// three chains for the MFMAs that computed one.  actor_critic_kernel is policy_kernel's twin for that tile: the same staging, tiling,
-// LDS images and hidden-layer loop -- kept as a copy, so that policy_kernel's code stays what it was --, and an output stage of its own:
-// lanes col = 0, 1, 2 of every 16-lane group hold the three results of the same four rows (twice: two row tiles), so they go through
-// the LDS image the last layer leaves free, as [column][row], and lane r < 32 picks up row r: one row per lane for the fp64
-// exponential, consecutive lanes on consecutive banks and consecutive addresses of every record.
-struct ActorCriticArgs {
-    PolicyArgs p;               // as policy_kernel takes it; wp / bp: the sets with the heads' output tile; actions may be null here
-    float* logp;                // [A*N], or null
-    float* value;               // [A*N], or null
-    float* mean;                // [A*N], or null
-    float* log_std;             // [A*N], or null
-    int has_logstd;             // a log-std head is installed (else ls = 0, std = 1)
-    int values_only;            // the bootstrap row: the value column alone
-};
-
-__global__ __launch_bounds__(64) void actor_critic_kernel(const ActorCriticArgs q) {
-    extern __shared__ __attribute__((aligned(16))) float policy_lds[];   // [2][POLICY_ROWS][stride]
-    const PolicyArgs& p = q.p;
-    const int lane = (int)threadIdx.x;
-    unsigned g0;
-    int nvalid, set = 0;
-    if (p.tpa > 0) {
-        const unsigned arena = blockIdx.x / (unsigned)p.tpa;
-        const int i0 = (int)(blockIdx.x - arena * (unsigned)p.tpa) * POLICY_ROWS;
-        g0 = arena * (unsigned)p.N + (unsigned)i0;
-        nvalid = p.N - i0 < POLICY_ROWS ? p.N - i0 : POLICY_ROWS;
-        if (p.set_of_arena != nullptr) set = p.set_of_arena[arena];
-    } else {
-        g0 = blockIdx.x * (unsigned)POLICY_ROWS;
-        nvalid = p.an - g0 < (unsigned)POLICY_ROWS ? (int)(p.an - g0) : POLICY_ROWS;
-    }
-    const int stride = p.stride;
-    float* in = policy_lds;
-    float* out = policy_lds + POLICY_ROWS * stride;
-#pragma unroll
-    for (int it = 0; it < POLICY_ROWS * 16 / 64; ++it) {
-        const int c4 = it * 64 + lane, row = c4 >> 4, c = (c4 & 15) * 4;
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (row < nvalid) {
-            const size_t at = (size_t)(g0 + (unsigned)row) * CA_OBS_DIM + (size_t)c;
-            v = *(const float4*)(p.obs + at);
-            if (p.obs_rec != nullptr) *(float4*)(p.obs_rec + at) = v;
-        }
-        *(float4*)(in + row * stride + c) = v;
-    }
-    __syncthreads();
-    const float* wset = p.wp + (size_t)set * p.wset;
-    const float* bset = p.bp + (size_t)set * p.bset;
-    const int col = lane & 15, grp = lane >> 4;
-    for (int l = 0; l < p.n_layers; ++l) {
-        const bool last = l == p.n_layers - 1;
-        const int K = p.width[l], tiles = last ? 1 : p.width[l + 1] >> 4;
-        const float* W = wset + p.wp_off[l];
-        const float* B = bset + p.bp_off[l];
-        const float* a0p = in + col * stride + grp;
-        const float* a1p = a0p + 16 * stride;
-        for (int jt = 0; jt < tiles; ++jt) {
-            const float bias = B[jt * 16 + col];
-            policy_f32x4 acc0 = {bias, bias, bias, bias}, acc1 = {bias, bias, bias, bias};
-            const float* wj = W + (size_t)jt * (size_t)K * 16 + lane;
-            for (int s0 = 0; s0 < (K >> 2); s0 += 4) {
-                float b[4], x0[4], x1[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    b[u] = wj[(s0 + u) * 64];
-                    x0[u] = a0p[(s0 + u) * 4];
-                    x1[u] = a1p[(s0 + u) * 4];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[u], b[u], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[u], b[u], acc1, 0, 0, 0);
-                }
-            }
-            if (!last) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = grp * 4 + r;
-                    out[row * stride + jt * 16 + col] = acc0[r] > 0.0f ? acc0[r] : 0.0f;
-                    out[(row + 16) * stride + jt * 16 + col] = acc1[r] > 0.0f ? acc1[r] : 0.0f;
-                }
-            } else if (col < 3) {   // D: column = lane & 15, row = 4 (lane >> 4) + register -> out[column][row], 3 x 32 floats
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    out[col * POLICY_ROWS + grp * 4 + r] = acc0[r];
-                    out[col * POLICY_ROWS + grp * 4 + r + 16] = acc1[r];
-                }
-            }
-        }
-        __syncthreads();
-        if (!last) { float* t = in; in = out; out = t; }
-    }
-    if (lane >= nvalid) return;   // (nvalid <= 32: one row per lane)
-    const unsigned g = g0 + (unsigned)lane;
-    const float value = out[2 * POLICY_ROWS + lane];
-    if (q.value != nullptr) q.value[g] = value;
-    if (q.values_only) return;
-    const float mean = out[lane], ls_raw = out[POLICY_ROWS + lane];
-    float ls = 0.0f, sd = 1.0f;
-    if (q.has_logstd) {
-        ls = fminf(fmaxf(ls_raw, CA_POLICY_LOGSTD_MIN), CA_POLICY_LOGSTD_MAX);
-        sd = (float)exp64((double)ls);
-    }
-    const float eps = p.noise != nullptr ? p.noise[g] : 0.0f;
-    float u = __fadd_rn(mean, __fmul_rn(sd, eps));
-    if (p.clip) u = fminf(fmaxf(u, -p.limit), p.limit);
-    if (p.actions != nullptr) p.actions[g] = u;
-    if (p.actions_rec != nullptr) p.actions_rec[g] = u;
-    if (q.logp != nullptr) q.logp[g] = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(eps, eps)), ls), 0.918938533f);
-    if (q.mean != nullptr) q.mean[g] = mean;
-    if (q.log_std != nullptr) q.log_std[g] = ls;
 }
 
 struct SampleRecArgs {

@@ -33,6 +33,14 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _is_tensor(x):
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _shape_of(x):
+    return None if x is None else tuple(x.shape if _is_tensor(x) else np.shape(x))
+
+
 _TRACE_CHANNELS = {"pos": _lib.TRACE_POS, "vel": _lib.TRACE_VEL}
 
 
@@ -1094,6 +1102,30 @@ class VecCollisionAvoidanceEnv:
             bufs[key] = self.host_array(shape, dtype)
         return bufs[key]
 
+    @staticmethod
+    def _seq_flags(with_obs, stats, autoreset, freeze, contacts):
+        """The flag word of a sequence call."""
+        return (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
+               (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+
+    def _seq_in(self, name, x, rows, tail=(), dtype=np.float32):
+        """The input x [rows, *tail] of a sequence call where the library reads it: a contiguous device tensor (use_torch), or the
+        handle's page-locked array `name` -- of at least one row -- with x in its first rows.  None stays None."""
+        if x is None:
+            return None
+        if self.use_torch:
+            return torch.as_tensor(x).detach().to(device=torch.device("cuda", self.device),
+                                                  dtype=torch.float32 if dtype is np.float32 else torch.int32).contiguous()
+        a = self._actseq_host(name, (max(rows, 1),) + tuple(tail), dtype)
+        a[:rows] = np.asarray(x.detach().cpu().numpy() if _is_tensor(x) else x, dtype)
+        return a
+
+    def _seq_ptr(self):
+        """The address of what _seq_in / _policy_bufs returned (an empty tensor has no address to hand over: None, as for None)."""
+        if self.use_torch:
+            return lambda t: t.data_ptr() if t is not None and t.numel() else None
+        return lambda a: a.ctypes.data if a is not None else None
+
     def rollout_actions(self, actions, hold=1, weights=None, returns=True, first_done=False, with_obs=False, stats=False,
                         autoreset=False, freeze=False, contacts=False, steps=None, _entry="ca_rollout_actions"):
         """`steps` step() calls under the action tensor `actions` [R, A, N] without returning to the host (ca_rollout_actions): row
@@ -1111,42 +1143,26 @@ class VecCollisionAvoidanceEnv:
         tensors, filled on the handle's stream; otherwise numpy goes in and out and the call synchronises.  contacts=True: also
         leave the contact report of the final state (last_contacts())."""
         on_torch = self.use_torch
-        if not (torch is not None and isinstance(actions, torch.Tensor)):
+        if not _is_tensor(actions):
             actions = np.asarray(actions, np.float32)
-        if weights is not None and not (torch is not None and isinstance(weights, torch.Tensor)):
+        if weights is not None and not _is_tensor(weights):
             weights = np.asarray(weights, np.float32)
         hold = int(hold)
         R, steps = action_seq_shape(tuple(actions.shape), self.A, self.N, hold, steps,
                                     None if weights is None else tuple(weights.shape))
-        if on_torch and not isinstance(actions, torch.Tensor):
-            actions = torch.as_tensor(actions)
-        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
-                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        flags = self._seq_flags(with_obs, stats, autoreset, freeze, contacts)
+        act, w, ptr = self._seq_in("actions", actions, R, (self.A, self.N)), self._seq_in("weights", weights, steps), self._seq_ptr()
         if on_torch:
             dev = torch.device("cuda", self.device)
-            act = actions.detach().to(device=dev, dtype=torch.float32).contiguous()
             if R == 0:   # (an empty tensor has no address to hand over)
                 act = torch.zeros((1, self.A, self.N), dtype=torch.float32, device=dev)
-            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
             ret = torch.empty((self.A, self.N), dtype=torch.float32, device=dev) if returns else None
             fd = torch.empty((self.A,), dtype=torch.int32, device=dev) if first_done else None
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
             if not act.is_cuda:
                 raise RuntimeError("rollout_actions: use_torch=True needs a device")
         else:
-            if torch is not None and isinstance(actions, torch.Tensor):
-                actions = actions.detach().cpu().numpy()
-            if torch is not None and isinstance(weights, torch.Tensor):
-                weights = weights.detach().cpu().numpy()
-            act = self._actseq_host("actions", (max(R, 1), self.A, self.N), np.float32)
-            act[:R] = np.asarray(actions, np.float32)
-            w = None
-            if weights is not None:
-                w = self._actseq_host("weights", (max(steps, 1),), np.float32)
-                w[:steps] = np.asarray(weights, np.float32)
             ret = self._actseq_host("returns", (self.A, self.N), np.float32) if returns else None
             fd = self._actseq_host("first_done", (self.A,), np.int32) if first_done else None
-            ptr = lambda a: a.ctypes.data if a is not None else None
         nbytes = lambda t, n: 0 if t is None else n * 4
         seq = _lib.ActionSeq(actions=ptr(act), actions_bytes=R * self.A * self.N * 4, hold=hold,
                              weights=ptr(w) if steps else None, weights_bytes=nbytes(w, steps),
@@ -1221,28 +1237,43 @@ class VecCollisionAvoidanceEnv:
         return {n: self._actseq_host("policy_" + n, tuple(max(int(d), 1) if k == 0 else int(d) for k, d in enumerate(shape)), dt)
                 for n, shape, dt in specs}
 
+    def _noise1(self, who, noise):
+        """The [A, N] noise of a single policy launch where the library reads it (_seq_in), or None."""
+        if noise is None:
+            return None
+        if not self.use_torch:
+            noise = np.asarray(noise.detach().cpu().numpy() if _is_tensor(noise) else noise, np.float32).reshape(self.A, self.N)
+        nz = self._seq_in("policy_noise1", noise, self.A, (self.N,))
+        if tuple(nz.shape) != (self.A, self.N):
+            raise ValueError("%s: noise must be [A=%d, N=%d], got %s" % (who, self.A, self.N, tuple(nz.shape)))
+        return nz
+
     def policy_actions(self, noise=None):
         """The policy's actions [A, N] for the observation buffer as it stands (ca_policy_actions: one launch; observe() or a step
         with_obs=True fills the buffer).  noise [A, N] float32 or None is added to the mean before the output mode."""
-        on_torch = self.use_torch
-        ptr = (lambda t: t.data_ptr()) if on_torch else (lambda a: a.ctypes.data)
-        out = self._policy_bufs([("act1", (self.A, self.N), np.float32)], on_torch)["act1"]
-        nz = None
-        if noise is not None:
-            if on_torch:
-                nz = torch.as_tensor(noise).detach().to(device=out.device, dtype=torch.float32).contiguous()
-            else:
-                if torch is not None and isinstance(noise, torch.Tensor):
-                    noise = noise.detach().cpu().numpy()
-                nz = self._actseq_host("policy_noise1", (self.A, self.N), np.float32)
-                nz[...] = np.asarray(noise, np.float32).reshape(self.A, self.N)
-            if tuple(nz.shape) != (self.A, self.N):
-                raise ValueError("policy_actions: noise must be [A=%d, N=%d], got %s" % (self.A, self.N, tuple(nz.shape)))
-        self._call("ca_policy_actions", self.h, ptr(nz) if nz is not None else None, ptr(out))
-        if on_torch:
+        ptr = self._seq_ptr()
+        out = self._policy_bufs([("act1", (self.A, self.N), np.float32)], self.use_torch)["act1"]
+        self._call("ca_policy_actions", self.h, ptr(self._noise1("policy_actions", noise)), ptr(out))
+        if self.use_torch:
             return out
         self.sync()
         return np.array(out)
+
+    def _policy_seq_in(self, sh, noise, weights):
+        """(noise, weights, ptr, size) of a policy rollout of the shapes sh: the two inputs where the library reads them, the address
+        of an array and the bytes of the array of a name."""
+        return (self._seq_in("policy_noise", noise, sh["R"], (self.A, self.N)), self._seq_in("policy_weights", weights, sh["weights"][0]),
+                self._seq_ptr(), lambda n: int(np.prod(sh[n])) * 4)
+
+    def _policy_seq_out(self, bufs, sh, names, with_obs):
+        """What a policy rollout returns: the arrays of `names` (None: not asked for) -- under numpy, after the call has finished,
+        copies of the rows the call filled -- and obs_last."""
+        if not self.use_torch:
+            self.sync()
+            bufs = {n: np.array(a) if n in ("returns", "first_done") else np.array(a[:sh[n][0]]) for n, a in bufs.items()}
+        out = {n: bufs.get(n) for n in names}
+        out["obs_last"] = self._obs_out() if with_obs else None
+        return out
 
     def rollout_policy(self, steps, hold=1, noise=None, weights=None, record=("obs", "actions", "rewards", "dones"), returns=True,
                        first_done=False, with_obs=False, stats=False, autoreset=False, freeze=False, contacts=False,
@@ -1261,31 +1292,14 @@ class VecCollisionAvoidanceEnv:
         for r in record:
             if r not in ("obs", "actions", "rewards", "dones"):
                 raise ValueError("rollout_policy: record holds %r; it may hold 'obs', 'actions', 'rewards', 'dones'" % (r,))
-        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
-        sh = policy_seq_shape(self.A, self.N, steps, hold, None if noise is None else tuple(noise.shape if is_t(noise) else np.shape(noise)),
-                              None if weights is None else tuple(weights.shape if is_t(weights) else np.shape(weights)))
+        sh = policy_seq_shape(self.A, self.N, steps, hold, _shape_of(noise), _shape_of(weights))
         steps, hold, R = int(steps), int(hold), sh["R"]
-        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
-                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        flags = self._seq_flags(with_obs, stats, autoreset, freeze, contacts)
         specs = [(n, sh[n], np.int32 if n in ("first_done", "dones") else np.float32)
                  for n, want in (("returns", returns), ("first_done", first_done), ("obs", "obs" in record), ("actions", "actions" in record),
                                  ("rewards", "rewards" in record), ("dones", "dones" in record)) if want]
         bufs = self._policy_bufs(specs, on_torch)
-        if on_torch:
-            dev = torch.device("cuda", self.device)
-            nz = None if noise is None else torch.as_tensor(noise).detach().to(device=dev, dtype=torch.float32).contiguous()
-            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        else:
-            nz = w = None
-            if noise is not None:
-                nz = self._actseq_host("policy_noise", (max(R, 1), self.A, self.N), np.float32)
-                nz[:R] = np.asarray(noise.detach().cpu().numpy() if is_t(noise) else noise, np.float32)
-            if weights is not None:
-                w = self._actseq_host("policy_weights", (max(steps, 1),), np.float32)
-                w[:steps] = np.asarray(weights.detach().cpu().numpy() if is_t(weights) else weights, np.float32)
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        size = lambda n: int(np.prod(sh[n])) * 4
+        nz, w, ptr, size = self._policy_seq_in(sh, noise, weights)
         b = bufs.get
         seq = _lib.PolicySeq(hold=hold, noise=ptr(nz) if R else None, noise_bytes=size("noise") if nz is not None else 0,
                              weights=ptr(w) if steps else None, weights_bytes=size("weights") if w is not None else 0,
@@ -1296,12 +1310,7 @@ class VecCollisionAvoidanceEnv:
                              rewards_out=ptr(b("rewards")) if steps else None, rewards_out_bytes=size("rewards") if "rewards" in bufs else 0,
                              done_out=ptr(b("dones")) if steps else None, done_out_bytes=size("dones") if "dones" in bufs else 0)
         self._call(_entry, self.h, steps, flags, C.byref(seq))
-        if not on_torch:
-            self.sync()
-            bufs = {n: np.array(a[:sh[n][0]]) if n in ("obs", "actions", "rewards", "dones") else np.array(a) for n, a in bufs.items()}
-        out = {n: bufs.get(n) for n in ("returns", "first_done", "obs", "actions", "rewards", "dones")}
-        out["obs_last"] = self._obs_out() if with_obs else None
-        return out
+        return self._policy_seq_out(bufs, sh, ("returns", "first_done", "obs", "actions", "rewards", "dones"), with_obs)
 
     # ---- PPO sample collection (ca_policy_set_heads, ca_policy_evaluate, ca_rollout_policy_sample, ca_gae) ---------
     def set_policy_heads(self, value=None, log_std=None):
@@ -1333,24 +1342,12 @@ class VecCollisionAvoidanceEnv:
         """The policy with its heads on the observation buffer as it stands (ca_policy_evaluate: one launch): dict(actions=, logp=,
         value=, mean=, log_std=), each [A, N] float32.  noise [A, N] is eps: action = out(mean + exp(log_std) * eps), logp the
         log-density of the unclipped sample (include/ca_env.h has the definition, bit for bit)."""
-        on_torch = self.use_torch
-        ptr = (lambda t: t.data_ptr()) if on_torch else (lambda a: a.ctypes.data)
         names = ("actions", "logp", "value", "mean", "log_std")
-        bufs = self._policy_bufs([("eval_" + n, (self.A, self.N), np.float32) for n in names], on_torch)
-        nz = None
-        if noise is not None:
-            if on_torch:
-                nz = torch.as_tensor(noise).detach().to(device=bufs["eval_logp"].device, dtype=torch.float32).contiguous()
-            else:
-                if torch is not None and isinstance(noise, torch.Tensor):
-                    noise = noise.detach().cpu().numpy()
-                nz = self._actseq_host("policy_noise1", (self.A, self.N), np.float32)
-                nz[...] = np.asarray(noise, np.float32).reshape(self.A, self.N)
-            if tuple(nz.shape) != (self.A, self.N):
-                raise ValueError("policy_evaluate: noise must be [A=%d, N=%d], got %s" % (self.A, self.N, tuple(nz.shape)))
+        ptr = self._seq_ptr()
+        bufs = self._policy_bufs([("eval_" + n, (self.A, self.N), np.float32) for n in names], self.use_torch)
         o = _lib.PolicyEval(**{n: ptr(bufs["eval_" + n]) for n in names})
-        self._call("ca_policy_evaluate", self.h, ptr(nz) if nz is not None else None, C.byref(o))
-        if on_torch:
+        self._call("ca_policy_evaluate", self.h, ptr(self._noise1("policy_evaluate", noise)), C.byref(o))
+        if self.use_torch:
             return {n: bufs["eval_" + n] for n in names}
         self.sync()
         return {n: np.array(bufs["eval_" + n]) for n in names}
@@ -1374,31 +1371,14 @@ class VecCollisionAvoidanceEnv:
                 raise ValueError("rollout_policy_sample: record holds %r; it may hold %s" % (r, ", ".join(repr(n) for n in self._SAMPLE_RECORDS)))
         if ("advantages" in record or "targets" in record) and "values" not in record:
             raise ValueError("rollout_policy_sample: 'advantages' and 'targets' need 'values' among the records")
-        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
-        sh = policy_sample_shape(self.A, self.N, steps, hold, None if noise is None else tuple(noise.shape if is_t(noise) else np.shape(noise)),
-                                 None if weights is None else tuple(weights.shape if is_t(weights) else np.shape(weights)))
+        sh = policy_sample_shape(self.A, self.N, steps, hold, _shape_of(noise), _shape_of(weights))
         steps, hold, R = int(steps), int(hold), sh["R"]
-        flags = (_lib.F_OBS if with_obs else 0) | (_lib.F_STATS if stats else 0) | (_lib.F_AUTORESET if autoreset else 0) | \
-                (_lib.F_FREEZE if freeze else 0) | (_lib.F_CONTACT if contacts else 0)
+        flags = self._seq_flags(with_obs, stats, autoreset, freeze, contacts)
         ints = ("first_done", "dones", "row_dones", "row_valid")
         wanted = [n for n, want in (("returns", returns), ("first_done", first_done)) if want] + [n for n in self._SAMPLE_RECORDS if n in record]
         bufs = self._policy_bufs([("sample_" + n, sh[n], np.int32 if n in ints else np.float32) for n in wanted], on_torch)
         bufs = {n[len("sample_"):]: a for n, a in bufs.items()}
-        if on_torch:
-            dev = torch.device("cuda", self.device)
-            nz = None if noise is None else torch.as_tensor(noise).detach().to(device=dev, dtype=torch.float32).contiguous()
-            w = None if weights is None else torch.as_tensor(weights).detach().to(device=dev, dtype=torch.float32).contiguous()
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        else:
-            nz = w = None
-            if noise is not None:
-                nz = self._actseq_host("policy_noise", (max(R, 1), self.A, self.N), np.float32)
-                nz[:R] = np.asarray(noise.detach().cpu().numpy() if is_t(noise) else noise, np.float32)
-            if weights is not None:
-                w = self._actseq_host("policy_weights", (max(steps, 1),), np.float32)
-                w[:steps] = np.asarray(weights.detach().cpu().numpy() if is_t(weights) else weights, np.float32)
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        size = lambda n: int(np.prod(sh[n])) * 4
+        nz, w, ptr, size = self._policy_seq_in(sh, noise, weights)
         kw = dict(hold=hold, noise=ptr(nz) if R else None, noise_bytes=size("noise") if nz is not None else 0,
                   weights=ptr(w) if steps else None, weights_bytes=size("weights") if w is not None else 0,
                   gamma=float(gamma))
@@ -1412,38 +1392,23 @@ class VecCollisionAvoidanceEnv:
             kw[member[n] + "_bytes"] = size(n)
         seq = _lib.PolicySampleSeq(**kw)
         self._call("ca_rollout_policy_sample", self.h, steps, flags, C.byref(seq))
-        if not on_torch:
-            self.sync()
-            bufs = {n: np.array(a[:sh[n][0]]) if n not in ("returns", "first_done") else np.array(a) for n, a in bufs.items()}
-        out = {n: bufs.get(n) for n in ("returns", "first_done") + self._SAMPLE_RECORDS}
-        out["obs_last"] = self._obs_out() if with_obs else None
-        return out
+        return self._policy_seq_out(bufs, sh, ("returns", "first_done") + self._SAMPLE_RECORDS, with_obs)
 
     def gae(self, rewards, values, done, valid=None, gamma=0.95, lam=1.0):
         """Generalised advantage estimation on the device (ca_gae): rewards [R, A, N], values [R + 1, A, N], done [R, A], valid
         [R, A] or None (all 1).  Returns (advantages, targets), each [R, A, N] float32; include/ca_env.h has the definition, bit for
         bit.  Device tensors in and out under use_torch, else numpy (the call synchronises)."""
         on_torch = self.use_torch
-        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
-        R = int(rewards.shape[0]) if is_t(rewards) else int(np.shape(rewards)[0])
+        R = int(_shape_of(rewards)[0])
         want = dict(rewards=(R, self.A, self.N), values=(R + 1, self.A, self.N), done=(R, self.A), valid=(R, self.A))
         given = dict(rewards=rewards, values=values, done=done, valid=valid)
         for n, x in given.items():
-            if x is not None and tuple(x.shape if is_t(x) else np.shape(x)) != want[n]:
-                raise ValueError("gae: %s must be %s, got shape %s" % (n, list(want[n]), tuple(x.shape if is_t(x) else np.shape(x))))
+            if x is not None and _shape_of(x) != want[n]:
+                raise ValueError("gae: %s must be %s, got shape %s" % (n, list(want[n]), _shape_of(x)))
         out = self._policy_bufs([("gae_advantages", want["rewards"], np.float32), ("gae_targets", want["rewards"], np.float32)], on_torch)
-        ins = {}
-        for n, x in given.items():
-            if x is None:
-                continue
-            dt = np.float32 if n in ("rewards", "values") else np.int32
-            if on_torch:
-                ins[n] = torch.as_tensor(x).detach().to(device=torch.device("cuda", self.device),
-                                                       dtype=torch.float32 if dt is np.float32 else torch.int32).contiguous()
-            else:
-                ins[n] = self._actseq_host("gae_" + n, want[n][:0] + (max(want[n][0], 1),) + want[n][1:], dt)
-                ins[n][:want[n][0]] = np.asarray(x.detach().cpu().numpy() if is_t(x) else x, dt)
-        ptr = (lambda t: t.data_ptr() if t.numel() else None) if on_torch else (lambda a: a.ctypes.data)
+        ins = {n: self._seq_in("gae_" + n, x, want[n][0], want[n][1:], np.float32 if n in ("rewards", "values") else np.int32)
+               for n, x in given.items() if x is not None}
+        ptr = self._seq_ptr()
         kw = dict(gamma=float(gamma))
         kw["lambda"] = float(lam)
         for n in ins:

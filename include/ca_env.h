@@ -893,7 +893,7 @@ int ca_debug_math(ca_env* env, int32_t op, const void* in, void* out, int32_t n)
  * slot keeps the numbering --, 1 step_kernel -- per STEP: a ca_rollout launch that advances T steps counts as one launch of
  * duration / T; on a tiled handle (CA_CREATE_TILED) every launch of the solve / advance / close sequence counts on its own, so a step
  * is three launches and its time three times the mean (CA_CREATE_TILED_GRID: the launches of the sort in front of them too) --, 2 obs_kernel, 3 the small kernels: reset_kernel, reset_arena_kernel, the ALAN select / update kernels, the record kernel of a
- * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel and the record kernel of ca_rollout_policy, actor_critic_kernel, sample_record_kernel and gae_kernel (ca_policy_evaluate, ca_rollout_policy_sample, ca_gae), nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), reward_begin_kernel and reward_terms_kernel (every step from actions while ca_reward_configure's terms are set; ca_reward_parts), each launch on its own), then clears them.  ca_profile(env, 0) switches
+ * recording rollout, contact_kernel (ca_contacts / CA_F_CONTACT), fork_kernel (ca_arena_gather: two, ca_snapshot_save / _load: one), policy_kernel<false> and the record kernel of ca_rollout_policy, policy_kernel<true>, sample_record_kernel and gae_kernel (ca_policy_evaluate, ca_rollout_policy_sample, ca_gae), nav_field_kernel (ca_nav_configure) and nav_pref_kernel (ca_nav_pref, ca_rollout_nav), nav_act_kernel and nav_reward_kernel (ca_nav_act, ca_nav_step, ca_rollout_nav_actions, ca_rollout_nav_policy), reward_begin_kernel and reward_terms_kernel (every step from actions while ca_reward_configure's terms are set; ca_reward_parts), each launch on its own), then clears them.  ca_profile(env, 0) switches
  * it off (default).  A sampled step costs ~10 us of dispatch serialisation; results never depend on it. */
 int ca_profile(ca_env* env, int32_t period);
 int ca_profile_read(ca_env* env, int32_t counts[4], float mean_ms[4]);

@@ -281,6 +281,28 @@ def test_sample_zero_steps_and_the_fields_of_rollout_policy():
     g.close(); twin.close()
 
 
+def test_values_only_launch_on_a_ragged_tile_with_a_set_per_arena():
+    """3 x 10 doorway after 5 steps, two weight sets, sets = [1, 0, 1]: 10-row padded tiles with a set per arena.  The bootstrap row
+    of a call of zero steps is the values-only launch alone: its bits are policy_evaluate()'s value and the definition's"""
+    A, N = 3, 10
+    p = H.scenario_params("doorway", N)
+    g = H.make_gpu(A, N, "doorway", p, seed=3)
+    layers = _layers((64, 64), 2, seed=2)
+    sets = np.asarray([1, 0, 1], np.int32)
+    act = np.random.RandomState(1).uniform(-np.pi, np.pi, (5, A, N)).astype(f32)
+    for t in range(5):
+        obs, *_ = g.step(act[t])
+    assert np.abs(obs).max() > 0
+    value, log_std = _heads(64, 2, seed=7)
+    g.set_policy(layers, sets=sets)
+    g.set_policy_heads(value=value, log_std=log_std)
+    out = g.rollout_policy_sample(0, record=("values",))
+    assert out["values"].shape == (1, A, N) and out["logp"] is None
+    H._eq(out["values"][0], _np(g.policy_evaluate()["value"]), "values only: the bootstrap row against policy_evaluate")
+    H._eq(out["values"][0], PP.heads_reference(obs, *_sets(layers), sets, value, log_std)[2], "values only: the bootstrap row against the definition")
+    g.close()
+
+
 # ---- ca_gae alone ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("R,A,N", [(5, 3, 10), (6, 2, 70), (1, 3, 10)], ids=["5x3x10", "6x2x70_a_wave_spans_arenas", "one_row"])
 def test_gae_on_synthetic_tensors(R, A, N):

@@ -185,8 +185,8 @@ def test_binding_restates_the_header():
 
 # ---- the compiler's metadata ----------------------------------------------------------------------------------------------------------
 def test_policy_kernels_use_no_scratch():
-    """tools/kernel_resources.py: the policy kernel runs on the f32-input MFMA with no scratch memory, no spilled register and no static
-    LDS (its LDS is dynamic: two images of 32 rows); the record kernel is a small kernel"""
+    """tools/kernel_resources.py: the policy kernel (the instance without heads of the one kernel template) runs on the f32-input
+    MFMA with no scratch memory, no spilled register and no static LDS (its LDS is dynamic: two images of 32 rows); the record kernel is a small kernel"""
     import shutil
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -195,13 +195,13 @@ def test_policy_kernels_use_no_scratch():
         pytest.skip("no hipcc")
     kr.ensure_asm()
     rows = {r["name"]: r for r in kr.parse()}
-    pol = [r for n, r in rows.items() if "policy_kernel" in n]
+    pol = [r for n, r in rows.items() if "policy_kernel<false>" in n]
     rec = [r for n, r in rows.items() if "policy_record_kernel" in n]
     assert len(pol) == 1 and len(rec) == 1, sorted(n for n in rows if "policy" in n)
     for r in pol + rec:
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["lds"] == 0, r
     assert pol[0]["vgpr"] <= 128 and rec[0]["vgpr"] <= 32, (pol, rec)
     asm = open(kr.ASM).read()
-    body = asm[asm.index("_ZN2ca13policy_kernelENS_10PolicyArgsE:"):]
+    body = asm[asm.index(pol[0]["sym"] + ":"):]
     body = body[:body.index(".Lfunc_end")]
     assert body.count("v_mfma_f32_16x16x4_f32") == 8 and "v_fma_f32" not in body and "v_fmac_f32" not in body

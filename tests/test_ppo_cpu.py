@@ -230,7 +230,7 @@ def test_binding_restates_the_header():
 
 # ---- the compiler's metadata ----------------------------------------------------------------------------------------------------------
 def test_ppo_kernels_use_no_scratch():
-    """tools/kernel_resources.py: the heads kernel runs on the f32-input MFMA like policy_kernel -- the same eight MFMAs, no fp32 FMA
+    """tools/kernel_resources.py: the heads kernel (policy_kernel<true>) runs on the f32-input MFMA like policy_kernel<false> -- the same eight MFMAs, no fp32 FMA
     (the chains are the MFMA's, the output stage multiplies and adds) --, and none of the three new kernels uses scratch memory, a
     spilled register or static LDS"""
     import shutil
@@ -241,13 +241,13 @@ def test_ppo_kernels_use_no_scratch():
         pytest.skip("no hipcc")
     kr.ensure_asm()
     rows = {r["name"]: r for r in kr.parse()}
-    new = {k: [r for n, r in rows.items() if k in n] for k in ("actor_critic_kernel", "sample_record_kernel", "gae_kernel")}
+    new = {k: [r for n, r in rows.items() if k in n] for k in ("policy_kernel<true>", "sample_record_kernel", "gae_kernel")}
     for k, found in new.items():
         assert len(found) == 1, (k, sorted(rows))
         r = found[0]
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0 and r["sgpr_spill"] == 0 and r["lds"] == 0, r
-    assert new["actor_critic_kernel"][0]["vgpr"] <= 128 and new["sample_record_kernel"][0]["vgpr"] <= 32 and new["gae_kernel"][0]["vgpr"] <= 64
+    assert new["policy_kernel<true>"][0]["vgpr"] <= 128 and new["sample_record_kernel"][0]["vgpr"] <= 32 and new["gae_kernel"][0]["vgpr"] <= 64
     asm = open(kr.ASM).read()
-    body = asm[asm.index("_ZN2ca19actor_critic_kernelENS_15ActorCriticArgsE:"):]
+    body = asm[asm.index(new["policy_kernel<true>"][0]["sym"] + ":"):]
     body = body[:body.index(".Lfunc_end")]
     assert body.count("v_mfma_f32_16x16x4_f32") == 8 and "v_fma_f32" not in body and "v_fmac_f32" not in body

@@ -131,7 +131,7 @@ def main():
                                                        prof["obs_kernel"][1] * 1e3, prof["reset_kernels"][0], prof["reset_kernels"][1] * 1e3))
         n, us = policy_kernel_us(env)
         est = 2.0 * macs * A * N / PEAK_F32_MATRIX * 1e6
-        lines.append("policy_kernel alone (%d profiled ca_policy_actions launches): %.2f us; %.2f G multiply-adds per launch = %.2f us at the f32 "
+        lines.append("policy_kernel<false> alone (%d profiled ca_policy_actions launches): %.2f us; %.2f G multiply-adds per launch = %.2f us at the f32 "
                      "matrix peak of %.1f TF (paper figure): %.0f %% of it" % (n, us, macs * A * N / 1e9, est, PEAK_F32_MATRIX / 1e12, 100.0 * est / us))
         env.close()
     text = "\n".join(lines)

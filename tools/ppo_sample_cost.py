@@ -4,11 +4,11 @@
 and its GAE launch; and what the library offered before: rollout_policy(T) with its four records, one batched torch forward over the
 recorded observations for the values (and one more for the bootstrap row), torch log-probabilities, and GAE as a reverse Python
 loop over the rows -- in ONE process, the variants alternated, every timed run at least --seconds long, --repeat runs of each.  Then
-one profiled call, and the heads kernel's own time beside policy_kernel's from ca_profile on the same handle.
+one profiled call, and the heads kernel's own time (policy_kernel<true>) beside policy_kernel<false>'s from ca_profile on the same handle.
 
   python tools/ppo_sample_cost.py [--shapes 1024x16,4096x64] [--repeat 5] [--seconds 0.5] [--out FILE]
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/ppo_sample_cost.py --probe 4096x64
-      (a run of its own: 50 launches each of policy_kernel and actor_critic_kernel on one handle, for the trace's per-launch times)
+      (a run of its own: 50 launches each of policy_kernel<false> and policy_kernel<true> on one handle, for the trace's per-launch times)
 
 The workload is bench.py's crowd (bench_params: a new goal whenever one is reached).  The bar: the new call's median no lower than the
 composition's median minus the composition's own spread (max - min of its repeats).
@@ -112,7 +112,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_sample_cost.txt"))
-    ap.add_argument("--probe", default=None, help="AxN: only launch policy_kernel and actor_critic_kernel 50 times each (for a kernel trace)")
+    ap.add_argument("--probe", default=None, help="AxN: only launch policy_kernel<false> and policy_kernel<true> 50 times each (for a kernel trace)")
     a = ap.parse_args()
     if a.probe:
         A, N = (int(v) for v in a.probe.split("x"))
@@ -155,7 +155,7 @@ def main():
                                                                    prof["obs_kernel"][1] * 1e3, prof["reset_kernels"][0], prof["reset_kernels"][1] * 1e3))
         n1, us1 = kernel_us(env, env.policy_actions)
         n2, us2 = kernel_us(env, env.policy_evaluate)
-        lines.append("per launch on this handle (ca_profile, %d launches each): policy_kernel %.2f us, actor_critic_kernel %.2f us" % (n1, us1, us2))
+        lines.append("per launch on this handle (ca_profile, %d launches each): policy_kernel<false> %.2f us, policy_kernel<true> %.2f us" % (n1, us1, us2))
         rew, val = torch.randn((T, A, N), device="cuda"), torch.randn((T + 1, A, N), device="cuda")
         done = torch.zeros((T, A), dtype=torch.int32, device="cuda")
         n3, us3 = kernel_us(env, lambda: env.gae(rew, val, done, gamma=GAMMA, lam=LAM))
