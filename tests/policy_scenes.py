@@ -47,15 +47,17 @@ def fma_exact(a, b, c):
 
 
 def fmaf32(a, b, c, counter=None):
-    """fmaf(a, b, c) elementwise on fp32 arrays (broadcast), exactly rounded for finite operands.  counter: a list that collects the
-    number of elements that needed the exact path."""
+    """fmaf(a, b, c) elementwise on fp32 arrays (broadcast), exactly rounded for finite operands, the overflow threshold included; inf
+    and NaN operands follow IEEE 754 through the float64 operations (inf * 0 and inf - inf are NaN, of no defined payload).  counter: a
+    list that collects the number of elements that needed the exact path."""
     a, b, c = np.broadcast_arrays(np.asarray(a, f32), np.asarray(b, f32), np.asarray(c, f32))
     with np.errstate(over="ignore", invalid="ignore"):
         s = a.astype(f64) * b.astype(f64) + c.astype(f64)
         r = s.astype(f32)
         toward = np.where(s > r.astype(f64), f32(np.inf), f32(-np.inf)).astype(f32)
         other = np.nextafter(r, toward)
-        mid = (r.astype(f64) + other.astype(f64)) * 0.5
+        edge = np.where(np.isinf(r) & np.isfinite(s), np.copysign(2.0 ** 128, s), r.astype(f64))     # (the midpoint below an overflow is FLT_MAX's and 2^128's)
+        mid = (edge + other.astype(f64)) * 0.5
         hazard = np.isfinite(s) & (r.astype(f64) != s) & (mid == s)
     if hazard.any():
         r = r.copy()

@@ -5,7 +5,8 @@ Everything is compared bit for bit:
   * ca_rollout_policy_sample against a twin handle driven call by call through observe / policy_evaluate / step: every field, the
     statistics and every record, on one handle of every form a step is launched in; its advantages and targets against
     gae_reference fed with the call's own records;
-  * ca_gae alone on synthetic tensors; the heads stay with the slot under fork(); set_policy drops them; refusals advance nothing;
+  * ca_gae alone on synthetic tensors, and at the row counts around its unroll with done, valid, gamma, lambda and the values at
+    their extremes; the heads stay with the slot under fork(); set_policy drops them; refusals advance nothing;
   * the trainer (collision_avoidance_amd/ppo.py): two iterations, and the reinstalled weights against the restatement."""
 import ctypes as C
 
@@ -320,6 +321,89 @@ def test_gae_on_synthetic_tensors(R, A, N):
     assert np.abs(adv).max() > 0
     with pytest.raises(ValueError, match="values must be"):
         g.gae(rew, val[:R], done)
+    g.close()
+
+
+def _gae_nan_eq(got, want, what):
+    """the same elements are NaN (the header defines no payload or sign for one); every other element has the same bits"""
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), (what, np.argwhere(gn)[:8].tolist(), np.argwhere(wn)[:8].tolist())
+    H._eq(np.where(gn, f32(0.0), got), np.where(wn, f32(0.0), want), what)
+
+
+def _gae_case(g, rew, val, done, valid, gamma, lam, what, eq=H._eq):
+    with np.errstate(all="ignore"):
+        wa, wt = PP.gae_reference(rew, val, done, valid, gamma, lam)
+    adv, tgt = g.gae(rew, val, done, valid, gamma=gamma, lam=lam)
+    eq(adv, wa, what + ": advantages")
+    eq(tgt, wt, what + ": targets")
+    return wa, wt
+
+
+@pytest.mark.parametrize("R", [2, 3, 4, 7, 8, 9])
+def test_gae_row_counts_around_the_unroll_and_edge_values(R):
+    """R below, at, beside and at twice the kernel's unroll of four rows; 2 x 70 so that a wave spans both arenas.  done and valid at
+    their extremes, gamma and lambda at 0 and 1, values at the ends of fp32, and non-finite values behind done and valid, which the
+    definition selects away (a product with 0 would keep them)."""
+    A, N = 2, 70
+    rs = np.random.RandomState(40 + R)
+    g = H.make_gpu(A, N, "crowd", H.scenario_params("crowd", N), seed=1)
+    rew, val = rs.standard_normal((R, A, N)).astype(f32), rs.standard_normal((R + 1, A, N)).astype(f32)
+    rnd_done = (rs.uniform(size=(R, A)) < 0.3).astype(np.int32)
+    rnd_valid = (rs.uniform(size=(R, A)) < 0.7).astype(np.int32)
+    zeros, ones = np.zeros((R, A), np.int32), np.ones((R, A), np.int32)
+    last, first = zeros.copy(), zeros.copy()
+    last[R - 1], first[0] = 1, 1
+    for done, valid, what in ((rnd_done, rnd_valid, "random done and valid"), (rnd_done, zeros, "valid all zero"), (ones, rnd_valid, "done all one"),
+                              (last, None, "done at the last row only"), (first, ones, "done at row 0 only"), (zeros, None, "never done")):
+        wa, _ = _gae_case(g, rew, val, done, valid, 0.95, 0.9, "R = %d, %s" % (R, what))
+        assert what == "valid all zero" or np.abs(wa).max() > 0
+    for gamma, lam in ((0.0, 0.9), (1.0, 0.9), (0.95, 0.0), (0.95, 1.0), (0.0, 0.0), (1.0, 1.0)):
+        _gae_case(g, rew, val, rnd_done, rnd_valid, gamma, lam, "R = %d, gamma %g, lambda %g" % (R, gamma, lam))
+    # the ends of fp32: subnormal values and rewards, -0, and 1e38, where gamma * v is finite and the sum is not
+    tiny = (rs.standard_normal((R + 1, A, N)) * 2.0 ** -135).astype(f32)
+    wa, wt = _gae_case(g, (rs.standard_normal((R, A, N)) * 2.0 ** -136).astype(f32), tiny, last, rnd_valid, 0.95, 0.9, "R = %d, subnormal" % R)
+    sub = lambda v: ((np.abs(v) > 0) & (np.abs(v) < np.finfo(f32).tiny)).sum()
+    assert sub(wa) >= A * N // 2 and sub(wt) >= A * N // 2
+    nz = np.where(rs.uniform(size=(R + 1, A, N)) < 0.5, f32(-0.0), f32(0.0)).astype(f32)
+    wa, wt = _gae_case(g, nz[:R].copy(), nz, rnd_done, rnd_valid, 0.95, 0.9, "R = %d, signed zeros" % R)
+    assert not wa.view(np.uint32).any() and not wt.view(np.uint32).any()                  # gamma lambda * (+0) is +0: every -0 ends as +0
+    big_v = (f32(1e38) * rs.choice([-1.0, 1.0], (R + 1, A, N))).astype(f32)
+    big_r = (f32(3e38) * rs.choice([-1.0, 1.0], (R, A, N))).astype(f32)
+    wa, _ = _gae_case(g, big_r, big_v, last, None, 0.95, 0.9, "R = %d, sums that overflow" % R, eq=_gae_nan_eq)
+    assert np.isinf(wa).any() and np.isfinite(wa).any()
+    # non-finite values that the definition never reads: the bootstrap row behind done[R - 1], a reward under valid = 0
+    for bad in (np.nan, np.inf, -np.inf):
+        v2, r2, d2, k2 = val.copy(), rew.copy(), rnd_done.copy(), ones.copy()
+        v2[R] = bad
+        d2[R - 1] = 1
+        r0 = R // 2
+        r2[r0, 1], k2[r0, 1] = bad, 0
+        with np.errstate(all="ignore"):
+            wa, wt = PP.gae_reference(r2, v2, d2, k2, 0.95, 0.9)
+        assert np.isfinite(wa).all() and np.isfinite(wt).all(), bad
+        _gae_case(g, r2, v2, d2, k2, 0.95, 0.9, "R = %d, %r behind done and valid" % (R, bad))
+        # ... and one in the middle: values[r0 + 1] behind done[r0]; row r0 + 1 itself reads it (its advantage is 0 under valid = 0, its
+        # target is not a number), the rows at and below r0 do not
+        v3, d3, k3 = val.copy(), zeros.copy(), ones.copy()
+        v3[r0 + 1, 0] = bad
+        d3[r0, 0] = 1
+        if r0 + 1 < R:
+            k3[r0 + 1, 0] = 0
+        with np.errstate(all="ignore"):
+            wa, wt = PP.gae_reference(rew, v3, d3, k3, 0.95, 0.9)
+        assert np.isfinite(wa[:r0 + 1]).all() and np.isfinite(wt[:r0 + 1]).all() and np.isfinite(wa).all(), bad
+        _gae_case(g, rew, v3, d3, k3, 0.95, 0.9, "R = %d, %r in values[%d] behind done[%d]" % (R, bad, r0 + 1, r0), eq=_gae_nan_eq)
+    g.close()
+
+
+def test_gae_of_zero_rows():
+    A, N = 3, 10
+    g = H.make_gpu(A, N, "crowd", H.scenario_params("crowd", N), seed=1)
+    adv, tgt = g.gae(np.zeros((0, A, N), f32), np.ones((1, A, N), f32), np.zeros((0, A), np.int32), np.zeros((0, A), np.int32))
+    assert adv.shape == (0, A, N) and tgt.shape == (0, A, N) and adv.dtype == f32 and tgt.dtype == f32
+    rew, val = np.ones((1, A, N), f32), np.ones((2, A, N), f32)                            # and the handle computes afterwards
+    _gae_case(g, rew, val, np.zeros((1, A), np.int32), None, 0.95, 0.9, "after zero rows")
     g.close()
 
 
